@@ -18,6 +18,11 @@ spawn -> finish (driver.c:791-821).
 
 Rank 0 prints ONE JSON line.  value = rays traced by all ranks per second / 1e6 (Mray/s,
 rays counted in-kernel), weak/strong: the frame is fixed, so scaling is "strong".
+
+A plain run sets up, warms up, times --steps frames and prints the line.  --full adds the measurements and checks the
+headline does not need: the roofline block, the SAH builder's frame (config.bvh.sah), the boundary cost (config.boundary),
+the CPU baseline (cpu_baseline) and, at N > 1, the one-rank hash check of the gathered frame (distributed) and the
+per-launch kernel time on one stream.  --dump-outputs DIR writes what the last timed frame delivered (see dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -47,11 +52,16 @@ def parse_args():
     ap.add_argument("--samples", type=int, default=0)
     ap.add_argument("--bounces", type=int, default=0)
     ap.add_argument("--slab", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: roofline, config.bvh.sah, config.boundary, cpu_baseline, "
+                         "and at N > 1 the one-rank check of the gathered frame (distributed)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed frame's outputs as DIR/<name>.npy (rank 0; float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle sample")
     ap.add_argument("--save", default="", help="write the last frame as PNG (rank 0)")
     ap.add_argument("--no-bvh-compare", action="store_true",
-                    help="skip the side measurement of the opt-in SAH builder (config.bvh.sah)")
+                    help="(--full) skip the side measurement of the opt-in SAH builder (config.bvh.sah) and config.boundary")
     ap.add_argument("--dry-run-sleep", type=float, default=0.0, help=argparse.SUPPRESS)   # tests: ranks linger this long
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: ranks rendezvous (gloo), exchange an empty tile buffer, rank 0 prints a "
@@ -441,6 +451,29 @@ def boundary_cost(rt, abi, hs, frames=8):
     return out
 
 
+DUMP_MAX_PIXELS = 1 << 22      # 4.2 M pixels x 3 x float32 = 48 MiB: frames up to this size are written whole (1080p is 2.1 M)
+COUNTER_NAMES = ("paths", "rays", "node_visits", "leaf_visits", "shades", "backgrounds", "textured")
+
+
+def dump_outputs(path, image, counters):
+    """--dump-outputs: what the timed path delivered in its last step, so that two builds can be compared output for output
+    (the inputs -- scene, camera, seed 0x1234ABCD -- are the same in every run with the same arguments).
+      image.npy     rank 0's finished frame, (h, w, 3), the u8 values as float32.  A frame of more than DUMP_MAX_PIXELS pixels
+                    is written as a fixed seeded sample of DUMP_MAX_PIXELS / 2 pixels, (n, 3), and image_pixels.npy holds their
+                    row-major indices (float64).
+      counters.npy  the in-kernel counters of the last frame summed over ranks (COUNTER_NAMES, float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = np.asarray(image)
+    h, w = img.shape[:2]
+    if h * w > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0x1234ABCD).choice(h * w, DUMP_MAX_PIXELS // 2, replace=False))
+        np.save(os.path.join(path, "image_pixels.npy"), idx.astype(np.float64))
+        img = img.reshape(h * w, -1)[idx]
+    np.save(os.path.join(path, "image.npy"), img.astype(np.float32))
+    np.save(os.path.join(path, "counters.npy"), np.asarray(counters, dtype=np.float64))
+
+
 def dry_run(args, world, rank):
     """CPU-only rehearsal of the N-rank plumbing: rendezvous, partition tables, tile exchange, MAX-over-ranks
     timing, one line from rank 0.  No kernel runs and the line says so."""
@@ -657,7 +690,7 @@ def main():
     n_launches = C.c_int32(0)
     last_ms = float(rt.lib.rt_kernel_timing_mean_ms(C.byref(n_launches)))
     kernel_ms_source = "HIP events around every launch of the timed region"
-    if overlap:
+    if overlap and args.full:
         # with consecutive frames' kernels on two streams an event interval also holds the time the OTHER frame's kernel kept
         # the CUs: the per-launch time the roofline uses comes from two launches on one stream after the timed region
         rt.lib.rt_kernel_timing_reset()
@@ -686,11 +719,16 @@ def main():
     tot = rt.render.Counters(*[int(v) for v in stats.tolist()[:7]])
     skipped_total = int(stats.tolist()[7])
     last_ms = float(kms.item())
+    if overlap and not args.full:
+        last_ms = None                  # the timed region's event intervals overlap two frames' kernels: not a per-launch time
 
-    # N > 1: what rank 0 holds after the gather must BE the frame -- the same bytes as one rank rendering every chunk (per-path
-    # seeds depend on pixel and sample only).  Checked after the timed region, reported in the line, and fatal when it fails.
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, host_images[(frame_no[0] - 1) & 1].numpy(), stats.tolist()[:7])
+
+    # N > 1 (--full): what rank 0 holds after the gather must BE the frame -- the same bytes as one rank rendering every chunk
+    # (per-path seeds depend on pixel and sample only).  Checked after the timed region, reported in the line, and fatal when it fails.
     dist_check = None
-    if rank == 0 and multi:
+    if rank == 0 and multi and args.full:
         import hashlib
         gathered = host_images[(frame_no[0] - 1) & 1].numpy()
         whole = abi.RT_Render_Params(w, h, s, b, 0x1234ABCD, 0, 1, args.slab, 0)
@@ -719,11 +757,6 @@ def main():
         names = ["spheres", "quad", "helmet", "tower", "helmet4k"]
         if args.config in names and tuple(CONFIGS[args.config][1:5]) == (w, h, s, b):
             workload += f" (BASELINE.json configs[{names.index(args.config)}])"
-        prof = measured_profile(workload)
-        pipeline = "wavefront pipeline (rt_wf_camera / shade / trace kernels; diagnostic library)" if wavefront else \
-            "rt_path_kernel_stream<16, true, 1, short reciprocal> (the product's one path kernel)"
-        if prof is not None and wavefront:
-            prof = None                                 # the committed profiles are of the tile-stream kernel
         out = {
             "metric": "Mray/s", "value": mrays, "unit": "Mray/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": sec_per_step * 1e3, "higher_is_better": True,
@@ -748,16 +781,22 @@ def main():
             "leaf_visits_per_ray": tot.leaf_visits / max(rays, 1),
             "shades_per_ray": tot.shades / max(rays, 1),
             "kernel_ms": last_ms,
-            "roofline": roofline_block(tot, rays_per_launch, last_ms, n_launches.value, prof, pipeline, kernel_ms_source,
-                                       profile_scale=(rays_per_launch / prof[0]["rays_per_launch"])
-                                       if prof and world > 1 and prof[0].get("rays_per_launch") else 1.0,
-                                       skipped_root_visits=skipped_total),
         }
-        if world == 1 and not args.no_bvh_compare:
+        if args.full:
+            prof = measured_profile(workload)
+            pipeline = "wavefront pipeline (rt_wf_camera / shade / trace kernels; diagnostic library)" if wavefront else \
+                "rt_path_kernel_stream<16, true, 1, short reciprocal> (the product's one path kernel)"
+            if prof is not None and wavefront:
+                prof = None                             # the committed profiles are of the tile-stream kernel
+            out["roofline"] = roofline_block(tot, rays_per_launch, last_ms, n_launches.value, prof, pipeline, kernel_ms_source,
+                                             profile_scale=(rays_per_launch / prof[0]["rays_per_launch"])
+                                             if prof and world > 1 and prof[0].get("rays_per_launch") else 1.0,
+                                             skipped_root_visits=skipped_total)
+        if args.full and world == 1 and not args.no_bvh_compare:
             out["config"]["bvh"]["sah"] = bvh_compare(rt, abi, args, cfg, host_images[(frame_no[0] - 1) & 1].numpy())
-        if world == 1 and not args.no_bvh_compare:
+        if args.full and world == 1 and not args.no_bvh_compare:
             out["config"]["boundary"] = boundary_cost(rt, abi, hs)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(hs, cfg, args.cpu_seconds)
         if dist_check is not None:
             out["distributed"] = dist_check

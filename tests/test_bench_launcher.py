@@ -94,7 +94,7 @@ def test_bench_distributed_pipeline_on_one_gpu(tmp_path):
     """The N > 1 frame pipeline of bench.py -- path kernels of consecutive frames on two streams with a device scene each,
     RCCL gather of the tiles on a third, untile, D2H -- rehearsed with ONE rank (RT_BENCH_FORCE_DIST=1): the frame it
     delivers is the frame of the plain single-GPU path, byte for byte, with and without the overlap."""
-    common = ("--steps", "3", "--warmup", "2", "--samples", "24", "--no-cpu-baseline", "--no-bvh-compare")
+    common = ("--steps", "3", "--warmup", "2", "--samples", "24", "--full", "--no-cpu-baseline", "--no-bvh-compare")
     imgs = []
     for name, env in (("plain", {}), ("dist", {"RT_BENCH_FORCE_DIST": "1"}),
                       ("dist_one_stream", {"RT_BENCH_FORCE_DIST": "1", "RT_BENCH_OVERLAP": "0"})):
@@ -114,7 +114,7 @@ def test_bench_two_ranks_on_one_gpu_deliver_the_same_frame(tmp_path):
     """`python bench.py --gpus 2` (the driver's form: the parent starts the ranks) with both ranks on GPU 0 and the tiles
     exchanged over gloo -- what a one-GPU box can run of the N > 1 path: lattice partition, two frames in flight, gather
     to rank 0, untile.  Rank 0's frame equals the single-GPU frame byte for byte."""
-    common = ("--steps", "3", "--warmup", "1", "--samples", "24", "--no-cpu-baseline", "--no-bvh-compare")
+    common = ("--steps", "3", "--warmup", "1", "--samples", "24", "--full", "--no-cpu-baseline", "--no-bvh-compare")
     one, two = str(tmp_path / "one.png"), str(tmp_path / "two.png")
     r = _run(*common, "--save", one)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -140,7 +140,7 @@ def test_bench_two_ranks_on_two_gpus_over_rccl(tmp_path):
     """Switches itself on when the box has two GPUs: `python bench.py --gpus 2` as the driver runs it -- one
     rank per GPU, the tile gather over RCCL / xGMI.  The line must say world 2 / nccl and carry the hash check; rank 0's frame is
     the single-GPU frame byte for byte."""
-    common = ("--steps", "3", "--warmup", "1", "--samples", "24", "--no-cpu-baseline", "--no-bvh-compare")
+    common = ("--steps", "3", "--warmup", "1", "--samples", "24", "--full", "--no-cpu-baseline", "--no-bvh-compare")
     one, two = str(tmp_path / "one.png"), str(tmp_path / "two.png")
     r = _run(*common, "--save", one)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -150,3 +150,54 @@ def test_bench_two_ranks_on_two_gpus_over_rccl(tmp_path):
     d = out["distributed"]
     assert out["n_gpus"] == 2 and d["world_size"] == 2 and d["backend"] == "nccl" and d["equal"]
     assert open(one, "rb").read() == open(two, "rb").read()
+
+
+def test_dump_outputs_stays_float_and_within_budget(tmp_path):
+    """--dump-outputs writes float32 / float64 arrays only, a 1080p frame whole, and a frame above the pixel cap as the same
+    seeded sample in every run (with the pixel indices beside it) -- under 64 MB in both cases."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "small"), small, list(range(1, 8)))
+    img = np.load(tmp_path / "small" / "image.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, small.astype(np.float32))
+    cnt = np.load(tmp_path / "small" / "counters.npy")
+    assert cnt.dtype == np.float64 and cnt.tolist() == list(range(1, 8)) and len(cnt) == len(bench.COUNTER_NAMES)
+    assert not (tmp_path / "small" / "image_pixels.npy").exists()
+
+    big = rng.integers(0, 256, (2160, 3840, 3), dtype=np.uint8)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big, [0] * 7)
+    a, b = (np.load(tmp_path / d / "image.npy") for d in ("big1", "big2"))
+    idx = np.load(tmp_path / "big1" / "image_pixels.npy")
+    assert a.dtype == np.float32 and idx.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(idx, np.load(tmp_path / "big2" / "image_pixels.npy"))
+    assert np.array_equal(a, big.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float32))
+    for d in ("small", "big1"):
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64 * 2 ** 20
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """A plain run (no --full) prints the headline line without the side measurements, and --dump-outputs holds the frame the
+    timed path delivered: the CPU oracle's image and ray count for the same scene, size and seed."""
+    import numpy as np
+    from raytracing_c_amd.configs import load_config
+    from tests import _oracle
+    w, h, s, b = 96, 64, 8, 4
+    r = _run("--config", "spheres", "--width", str(w), "--height", str(h), "--samples", str(s), "--bounces", str(b),
+             "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "Mray/s" and out["unit"] == "Mray/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"roofline", "cpu_baseline", "distributed"} & set(out) and not {"sah"} & set(out["config"]["bvh"])
+    hs, _ = load_config("spheres")
+    want = _oracle.render(hs, w, h, s, b)
+    img = np.load(tmp_path / "image.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, want["image"].astype(np.float32))
+    cnt = np.load(tmp_path / "counters.npy")
+    assert cnt[1] == want["counters"]["rays"] == out["rays_per_frame"]

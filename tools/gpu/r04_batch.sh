@@ -10,7 +10,7 @@ if [ -z "${SKIP_AB:-}" ]; then
   mkdir -p tools/exp && cp raytracing_c_amd/librt_hip_v1.so tools/exp/librt_v1.so
   RT_EXP_RANKS="" RT_EXP_REPS=3 bash tools/exp_libs.sh $out/ab.log v1 hip || exit 1
 fi
-timeout -k 10 300 python bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 cat $out/bench.json
 if [ -z "${SKIP_PROF:-}" ]; then
   STEPS=9 bash tools/profile_gpu.sh $tag > $out/profile.log 2>&1

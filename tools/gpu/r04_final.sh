@@ -7,6 +7,6 @@ timeout -k 10 300 python tools/boundary.py 12 > $out/boundary.md 2> $out/boundar
 cat $out/boundary.md
 timeout -k 10 500 python tools/run_configs.py > $out/configs.md 2> $out/configs.err || { tail -5 $out/configs.err; exit 1; }
 cat $out/configs.md
-timeout -k 10 300 python bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 STEPS=9 bash tools/profile_gpu.sh $tag > $out/profile.log 2>&1
 tail -2 $out/profile.log
