@@ -1,0 +1,363 @@
+// rt_diag.cpp -- the host side of what only librt_hip_diag.so has (-DRT_DIAG_VARIANTS, include/rt_hip_diag.h).
+
+#include "rt_host.h"
+
+#ifndef RT_DIAG_VARIANTS
+#error rt_diag.cpp belongs to the diagnostic library only (-DRT_DIAG_VARIANTS)
+#endif
+
+// unit-test kernels (rt_kernels_diag.hip, rt_kernels.hip) and the wavefront pipeline (rt_wavefront.hip)
+extern "C" {
+int rt_launch_test_math(int op, int n, const float *x, const float *y, float *out, hipStream_t stream);
+int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_srgb_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_trace(const RT_KParams *P, int n, const float *rays, float *out_t, int *out_tri, float *out_uv,
+                         hipStream_t stream);
+int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, const float *pyr, int exit_lanes, int n_blocks,
+                                int smem_bytes, float *out_t, int *out_tri, float *out_uv, unsigned long long *visits,
+                                hipStream_t stream);
+int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const float *uv, float *out, hipStream_t stream);
+int rt_wf_launch_camera(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
+int rt_wf_launch_trace(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
+int rt_wf_launch_shade(const RT_KParams *P, int n_blocks, int first, hipStream_t stream);
+}
+
+// 0 = tile-stream path kernel (the product's ONE kernel), 1 = wavefront pipeline (rt_wavefront.hip:
+// same images and counters, measured slower on every BASELINE config -- profiles/r03_experiments.md -- kept for measurements)
+std::atomic<int>            g_pipeline{0};
+static std::atomic<int64_t> g_wf_cap_records{(int64_t)96 << 20};
+
+extern "C" int rt_set_pipeline(i32 pipeline) {
+  if (pipeline != 0 && pipeline != 1) return rt_fail("rt_set_pipeline: %d is not 0 (tile stream) or 1 (wavefront)", pipeline);
+  g_pipeline.store(pipeline);
+  return 0;
+}
+extern "C" i32 rt_get_pipeline(void) { return g_pipeline.load(); }
+extern "C" void rt_set_wavefront_capacity(i64 records) {
+  if (records >= 1024) g_wf_cap_records.store(records);
+}
+
+// A test process that has both libraries mapped builds its scenes with the product's token addresses (rt_host.cpp)
+extern "C" void rt_diag_set_tokens(void *disney, void *debug, void *background) {
+  if (disney) g_tok_disney = (Shader_Proc)disney;
+  if (debug) g_tok_debug = (Shader_Proc)debug;
+  if (background) g_tok_background = (Background_Proc)background;
+}
+
+// ---- wavefront pipeline (rt_wavefront.hip; diagnostic library only) --------------------------------------------------
+// Camera kernel -> (shade, trace) per bounce, joined by record queues in HBM.  The queues are sized for `cap` camera-ray
+// hits per pass (grown on demand, never beyond rt_set_wavefront_capacity() records); a frame with more first hits than
+// that takes several passes: the camera kernel stops taking units when its hit queue is nearly full, the bounces run, and
+// the host -- which reads one control word after every pass -- launches it again; tile_next / work_head keep the position.
+static int wavefront_ensure_queues(RT_Device_Scene *d, int64_t paths, int cam_waves, int max_waves) {
+  const int64_t cap = g_wf_cap_records.load();
+  const int64_t want = paths < cap ? paths : cap;
+  // chunks: a closed chunk holds at least WF_CHUNK - 63 records; every wave leaves one open chunk behind
+  const int64_t fill = WF_CHUNK - 63;
+  const int64_t soft = (want + fill - 1) / fill + cam_waves + 1;
+  if (d->wf_ctl && d->wf_soft0 >= soft && d->wf_waves >= max_waves) return 0;
+  (void)hipFree(d->wf_hit0); (void)hipFree(d->wf_hit); (void)hipFree(d->wf_ray[0]); (void)hipFree(d->wf_ray[1]);
+  (void)hipFree(d->wf_cnt); (void)hipFree(d->wf_ctl);
+  d->wf_hit0 = d->wf_hit = d->wf_ray[0] = d->wf_ray[1] = d->wf_cnt = d->wf_ctl = nullptr;
+  d->wf_soft0 = 0;
+  const int64_t hard = soft + 2 * (int64_t)cam_waves + 8;                      // a stopped wave closes at most two more chunks
+  const int64_t ray_chunks = (hard * WF_CHUNK + fill - 1) / fill + max_waves + 8;   // rays <= hits
+  const int64_t hit_chunks = (ray_chunks * WF_CHUNK + fill - 1) / fill + max_waves + 8;   // hits <= rays
+  HIP_TRY(hipMalloc(&d->wf_hit0, (size_t)hard * WF_HIT0_FIELDS * WF_CHUNK * 4));
+  HIP_TRY(hipMalloc(&d->wf_hit, (size_t)hit_chunks * WF_HIT_FIELDS * WF_CHUNK * 4));
+  HIP_TRY(hipMalloc(&d->wf_ray[0], (size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK * 4));
+  HIP_TRY(hipMalloc(&d->wf_ray[1], (size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK * 4));
+  HIP_TRY(hipMalloc(&d->wf_cnt, (size_t)(hard + hit_chunks + 2 * ray_chunks) * 4));
+  HIP_TRY(hipMalloc(&d->wf_ctl, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4));
+  if (!d->wf_ctl_host) HIP_TRY(hipHostMalloc((void **)&d->wf_ctl_host, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4, hipHostMallocDefault));
+  d->wf_soft0 = soft; d->wf_hard0 = hard; d->wf_ray_chunks = ray_chunks; d->wf_hit_chunks = hit_chunks;
+  d->wf_waves = max_waves;
+  return 0;
+}
+
+// K: filled for the tile-stream kernel (units, tile counters, schedule feedback)
+int launch_wavefront(Device &D, RT_Device_Scene *d, RT_KParams &K, hipStream_t stream) {
+  if (K.width > 65535 || K.height > 65535) return rt_fail("the wavefront pipeline packs a pixel into 16 + 16 bits: %dx%d is too large", K.width, K.height);
+  int geometry = knob_int("RT_WF_GEOMETRY", 0);
+  if (geometry < 0 || geometry > 2) geometry = 0;
+  int geometry_cam = knob_int("RT_WF_GEOMETRY_CAM", geometry);
+  if (geometry_cam < 0 || geometry_cam > 2) geometry_cam = 0;
+  const int lds_limit = 160 * 1024;
+  static const int wpb_of[3] = {16, 12, 10}, bpc_of[3] = {1, 2, 2};
+  const int wpb_cam = wpb_of[geometry_cam], bpc_cam = bpc_of[geometry_cam], wpb_tr = wpb_of[geometry], bpc_tr = bpc_of[geometry];
+  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;                   // perm stack + accumulator tile
+  const int cam_blocks = D.num_cus * bpc_cam, cam_waves = cam_blocks * wpb_cam;
+  const int tr_blocks = D.num_cus * bpc_tr, tr_waves = tr_blocks * wpb_tr;
+  int shade_blocks_per_cu = knob_int("RT_WF_SHADE_BLOCKS", 5);
+  if (shade_blocks_per_cu < 1 || shade_blocks_per_cu > 8) shade_blocks_per_cu = 5;
+  const int shade_blocks = D.num_cus * shade_blocks_per_cu, shade_waves = shade_blocks * 4;
+  const int max_waves = std::max(std::max(cam_waves, tr_waves), shade_waves);
+  auto lds_nodes_for = [&](int waves_per_block, int blocks_per_cu) {
+    int room = (lds_limit / blocks_per_cu - waves_per_block * per_wave) / 208;
+    if (room < 0) room = 0;
+    int n = d->n_nodes < room ? d->n_nodes : room;
+    if (!d->boxes_ordered) n = 0;
+    int v = knob_int("RT_LDS_NODES", n);
+    if (v >= 0 && v < n) n = v;
+    return n;
+  };
+  const int n_lds_cam = lds_nodes_for(wpb_cam, bpc_cam), n_lds_trace = lds_nodes_for(wpb_tr, bpc_tr);
+  const int smem_cam = n_lds_cam * 208 + wpb_cam * per_wave;
+  const int smem_trace = n_lds_trace * 208 + wpb_tr * per_wave;
+
+  const int64_t paths = (int64_t)K.n_tiles * 64 * (K.sample_end - K.sample_first);
+  if (wavefront_ensure_queues(d, paths, cam_waves, max_waves) != 0) return -1;
+  K.wf_hit0 = d->wf_hit0; K.wf_hit = d->wf_hit; K.wf_ray[0] = d->wf_ray[0]; K.wf_ray[1] = d->wf_ray[1];
+  K.wf_cnt_hit0 = d->wf_cnt;
+  K.wf_cnt_hit = d->wf_cnt + d->wf_hard0;
+  K.wf_cnt_ray[0] = K.wf_cnt_hit + d->wf_hit_chunks;
+  K.wf_cnt_ray[1] = K.wf_cnt_ray[0] + d->wf_ray_chunks;
+  K.wf_ctl = d->wf_ctl;
+  K.wf_soft_chunks = (int32_t)(d->wf_soft0 > 0x7fffffff ? 0x7fffffff : d->wf_soft0);
+  K.park = nullptr;
+  HIP_TRY(hipMemsetAsync(d->wf_ctl, 0, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4, stream));
+
+  for (int pass = 0; pass < (1 << 20); pass++) {
+    if (pass > 0) HIP_TRY(hipMemsetAsync(d->wf_ctl + WF_STOPPED * WF_CTL_STRIDE, 0, 4, stream));
+    K.n_lds_nodes = n_lds_cam;
+    K.pyr_nodes = knob_int("RT_PYRAMID", 1) ? n_lds_cam : 0;
+    K.wf_n_waves = cam_waves;
+    int rc = rt_wf_launch_camera(&K, cam_blocks, geometry_cam, smem_cam, stream);
+    if (rc != 0) return rt_fail("camera kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    for (int b = 0; b < K.max_bounces; b++) {
+      K.wf_bounce = b;
+      K.wf_n_waves = shade_waves;
+      rc = rt_wf_launch_shade(&K, shade_blocks, b == 0, stream);
+      if (rc != 0) return rt_fail("shade kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (b + 1 >= K.max_bounces) break;
+      K.wf_bounce = b + 1;
+      K.wf_n_waves = tr_waves;
+      K.n_lds_nodes = n_lds_trace;
+      rc = rt_wf_launch_trace(&K, tr_blocks, geometry, smem_trace, stream);
+      if (rc != 0) return rt_fail("trace kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (b >= 7 && (b & 3) == 3) {
+        // long bounce limits: most paths have ended long before; every fourth bounce look at the hit queue the next shade
+        // kernel would read and stop launching when a whole bounce produced no hit
+        HIP_TRY(hipMemcpyAsync(d->wf_ctl_host, d->wf_ctl, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (d->wf_ctl_host[WF_HIT_ALLOC * WF_CTL_STRIDE] == 0) break;
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(d->wf_ctl_host, d->wf_ctl, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (d->wf_ctl_host[WF_STOPPED * WF_CTL_STRIDE] == 0) break;
+  }
+  return 0;
+}
+
+// fault injection for tests/test_gpu_multi_device.py (diagnostic library only): bit 0 = pretend no device has peer access
+// to slot 0 (staged tile copies), bits 8.. = 1 + the slot whose frame fails
+static std::atomic<int> g_multi_fault{0};
+extern "C" void rt_diag_multi_fault(i32 no_peer, i32 failing_slot) {
+  g_multi_fault.store((no_peer ? 1 : 0) | ((failing_slot >= 0 ? failing_slot + 1 : 0) << 8));
+}
+bool fault_no_peer() { return (g_multi_fault.load() & 1) != 0; }
+bool fault_fails(int slot) { return (g_multi_fault.load() >> 8) == slot + 1; }
+
+// Block ledger of a -DRT_LEDGER build of the tile-stream kernel (LG_* slots, rt_dev.hip.h): out[0 .. n) = counters[8 .. 8 + n).
+extern "C" int rt_get_ledger(u64 *out, i32 n) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0 || !out || n < 0 || n > RT_N_COUNTERS - 8) return -1;
+  unsigned long long c[RT_N_COUNTERS];
+  if (read_counters(D, c) != 0) return -1;
+  for (int i = 0; i < n; i++) out[i] = c[8 + i];
+  return 0;
+}
+
+// Block statistics of the diagnostic kernel (RT_KERNEL=4): 8 pairs (executions, lanes) for
+// shade, environment, regenerate, leaf-scalar, leaf-vector, node-scalar, node-vector, pop.
+extern "C" int rt_get_sched_stats(u64 out[32]) { return rt_get_ledger(out, 32); }
+
+// Diagnostic kernel (RT_KERNEL=4): per wave start time, end time (100 MHz ticks) and items processed.
+extern "C" int rt_get_wave_times(u64 *out, i32 max_waves) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0 || !out || !D.ws.wave_times) return -1;
+  int n = D.ws.wave_times_n < max_waves ? D.ws.wave_times_n : max_waves;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, D.ws.wave_times, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+  return n;
+}
+
+// ---------------------------------------------------------------------------------
+// unit-level device entry points (include/rt_hip_diag.h; diagnostic library only)
+
+extern "C" int rt_test_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (n <= 0 || !x || !out) return rt_fail("rt_test_math: bad arguments");
+  DevBuf bx, by, bout;
+  size_t bytes = (size_t)n * sizeof(float);
+  HIP_TRY(bx.alloc(bytes));
+  HIP_TRY(bout.alloc(bytes));
+  float *dx = bx.as<float>(), *dy = nullptr, *dout = bout.as<float>();
+  HIP_TRY(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
+  if (y) {
+    HIP_TRY(by.alloc(bytes));
+    dy = by.as<float>();
+    HIP_TRY(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
+  }
+  int rc = rt_launch_test_math(op, n, dx, dy, dout, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_math failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int run_sweep(int (*launch)(unsigned long long *, hipStream_t), const char *name, u64 *out, int n_out) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (!out) return rt_fail("%s: NULL", name);
+  DevBuf b;
+  HIP_TRY(b.alloc((size_t)n_out * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(b.p, 0, (size_t)n_out * sizeof(unsigned long long)));
+  int rc = launch(b.as<unsigned long long>(), nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, b.p, (size_t)n_out * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("%s failed: %s", name, hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// rcp_exact() (the six-instruction reciprocal of the leaf blocks) against the IEEE quotient over all 2^32 bit patterns:
+// out[0] differing patterns inside its domain (must be 0), out[1] patterns outside the domain, out[2] differing ones
+// among those, out[3] first differing pattern inside the domain + 1; out[4], out[5]: the same for rcp_leaf() (rt_hip_diag.h).
+extern "C" int rt_test_rcp_sweep(u64 out[6]) { return run_sweep(rt_launch_test_rcp_sweep, "rt_test_rcp_sweep", out, 6); }
+
+// The kernels' sRGB decode of a texture sample (division by 1.055 as a corrected multiplication) against
+// rt_srgb_to_linear1() for every float in [0, 2] (and 4 M negative ones): out[0] patterns compared, out[1] differing (0 expected),
+// out[2] first differing pattern + 1.
+extern "C" int rt_test_srgb_sweep(u64 out[3]) { return run_sweep(rt_launch_test_srgb_sweep, "rt_test_srgb_sweep", out, 3); }
+
+// The tile-stream kernel's shift-based fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit
+// patterns: out[0] differing patterns (0 expected), out[1] first differing pattern + 1.
+extern "C" int rt_test_quantize_sweep(u64 out[2]) { return run_sweep(rt_launch_test_quantize_sweep, "rt_test_quantize_sweep", out, 2); }
+
+// The tile order the preparation kernel derives from per-tile costs (rays of the previous launch): order[] must be a
+// permutation of 0 .. n_tiles - 1 with non-increasing cost buckets (rt_kernels.hip: cost_bucket, 4 per power of two).
+extern "C" int rt_test_tile_order(i32 n_tiles, u32 const *cost, u32 *order) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (n_tiles <= 0 || !cost || !order) return rt_fail("rt_test_tile_order: bad arguments");
+  DevBuf bc, bo, bn, bk, bw, bz;
+  HIP_TRY(bc.alloc((size_t)n_tiles * 4));
+  HIP_TRY(bo.alloc((size_t)n_tiles * 4));
+  HIP_TRY(bn.alloc(((size_t)n_tiles + (size_t)(n_tiles + 63) / 64) * 4));
+  HIP_TRY(bk.alloc(RT_N_COUNTERS * 8));
+  HIP_TRY(bw.alloc(64));
+  HIP_TRY(bz.alloc((size_t)n_tiles * 4));
+  HIP_TRY(hipMemcpy(bc.p, cost, (size_t)n_tiles * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(bo.p, 0xFF, (size_t)n_tiles * 4));
+  int rc = rt_launch_prepare(n_tiles, bn.as<uint32_t>(), bn.as<uint32_t>() + n_tiles, bk.as<unsigned long long>(), bw.as<uint32_t>(),
+                             bz.as<uint32_t>(), bc.as<uint32_t>(), bo.as<uint32_t>(), nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(order, bo.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_tile_order failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_trace(RT_Device_Scene *d, i32 n, f32 const *rays, f32 *out_t, i32 *out_tri, f32 *out_uv) {
+  if (!d || n <= 0 || !rays || !out_t || !out_tri || !out_uv) return rt_fail("rt_test_trace: bad arguments");
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  DevBuf br, bt, btri, buv;
+  HIP_TRY(br.alloc((size_t)n * 24));
+  HIP_TRY(bt.alloc((size_t)n * 4));
+  HIP_TRY(btri.alloc((size_t)n * 4));
+  HIP_TRY(buv.alloc((size_t)n * 8));
+  float *dr = br.as<float>(), *dt = bt.as<float>(), *duv = buv.as<float>();
+  int   *dtri = btri.as<int>();
+  HIP_TRY(hipMemcpy(dr, rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_trace(&K, n, dr, dt, dtri, duv, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out_t, dt, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_tri, dtri, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_uv, duv, (size_t)n * 8, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_trace failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// n rays through traversal_blocks() -- the NODE / LEAF / pop code of the path kernels -- in the path kernel's launch geometry.
+//   pyramid: NULL, or 19 floats (4 outward plane normals at [4 q .. 4 q + 2], the rays' common origin at [16 .. 18]): every
+//            ray is then treated as a camera ray of one tile and node blocks take the pyramid-culled form where the path
+//            kernel would; the caller guarantees that every ray starts at that origin and lies inside the four planes
+//   exit_lanes: 1 .. 64, how many finished lanes end a round of blocks (the path kernel's `sched_thresh`, 48)
+//   mode: 0 = the instance the path kernel would choose for this scene, 1 = force the IEEE division in the leaf blocks,
+//         2 = nodes from L1 / L2 instead of the LDS copy
+//   visits: [0] += ray_aabbs_hit_8 equivalents, [1] += ray_triangles_hit_8 equivalents
+extern "C" int rt_test_trace_stream(RT_Device_Scene *d, i32 n, f32 const *rays, f32 const *pyramid, i32 exit_lanes, i32 mode,
+                                    f32 *out_t, i32 *out_tri, f32 *out_uv, u64 visits[2]) {
+  if (!d || n <= 0 || !rays || !out_t || !out_tri || !out_uv || !visits) return rt_fail("rt_test_trace_stream: bad arguments");
+  if (exit_lanes < 1 || exit_lanes > 64) return rt_fail("rt_test_trace_stream: exit_lanes %d outside [1, 64]", exit_lanes);
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
+  int room = (160 * 1024 - 16 * per_wave) / 208;
+  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
+  if (!d->boxes_ordered || mode == 2) K.n_lds_nodes = 0;
+  K.pyr_nodes = K.n_lds_nodes;
+  // the short reciprocal is valid while |det| < 2^102: edges <= 2^38 (as for frames) and, here, ray directions <= 2^16
+  float dir_max = 0.0f;
+  for (i32 i = 0; i < n; i++)
+    for (int k = 3; k < 6; k++) {
+      float m = fabsf(rays[(size_t)i * 6 + k]);
+      if (!(m <= dir_max)) dir_max = m;
+    }
+  K.short_div = (mode != 1 && d->max_edge <= 0x1p38f && dir_max <= 0x1p16f) ? 1 : 0;
+  const int smem = K.n_lds_nodes * 208 + 16 * per_wave;
+  int n_blocks = (n + 16 * 64 * 4 - 1) / (16 * 64 * 4);                 // ~4 rays per lane
+  if (n_blocks > D.num_cus) n_blocks = D.num_cus;
+  if (n_blocks < 1) n_blocks = 1;
+  DevBuf br, bp, bt, btri, buv, bv;
+  HIP_TRY(br.alloc((size_t)n * 24));
+  HIP_TRY(bp.alloc(19 * 4));
+  HIP_TRY(bt.alloc((size_t)n * 4));
+  HIP_TRY(btri.alloc((size_t)n * 4));
+  HIP_TRY(buv.alloc((size_t)n * 8));
+  HIP_TRY(bv.alloc(16));
+  HIP_TRY(hipMemcpy(br.p, rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  if (pyramid) HIP_TRY(hipMemcpy(bp.p, pyramid, 19 * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(bv.p, 0, 16));
+  int rc = rt_launch_test_trace_stream(&K, n, br.as<float>(), pyramid ? bp.as<float>() : nullptr, exit_lanes, n_blocks, smem,
+                                       bt.as<float>(), btri.as<int>(), buv.as<float>(), bv.as<unsigned long long>(), nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out_t, bt.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_tri, btri.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_uv, buv.p, (size_t)n * 8, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(visits, bv.p, 16, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_trace_stream failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_texture(RT_Device_Scene *d, i32 tex, i32 n, f32 const *uv, f32 *out_rgb) {
+  if (!d || n <= 0 || !uv || !out_rgb) return rt_fail("rt_test_texture: bad arguments");
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  if (tex < 0) tex = d->bg_texture;
+  if (tex >= d->n_textures) return rt_fail("rt_test_texture: texture %d of %d", tex, d->n_textures);
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  DevBuf buv, bout;
+  HIP_TRY(buv.alloc((size_t)n * 8));
+  HIP_TRY(bout.alloc((size_t)n * 12));
+  float *duv = buv.as<float>(), *dout = bout.as<float>();
+  HIP_TRY(hipMemcpy(duv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_texture(&K, tex, n, duv, dout, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out_rgb, dout, (size_t)n * 12, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_texture failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}

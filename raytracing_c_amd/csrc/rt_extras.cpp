@@ -1,0 +1,131 @@
+// rt_extras.cpp -- the reference's other GPU entry points: lightmap bake, scene_init on the GPU, the denoiser.
+
+#include "rt_host.h"
+
+// raytracer.c:722-784 on the GPU; semantics and the three documented choices
+// (last triangle wins, texels outside the image skipped, per-texel seeding) are in oracle/oracle.h.
+static int lightmap_bake_locked(Device &D, Image const *lightmap, Scene const *scene, isize samples) {
+  if (ensure_device(D) != 0) return -1;
+  if (!lightmap || !scene || !lightmap->pixels.data) return rt_fail("lightmap_bake: NULL argument");
+  if (lightmap->pixel_type != PT_u8 || lightmap->components < 3) return rt_fail("lightmap_bake: need a u8 image with >= 3 components");
+  if (samples <= 0 || lightmap->width <= 0 || lightmap->height <= 0 || lightmap->stride < lightmap->width)
+    return rt_fail("lightmap_bake: bad size or sample count");
+  RT_Device_Scene *d = cached_scene_locked(D, scene, nullptr, nullptr);
+  if (!d) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  K.max_bounces = 8;            // cast_ray(scene, r, 8), raytracer.c:774
+  K.seed = g_seed.load();
+  const Triangles &T = scene->triangles;
+  std::vector<float> verts((size_t)T.len * 9);
+  for (int i = 0; i < T.len; i++)
+    for (int k = 0; k < 3; k++) {
+      verts[(size_t)i * 9 + 0 + k] = T.x[k][i];
+      verts[(size_t)i * 9 + 3 + k] = T.y[k][i];
+      verts[(size_t)i * 9 + 6 + k] = T.z[k][i];
+    }
+  size_t pb = (size_t)lightmap->stride * lightmap->height * lightmap->components;
+  size_t ob = (size_t)lightmap->width * lightmap->height * sizeof(int);
+  DevBuf b_verts, b_owner, b_pixels;
+  HIP_TRY(b_verts.alloc(verts.size() * sizeof(float)));
+  HIP_TRY(b_owner.alloc(ob));
+  HIP_TRY(b_pixels.alloc(pb));
+  float *dv = b_verts.as<float>();
+  int *dow = b_owner.as<int>();
+  uint8_t *dp = b_pixels.as<uint8_t>();
+  HIP_TRY(hipMemcpy(dv, verts.data(), verts.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(dow, 0xFF, ob));                                        // owner = -1
+  HIP_TRY(hipMemcpy(dp, lightmap->pixels.data, pb, hipMemcpyHostToDevice));   // untouched texels keep their value
+  int rc = rt_launch_lightmap(&K, dv, T.len, (int)lightmap->width, (int)lightmap->height, (int)lightmap->stride,
+                              (int)lightmap->components, (int)samples, dow, dp, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(lightmap->pixels.data, dp, pb, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("lightmap_bake failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" void lightmap_bake(Image const *lightmap, Scene const *scene, isize samples) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  forget_multi_counters();
+  lightmap_bake_locked(D, lightmap, scene, samples);
+}
+
+// ---------------------------------------------------------------------------------
+// scene_init on the GPU (csrc/rt_build.hip): same Scene, byte for byte, as scene_init()
+
+extern "C" int rt_gpu_build(const Triangle *h_tris, long n_in, long depth, BVH_Node *h_nodes, long n_internal, float *h_block,
+                            long block_len, char *err, int err_len);
+
+extern "C" int scene_init_gpu(Scene *scene, Triangle_Slice src, Allocator allocator) {
+  if (!scene) return rt_fail("scene_init_gpu: scene is NULL");
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  if (src.len < 0 || (src.len > 0 && !src.data)) return rt_fail("scene_init_gpu: bad triangle slice");
+  if (src.len > (isize)1 << 27) return rt_fail("scene_init_gpu: %ld triangles are too many", (long)src.len);
+  // The GPU build orders centroid keys with a radix sort of their bit patterns, which equals the `<` order of scene_init's
+  // merge sort for every number including the infinities -- but not for NaN (`<` leaves a NaN where it stands, the radix
+  // order puts it behind +inf).  A soup with a NaN coordinate is therefore built by scene_init itself: same Scene by definition.
+  for (isize i = 0; i < src.len; i++)
+    for (int v = 0; v < 3; v++) {
+      const Vec3 &q = src.data[i].positions[v];
+      if (q.x != q.x || q.y != q.y || q.z != q.z) {
+        scene_init(scene, src, allocator);
+        return 0;
+      }
+    }
+  if (!rt_scene_alloc(scene, src.len, allocator)) return rt_fail("scene_init_gpu: the allocator failed");   // (drops a stale device copy)
+  char err[256] = "";
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  int rc = rt_gpu_build(src.data, (long)src.len, (long)scene->bvh.depth, scene->bvh.nodes.data, (long)scene->bvh.nodes.len,
+                        scene->triangles.x[0], (long)scene->triangles.len, err, (int)sizeof err);
+  if (rc != 0) return rt_fail("scene_init_gpu: %s", err);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// denoiser (reference denoiser.h / denoiser.c:131-153), SURVEY.md section 8f #3
+
+extern "C" int rt_denoise(i32 width, i32 height, void const *d_src, void *d_dst, void *stream) {
+  {
+    Device &D = dev0();
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  if (width <= 0 || height <= 0 || !d_src || !d_dst || d_src == d_dst) return rt_fail("rt_denoise: bad arguments");
+  int rc = rt_launch_denoise(width, height, width, 3, width, 3, (const uint8_t *)d_src, (uint8_t *)d_dst, (hipStream_t)stream);
+  if (rc != 0) return rt_fail("denoise kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int denoise_host(Image const *src, Image const *dst) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (!src || !dst || !src->pixels.data || !dst->pixels.data) return rt_fail("denoise_image: NULL image");
+  if (src->pixels.data == dst->pixels.data) return rt_fail("denoise_image: src and dst must differ (denoiser.c:134)");
+  if (src->width != dst->width || src->height != dst->height) return rt_fail("denoise_image: size mismatch");
+  if (src->components < 1 || dst->components < 1 || src->stride < src->width || dst->stride < dst->width)
+    return rt_fail("denoise_image: bad layout");
+  size_t sb = (size_t)src->stride * src->height * src->components;
+  size_t db = (size_t)dst->stride * dst->height * dst->components;
+  DevBuf b_src, b_dst;
+  HIP_TRY(b_src.alloc(sb));
+  HIP_TRY(b_dst.alloc(db));
+  uint8_t *ds = b_src.as<uint8_t>(), *dd = b_dst.as<uint8_t>();
+  HIP_TRY(hipMemcpy(ds, src->pixels.data, sb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dd, dst->pixels.data, db, hipMemcpyHostToDevice));     // components beyond 3 keep their values
+  int rc = rt_launch_denoise((int)src->width, (int)src->height, (int)src->stride, (int)src->components,
+                             (int)dst->stride, (int)dst->components, ds, dd, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(dst->pixels.data, dd, db, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("denoise_image failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" void denoise_image(Image const *src, Image const *dst, isize n_threads) {
+  (void)n_threads;      // the reference's CPU thread count (denoiser.c:131); one kernel launch here
+  denoise_host(src, dst);
+}

@@ -1,0 +1,348 @@
+// rt_host.h -- internal header of the host side of librt_hip.so: the reference's render entry points
+// (raytracer.h:51-56) and the device-control calls of include/rt_hip.h, in one unit per concern:
+//   rt_host.cpp       errors, configuration, device slots, seed, material / background tokens
+//   rt_residency.cpp  scene upload, fingerprints and stamps, rt_scene_touch / verify / invalidate / set_static, the per-device cache
+//   rt_partition.cpp  chunk counts and owners, partition tables, device chunk lists
+//   rt_launch.cpp     launch set-up (fill_kparams, render_accumulate_locked), resolve / untile, workspace buffers, counters, kernel timing
+//   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
+//   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
+//   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
+//   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
+//
+// (Comments in the kernel sources still cite rt_api.cpp, the one file these units were split from: those sources are hashed
+// into the committed profiles, buildinfo.kernel_source_hash, and stay as they are.)
+//
+// Nothing on the host side computes a pixel on the CPU: every entry point either
+// drives the gfx950 kernels of rt_kernels.hip / rt_wavefront.hip or fails with rt_last_error().
+//
+// State is kept PER DEVICE (struct Device): HIP context, workspace, scene cache, launch timing.  Slot 0 is the
+// process's primary device (rt_init); slots 1 .. N-1 exist when a frame behind render_thread_proc / render() is spread
+// over N GPUs (RT_DEVICES, rt_set_devices).  The product library reads its configuration ONCE (config()); the RT_*
+// experiment knobs of earlier rounds exist only in the diagnostic build (-DRT_DIAG_VARIANTS, librt_hip_diag.so).
+//
+// Lock order everywhere: slot 0's Device::mutex -> slot r's -> g_partition_mutex (rt_partition.cpp).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/rt_hip.h"
+#include "rt_device.h"
+
+// launchers in rt_kernels.hip, rt_denoise.hip
+extern "C" {
+int rt_launch_path_kernel(const RT_KParams *P, int n_waves, int variant, int smem_bytes, int wg_waves, hipStream_t stream);
+int rt_launch_prepare(int n_tiles, uint32_t *tile_next, uint32_t *open_groups, unsigned long long *counters, uint32_t *work_head,
+                      uint32_t *cost_cur, const uint32_t *cost_prev, uint32_t *order, hipStream_t stream);
+int rt_launch_resolve(int width, int height, int samples, int chunks_x, const int32_t *local_chunks, int n_local_chunks,
+                      const unsigned long long *accum, uint8_t *tiles, uint8_t *image, float *linear,
+                      hipStream_t stream);
+int rt_launch_untile(int width, int height, int chunks_x, int n_chunks, const int32_t *owner_slot,
+                     const uint8_t *all_tiles, uint8_t *image, hipStream_t stream);
+int rt_launch_lightmap(const RT_KParams *P, const float *verts, int n_tris, int lw, int lh, int stride, int comp,
+                       int samples, int *owner, uint8_t *pixels, hipStream_t stream);
+int rt_launch_denoise(int width, int height, int src_stride, int src_comp, int dst_stride, int dst_comp,
+                      const uint8_t *src, uint8_t *dst, hipStream_t stream);
+int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, int y0, int stride, int comp, uint32_t *out,
+                           hipStream_t stream);
+}
+
+// ---------------------------------------------------------------------------------
+// errors
+
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) return rt_fail("%s failed: %s", #expr, hipGetErrorString(e_));      \
+  } while (0)
+
+// Temporary device buffer that is released on every exit path (HIP_TRY returns early).
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+  template <typename T> T *as() const { return (T *)p; }
+};
+
+static inline double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+static inline float event_ms(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return -1.0f;
+  return ms;
+}
+
+// ---------------------------------------------------------------------------------
+// configuration: read once, never per launch
+//
+// Product library: RT_DEVICES (GPUs a frame behind render_thread_proc / render() is spread over, default 1) and
+// RT_DEVICES_REHEARSE (=1: the N logical devices all map onto the primary GPU -- what a one-GPU box can run of the
+// N-GPU path), overridable by rt_set_devices().  Nothing else in the environment changes what the library does.
+// Diagnostic library (-DRT_DIAG_VARIANTS): the experiment knobs of earlier rounds (RT_KERNEL, RT_SCHED_THRESH, ...),
+// read at every launch so that one process can A/B them (tools/exp_kernels.py, tests/test_gpu_diag.py).
+
+#ifdef RT_DIAG_VARIANTS
+static inline int knob_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline bool knob_is(const char *name, const char *value) {
+  const char *e = getenv(name);
+  return e && strcmp(e, value) == 0;
+}
+static inline bool knob_set(const char *name) { return getenv(name) != nullptr; }
+#else
+static inline int knob_int(const char *, int dflt) { return dflt; }
+static inline bool knob_is(const char *, const char *) { return false; }
+static inline bool knob_set(const char *) { return false; }
+#endif
+
+#define RT_MAX_DEVICES 16
+
+struct Config {
+  int  devices = 1;
+  bool rehearse = false;
+};
+
+// ---------------------------------------------------------------------------------
+// per-device state
+
+struct Partition;
+struct RT_Device_Scene;
+
+struct FrameTiming {          // the most recent frame through render_thread_proc / render / rt_render_frame
+  float stamp_ms = 0, upload_ms = 0, enqueue_ms = 0, gpu_prep_ms = 0, gpu_path_ms = 0, gpu_resolve_ms = 0, gpu_copy_ms = 0,
+        total_ms = 0, verify_ms = 0, gather_ms = 0;
+  int   n_devices = 1, slowest_device = 0;
+};
+
+#ifndef RT_FRAME_LANES
+#define RT_FRAME_LANES   2                       // frames in flight behind rt_frame_begin / rt_frame_end
+#endif
+#define RT_LAUNCH_STATES (1 + RT_FRAME_LANES)
+
+struct Workspace {
+  unsigned long long *accum = nullptr;
+  size_t              accum_elems = 0;
+  uint8_t            *image = nullptr;
+  float              *linear = nullptr;
+  size_t              image_pixels = 0;
+  uint8_t            *tiles = nullptr;        // multi-device frames: this device's compact tiles
+  size_t              tiles_bytes = 0;
+  uint8_t            *all_tiles = nullptr;    // slot 0: the tiles of every device, rank-major
+  size_t              all_tiles_bytes = 0;
+  uint8_t            *tiles_host = nullptr;   // pinned: a device without peer access to slot 0 stages its tiles here
+  size_t              tiles_host_bytes = 0;
+  unsigned long long *counters_host = nullptr;   // pinned: ray counters of a multi-device frame, copied asynchronously
+  // HIP event pairs around every path-kernel launch since the last timing reset
+  std::vector<hipEvent_t> ev0, ev1;
+  size_t              n_timed = 0;
+  hipEvent_t          ev_frame[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // frame start, prep done, path done, resolve done, copy done
+  unsigned long long *wave_times = nullptr;   // diagnostic kernel (RT_KERNEL=4) / RT_WAVE_TIMES
+  int                 wave_times_n = 0;
+};
+#define RT_MAX_TIMED 256
+
+struct DevPartition {
+  const Partition        *host = nullptr;
+  std::vector<int32_t *>  d_lists;            // device copies of the ranks' chunk lists, uploaded on first use
+  int32_t                *d_owner_slot = nullptr;
+};
+
+// A frame in flight behind rt_frame_begin() / rt_frame_end() (slot 0): its own stream, accumulators and image buffer, and launch
+// state 1 + lane of the device scene it renders from -- two frames overlap on the GPU, the second fills the CUs the first one's
+// thinning bounce chains leave idle (profiles/r05_small_launch.md: a launch ends 0.6 - 1.0 ms after its last unit is handed out).
+struct FrameLane {
+  bool        busy = false;                   // begun, not yet ended
+  bool        finished = false;               // rendered synchronously inside rt_frame_begin (a multi-device frame): nothing to wait for
+  bool        ending = false;                 // a thread is inside rt_frame_end for this lane, waiting without the mutex
+  int         rc = 0;
+  hipStream_t stream = nullptr;
+  Workspace   ws;
+  Scene const *scene = nullptr;
+  Image       image;                          // the caller's Image header (the pixels stay the caller's)
+  RT_Render_Params p;
+  Camera      camera;                         // scene->camera when the frame began
+  RT_Device_Scene *d = nullptr;               // the copy the frame renders from; nullptr once that copy was dropped (free_device_scene waits first)
+  uint64_t    fp = 0;                         // full fingerprint of that copy when the frame began
+  bool        verify = false;
+  FrameTiming timing;
+  double      t_begin = 0.0;
+};
+
+struct Device {
+  int        slot = 0, phys = 0;
+  bool       ready = false;
+  bool       peer_ok = true;                  // slots >= 1: direct copies into slot 0's memory are possible (xGMI peer access)
+  hipStream_t mstream = nullptr;              // multi-device frames: this slot's own stream (slots rehearsed on ONE GPU overlap on it)
+  int        num_cus = 0;
+  std::mutex mutex;                           // serialises frames, the scene cache and the workspace of this device
+  Workspace  ws;
+  unsigned long long *last_counters = nullptr;   // counters of the most recent path-kernel launch
+  std::unordered_map<const Scene *, RT_Device_Scene *> scene_cache;
+  std::unordered_map<RT_Device_Scene *, Camera>        cameras;
+  std::vector<DevPartition>                            parts;   // guarded by g_partition_mutex
+  FrameTiming timing;
+  FrameLane  lanes[RT_FRAME_LANES];           // slot 0 only
+};
+
+// Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
+struct DeviceGuard {
+  int  prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(const Device &D) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != D.phys) switched = hipSetDevice(D.phys) == hipSuccess;
+  }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+};
+
+// ---------------------------------------------------------------------------------
+// scene residency
+
+struct FpBlock {            // one block of a host scene's full fingerprint (scene_fingerprint_blocks)
+  const void *begin;
+  size_t      bytes;
+  uint64_t    h;
+};
+
+// What ONE launch of the path kernel writes besides the accumulators: counters, work head, the tiles' unit counters, parked hits,
+// the schedule feedback.  A device scene owns several (RT_Device_Scene::ls), allocated on first use.
+struct LaunchState {
+  unsigned long long *counters = nullptr;      // RT_N_COUNTERS
+  uint32_t           *work_head = nullptr;
+  uint32_t           *tile_next = nullptr;     // tile-stream kernel: chunks handed out per tile
+  int32_t             tile_next_n = 0;
+  uint32_t           *park = nullptr;          // tile-stream kernel: parked hits, [waves][18][128]
+  int32_t             park_waves = 0;
+  // schedule feedback: rays per 8x8 tile of the previous launch of the same frame shape -> visiting order of the next
+  uint32_t    *cost[2] = {nullptr, nullptr};   // [cur] is written by the running launch, [cur^1] is last launch's
+  uint32_t    *order = nullptr;
+  int32_t      sched_tiles = 0, sched_cur = 0;
+  bool         sched_valid = false;            // cost[cur^1] holds the costs of a launch with sched_key
+  uint64_t     sched_key = 0;
+};
+
+struct RT_Device_Scene {
+  Device      *dev = nullptr;
+  float       *nodes = nullptr;
+  float       *leaves = nullptr;
+  float       *tris = nullptr;
+  float       *mats = nullptr;
+  RT_DTexture *textures = nullptr;
+  uint32_t    *texels = nullptr;
+  int32_t      depth = 0, last_row_offset = 0, bg_texture = -1, n_nodes = 0;
+  int32_t      n_triangles = 0, n_materials = 0, n_textures = 0;
+  int64_t      bytes = 0;
+  float        max_edge = 0.0f;   // largest |component| of an edge b - a, c - a in the leaf tiles (NaN if one is NaN)
+  bool         boxes_ordered = true;      // every child box of every node has min <= max on every axis (no NaN either)
+  // what the host Scene looked like at upload: the per-frame stamp (scene_stamp) re-reads exactly this much of it
+  uint64_t     stamp = 0;
+  std::vector<const void *> mat_ptrs;     // distinct shader.data pointers, upload order
+  std::vector<int32_t>      mat_first_tri;   // a triangle that uses mat_ptrs[k]
+  // the FULL fingerprint of the host scene this copy was made from (scene_fingerprint_blocks), refreshed by rt_scene_touch:
+  // every device slot checks a frame against ITS OWN copy's value
+  std::vector<FpBlock>      fp_blocks;
+  uint64_t                  full_fp = 0;
+  // what rt_scene_touch() needs to patch the copy in place
+  std::unordered_map<uint64_t, int> mat_map;            // (shader.data, kind) -> material id
+  std::vector<const Image *>        tex_sources;        // Image of texture k (pool order; the background is one of them)
+  std::vector<RT_DTexture>          tex_descs;          // its slot in the texel pool
+  // launch state: RT_LAUNCH_STATES of them, so that launches of ONE device scene can be in flight on several streams at once
+  // ([0]: the blocking entry points and rt_render_accumulate; [1 + k]: frame lane k of rt_frame_begin / rt_frame_end)
+  LaunchState ls[RT_LAUNCH_STATES];
+  // wavefront pipeline (rt_wavefront.hip): record queues between the camera / shade / trace kernels
+  uint32_t           *wf_hit0 = nullptr, *wf_hit = nullptr, *wf_ray[2] = {nullptr, nullptr};
+  uint32_t           *wf_cnt = nullptr;        // records per chunk: hit0 | hit | ray[0] | ray[1]
+  uint32_t           *wf_ctl = nullptr;        // WF_N_CTL control words, one per 64-byte line
+  uint32_t           *wf_ctl_host = nullptr;   // pinned copy the host reads after a pass
+  int64_t             wf_soft0 = 0, wf_hard0 = 0, wf_ray_chunks = 0, wf_hit_chunks = 0;   // capacities in chunks
+  int32_t             wf_waves = 0;            // waves the capacities were sized for
+};
+
+// ---------------------------------------------------------------------------------
+// what one unit defines and another calls.  Hidden: none of it is exported from the library (the types above keep default
+// visibility, so the library's export list is what it was).
+
+#pragma GCC visibility push(hidden)
+
+// rt_host.cpp
+int    rt_fail(const char *fmt, ...);                   // sets rt_last_error(), returns -1
+Config config();
+int    ensure_device(Device &D);                        // D.mutex held (or single-threaded start-up); makes D's GPU current
+extern Device           g_devs[RT_MAX_DEVICES];
+extern int              g_primary;                      // physical device of slot 0
+extern std::atomic<u32> g_seed;
+extern std::mutex       g_multi_mutex;                  // counters of the last multi-device frame
+extern RT_Counters      g_multi_counters;
+extern bool             g_multi_counters_valid;
+extern Shader_Proc      g_tok_disney, g_tok_debug;      // what rt_scene_upload recognises as the device materials ...
+extern Background_Proc  g_tok_background;               // ... and the device background (rt_diag_set_tokens may change them)
+static inline Device &dev0() { return g_devs[0]; }
+
+// rt_residency.cpp
+void             free_device_scene(RT_Device_Scene *d);            // d->dev->mutex held, d's device current
+uint64_t         scene_fingerprint(Scene const *scene);
+bool             scene_is_static(Scene const *scene);               // takes g_static_mutex
+int              drop_stale_copies(Scene const *scene, uint64_t now, int first_slot);   // takes each slot's mutex; returns copies dropped
+void             scene_only_kparams(RT_KParams *K, RT_Device_Scene *d);
+RT_Device_Scene *cached_scene_locked(Device &D, Scene const *scene, float *stamp_ms, float *upload_ms);   // D.mutex held
+
+// rt_partition.cpp
+void remap_device_slots();                                                          // takes slot 0's mutex, then each slot's
+bool partition_args_ok(i32 width, i32 height, i32 world);
+int  device_chunk_list(Device &D, int width, int height, int rank, int world, const int32_t **d_list, int *n_local);   // D's GPU current; takes g_partition_mutex
+int  device_owner_table(Device &D, int width, int height, int world, const int32_t **d_table, int *n_chunks);      // D's GPU current; takes g_partition_mutex
+
+// rt_launch.cpp
+int check_params(RT_Render_Params const *p);
+// Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
+// ev_prep (optional): recorded between the per-launch preparation and the path kernel.
+int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
+                             hipStream_t stream, hipEvent_t ev_prep = nullptr, int launch_state = 0);
+int resolve_on(Device &D, RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image, void *d_linear,
+               hipStream_t stream);                                                 // D's GPU current
+int untile_on(Device &D, i32 width, i32 height, i32 world, void const *d_all_tiles, void *d_image, hipStream_t stream);   // D's GPU current
+int ensure_ws_buffers(Workspace &W, int width, int height, size_t tiles_bytes, size_t all_tiles_bytes, bool want_linear = true);
+int copy_image_out(Image const *image, const uint8_t *d_image, int width, int height, hipStream_t stream);
+int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]);                  // D.mutex held, D's GPU current
+
+// rt_frames.cpp
+void forget_multi_counters();                                                       // takes g_multi_mutex
+// The one-device frame sequence on `stream`: event 0, accumulator clear, path tracer (launch state `launch_state`), event 2,
+// resolve into tiles / image / linear, event 3.  D.mutex held, D's GPU current.
+int  enqueue_frame(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, Workspace &W, hipStream_t stream,
+                   int launch_state, uint8_t *tiles, uint8_t *image, float *linear);
+void frame_split(Workspace &W, FrameTiming &T);                                     // the four GPU spans between W's frame events
+
+// rt_multi.cpp
+int render_frame_multi(Scene const *scene, Image const *image, RT_Render_Params base, int world);   // slot 0's mutex held
+
+// rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
+#ifdef RT_DIAG_VARIANTS
+extern std::atomic<int> g_pipeline;                     // 0 = tile-stream path kernel, 1 = wavefront pipeline
+int  launch_wavefront(Device &D, RT_Device_Scene *d, RT_KParams &K, hipStream_t stream);   // D.mutex held, D's GPU current
+bool fault_no_peer();
+bool fault_fails(int slot);
+#else
+static inline bool fault_no_peer() { return false; }
+static inline bool fault_fails(int) { return false; }
+#endif
+
+#pragma GCC visibility pop

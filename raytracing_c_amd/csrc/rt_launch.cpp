@@ -1,0 +1,484 @@
+// rt_launch.cpp -- one launch of the path tracer, resolve and untile, workspace buffers, counters and kernel timing.
+
+#include "rt_host.h"
+
+int check_params(RT_Render_Params const *p) {
+  if (!p) return rt_fail("render params are NULL");
+  if (p->width <= 0 || p->height <= 0) return rt_fail("image size %dx%d is invalid", p->width, p->height);
+  if ((int64_t)p->width * p->height > (int64_t)1 << 28) return rt_fail("image %dx%d is too large", p->width, p->height);
+  if (p->samples <= 0) return rt_fail("samples must be positive (got %d)", p->samples);
+  if (p->max_bounces < 0) return rt_fail("max_bounces must be >= 0 (got %d)", p->max_bounces);
+  if (p->world <= 0 || p->rank < 0 || p->rank >= p->world) return rt_fail("rank %d / world %d is invalid", p->rank, p->world);
+  if (p->sample_first < 0 || p->sample_count < 0 || p->sample_first + p->sample_count > p->samples)
+    return rt_fail("sample range [%d, +%d) outside [0, %d)", p->sample_first, p->sample_count, p->samples);
+  return 0;
+}
+
+static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
+                        void *d_accum) {
+  scene_only_kparams(K, d);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) K->cam[i][j] = cam->view_matrix.rows[i][j];
+  K->focal_length = cam->focal_length;
+  {
+    volatile float fw = (float)p->width, fh = (float)p->height;      // plain IEEE fp32 divisions, as the kernel used to do
+    volatile float iw = 1.0f / fw, ih = 1.0f / fh, asp = fw / fh;
+    K->inv_width = iw;
+    K->inv_height = ih;
+    K->aspect = asp;
+  }
+  K->width = p->width;
+  K->height = p->height;
+  K->samples = p->samples;
+  K->max_bounces = p->max_bounces;
+  K->seed = p->seed;
+  K->chunks_x = (p->width + RT_CHUNK_SIZE - 1) / RT_CHUNK_SIZE;
+  K->n_chunks = rt_chunk_count(p->width, p->height);
+  K->rank = p->rank;
+  K->world = p->world;
+  {
+    int n_local = 0;
+    if (device_chunk_list(D, p->width, p->height, p->rank, p->world, &K->local_chunks, &n_local) != 0) return -1;
+    K->n_local_chunks = n_local;
+  }
+  K->sample_first = p->sample_first;
+  K->sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
+  int n_samples = K->sample_end - K->sample_first;
+  // (work items of the diagnostic kernel generations: samples per item = the largest of 32 / 16 / 8 that still leaves 24
+  // items per wave)
+  int slab = p->slab;
+  if (slab <= 0) {
+    slab = 8;
+    for (int cand = 32; cand > 8; cand >>= 1) {
+      int64_t items = (int64_t)K->n_local_chunks * 16 * ((n_samples + cand - 1) / cand);
+      if (items >= (int64_t)24 * D.num_cus * 16) { slab = cand; break; }
+    }
+  }
+  int shift = 0;
+  while ((1 << shift) < slab && (1 << shift) < n_samples) shift++;
+  K->slab_shift = shift;
+  K->n_slabs = (n_samples + (1 << shift) - 1) >> shift;
+  int64_t n_work = (int64_t)K->n_local_chunks * 16 * K->n_slabs;
+  if (n_work > 0x7fffffff) return rt_fail("too many work items (%lld)", (long long)n_work);
+  K->n_work = (int32_t)n_work;
+  K->accum = (unsigned long long *)d_accum;
+  K->counters = d->ls[0].counters;      // (render_accumulate_locked puts the launch state it was asked for)
+  K->work_head = d->ls[0].work_head;
+  return 0;
+}
+
+// Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
+// ev_prep (optional): recorded between the per-launch preparation and the path kernel.
+int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
+                             hipStream_t stream, hipEvent_t ev_prep, int launch_state) {
+  if (ensure_device(D) != 0) return -1;
+  if (check_params(p) != 0) return -1;
+  if (!d || !d_accum) return rt_fail("rt_render_accumulate: NULL scene or accumulation buffer");
+  if (d->dev != &D) return rt_fail("rt_render_accumulate: the scene was uploaded to another device");
+  RT_KParams K;
+  if (fill_kparams(D, &K, d, cam, p, d_accum) != 0) return -1;
+  if (launch_state < 0 || launch_state >= RT_LAUNCH_STATES) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
+  LaunchState &L = d->ls[launch_state];
+  if (!L.counters) HIP_TRY(hipMalloc((void **)&L.counters, RT_N_COUNTERS * sizeof(unsigned long long)));
+  if (!L.work_head) HIP_TRY(hipMalloc((void **)&L.work_head, 64));
+  K.counters = L.counters;
+  K.work_head = L.work_head;
+  D.last_counters = L.counters;
+  // 5 = the tile-stream kernel (the product's only generation); 1-4 exist in the diagnostic build
+  int variant = knob_int("RT_KERNEL", 5);
+  if (variant < 1 || variant > 5) variant = 5;
+  bool wavefront = false;
+#ifdef RT_DIAG_VARIANTS
+  wavefront = (g_pipeline.load() == 1 || knob_is("RT_PIPELINE", "wf")) && variant == 5;
+#endif
+
+  // persistent grid: 16 waves per CU (4 per SIMD at <= 128 VGPRs), never more waves than work items
+  int waves_per_cu = knob_int("RT_WAVES_PER_CU", 0);
+  const bool waves_per_cu_default = waves_per_cu <= 0;
+  if (waves_per_cu_default) waves_per_cu = 16;
+  int wg_waves = 16;                 // waves per workgroup of the tile-stream kernel: 8 / 12 / 16, chosen below
+  int n_waves = D.num_cus * waves_per_cu;
+  if (n_waves > K.n_work && K.n_work > 0) n_waves = K.n_work;
+  K.sched_thresh = knob_int("RT_SCHED_THRESH", 48);
+  if (K.sched_thresh < 1 || K.sched_thresh > 64) K.sched_thresh = 48;
+  // dynamic LDS per workgroup: per wave (perm stack: depth x 256 B, accumulator tile: 1536 B) and as many leading BVH
+  // nodes (level order) as fit in the 160 KB of a CU at 208 B each
+  const int lds_limit = 160 * 1024 - 64;      // (- the kernel's static LDS: the 32-byte sRGB scale table, rt_dev.hip.h rt_pow24_lds)
+  int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
+  int smem = 0;
+  K.n_lds_nodes = 0;
+  if (variant == 2) {
+    smem = 4 * per_wave;
+  } else if (variant != 1) {
+    // Workgroup size by the size of the launch (round 5, profiles/r05_small_launch.md section 3).  A launch ends with every wave
+    // running the bounce chains of its last paths on thinning lanes, and at four waves per SIMD those thin waves are ISSUE-bound:
+    // with two waves per SIMD a bounce of such a chain takes half the time.  A launch with little work per wave slot is mostly
+    // that tail -- config #1: 0.58 ms with 16-wave workgroups, 0.41 with 8 -- one with much work needs all four waves per SIMD
+    // for its body (the driver's default frame: 2.60 / 2.89 / 3.48 ms with 16 / 12 / 8).  One workgroup per CU either way (the
+    // tree fills the LDS).  Measured crossovers, in wave-fulls of paths per slot of the 16-wave grid: tower 640x360x16 (14) 0.91 /
+    // 0.76 / 0.69 ms, spheres 512^2 x 16 (16) 0.83 / 0.74 / 0.75, helmet 512^2 x 16 (16) 1.23 / 1.17 / 1.41, 64 and more: 16 wins.
+    int waves_per_block = 16;
+    if (variant == 5) {
+      const int64_t paths = (int64_t)K.n_local_chunks * 1024 * (int64_t)(K.sample_end - K.sample_first);
+      int64_t per_slot = paths / ((int64_t)D.num_cus * 16 * 64);
+      // (a depth-0 scene -- one leaf group, no node blocks -- traces a ray in a quarter of the instructions: its launches are as
+      //  short as launches a quarter their size; quad 256^2 / 512^2 / 768^2 / 1024^2 x 64 spp: best with 8 / 12 / 12 / 16 waves,
+      //  0.43 / 0.90 / 1.62 / 2.43 ms against 0.59 / 0.99 / 1.67 / 2.43 with 16, gpurun_out/r05s/wg.md)
+      if (K.depth == 0) per_slot /= 4;
+      waves_per_block = per_slot < 12 ? 8 : (per_slot < 40 ? 12 : 16);
+      const int v = knob_int("RT_WG_WAVES", 0);
+      if (v == 8 || v == 12 || v == 16) waves_per_block = v;
+      if (waves_per_cu_default) waves_per_cu = waves_per_block;
+      n_waves = D.num_cus * waves_per_cu;
+      if (n_waves > K.n_work && K.n_work > 0) n_waves = K.n_work;
+    }
+    wg_waves = waves_per_block;
+    int room = (lds_limit - waves_per_block * per_wave) / 208;
+    if (room < 0) room = 0;
+    K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
+    if (variant == 5 && !d->boxes_ordered) K.n_lds_nodes = 0;      // (the tile-stream kernel's LDS node blocks assume min <= max)
+    int v = knob_int("RT_LDS_NODES", K.n_lds_nodes);
+    if (v >= 0 && v < K.n_lds_nodes) K.n_lds_nodes = v;
+    smem = K.n_lds_nodes * 208 + waves_per_block * per_wave;
+  }
+
+  // ---- schedule feedback: visit expensive tiles first (costs = rays per tile of the previous launch of this view) ----
+  K.order = nullptr;
+  K.tile_cost = nullptr;
+  K.n_tiles = K.n_local_chunks * 16;
+  const uint32_t *cost_prev = nullptr;
+  if (variant != 1 && !knob_is("RT_ORDER", "identity") && K.n_tiles > 0) {
+    const int n_tiles = K.n_tiles;
+    // the costs of a launch are reusable by a launch of the same frame shape, partition and bounce limit -- NOT only of the same
+    // view: for a camera that moves between frames the previous view's costs are still a better guide than none (helmet, a rotation
+    // of 0.5 / 2 / 10 degrees per frame: -0.7 / -0.8 / -0.2 % kernel time at 256 spp, -2.3 % at 1024^2 x 64 spp against the identity
+    // order, tools/exp_moving.py, profiles/r05_experiments.md section 4), and an order is only ever a schedule, never a pixel
+    uint64_t key = 1469598103934665603ull;
+    auto mix = [&key](const void *ptr, size_t n) {
+      const unsigned char *b = (const unsigned char *)ptr;
+      for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; }
+    };
+    int32_t ids[6] = {K.width, K.height, K.rank, K.world, K.max_bounces, n_tiles};
+    mix(ids, sizeof ids);
+    if (L.sched_tiles != n_tiles) {
+      (void)hipFree(L.cost[0]); (void)hipFree(L.cost[1]); (void)hipFree(L.order);
+      L.cost[0] = L.cost[1] = L.order = nullptr;
+      L.sched_tiles = 0;
+      L.sched_valid = false;
+      HIP_TRY(hipMalloc(&L.cost[0], (size_t)n_tiles * 4));
+      HIP_TRY(hipMalloc(&L.cost[1], (size_t)n_tiles * 4));
+      HIP_TRY(hipMalloc(&L.order, (size_t)n_tiles * 4));
+      L.sched_tiles = n_tiles;
+    }
+    if (L.sched_valid && L.sched_key == key) {
+      cost_prev = L.cost[L.sched_cur ^ 1];
+      K.order = L.order;
+    }
+    K.tile_cost = L.cost[L.sched_cur];
+    L.sched_cur ^= 1;                // after this launch, cost[sched_cur ^ 1] is the buffer just written
+    L.sched_key = key;
+    L.sched_valid = true;
+  }
+
+  if (variant == 5) {
+    // unit = 2 neighbouring pixels x `slab` samples, default 64 (128 paths, pixel-major: the 64 lanes of a wave sit on one
+    // pixel, then on its neighbour); it is also the granularity at which waves share a tile at the end of a launch.
+    // Measured, helmet frame / rank 0 of 8: 32 samples 36.9 / 5.39 ms, 64 36.15 / 5.31, 128 36.6.
+    const int n_samples = K.sample_end - K.sample_first;
+    int cs = p->slab > 0 ? p->slab : 64;
+    int cshift = 0;
+    while ((1 << cshift) < cs && (1 << cshift) < n_samples) cshift++;
+    K.chunk_shift = cshift;
+    K.n_sample_blocks = (n_samples + (1 << cshift) - 1) >> cshift;
+    K.n_chunks_tile = 32 * K.n_sample_blocks;          // units: 8 rows x sample blocks x 4 pixel pairs
+    K.drain_thresh = knob_int("RT_DRAIN_THRESH", K.sched_thresh);
+    if (K.drain_thresh < 1 || K.drain_thresh > 64) K.drain_thresh = K.sched_thresh;
+    if (L.tile_next_n < K.n_tiles) {
+      (void)hipFree(L.tile_next);
+      L.tile_next = nullptr;
+      L.tile_next_n = 0;
+      // [n_tiles] chunk counters, then [ceil(n_tiles / 64)] open-tile counts of the groups
+      HIP_TRY(hipMalloc(&L.tile_next, ((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)) * 4));
+      L.tile_next_n = K.n_tiles;
+    }
+    K.tile_next = L.tile_next;
+    K.open_groups = L.tile_next + L.tile_next_n;
+    int64_t chunks = (int64_t)K.n_tiles * K.n_chunks_tile;
+    n_waves = D.num_cus * waves_per_cu;
+    if ((int64_t)n_waves > chunks) n_waves = (int)chunks;
+    // units per atomic: 1 unit of 128 paths (what a wave still holds when the launch runs dry is its tail); smaller
+    // units (few samples) are taken in pairs.  Measured with units of 128 paths: frame 1 -> 36.25 ms, 2 -> 36.4, 4 -> 37.2.
+    K.grab_max = (cshift >= 6 || (int64_t)K.n_tiles < (int64_t)2 * n_waves) ? 1 : 2;
+    {
+      int v = knob_int("RT_GRAB", 0);
+      if (v == 1 || v == 2 || v == 4) K.grab_max = v;
+    }
+    K.pyr_nodes = knob_int("RT_PYRAMID", 1) ? K.n_lds_nodes : 0;
+    // Leaf blocks with the short reciprocal (rcp_exact, rt_dev.hip.h): equal to the IEEE division while every triangle
+    // determinant |e1 . (d x e2)| <= 6 D E^2 stays below 2^102.  E = largest edge component of the scene; D = largest
+    // component of a ray direction: <= 3 max|view matrix entry| for camera rays (the direction is normalised before the
+    // matrix is applied), < 2 for the normalised directions that shading emits.  E <= 2^38 and matrix entries <= 2^16
+    // give 6 D E^2 < 2^97.  Anything else -- or a NaN -- renders with the kernel that divides.
+    float cam_max = 0.0f;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        float m = fabsf(K.cam[i][j]);
+        if (!(m <= cam_max)) cam_max = m;
+      }
+    K.short_div = (d->max_edge <= 0x1p38f && cam_max <= 0x1p16f) ? 1 : 0;
+    if (knob_int("RT_SHORT_DIV", 1) == 0) K.short_div = 0;
+    // hits parked until a dense shade block can be made of them: RT_PARK_RECORD_DWORDS = 18 fields x 128 records per wave
+    K.park = nullptr;
+    if (!wavefront && knob_int("RT_PARK", 1) != 0 && K.max_bounces < (1 << 26)) {      // (a parked record keeps the bounce count in 26 bits)
+      const int grid_waves = (n_waves + wg_waves - 1) / wg_waves * wg_waves;         // whole workgroups are launched
+      if (L.park_waves < grid_waves) {
+        (void)hipFree(L.park);
+        L.park = nullptr;
+        L.park_waves = 0;
+        const size_t slice_bytes = (size_t)RT_PARK_RECORD_DWORDS * 4;      // a wave's slice: 18 fields x 128 records (rt_device.h)
+        HIP_TRY(hipMalloc(&L.park, (size_t)grid_waves * slice_bytes));
+        L.park_waves = grid_waves;
+      }
+      K.park = L.park;
+    }
+  }
+
+  // ---- ONE preparation launch: counters, work head, tile / unit counters, this launch's cost buffer, tile order ----
+  {
+    int rc2 = rt_launch_prepare(K.n_tiles, variant == 5 ? K.tile_next : nullptr, variant == 5 ? K.open_groups : nullptr, L.counters,
+                                L.work_head, K.tile_cost, cost_prev, cost_prev ? L.order : nullptr, stream);
+    if (rc2 != 0) return rt_fail("prepare kernel launch failed: %s", hipGetErrorString((hipError_t)rc2));
+  }
+  if (ev_prep) HIP_TRY(hipEventRecord(ev_prep, stream));
+  if (K.n_work == 0) return 0;
+
+  K.wave_times = nullptr;
+  if (variant == 4 || (variant == 5 && knob_set("RT_WAVE_TIMES"))) {      // wave timeline (tools/exp_waves.py)
+    if (!D.ws.wave_times) HIP_TRY(hipMalloc(&D.ws.wave_times, (size_t)65536 * 3 * 8));
+    HIP_TRY(hipMemsetAsync(D.ws.wave_times, 0, (size_t)65536 * 3 * 8, stream));
+    K.wave_times = D.ws.wave_times;
+    if (n_waves > 65536) n_waves = 65536;          // the diagnostic buffer holds that many waves
+    D.ws.wave_times_n = n_waves;
+  }
+
+  size_t slot = D.ws.n_timed % RT_MAX_TIMED;
+  if (slot >= D.ws.ev0.size()) {
+    hipEvent_t a, b;
+    HIP_TRY(hipEventCreate(&a));
+    HIP_TRY(hipEventCreate(&b));
+    D.ws.ev0.push_back(a);
+    D.ws.ev1.push_back(b);
+  }
+  HIP_TRY(hipEventRecord(D.ws.ev0[slot], stream));
+#ifdef RT_DIAG_VARIANTS
+  if (wavefront) {
+    if (launch_wavefront(D, d, K, stream) != 0) return -1;
+  } else
+#endif
+  {
+    int rc = rt_launch_path_kernel(&K, n_waves, variant, smem, wg_waves, stream);
+    if (rc != 0) return rt_fail("path kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  HIP_TRY(hipEventRecord(D.ws.ev1[slot], stream));
+  D.ws.n_timed += 1;
+  return 0;
+}
+
+extern "C" int rt_set_camera(RT_Device_Scene *dscene, Camera const *camera) {
+  if (!dscene || !camera) return rt_fail("rt_set_camera: NULL argument");
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  D.cameras[dscene] = *camera;
+  return 0;
+}
+
+extern "C" int rt_render_accumulate(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_accum,
+                                    void *stream) {
+  if (!dscene) return rt_fail("rt_render_accumulate: NULL scene or accumulation buffer");
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  auto it = D.cameras.find(dscene);
+  if (it == D.cameras.end()) return rt_fail("rt_render_accumulate: no camera set for this scene (rt_set_camera)");
+  forget_multi_counters();             // rt_get_counters() now means THIS launch, not an older multi-device frame
+  return render_accumulate_locked(D, dscene, &it->second, params, d_accum, (hipStream_t)stream);
+}
+
+int resolve_on(Device &D, RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image, void *d_linear,
+               hipStream_t stream) {
+  if (check_params(p) != 0) return -1;
+  if (!d_accum) return rt_fail("rt_resolve: NULL accumulation buffer");
+  int chunks_x = (p->width + RT_CHUNK_SIZE - 1) / RT_CHUNK_SIZE;
+  const int32_t *d_list = nullptr;
+  int n_local = 0;
+  if (device_chunk_list(D, p->width, p->height, p->rank, p->world, &d_list, &n_local) != 0) return -1;
+  int rc = rt_launch_resolve(p->width, p->height, p->samples, chunks_x, d_list, n_local,
+                             (const unsigned long long *)d_accum, (uint8_t *)d_tiles, (uint8_t *)d_image,
+                             (float *)d_linear, stream);
+  if (rc != 0) return rt_fail("resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_resolve(RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image,
+                          void *d_linear, void *stream) {
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return resolve_on(D, p, d_accum, d_tiles, d_image, d_linear, (hipStream_t)stream);
+}
+
+int untile_on(Device &D, i32 width, i32 height, i32 world, void const *d_all_tiles, void *d_image, hipStream_t stream) {
+  if (width <= 0 || height <= 0 || world <= 0 || !d_all_tiles || !d_image) return rt_fail("rt_untile: bad arguments");
+  int chunks_x = (width + RT_CHUNK_SIZE - 1) / RT_CHUNK_SIZE;
+  const int32_t *d_table = nullptr;
+  int n_chunks = 0;
+  if (!partition_args_ok(width, height, world)) return rt_fail("rt_untile: bad arguments");
+  if (device_owner_table(D, width, height, world, &d_table, &n_chunks) != 0) return -1;
+  int rc = rt_launch_untile(width, height, chunks_x, n_chunks, d_table, (const uint8_t *)d_all_tiles,
+                            (uint8_t *)d_image, stream);
+  if (rc != 0) return rt_fail("untile kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_untile(i32 width, i32 height, i32 world, void const *d_all_tiles, void *d_image, void *stream) {
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return untile_on(D, width, height, world, d_all_tiles, d_image, (hipStream_t)stream);
+}
+
+int ensure_ws_buffers(Workspace &W, int width, int height, size_t tiles_bytes, size_t all_tiles_bytes, bool want_linear) {
+  size_t pixels = (size_t)width * height;
+  if (W.accum_elems < pixels * 3) {
+    (void)hipFree(W.accum);
+    W.accum = nullptr;
+    W.accum_elems = 0;
+    HIP_TRY(hipMalloc(&W.accum, pixels * 3 * sizeof(unsigned long long)));
+    W.accum_elems = pixels * 3;
+  }
+  if (W.image_pixels < pixels) {
+    (void)hipFree(W.image);
+    (void)hipFree(W.linear);
+    W.image = nullptr;
+    W.linear = nullptr;
+    W.image_pixels = 0;
+    HIP_TRY(hipMalloc(&W.image, pixels * 3));
+    if (want_linear) HIP_TRY(hipMalloc(&W.linear, pixels * 3 * sizeof(float)));      // (a frame lane has no fp32 output)
+    W.image_pixels = pixels;
+  }
+  if (W.tiles_bytes < tiles_bytes) {
+    (void)hipFree(W.tiles);
+    W.tiles = nullptr;
+    W.tiles_bytes = 0;
+    HIP_TRY(hipMalloc(&W.tiles, tiles_bytes));
+    W.tiles_bytes = tiles_bytes;
+  }
+  if (W.all_tiles_bytes < all_tiles_bytes) {
+    (void)hipFree(W.all_tiles);
+    W.all_tiles = nullptr;
+    W.all_tiles_bytes = 0;
+    HIP_TRY(hipMalloc(&W.all_tiles, all_tiles_bytes));
+    W.all_tiles_bytes = all_tiles_bytes;
+  }
+  for (int i = 0; i < 5; i++)
+    if (!W.ev_frame[i]) HIP_TRY(hipEventCreate(&W.ev_frame[i]));
+  return 0;
+}
+
+int copy_image_out(Image const *image, const uint8_t *d_image, int width, int height, hipStream_t stream) {
+  size_t pixels = (size_t)width * height;
+  if (!image->pixels.data) return 0;
+  if (image->components == 3 && image->stride == image->width) {
+    HIP_TRY(hipMemcpyAsync(image->pixels.data, d_image, pixels * 3, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  } else {
+    std::vector<uint8_t> tmp(pixels * 3);
+    HIP_TRY(hipMemcpy(tmp.data(), d_image, pixels * 3, hipMemcpyDeviceToHost));
+    for (isize y = 0; y < image->height; y++)
+      for (isize x = 0; x < image->width; x++)
+        for (int c = 0; c < 3; c++)
+          image->pixels.data[image->components * (x + y * image->stride) + c] = tmp[((size_t)y * width + x) * 3 + c];
+  }
+  return 0;
+}
+
+// Of the node visits of the last rt_render_accumulate launch: how many were COUNTED but not executed -- the one root visit of
+// every camera path whose tile's pixel pyramid misses every child of the root (the reference, and the oracle, spend and count
+// it; the kernel proves its outcome per tile and skips it).  bench.py's roofline carries it as a footnote.
+extern "C" int rt_get_skipped_root_visits(u64 *out) {
+  if (!out) return rt_fail("rt_get_skipped_root_visits: NULL");
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  unsigned long long c[RT_N_COUNTERS];
+  if (read_counters(D, c) != 0) return -1;
+  *out = c[7];
+  return 0;
+}
+
+int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]) {
+  HIP_TRY(hipDeviceSynchronize());
+  if (!D.last_counters) { memset(c, 0, RT_N_COUNTERS * sizeof(unsigned long long)); return 0; }
+  HIP_TRY(hipMemcpy(c, D.last_counters, RT_N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int rt_get_counters(RT_Counters *out) {
+  if (!out) return rt_fail("rt_get_counters: NULL");
+  {
+    std::lock_guard<std::mutex> lk(g_multi_mutex);
+    if (g_multi_counters_valid) { *out = g_multi_counters; return 0; }
+  }
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  unsigned long long c[RT_N_COUNTERS];
+  if (read_counters(D, c) != 0) return -1;
+  out->paths = c[0];
+  out->rays = c[1];
+  out->node_visits = c[2];
+  out->leaf_visits = c[3];
+  out->shades = c[4];
+  out->backgrounds = c[5];
+  out->textured = c[6];
+  return 0;
+}
+
+static float timed_slot_ms(Workspace &W, size_t slot) {
+  if (hipEventSynchronize(W.ev1[slot]) != hipSuccess) return -1.0f;
+  return event_ms(W.ev0[slot], W.ev1[slot]);
+}
+
+extern "C" f32 rt_last_kernel_ms(void) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (!D.ready || D.ws.n_timed == 0) return -1.0f;
+  DeviceGuard guard(D);
+  return timed_slot_ms(D.ws, (D.ws.n_timed - 1) % RT_MAX_TIMED);
+}
+
+extern "C" void rt_kernel_timing_reset(void) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  D.ws.n_timed = 0;
+}
+
+extern "C" f32 rt_kernel_timing_mean_ms(i32 *n_launches) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  size_t n = D.ws.n_timed < RT_MAX_TIMED ? D.ws.n_timed : RT_MAX_TIMED;
+  if (n_launches) *n_launches = (i32)n;
+  if (!D.ready || n == 0) return -1.0f;
+  DeviceGuard guard(D);
+  double sum = 0.0;
+  for (size_t i = 0; i < n; i++) {
+    float ms = timed_slot_ms(D.ws, i);
+    if (ms < 0.0f) return -1.0f;
+    sum += ms;
+  }
+  return (float)(sum / (double)n);
+}

@@ -17,7 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* The device layer (rt_api.cpp) keeps an HBM copy per Scene*: building into or freeing a Scene drops it.  Weak, so
+/* The device layer (rt_residency.cpp) keeps an HBM copy per Scene*: building into or freeing a Scene drops it.  Weak, so
  * that this file also links on its own (host-only tools, the sanitizer build of tests/c/). */
 extern void rt_scene_invalidate(Scene const *scene) __attribute__((weak));
 
@@ -309,7 +309,7 @@ static void *build_job_run(void *arg) {
  * caller's slice in place). */
 /* The allocation half of scene_init (scene.c:416-424): depth and node count from the triangle count, zeroed node array,
  * zeroed SoA + AoS triangle block.  false (and an empty scene, which the upload refuses) when the allocator fails.
- * Shared by scene_init, scene_init_sah and the GPU builder scene_init_gpu (rt_api.cpp). */
+ * Shared by scene_init, scene_init_sah and the GPU builder scene_init_gpu (rt_extras.cpp). */
 bool rt_scene_alloc(Scene *scene, isize n_triangles, Allocator allocator) {
   if (rt_scene_invalidate) rt_scene_invalidate(scene);      /* a device copy of what this Scene held before is stale */
   isize depth      = bvh_required_depth(n_triangles);

@@ -174,7 +174,7 @@ def test_tile_frustum_root_culling_never_changes_a_ray(oracle, name):
 @pytest.mark.parametrize("scale", [2.0 ** 36, 2.0 ** 39, 2.0 ** 45, 2.0 ** -30])
 def test_scene_scale_selects_the_division(oracle, scale):
     """Leaf blocks use the short reciprocal only while the host can bound every triangle determinant below 2^102
-    (largest edge component <= 2^38, rt_api.cpp); a scene beyond that is rendered by the kernel that divides.  Either
+    (largest edge component <= 2^38, rt_launch.cpp); a scene beyond that is rendered by the kernel that divides.  Either
     way the frame equals the oracle's: scenes of 1e11, 1e12 and 1e13.5 units across the switch, and a tiny one."""
     import raytracing_c_amd as rt
     from tests import _oracle

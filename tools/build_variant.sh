@@ -9,8 +9,9 @@ tmp=$(mktemp -d)
 srcs="rt_kernels"; [ -n "$DIAG" ] && { srcs="rt_kernels rt_kernels_diag rt_wavefront"; F="$F -DRT_DIAG_VARIANTS"; }
 objs=""
 for f in $srcs; do /opt/rocm/bin/hipcc $F "$@" -c $f.hip -o $tmp/$f.o || exit 1; objs="$objs $tmp/$f.o"; done
-/opt/rocm/bin/hipcc $F "$@" -c rt_api.cpp -o $tmp/rt_api.o || exit 1
+units="rt_host rt_residency rt_partition rt_launch rt_frames rt_multi rt_extras"; [ -n "$DIAG" ] && units="$units rt_diag"
+for f in $units; do /opt/rocm/bin/hipcc $F "$@" -c $f.cpp -o $tmp/$f.o || exit 1; objs="$objs $tmp/$f.o"; done
 make -s rt_denoise.o rt_build.o rt_scene_build.o
 mkdir -p ../../tools/exp
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/exp/librt_$name.so $objs $tmp/rt_api.o rt_denoise.o rt_build.o rt_scene_build.o -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/exp/librt_$name.so $objs rt_denoise.o rt_build.o rt_scene_build.o -lpthread
 rm -rf $tmp; ls -la ../../tools/exp/librt_$name.so

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU experiment: a camera that moves every frame.  The tile order of a launch comes from the rays per tile of the PREVIOUS launch
-(schedule feedback, rt_api.cpp); this renders N frames of the helmet, each from a camera rotated about the model by `step` degrees
+(schedule feedback, rt_launch.cpp); this renders N frames of the helmet, each from a camera rotated about the model by `step` degrees
 more than the last, and prints the path kernel's ms per frame -- with a library that keys the feedback on the exact view the order
 of a moved camera is the identity, with one that keys it on the frame's shape alone it is the previous view's.
 

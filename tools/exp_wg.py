@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Workgroup-size sweep (diagnostic library: RT_WG_WAVES = 8 / 12 / 16 overrides the library's choice): kernel ms of a list of
-launches per workgroup size.  Evidence for the selection rule of rt_api.cpp (profiles/r05_small_launch.md section 3).
+launches per workgroup size.  Evidence for the selection rule of rt_launch.cpp (profiles/r05_small_launch.md section 3).
     RT_LIB_PATH=raytracing_c_amd/librt_hip_diag.so python tools/exp_wg.py"""
 import ctypes as C
 import os
