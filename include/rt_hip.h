@@ -193,6 +193,33 @@ extern int rt_render_frame(Scene const *scene, Image const *image, isize samples
 extern int rt_frame_begin(Scene const *scene, Image const *image, isize samples, isize max_bounces);
 extern int rt_frame_end(int ticket);
 
+/* Several views of ONE scene in ONE launch of the path kernel.  A launch ends 0.6 - 1.0 ms after its last unit of work was
+ * handed out (see rt_frame_begin); K views rendered as K frames pay that K times, a batch pays it once: the tiles of all views
+ * go into one work queue.  Use it for the faces of a cube map or light probe, a stereo pair, a turntable, a camera sweep.
+ *   views[v]  : the camera of view v (view_matrix, fov, focal_length, exactly as Scene.camera) and its frame seed -- what
+ *               rt_set_seed() is to rt_render_frame()
+ *   images[v] : receives view v; every image has the same width and height (stride and pixels per image; pixels.data may be
+ *               NULL as in rt_render_frame)
+ *   linear    : optional f32[n_views][height][width][3];  accum: optional u64[n_views][height][width][3]
+ * Every view gets the same pixels, linear values and radiance sums as rt_render_frame() with scene->camera = views[v].camera
+ * and rt_set_seed(views[v].seed), bit for bit; the scene check is rt_render_frame()'s.  rt_get_counters(),
+ * rt_get_skipped_root_visits(), rt_get_frame_timing() and the kernel timing describe the whole batch afterwards.  One device
+ * only: with rt_device_count() > 1 the call fails.  Arguments are checked before the GPU is touched: n_views > 0, equal image
+ * sizes, >= 3 components and stride >= width per image, n_views x width x height <= 2^28 pixels and n_views x 16 tiles per
+ * 32x32 chunk < 2^31.  0 on success, -1 + rt_last_error(). */
+typedef struct {
+  Camera camera;
+  u32    seed;
+} RT_View;
+extern int rt_render_views(Scene const *scene, i32 n_views, RT_View const *views, Image const *images, isize samples,
+                           isize max_bounces, f32 *linear, u64 *accum);
+/* The device-level form, like rt_render_accumulate(): d_accum = u64[n_views][height][width][3] on the device, zero for this
+ * rank's chunks on entry; params->seed is ignored (every view has its own); rank / world and sample_first / sample_count are
+ * honoured, so a batch can be filled progressively and view v resolved with rt_resolve(params, d_accum + v * height * width * 3,
+ * ...).  Only enqueues work on `stream`, on the device the scene was uploaded to. */
+extern int rt_render_accumulate_views(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_views,
+                                      RT_View const *views, void *d_accum, void *stream);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

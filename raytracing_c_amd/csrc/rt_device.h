@@ -68,6 +68,15 @@ typedef struct {
 } RT_DTexture;
 #define RT_TEX_TILE_INDEX(x, y, tpr) ((((y) >> 2) * (tpr) + ((x) >> 2)) * 16 + (((y) & 3) << 2) + ((x) & 3))
 
+/* One view of a multi-view launch: what RT_KParams.cam / focal_length / seed are to a one-view launch.  64 bytes, so that a
+ * view's record is one aligned block of scalar loads. */
+typedef struct RT_KView {
+  float    cam[3][4];          /* rows 0..2 of view_matrix */
+  float    focal_length;
+  uint32_t seed;
+  uint32_t pad[2];
+} RT_KView;
+
 typedef struct {
   /* scene */
   const float    *nodes;
@@ -126,6 +135,12 @@ typedef struct {
   int32_t wf_soft_chunks;      /* camera kernel: a wave that is handed chunk >= this of wf_hit0 stops taking units      */
   int32_t wf_bounce;           /* shade / trace kernels: bounce index of the records they read                          */
   int32_t wf_n_waves;          /* waves of this launch (the last one to finish resets the control words it consumed)    */
+  /* multi-view launches (rt_render_views): K views of one scene share one tile list -- tile t renders view t / tiles_per_view.
+   * Appended, so that every field above keeps its kernarg offset (the one-view instances do not read these). */
+  const RT_KView *views;       /* [n_views] camera and seed of every view, on the device (NULL: a one-view launch)          */
+  int32_t n_views;             /* views of this launch; 0 = one view, the camera / seed above                                */
+  int32_t tiles_per_view;      /* n_local_chunks * 16                                                                         */
+  int32_t pixels_per_view;     /* width * height: view v accumulates into accum + v * pixels_per_view * 3                    */
 } RT_KParams;
 
 #define WF_CHUNK        256

@@ -23,12 +23,17 @@ static int frame_params(Image const *image, isize samples, isize max_bounces, u3
 }
 
 int enqueue_frame(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, Workspace &W, hipStream_t stream,
-                  int launch_state, uint8_t *tiles, uint8_t *image, float *linear) {
+                  int launch_state, uint8_t *tiles, uint8_t *image, float *linear, ViewBatch const *batch) {
+  const int nv = batch ? batch->n : 1;
+  const size_t view3 = (size_t)p->width * p->height * 3;      // elements of one view's accumulator / image / linear values
   HIP_TRY(hipEventRecord(W.ev_frame[0], stream));
-  HIP_TRY(hipMemsetAsync(W.accum, 0, (size_t)p->width * p->height * 3 * sizeof(unsigned long long), stream));
-  if (render_accumulate_locked(D, d, cam, p, W.accum, stream, W.ev_frame[1], launch_state) != 0) return -1;
+  HIP_TRY(hipMemsetAsync(W.accum, 0, view3 * nv * sizeof(unsigned long long), stream));
+  if (render_accumulate_locked(D, d, cam, p, W.accum, stream, W.ev_frame[1], launch_state, batch) != 0) return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[2], stream));
-  if (resolve_on(D, p, W.accum, tiles, image, linear, stream) != 0) return -1;
+  for (int v = 0; v < nv; v++)
+    if (resolve_on(D, p, W.accum + v * view3, tiles, image ? image + v * view3 : nullptr, linear ? linear + v * view3 : nullptr,
+                   stream) != 0)
+      return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[3], stream));
   return 0;
 }
@@ -40,8 +45,10 @@ void frame_split(Workspace &W, FrameTiming &T) {
   T.gpu_copy_ms = event_ms(W.ev_frame[3], W.ev_frame[4]);
 }
 
+// batch (rt_render_views): `image` points to batch->n images of one size, linear / accum hold batch->n views one after the other.
 static int render_frame_locked(Scene const *scene, Image const *image, isize samples, isize max_bounces,
-                               f32 *linear, u64 *accum, Camera const *camera = nullptr, u32 const *seed = nullptr) {
+                               f32 *linear, u64 *accum, Camera const *camera = nullptr, u32 const *seed = nullptr,
+                               ViewBatch const *batch = nullptr) {
   Device &D = dev0();
   const double t_start = now_ms();
   if (ensure_device(D) != 0) return -1;
@@ -51,11 +58,14 @@ static int render_frame_locked(Scene const *scene, Image const *image, isize sam
   if (frame_params(image, samples, max_bounces, seed ? *seed : g_seed.load(), "render", &p) != 0) return -1;
   forget_multi_counters();
   const int world = rt_device_count();
+  if (batch && world > 1)
+    return rt_fail("rt_render_views: a batch of views renders on one device, and %d are set (rt_set_devices)", world);
   if (world > 1 && !linear && !accum && rt_chunk_count(p.width, p.height) >= world)
     return render_frame_multi(scene, image, p, world);
 
   FrameTiming T;
-  if (ensure_ws_buffers(D.ws, p.width, p.height, 0, 0) != 0) return -1;
+  const int nv = batch ? batch->n : 1;
+  if (ensure_ws_buffers(D.ws, p.width, p.height * nv, 0, 0) != 0) return -1;      // (a batch: nv images one after the other)
   Workspace &W = D.ws;
   size_t pixels = (size_t)p.width * p.height;
   hipStream_t stream = nullptr;
@@ -67,7 +77,8 @@ static int render_frame_locked(Scene const *scene, Image const *image, isize sam
     T.stamp_ms += stamp_ms;
     T.upload_ms += upload_ms;
     const double t_enq = now_ms();
-    if (enqueue_frame(D, d, camera ? camera : &scene->camera, &p, W, stream, 0, nullptr, W.image, linear ? W.linear : nullptr) != 0)
+    if (enqueue_frame(D, d, camera ? camera : &scene->camera, &p, W, stream, batch ? RT_VIEWS_STATE : 0, nullptr, W.image,
+                      linear ? W.linear : nullptr, batch) != 0)
       return -1;
     T.enqueue_ms = (float)(now_ms() - t_enq);
     // the full content check of the host scene, on this thread, while the GPU renders (see rt_scene_touch): a frame of an
@@ -82,10 +93,11 @@ static int render_frame_locked(Scene const *scene, Image const *image, isize sam
     D.scene_cache.erase(scene);
   }
 
-  if (copy_image_out(image, W.image, p.width, p.height, stream) != 0) return -1;
+  for (int v = 0; v < nv; v++)
+    if (copy_image_out(&image[v], W.image + v * pixels * 3, p.width, p.height, stream) != 0) return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
-  if (linear) HIP_TRY(hipMemcpy(linear, W.linear, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (accum) HIP_TRY(hipMemcpy(accum, W.accum, pixels * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (linear) HIP_TRY(hipMemcpy(linear, W.linear, nv * pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (accum) HIP_TRY(hipMemcpy(accum, W.accum, nv * pixels * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
   frame_split(W, T);
@@ -99,6 +111,34 @@ extern "C" int rt_render_frame(Scene const *scene, Image const *image, isize sam
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
   return render_frame_locked(scene, image, samples, max_bounces, linear, accum);
+}
+
+// K views of one scene in one launch: the frame sequence above with a view table (rt_hip.h).  Every argument is checked before the
+// device is touched.
+extern "C" int rt_render_views(Scene const *scene, i32 n_views, RT_View const *views, Image const *images, isize samples,
+                               isize max_bounces, f32 *linear, u64 *accum) {
+  const char *who = "rt_render_views";
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  if (!views) return rt_fail("%s: views is NULL", who);
+  if (!images) return rt_fail("%s: images is NULL", who);
+  if (n_views <= 0) return rt_fail("%s: n_views must be positive (got %d)", who, n_views);
+  RT_Render_Params p;
+  if (frame_params(&images[0], samples, max_bounces, 0, who, &p) != 0) return -1;
+  if (check_views(n_views, views, p.width, p.height, who) != 0) return -1;      // (before images[1 ..] are read)
+  for (i32 v = 1; v < n_views; v++) {
+    Image const &im = images[v];
+    if (im.width != images[0].width || im.height != images[0].height)
+      return rt_fail("%s: image %d is %ldx%ld, image 0 is %ldx%ld: every view must have the same size", who, v, (long)im.width,
+                     (long)im.height, (long)images[0].width, (long)images[0].height);
+    if (im.pixels.data && im.components < 3) return rt_fail("%s: image %d needs >= 3 components", who, v);
+    if (im.pixels.data && im.stride < im.width) return rt_fail("%s: image %d stride < width", who, v);
+  }
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  ViewBatch batch;
+  batch.n = n_views;
+  batch.views = views;
+  return render_frame_locked(scene, images, samples, max_bounces, linear, accum, &views[0].camera, &views[0].seed, &batch);
 }
 
 extern "C" int render(Scene *scene, Image *image, isize samples, isize max_bounces) {

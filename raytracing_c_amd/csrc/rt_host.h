@@ -137,6 +137,13 @@ struct FrameTiming {          // the most recent frame through render_thread_pro
 #define RT_FRAME_LANES   2                       // frames in flight behind rt_frame_begin / rt_frame_end
 #endif
 #define RT_LAUNCH_STATES (1 + RT_FRAME_LANES)
+#define RT_VIEWS_STATE   RT_LAUNCH_STATES        // the launch state of view batches (rt_render_views, rt_render_accumulate_views)
+
+// K views of one frame (rt_render_views): one launch, the tiles of every view in one work queue.
+struct ViewBatch {
+  int            n = 0;
+  RT_View const *views = nullptr;
+};
 
 struct Workspace {
   unsigned long long *accum = nullptr;
@@ -237,6 +244,11 @@ struct LaunchState {
   int32_t      sched_tiles = 0, sched_cur = 0;
   bool         sched_valid = false;            // cost[cur^1] holds the costs of a launch with sched_key
   uint64_t     sched_key = 0;
+  // view batches: the device view table of the launch, filled from a pinned copy on the launch's stream
+  RT_KView    *views = nullptr;
+  RT_KView    *views_host = nullptr;
+  int32_t      views_cap = 0;
+  hipEvent_t   views_copied = nullptr;         // recorded after the table's copy: views_host may be rewritten once it completed
 };
 
 struct RT_Device_Scene {
@@ -264,9 +276,11 @@ struct RT_Device_Scene {
   std::unordered_map<uint64_t, int> mat_map;            // (shader.data, kind) -> material id
   std::vector<const Image *>        tex_sources;        // Image of texture k (pool order; the background is one of them)
   std::vector<RT_DTexture>          tex_descs;          // its slot in the texel pool
-  // launch state: RT_LAUNCH_STATES of them, so that launches of ONE device scene can be in flight on several streams at once
-  // ([0]: the blocking entry points and rt_render_accumulate; [1 + k]: frame lane k of rt_frame_begin / rt_frame_end)
-  LaunchState ls[RT_LAUNCH_STATES];
+  // launch state: RT_LAUNCH_STATES + 1 of them, so that launches of ONE device scene can be in flight on several streams at once
+  // ([0]: the blocking entry points and rt_render_accumulate; [1 + k]: frame lane k of rt_frame_begin / rt_frame_end;
+  // [RT_VIEWS_STATE]: view batches -- their tile list is K times as long, and a state of their own keeps the schedule feedback
+  // of single frames and of batches from replacing each other)
+  LaunchState ls[RT_LAUNCH_STATES + 1];
   // wavefront pipeline (rt_wavefront.hip): record queues between the camera / shade / trace kernels
   uint32_t           *wf_hit0 = nullptr, *wf_hit = nullptr, *wf_ray[2] = {nullptr, nullptr};
   uint32_t           *wf_cnt = nullptr;        // records per chunk: hit0 | hit | ray[0] | ray[1]
@@ -312,10 +326,13 @@ int  device_owner_table(Device &D, int width, int height, int world, const int32
 
 // rt_launch.cpp
 int check_params(RT_Render_Params const *p);
+int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who);   // the batch's sizes; no device needed
 // Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
-// ev_prep (optional): recorded between the per-launch preparation and the path kernel.
+// ev_prep (optional): recorded between the per-launch preparation and the path kernel.  batch (optional): K views in one launch
+// (cam and p->seed are ignored; d_accum holds K images).
 int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
-                             hipStream_t stream, hipEvent_t ev_prep = nullptr, int launch_state = 0);
+                             hipStream_t stream, hipEvent_t ev_prep = nullptr, int launch_state = 0,
+                             ViewBatch const *batch = nullptr);
 int resolve_on(Device &D, RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image, void *d_linear,
                hipStream_t stream);                                                 // D's GPU current
 int untile_on(Device &D, i32 width, i32 height, i32 world, void const *d_all_tiles, void *d_image, hipStream_t stream);   // D's GPU current
@@ -326,9 +343,10 @@ int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]);              
 // rt_frames.cpp
 void forget_multi_counters();                                                       // takes g_multi_mutex
 // The one-device frame sequence on `stream`: event 0, accumulator clear, path tracer (launch state `launch_state`), event 2,
-// resolve into tiles / image / linear, event 3.  D.mutex held, D's GPU current.
+// resolve into tiles / image / linear, event 3.  D.mutex held, D's GPU current.  batch (optional): K views, W.accum / image /
+// linear hold K images one after the other, one resolve per view (tiles must be NULL).
 int  enqueue_frame(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, Workspace &W, hipStream_t stream,
-                   int launch_state, uint8_t *tiles, uint8_t *image, float *linear);
+                   int launch_state, uint8_t *tiles, uint8_t *image, float *linear, ViewBatch const *batch = nullptr);
 void frame_split(Workspace &W, FrameTiming &T);                                     // the four GPU spans between W's frame events
 
 // rt_multi.cpp

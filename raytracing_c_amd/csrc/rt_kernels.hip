@@ -65,7 +65,14 @@ __global__ void rt_ledger_reduce_kernel(unsigned long long *counters) {
 }
 #endif
 
-template <int WAVES, bool LDSN, int MIN_WAVES_PER_SIMD, bool SHORT_DIV>
+// Multi-view launches (VIEWS, rt_render_views): the tile list is n_views x n_local_chunks x 16 tiles long, tile t renders view
+// t / tiles_per_view.  A wave keeps only the pointer to its tile's view record (scalar, constant address space) and reads the
+// camera and seed from it where the one-view kernel reads them from the kernel arguments.
+typedef const RT_KView __attribute__((address_space(4))) *RT_KViewP;
+template <bool VIEWS> struct CamSrc { typedef RT_KArgs type; };       // where camera and seed come from
+template <> struct CamSrc<true> { typedef RT_KViewP type; };
+
+template <int WAVES, bool LDSN, int MIN_WAVES_PER_SIMD, bool SHORT_DIV, bool VIEWS>
 __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel_stream(RT_KParams P) {
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
@@ -195,9 +202,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     }
 
     int tile_x0, tile_y0;
+    RT_KViewP vrec = nullptr;             // VIEWS: the record of this tile's view
     {
       RT_KArgs A = cold_args();
-      const int lchunk = tile_idx >> 4, sub = tile_idx & 15;
+      int vt = tile_idx;                  // the tile within its view
+      if constexpr (VIEWS) {
+        const int tu = __builtin_amdgcn_readfirstlane(tile_idx);
+        const uint32_t view = (uint32_t)tu / (uint32_t)A->tiles_per_view;
+        vt = tu - (int)view * A->tiles_per_view;
+        vrec = (RT_KViewP)A->views + view;
+      }
+      const int lchunk = vt >> 4, sub = vt & 15;
       const int chunk = A->local_chunks[lchunk];
       const int chunks_x = A->chunks_x;
       tile_x0 = (chunk % chunks_x) * 32 + (sub & 3) * 8;
@@ -221,21 +236,23 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     bool tile_root_miss = false;
     if (leaf_level >= 0) {
       RT_KArgs A = cold_args();
+      typename CamSrc<VIEWS>::type S;
+      if constexpr (VIEWS) S = vrec; else S = A;
       const float m = 0.05f;                                   // footprint margin in pixels
       const float ux0 = ((float)tile_x0 - 0.5f - m) * 2.0f * A->inv_width - 1.0f;
       const float ux1 = ((float)tile_x0 + 7.5f + m) * 2.0f * A->inv_width - 1.0f;
       const float uy0 = ((float)tile_y0 - 0.5f - m) * 2.0f * A->inv_height - 1.0f;
       const float uy1 = ((float)tile_y0 + 7.5f + m) * 2.0f * A->inv_height - 1.0f;
-      const float asp = A->aspect, fl = A->focal_length;
+      const float asp = A->aspect, fl = S->focal_length;
       rt_v3 c[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         float cx = ((q == 1 || q == 2) ? ux1 : ux0) * asp, cy = -((q >= 2) ? uy1 : uy0), cz = -fl;
-        c[q] = rt_v3_make(A->cam[0][0] * cx + A->cam[0][1] * cy + A->cam[0][2] * cz,
-                          A->cam[1][0] * cx + A->cam[1][1] * cy + A->cam[1][2] * cz,
-                          A->cam[2][0] * cx + A->cam[2][1] * cy + A->cam[2][2] * cz);
+        c[q] = rt_v3_make(S->cam[0][0] * cx + S->cam[0][1] * cy + S->cam[0][2] * cz,
+                          S->cam[1][0] * cx + S->cam[1][1] * cy + S->cam[1][2] * cz,
+                          S->cam[2][0] * cx + S->cam[2][1] * cy + S->cam[2][2] * cz);
       }
-      const rt_v3 o = rt_v3_make(A->cam[0][3], A->cam[1][3], A->cam[2][3]);
+      const rt_v3 o = rt_v3_make(S->cam[0][3], S->cam[1][3], S->cam[2][3]);
       rt_v3 pn[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -309,14 +326,16 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     // NaN-free (such a ray does not take the shortcut: its root visit must be computed, see tile_root_miss).
     if (tile_root_miss && cold_args()->max_bounces > 0) {
       RT_KArgs A = cold_args();
+      typename CamSrc<VIEWS>::type S;
+      if constexpr (VIEWS) S = vrec; else S = A;
       const int width = A->width, height = A->height, sample_first = A->sample_first, sample_end = A->sample_end;
       const uint32_t n_sb = (uint32_t)A->n_sample_blocks, gmax = (uint32_t)A->grab_max;
       PrimaryParams PP;
 #pragma unroll
       for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 4; j++) PP.cam[i][j] = A->cam[i][j];
-      PP.focal_length = A->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+        for (int j = 0; j < 4; j++) PP.cam[i][j] = S->cam[i][j];
+      PP.focal_length = S->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
       ShadeParamsLds SP;
       SP.tris = nullptr; SP.mats = nullptr; SP.textures = A->textures; SP.texels = A->texels;
       SP.bg_texture = A->bg_texture; SP.max_bounces = A->max_bounces;
@@ -609,15 +628,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 #endif
           LGM("prim_begin");
           if (got) {
+            typename CamSrc<VIEWS>::type S;
+            if constexpr (VIEWS) S = vrec; else S = A;
             pix = gp;
             bounce = 0;
-            rng = rt_path_seed(A->seed, (uint32_t)(gx + gy * width), (uint32_t)gs);
+            rng = rt_path_seed(S->seed, (uint32_t)(gx + gy * width), (uint32_t)gs);
             PrimaryParams PP;
 #pragma unroll
             for (int i = 0; i < 3; i++)
 #pragma unroll
-              for (int j = 0; j < 4; j++) PP.cam[i][j] = A->cam[i][j];
-            PP.focal_length = A->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+              for (int j = 0; j < 4; j++) PP.cam[i][j] = S->cam[i][j];
+            PP.focal_length = S->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
             primary_ray(PP, gx, gy, gs, org, dir);
             tint = rt_v3_make(1, 1, 1);
             emis = rt_v3_make(0, 0, 0);
@@ -687,7 +708,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       RT_KArgs A = cold_args();
       const int width = A->width;
       if (x < width && y < A->height && (r | g | b) != 0ull) {
-        unsigned long long *dst = A->accum + ((size_t)y * width + x) * 3;
+        unsigned long long *base = A->accum;
+        if constexpr (VIEWS) base += (size_t)(vrec - (RT_KViewP)A->views) * (size_t)A->pixels_per_view * 3;   // this tile's view
+        unsigned long long *dst = base + ((size_t)y * width + x) * 3;
         atomicAdd(dst + 0, r);
         atomicAdd(dst + 1, g);
         atomicAdd(dst + 2, b);
@@ -1242,7 +1265,7 @@ extern "C" int rt_launch_test_trace_stream(const RT_KParams *P, int n, const flo
 // ---------------------------------------------------------------------------------
 // launchers (called from rt_api.cpp)
 
-template <int WAVES, bool LDSN, int MINW, bool SHORT_DIV>
+template <int WAVES, bool LDSN, int MINW, bool SHORT_DIV, bool VIEWS>
 static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipStream_t stream) {
   // (the attribute belongs to the kernel ON ONE DEVICE: a frame spread over N GPUs launches from N devices)
   static unsigned attr_devices = 0;
@@ -1250,7 +1273,7 @@ static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipSt
   (void)hipGetDevice(&dev);
   if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(&attr_devices, __ATOMIC_RELAXED) & (1u << dev)))) {
     // (dynamic + the kernel's 32 static bytes, rt_pow24_lds, must stay within the 160 KB of a CU)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
     if (e != hipSuccess) return (int)e;
     if (dev < 32) __atomic_fetch_or(&attr_devices, 1u << dev, __ATOMIC_RELAXED);
@@ -1264,7 +1287,7 @@ static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipSt
     if (e != hipSuccess) return (int)e;
   }
 #endif
-  hipLaunchKernelGGL((rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV>), dim3((n_waves + WAVES - 1) / WAVES),
+  hipLaunchKernelGGL((rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>), dim3((n_waves + WAVES - 1) / WAVES),
                      dim3(WAVES * 64), smem_bytes, stream, *P);
 #ifdef RT_LEDGER
   hipLaunchKernelGGL(rt_ledger_reduce_kernel, dim3(1), dim3(RT_LEDGER_ROW), 0, stream, P->counters);
@@ -1281,6 +1304,18 @@ extern "C" int rt_launch_path_kernel_diag(const RT_KParams *P, int n_waves, int 
 #endif
 extern "C" int rt_math_contract(void) { return RT_MATH_CONTRACT; }      // include/rt_math.h: 2 = explicit FMA, 1 = -DRT_MATH_NO_FMA
 
+template <bool VIEWS>
+static int launch_stream_wg(const RT_KParams *P, int n_waves, int smem_bytes, int wg_waves, hipStream_t stream) {
+  if (wg_waves == 8)
+    return P->short_div ? launch_stream<8, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<8, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
+  if (wg_waves == 12)
+    return P->short_div ? launch_stream<12, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<12, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
+  return P->short_div ? launch_stream<16, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                      : launch_stream<16, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
+}
+
 // variant 5 = the tile-stream kernel, the only path kernel of the product library; 1-4 exist in the diagnostic build only
 // `wg_waves` = waves per workgroup, 8 / 12 / 16 (one workgroup per CU: 2 / 3 / 4 waves per SIMD), chosen by rt_api.cpp from the size
 // of the launch; the same kernel source, three instances of its launch geometry.
@@ -1289,14 +1324,8 @@ extern "C" int rt_launch_path_kernel(const RT_KParams *P, int n_waves, int varia
   if (variant >= 1 && variant <= 4) return rt_launch_path_kernel_diag(P, n_waves, variant, smem_bytes, stream);
 #endif
   (void)variant;
-  if (wg_waves == 8)
-    return P->short_div ? launch_stream<8, true, RT_STREAM_MINW, true>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<8, true, RT_STREAM_MINW, false>(P, n_waves, smem_bytes, stream);
-  if (wg_waves == 12)
-    return P->short_div ? launch_stream<12, true, RT_STREAM_MINW, true>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<12, true, RT_STREAM_MINW, false>(P, n_waves, smem_bytes, stream);
-  return P->short_div ? launch_stream<16, true, RT_STREAM_MINW, true>(P, n_waves, smem_bytes, stream)
-                      : launch_stream<16, true, RT_STREAM_MINW, false>(P, n_waves, smem_bytes, stream);
+  if (P->n_views > 0) return launch_stream_wg<true>(P, n_waves, smem_bytes, wg_waves, stream);      // one launch, K views
+  return launch_stream_wg<false>(P, n_waves, smem_bytes, wg_waves, stream);
 }
 
 extern "C" int rt_launch_resolve(int width, int height, int samples, int chunks_x, const int32_t *local_chunks,

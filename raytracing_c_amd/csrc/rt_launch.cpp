@@ -14,8 +14,22 @@ int check_params(RT_Render_Params const *p) {
   return 0;
 }
 
+int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who) {
+  if (n_views <= 0) return rt_fail("%s: n_views must be positive (got %d)", who, n_views);
+  if (!views) return rt_fail("%s: views is NULL", who);
+  if (width <= 0 || height <= 0) return rt_fail("%s: image size %dx%d is invalid", who, width, height);
+  // (the kernel's pixel and tile indices are 32-bit: the bound check_params puts on one frame, over the whole batch)
+  if ((int64_t)n_views * width * height > (int64_t)1 << 28)
+    return rt_fail("%s: %d views of %dx%d are too many pixels (more than 2^28)", who, n_views, width, height);
+  if ((int64_t)n_views * rt_chunk_count(width, height) * 16 > (int64_t)0x7fffffff)
+    return rt_fail("%s: %d views of %dx%d are too many tiles (2^31 or more)", who, n_views, width, height);
+  return 0;
+}
+
 static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
-                        void *d_accum) {
+                        void *d_accum, ViewBatch const *batch) {
+  const int nv = batch ? batch->n : 1;
+  if (batch) cam = &batch->views[0].camera;      // (the kernel reads every view's camera from the view table)
   scene_only_kparams(K, d);
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 4; j++) K->cam[i][j] = cam->view_matrix.rows[i][j];
@@ -58,26 +72,33 @@ static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera con
   while ((1 << shift) < slab && (1 << shift) < n_samples) shift++;
   K->slab_shift = shift;
   K->n_slabs = (n_samples + (1 << shift) - 1) >> shift;
-  int64_t n_work = (int64_t)K->n_local_chunks * 16 * K->n_slabs;
+  int64_t n_work = (int64_t)K->n_local_chunks * 16 * K->n_slabs * nv;
   if (n_work > 0x7fffffff) return rt_fail("too many work items (%lld)", (long long)n_work);
   K->n_work = (int32_t)n_work;
   K->accum = (unsigned long long *)d_accum;
   K->counters = d->ls[0].counters;      // (render_accumulate_locked puts the launch state it was asked for)
   K->work_head = d->ls[0].work_head;
+  if (batch) {
+    K->n_views = nv;
+    K->tiles_per_view = K->n_local_chunks * 16;
+    K->pixels_per_view = p->width * p->height;
+  }
   return 0;
 }
 
 // Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
 // ev_prep (optional): recorded between the per-launch preparation and the path kernel.
 int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
-                             hipStream_t stream, hipEvent_t ev_prep, int launch_state) {
+                             hipStream_t stream, hipEvent_t ev_prep, int launch_state, ViewBatch const *batch) {
   if (ensure_device(D) != 0) return -1;
   if (check_params(p) != 0) return -1;
   if (!d || !d_accum) return rt_fail("rt_render_accumulate: NULL scene or accumulation buffer");
   if (d->dev != &D) return rt_fail("rt_render_accumulate: the scene was uploaded to another device");
+  if (batch && check_views(batch->n, batch->views, p->width, p->height, "view batch") != 0) return -1;
+  const int nv = batch ? batch->n : 1;
   RT_KParams K;
-  if (fill_kparams(D, &K, d, cam, p, d_accum) != 0) return -1;
-  if (launch_state < 0 || launch_state >= RT_LAUNCH_STATES) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
+  if (fill_kparams(D, &K, d, cam, p, d_accum, batch) != 0) return -1;
+  if (launch_state < 0 || launch_state > RT_VIEWS_STATE) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
   LaunchState &L = d->ls[launch_state];
   if (!L.counters) HIP_TRY(hipMalloc((void **)&L.counters, RT_N_COUNTERS * sizeof(unsigned long long)));
   if (!L.work_head) HIP_TRY(hipMalloc((void **)&L.work_head, 64));
@@ -91,6 +112,9 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
 #ifdef RT_DIAG_VARIANTS
   wavefront = (g_pipeline.load() == 1 || knob_is("RT_PIPELINE", "wf")) && variant == 5;
 #endif
+  if (batch && (variant != 5 || wavefront))
+    return rt_fail("view batch: a batch of views needs the tile-stream path kernel (%s is set)",
+                   wavefront ? "the wavefront pipeline" : "another kernel generation, RT_KERNEL");
 
   // persistent grid: 16 waves per CU (4 per SIMD at <= 128 VGPRs), never more waves than work items
   int waves_per_cu = knob_int("RT_WAVES_PER_CU", 0);
@@ -119,7 +143,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
     // 0.76 / 0.69 ms, spheres 512^2 x 16 (16) 0.83 / 0.74 / 0.75, helmet 512^2 x 16 (16) 1.23 / 1.17 / 1.41, 64 and more: 16 wins.
     int waves_per_block = 16;
     if (variant == 5) {
-      const int64_t paths = (int64_t)K.n_local_chunks * 1024 * (int64_t)(K.sample_end - K.sample_first);
+      const int64_t paths = (int64_t)K.n_local_chunks * 1024 * (int64_t)(K.sample_end - K.sample_first) * nv;
       int64_t per_slot = paths / ((int64_t)D.num_cus * 16 * 64);
       // (a depth-0 scene -- one leaf group, no node blocks -- traces a ray in a quarter of the instructions: its launches are as
       //  short as launches a quarter their size; quad 256^2 / 512^2 / 768^2 / 1024^2 x 64 spp: best with 8 / 12 / 12 / 16 waves,
@@ -145,7 +169,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   // ---- schedule feedback: visit expensive tiles first (costs = rays per tile of the previous launch of this view) ----
   K.order = nullptr;
   K.tile_cost = nullptr;
-  K.n_tiles = K.n_local_chunks * 16;
+  K.n_tiles = K.n_local_chunks * 16 * nv;      // (a batch: the tiles of view v are [v * tiles_per_view, (v + 1) * tiles_per_view))
   const uint32_t *cost_prev = nullptr;
   if (variant != 1 && !knob_is("RT_ORDER", "identity") && K.n_tiles > 0) {
     const int n_tiles = K.n_tiles;
@@ -220,11 +244,12 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
     // matrix is applied), < 2 for the normalised directions that shading emits.  E <= 2^38 and matrix entries <= 2^16
     // give 6 D E^2 < 2^97.  Anything else -- or a NaN -- renders with the kernel that divides.
     float cam_max = 0.0f;
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        float m = fabsf(K.cam[i][j]);
-        if (!(m <= cam_max)) cam_max = m;
-      }
+    for (int v = 0; v < nv; v++)                 // (a batch: over the cameras of all views)
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+          float m = fabsf(batch ? batch->views[v].camera.view_matrix.rows[i][j] : K.cam[i][j]);
+          if (!(m <= cam_max)) cam_max = m;
+        }
     K.short_div = (d->max_edge <= 0x1p38f && cam_max <= 0x1p16f) ? 1 : 0;
     if (knob_int("RT_SHORT_DIV", 1) == 0) K.short_div = 0;
     // hits parked until a dense shade block can be made of them: RT_PARK_RECORD_DWORDS = 18 fields x 128 records per wave
@@ -241,6 +266,34 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
       }
       K.park = L.park;
     }
+  }
+
+  // ---- a batch: the view table, on the launch's stream.  The pinned copy is rewritten only once the previous table's copy is done
+  // (which waits for the launches queued before it on that stream, at most one launch ahead of this one) ----
+  K.views = nullptr;
+  if (batch) {
+    if (L.views_cap < nv) {
+      (void)hipFree(L.views);
+      if (L.views_host) (void)hipHostFree(L.views_host);
+      L.views = L.views_host = nullptr;
+      L.views_cap = 0;
+      HIP_TRY(hipMalloc(&L.views, (size_t)nv * sizeof(RT_KView)));
+      HIP_TRY(hipHostMalloc(&L.views_host, (size_t)nv * sizeof(RT_KView), hipHostMallocDefault));
+      L.views_cap = nv;
+    }
+    if (!L.views_copied) HIP_TRY(hipEventCreateWithFlags(&L.views_copied, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(L.views_copied));
+    for (int v = 0; v < nv; v++) {
+      RT_KView &r = L.views_host[v];
+      memset(&r, 0, sizeof r);
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 4; j++) r.cam[i][j] = batch->views[v].camera.view_matrix.rows[i][j];
+      r.focal_length = batch->views[v].camera.focal_length;
+      r.seed = batch->views[v].seed;
+    }
+    HIP_TRY(hipMemcpyAsync(L.views, L.views_host, (size_t)nv * sizeof(RT_KView), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(L.views_copied, stream));
+    K.views = L.views;
   }
 
   // ---- ONE preparation launch: counters, work head, tile / unit counters, this launch's cost buffer, tile order ----
@@ -302,6 +355,22 @@ extern "C" int rt_render_accumulate(RT_Device_Scene *dscene, RT_Render_Params co
   if (it == D.cameras.end()) return rt_fail("rt_render_accumulate: no camera set for this scene (rt_set_camera)");
   forget_multi_counters();             // rt_get_counters() now means THIS launch, not an older multi-device frame
   return render_accumulate_locked(D, dscene, &it->second, params, d_accum, (hipStream_t)stream);
+}
+
+extern "C" int rt_render_accumulate_views(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_views,
+                                          RT_View const *views, void *d_accum, void *stream) {
+  // (everything that can be checked without the device is checked before it is touched)
+  if (!dscene || !d_accum) return rt_fail("rt_render_accumulate_views: NULL scene or accumulation buffer");
+  if (check_params(params) != 0) return -1;
+  if (check_views(n_views, views, params->width, params->height, "rt_render_accumulate_views") != 0) return -1;
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  forget_multi_counters();
+  ViewBatch batch;
+  batch.n = n_views;
+  batch.views = views;
+  return render_accumulate_locked(D, dscene, &views[0].camera, params, d_accum, (hipStream_t)stream, nullptr, RT_VIEWS_STATE, &batch);
 }
 
 int resolve_on(Device &D, RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image, void *d_linear,

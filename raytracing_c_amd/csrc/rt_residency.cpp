@@ -25,6 +25,9 @@ void free_device_scene(RT_Device_Scene *d) {      // d->dev->mutex held, d's dev
     (void)hipFree(L.cost[0]);
     (void)hipFree(L.cost[1]);
     (void)hipFree(L.order);
+    (void)hipFree(L.views);
+    if (L.views_host) (void)hipHostFree(L.views_host);
+    if (L.views_copied) (void)hipEventDestroy(L.views_copied);
   }
   (void)hipFree(d->wf_hit0);
   (void)hipFree(d->wf_hit);

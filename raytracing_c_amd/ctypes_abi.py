@@ -132,6 +132,10 @@ class RT_Render_Params(C.Structure):  # rt_hip.h
                 ("flags", C.c_int32), ("sample_first", C.c_int32), ("sample_count", C.c_int32)]
 
 
+class RT_View(C.Structure):  # rt_hip.h: one view of rt_render_views / rt_render_accumulate_views
+    _fields_ = [("camera", Camera), ("seed", C.c_uint32)]
+
+
 assert C.sizeof(BVH_Node) == 192
 assert C.sizeof(Triangle) == 112
 assert C.sizeof(Triangle_AOS) == 112
@@ -158,7 +162,8 @@ EXPORTED_SYMBOLS = [
     "rt_scene_verify", "rt_scene_touch", "rt_scene_set_static", "rt_get_frame_timing",
     "rt_scene_upload", "rt_scene_release", "rt_scene_invalidate", "rt_scene_device_bytes", "rt_set_camera",
     "rt_chunk_count", "rt_chunk_owner", "rt_local_chunk_count", "rt_max_local_chunk_count", "rt_local_chunk_list", "rt_render_accumulate", "rt_resolve", "rt_untile",
-    "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
+    "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_render_views", "rt_render_accumulate_views",
+    "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 
 # include/rt_hip_diag.h: exported by librt_hip_diag.so only (which also exports everything above); the product library must

@@ -126,6 +126,9 @@ def _declare(d):
     if hasattr(d, "rt_frame_begin"):                       # (absent from older builds loaded as A/B partners)
         d.rt_frame_begin.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize]
         d.rt_frame_end.argtypes = [C.c_int]
+    if hasattr(d, "rt_render_views"):
+        d.rt_render_views.argtypes = [P(abi.Scene), C.c_int32, P(abi.RT_View), P(abi.Image), abi.isize, abi.isize, vp, vp]
+        d.rt_render_accumulate_views.argtypes = [vp, P(abi.RT_Render_Params), C.c_int32, P(abi.RT_View), vp, vp]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import ctypes_abi as abi
 from .native import lib as _lib, last_error
-from .scene import HostScene, make_image
+from .scene import HostScene, make_image, set_camera
 
 
 @dataclass
@@ -58,6 +58,56 @@ def render_frame(hs: HostScene, width, height, samples, max_bounces, seed=0x1234
     if rc != 0:
         raise RuntimeError("rt_render_frame failed: " + last_error(lib))
     return dict(image=out, linear=linear, accum=accum, counters=get_counters(lib))
+
+
+def make_views(cameras, seeds=None):
+    """ctypes array of RT_View from `cameras` (abi.Camera values or (4x4 view matrix, yfov) pairs) and `seeds` (default: the
+    library's default frame seed for every view)."""
+    cameras = list(cameras)
+    if seeds is None:
+        seeds = [0x1234ABCD] * len(cameras)
+    seeds = list(seeds)
+    if len(seeds) != len(cameras):
+        raise ValueError(f"{len(cameras)} cameras but {len(seeds)} seeds")
+    views = (abi.RT_View * max(len(cameras), 1))()
+    for v, (cam, seed) in enumerate(zip(cameras, seeds)):
+        if isinstance(cam, abi.Camera):
+            C.memmove(C.byref(views[v].camera), C.byref(cam), C.sizeof(abi.Camera))
+        else:
+            matrix, yfov = cam
+            set_camera(views[v].camera, matrix, yfov)
+        views[v].seed = int(seed) & 0xFFFFFFFF
+    return views
+
+
+def render_views(hs: HostScene, cameras, width, height, samples, max_bounces, seeds=None, want_linear=False,
+                 want_accum=False, lib=None):
+    """K views of one scene in ONE launch of the path kernel (rt_render_views).  `cameras`: abi.Camera values or
+    (4x4 view matrix, yfov) pairs; `seeds`: one frame seed per view (default 0x1234ABCD each).  Returns one dict per view
+    like render_frame (image, linear, accum, counters = the counters of the whole batch)."""
+    lib = lib or _lib
+    views = make_views(cameras, seeds)
+    k = len(cameras)
+    out = np.zeros((k, height, width, 3), np.uint8)
+    images = (abi.Image * max(k, 1))()
+    for v in range(k):
+        images[v].components = 3
+        images[v].pixel_type = 0
+        images[v].width = width
+        images[v].stride = width
+        images[v].height = height
+        images[v].pixels.data = out[v].ctypes.data
+        images[v].pixels.len = out[v].size
+    linear = np.zeros((k, height, width, 3), np.float32) if want_linear else None
+    accum = np.zeros((k, height, width, 3), np.uint64) if want_accum else None
+    rc = lib.rt_render_views(C.byref(hs.scene), k, views, images, samples, max_bounces,
+                             linear.ctypes.data if want_linear else None,
+                             accum.ctypes.data if want_accum else None)
+    if rc != 0:
+        raise RuntimeError("rt_render_views failed: " + last_error(lib))
+    counters = get_counters(lib)
+    return [dict(image=out[v], linear=None if linear is None else linear[v], accum=None if accum is None else accum[v],
+                 counters=counters) for v in range(k)]
 
 
 def frame_begin(hs: HostScene, width, height, samples, max_bounces, seed=0x1234ABCD, lib=None):

@@ -108,7 +108,7 @@ def main(tag, out):
     coef_static = np.where(np.isnan(prior), coef, prior)
     rel_static = (X @ coef_static) / y - 1.0
     head, L, total = counts[0], counts[0]["ledger"], y[0]
-    lines = ["# Block ledger of `rt_path_kernel_stream<16, true, 1, true>` -- config #3 (helmet 1920x1080, 256 spp, 8 bounces), 1 x MI355X", "",
+    lines = ["# Block ledger of `rt_path_kernel_stream<16, true, 1, true, false>` -- config #3 (helmet 1920x1080, 256 spp, 8 bounces), 1 x MI355X", "",
              "Where the VALU wave-instructions of the product kernel go, block by block (VERDICT r03 #2).", "",
              "* **Executions and lanes**: counted by a `-DRT_LEDGER=1` build of the same kernel (`tools/exp_ledger.py`, `tools/gpu/ledger.sh`): one row",
              "  of counters per wave in memory, bumped by lane 0 with atomics that return nothing.  (As scalar registers the counters did not fit",
