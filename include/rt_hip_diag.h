@@ -1,9 +1,9 @@
 /* rt_hip_diag.h -- entry points of the DIAGNOSTIC library librt_hip_diag.so (make -C raytracing_c_amd/csrc diag,
  * -DRT_DIAG_VARIANTS) that the product library librt_hip.so does NOT export: unit-level device entry points for the parity
  * tests, the wavefront pipeline (built and measured in round 3, slower than the tile-stream kernel on every BASELINE
- * configuration: profiles/r03_experiments.md), per-block statistics of the diagnostic kernel generations.  The diagnostic
- * library is built from the same sources and exports everything rt_hip.h declares as well; tests load it beside the product
- * library (raytracing_c_amd.native.diag).  Nothing here is part of the drop-in boundary.
+ * configuration: profiles/r03_experiments.md), the block ledger and the wave timeline of the path kernel.  The diagnostic
+ * library links the product's kernel object, reads the RT_* experiment knobs and exports everything rt_hip.h declares as
+ * well; tests load it beside the product library (raytracing_c_amd.native.diag).  Nothing here is part of the drop-in boundary.
  */
 #ifndef RT_HIP_DIAG_H
 #define RT_HIP_DIAG_H
@@ -31,17 +31,12 @@ extern int  rt_set_pipeline(i32 pipeline);
 extern i32  rt_get_pipeline(void);
 extern void rt_set_wavefront_capacity(i64 records);
 
-/* Diagnostic kernel only (env RT_KERNEL=4): out[0..15] = 8 pairs (times a block ran, lanes it ran with) for
- * shade, environment, regenerate, leaf (uniform), leaf (per lane), node (uniform), node (per lane), pop;
- * out[16..23] = shader-clock cycles the waves spent in S blocks with shading (16), S blocks without (17), leaf
- * blocks (19), node blocks (21), pop loops (23), summed over waves; out[24] = cycles of the whole wave loops. */
-extern int rt_get_sched_stats(u64 out[32]);
 /* Block ledger of a -DRT_LEDGER build of the tile-stream kernel (tools/exp_ledger.py): out[0 .. n) = the LG_* slots of
  * csrc/rt_dev.hip.h of the last launch (all zero in other builds). */
 extern int rt_get_ledger(u64 *out, i32 n);
-/* ... and per wave (start tick, end tick, items) of the last diagnostic launch; ticks are 10 ns.  Returns the wave count. */
+/* RT_WAVE_TIMES set in the environment: per wave of the last launch (start tick, end tick, (tick of its last grab - start) << 16
+ * | tiles it owned); ticks are 10 ns.  Returns the wave count (-1: no such launch). */
 extern int rt_get_wave_times(u64 *out, i32 max_waves);
-
 
 /* ---- unit-level device entry points (parity tests call the same device
  * functions the render kernel uses) ------------------------------------------ */

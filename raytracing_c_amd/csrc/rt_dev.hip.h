@@ -1,7 +1,6 @@
 // rt_dev.hip.h -- device functions shared by the gfx950 kernels of the render hot path (rt_kernels.hip: the
-// tile-stream path kernel, lightmap, unit-test kernels; rt_wavefront.hip: the split traversal / shading kernels;
-// rt_kernels_diag.hip: the superseded kernel generations kept for bisecting).  Everything here is
-// __device__ __forceinline__: each translation unit gets its own copy.
+// tile-stream path kernel, lightmap; rt_wavefront.hip: the split traversal / shading kernels; rt_kernels_test.hip: the
+// unit-test kernels).  Everything here is __device__ __forceinline__: each translation unit gets its own copy.
 //
 // Reference functions restated here (per-lane arithmetic identical to oracle/oracle.c):
 //   ray_aabbs_hit_8      raytracer.c:190-230   slab_entry, node_enter, node_enter_few
@@ -138,9 +137,9 @@ __device__ __forceinline__ float4 ld4(const float *base, int idx4) {
 }
 
 // Scalar-cache reads: a pointer in the constant address space with a uniform (SGPR) address makes hipcc emit
-// s_load_dwordx16 instead of one vector load per lane.  Used by the plain kernel (rt_path_kernel / trace_ray) for
-// wave-uniform nodes and leaves; the scheduled kernel dropped these paths (LDS broadcast reads are faster and the
-// 48 / 72 SGPRs per node / leaf tile cost it 34 spilled SGPRs).
+// s_load_dwordx16 instead of one vector load per lane.  Used by the plain loop (trace_ray) for wave-uniform nodes and
+// leaves; the path kernel's traversal blocks do without (LDS broadcast reads are faster and the 48 / 72 SGPRs per
+// node / leaf tile cost it 34 spilled SGPRs).
 typedef const float __attribute__((address_space(4))) cfloat;
 __device__ __forceinline__ cfloat *as_scalar_ptr(const float *p) { return (cfloat *)(unsigned long long)p; }
 
@@ -228,8 +227,7 @@ __device__ __forceinline__ float slab_entry_child_any(const float *n, const Ray3
 // the 8 ranks are a permutation and the word needs no per-child condition.
 #define NODE_GLOBAL 0     // per-lane vector loads from HBM/L2/L1
 #define NODE_SCALAR 1     // wave-uniform node: s_load through the scalar cache
-#define NODE_LDS    2     // per-lane reads from the workgroup's LDS copy of the top of the tree
-#define NODE_LDS_ORDERED 3   // NODE_LDS with the slab planes picked by address (FAST rays, boxes with min <= max)
+#define NODE_LDS_ORDERED 3   // per-lane reads from the workgroup's LDS copy of the top of the tree, the slab planes picked by address (FAST rays, boxes with min <= max)
 #define RT_LDS_NODE_F4 13 // LDS node stride in float4 (12 data + 1 pad: 13 is odd, so random nodes spread over all 16-byte slots of a bank row)
 
 // float4 index of LDS node `node`: a 24-bit multiply is full rate, v_mul_lo_u32 a quarter
@@ -246,7 +244,8 @@ __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &
     for (int k = 0; k < 8; k++) {
       d[k] = as_i(slab_entry<FAST>(r, bs, nb[k], nb[8 + k], nb[16 + k], nb[24 + k], nb[32 + k], nb[40 + k], hit_t));
     }
-  } else if (FAST && MODE == NODE_LDS_ORDERED) {
+  } else if (MODE == NODE_LDS_ORDERED) {
+    static_assert(FAST || MODE != NODE_LDS_ORDERED, "the ordered LDS form is for FAST rays only");
     // Near and far plane of every slab picked by ADDRESS from the sign of the reciprocal direction instead of by min / max
     // of the two distances: with min <= max in every box (checked at upload, rt_api.cpp) and NaN-free operands,
     // t(mn) <= t(mx) for inv > 0 and >= for inv < 0 -- rounding is monotonic, for (p - o) * inv and for fma(p, inv, bias)
@@ -272,8 +271,7 @@ __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &
       }
     }
   } else {
-    const float4 *nb = (MODE == NODE_LDS || MODE == NODE_LDS_ORDERED) ? (lds_nodes + lds_node_f4(node))
-                                          : (reinterpret_cast<const float4 *>(P.nodes) + (size_t)node * 12);
+    const float4 *nb = reinterpret_cast<const float4 *>(P.nodes) + (size_t)node * 12;
 #pragma unroll
     for (int h = 0; h < 2; h++) {          // children 0-3, then 4-7: half the node in registers at a time
       float4 mnx = nb[0 + h], mny = nb[2 + h], mnz = nb[4 + h];
@@ -1056,12 +1054,6 @@ __device__ __forceinline__ void ray_setup(Ray3 &r, rt_v3 o, rt_v3 d) {
     r.inv_z = 1.0f / d.z;
   }
   r.fast = rt_slab_fast(o.x, o.y, o.z, r.inv_x, r.inv_y, r.inv_z, rt_slab_bias(o.x, r.inv_x), rt_slab_bias(o.y, r.inv_y), rt_slab_bias(o.z, r.inv_z));
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // One accepted closest hit -> pass-through or material evaluation and the next ray of the path

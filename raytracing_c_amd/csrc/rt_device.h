@@ -1,5 +1,5 @@
 /* rt_device.h -- layout of the flattened scene in HBM and the kernel argument
- * block.  Shared by rt_api.cpp (host, fills it) and rt_kernels.hip (reads it).
+ * block.  Shared by the host units (rt_launch.cpp fills it) and the kernels (read it).
  *
  * HBM layout (all read-only during a frame, 16-byte aligned):
  *   nodes   : BVH_Node as is, 12 float4 per node                 192 B / node
@@ -28,12 +28,12 @@
 #define RT_MAT_DISNEY 0
 #define RT_MAT_DEBUG  1
 
-#define RT_TILE      8       /* work item = 8x8 pixel tile x sample slab */
+#define RT_TILE      8       /* a tile = 8x8 pixels */
 #define RT_TILE_PIX  64
 
 #define RT_PARK_RECORD_DWORDS (18 * 128)   /* a wave's slice of RT_KParams.park: RT_PARK_FIELDS x RT_PARK_CAP (rt_dev.hip.h) */
-#define RT_N_COUNTERS 136    /* 0..6 ray counters; 8..23 block statistics of the diagnostic kernel, 24..39 its cycle sums; or 8..135 the
-                              * block ledger of the tile-stream kernel (-DRT_LEDGER builds, LG_* slots in rt_dev.hip.h) */
+#define RT_N_COUNTERS 136    /* 0..6 ray counters, 7 skipped root visits; 8..135 the block ledger of the path kernel (-DRT_LEDGER
+                              * builds, LG_* slots in rt_dev.hip.h) */
 
 /* triangle record, 28 floats:
  *  [0..2] face normal      [3]  material id (int bits)
@@ -99,9 +99,7 @@ typedef struct {
   uint32_t seed;
   int32_t chunks_x, n_chunks;
   int32_t rank, world, n_local_chunks;
-  int32_t slab_shift;          /* samples per work item = 1 << slab_shift */
-  int32_t n_slabs;             /* ceil((sample_end - sample_first) / slab) */
-  int32_t n_work;              /* n_local_chunks * 16 * n_slabs           */
+  int32_t unused_pad[3];       /* no kernel reads these (work items of retired kernels): they keep the offsets below; zero */
   int32_t sched_thresh;        /* lanes waiting for shade / environment / regeneration that trigger that block */
   int32_t n_lds_nodes;         /* BVH nodes [0, n) are also in the workgroup's LDS   */
   /* outputs */
@@ -111,8 +109,8 @@ typedef struct {
   const int32_t *local_chunks; /* global chunk index of this rank's l-th chunk (partition table) */
   const uint32_t *order;       /* tile visiting order (NULL = identity)   */
   uint32_t *tile_cost;         /* rays per tile of THIS launch (NULL = off)*/
-  unsigned long long *wave_times; /* diagnostic kernel: per wave start, end (100 MHz), items */
-  /* tile-stream kernel (variant 5): a tile hands out units = 2 pixels x (1 << chunk_shift) samples */
+  unsigned long long *wave_times; /* RT_WAVE_TIMES (diagnostic library): per wave start, end (100 MHz), last grab | tiles; NULL = off */
+  /* a tile hands out units = 2 pixels x (1 << chunk_shift) samples */
   uint32_t *tile_next;         /* [n_tiles] chunks handed out so far (zero at launch)                       */
   uint32_t *open_groups;       /* [ceil(n_tiles / 64)] tiles of the group that still have chunks            */
   int32_t n_tiles;             /* n_local_chunks * 16                                                       */
@@ -121,7 +119,7 @@ typedef struct {
   int32_t n_sample_blocks;     /* ceil(samples of this launch / samples per unit)                           */
   int32_t drain_thresh;        /* lanes waiting for S that trigger it once the wave's tile is exhausted     */
   int32_t grab_max;            /* units a wave takes per atomic while its tile has plenty left (1, 2 or 4)   */
-  uint32_t *park;              /* tile-stream kernel: [waves][18][128] dwords, hits parked until a dense shade block (nullptr = off) */
+  uint32_t *park;              /* [waves][18][128] dwords, hits parked until a dense shade block (nullptr = off) */
   int32_t short_div;           /* 1: leaf blocks take 1 / det from rcp_exact() (host-checked determinant bound), 0: IEEE division */
   int32_t pyr_nodes;           /* node blocks of camera rays on nodes [0, n) test only the children the tile's pyramid can touch; 0 = off */
   /* wavefront pipeline (rt_wavefront.hip): camera / trace / shade kernels joined by record queues in HBM.  A queue is

@@ -6,7 +6,7 @@
 #error rt_diag.cpp belongs to the diagnostic library only (-DRT_DIAG_VARIANTS)
 #endif
 
-// unit-test kernels (rt_kernels_diag.hip, rt_kernels.hip) and the wavefront pipeline (rt_wavefront.hip)
+// unit-test kernels (rt_kernels_test.hip) and the wavefront pipeline (rt_wavefront.hip)
 extern "C" {
 int rt_launch_test_math(int op, int n, const float *x, const float *y, float *out, hipStream_t stream);
 int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream);
@@ -171,11 +171,8 @@ extern "C" int rt_get_ledger(u64 *out, i32 n) {
   return 0;
 }
 
-// Block statistics of the diagnostic kernel (RT_KERNEL=4): 8 pairs (executions, lanes) for
-// shade, environment, regenerate, leaf-scalar, leaf-vector, node-scalar, node-vector, pop.
-extern "C" int rt_get_sched_stats(u64 out[32]) { return rt_get_ledger(out, 32); }
-
-// Diagnostic kernel (RT_KERNEL=4): per wave start time, end time (100 MHz ticks) and items processed.
+// RT_WAVE_TIMES: per wave of the last launch its start time, end time (100 MHz ticks) and (time of its last grab - start) << 16 |
+// tiles it owned.  Returns the number of waves written.
 extern "C" int rt_get_wave_times(u64 *out, i32 max_waves) {
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);

@@ -9,16 +9,16 @@
 //   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
 //
-// (Comments in the kernel sources still cite rt_api.cpp, the one file these units were split from: those sources are hashed
-// into the committed profiles, buildinfo.kernel_source_hash, and stay as they are.)
+// (Comments in rt_dev.hip.h and rt_wavefront.hip still cite rt_api.cpp, the one file these units were split from.)
 //
 // Nothing on the host side computes a pixel on the CPU: every entry point either
-// drives the gfx950 kernels of rt_kernels.hip / rt_wavefront.hip or fails with rt_last_error().
+// drives the gfx950 kernels of rt_kernels.hip (one object, shared by both libraries) / rt_wavefront.hip and rt_kernels_test.hip
+// (diagnostic library only) or fails with rt_last_error().
 //
 // State is kept PER DEVICE (struct Device): HIP context, workspace, scene cache, launch timing.  Slot 0 is the
 // process's primary device (rt_init); slots 1 .. N-1 exist when a frame behind render_thread_proc / render() is spread
 // over N GPUs (RT_DEVICES, rt_set_devices).  The product library reads its configuration ONCE (config()); the RT_*
-// experiment knobs of earlier rounds exist only in the diagnostic build (-DRT_DIAG_VARIANTS, librt_hip_diag.so).
+// experiment knobs exist only in the host units of the diagnostic build (-DRT_DIAG_VARIANTS, librt_hip_diag.so).
 //
 // Lock order everywhere: slot 0's Device::mutex -> slot r's -> g_partition_mutex (rt_partition.cpp).
 #pragma once
@@ -43,7 +43,7 @@
 
 // launchers in rt_kernels.hip, rt_denoise.hip
 extern "C" {
-int rt_launch_path_kernel(const RT_KParams *P, int n_waves, int variant, int smem_bytes, int wg_waves, hipStream_t stream);
+int rt_launch_path_kernel(const RT_KParams *P, int n_waves, int smem_bytes, int wg_waves, hipStream_t stream);
 int rt_launch_prepare(int n_tiles, uint32_t *tile_next, uint32_t *open_groups, unsigned long long *counters, uint32_t *work_head,
                       uint32_t *cost_cur, const uint32_t *cost_prev, uint32_t *order, hipStream_t stream);
 int rt_launch_resolve(int width, int height, int samples, int chunks_x, const int32_t *local_chunks, int n_local_chunks,
@@ -95,7 +95,7 @@ static inline float event_ms(hipEvent_t a, hipEvent_t b) {
 // Product library: RT_DEVICES (GPUs a frame behind render_thread_proc / render() is spread over, default 1) and
 // RT_DEVICES_REHEARSE (=1: the N logical devices all map onto the primary GPU -- what a one-GPU box can run of the
 // N-GPU path), overridable by rt_set_devices().  Nothing else in the environment changes what the library does.
-// Diagnostic library (-DRT_DIAG_VARIANTS): the experiment knobs of earlier rounds (RT_KERNEL, RT_SCHED_THRESH, ...),
+// Diagnostic library (-DRT_DIAG_VARIANTS): the experiment knobs (RT_SCHED_THRESH, RT_WG_WAVES, RT_PIPELINE, ...),
 // read at every launch so that one process can A/B them (tools/exp_kernels.py, tests/test_gpu_diag.py).
 
 #ifdef RT_DIAG_VARIANTS
@@ -162,7 +162,7 @@ struct Workspace {
   std::vector<hipEvent_t> ev0, ev1;
   size_t              n_timed = 0;
   hipEvent_t          ev_frame[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // frame start, prep done, path done, resolve done, copy done
-  unsigned long long *wave_times = nullptr;   // diagnostic kernel (RT_KERNEL=4) / RT_WAVE_TIMES
+  unsigned long long *wave_times = nullptr;   // RT_WAVE_TIMES (diagnostic library): the wave timeline of the last launch
   int                 wave_times_n = 0;
 };
 #define RT_MAX_TIMED 256

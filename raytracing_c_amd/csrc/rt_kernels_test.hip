@@ -1,0 +1,252 @@
+// rt_kernels_test.hip -- unit-level kernels for parity tests and their launchers (called from rt_diag.cpp): compiled into the
+// DIAGNOSTIC library only (librt_hip_diag.so, include/rt_hip_diag.h).  They instantiate the same device functions as the
+// product's kernels (rt_dev.hip.h; traversal_blocks() is the path kernel's own traversal); the product library carries no
+// test entry point.
+
+#include "rt_dev.hip.h"
+
+__global__ void rt_test_math_kernel(int op, int n, const float *x, const float *y, float *out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a = x[i], b = y ? y[i] : 0.0f, s, c;
+  float r = 0.0f;
+  switch (op) {
+  case 0: r = rt_logf(a); break;
+  case 1: r = rt_expf(a); break;
+  case 2: r = rt_powf(a, b); break;
+  case 3: rt_sincosf(a, &s, &c); r = s; break;
+  case 4: rt_sincosf(a, &s, &c); r = c; break;
+  case 5: r = rt_atan2f(a, b); break;
+  case 6: r = rt_asinf(a); break;
+  case 7: r = rt_srgb_to_linear1(a); break;
+  case 8: r = rt_linear_to_srgb(a); break;
+  case 9: r = rt_sqrtf(a); break;
+  case 10: r = 1.0f / a; break;
+  case 11: r = rcp_exact(a); break;
+  case 12: r = rcp_exact_outside(a) ? 1.0f : 0.0f; break;
+  case 13: r = srgb_to_linear_tex1(a); break;
+  default: break;
+  }
+  out[i] = r;
+}
+
+// All 2^32 bit patterns x: rcp_exact(x) against the IEEE quotient 1.0f / x.  counts[0] = patterns inside the claimed
+// domain (|x| < 2^102, infinity, NaN) that differ (NaN equals NaN), counts[1] = patterns outside it, counts[2] = of those,
+// how many differ (why the domain ends there), counts[3] = first differing pattern inside the domain + 1.
+// rcp_leaf(x), the leaf blocks' form without the fix-up: counts[4] = finite non-zero patterns with |x| < 2^102 that differ from
+// 1.0f / x, counts[5] = patterns x = +-0, +-infinity, NaN for which it is NOT NaN (what the leaf blocks' argument rests on).
+__global__ void rt_test_rcp_sweep_kernel(unsigned long long *counts) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad_in = 0, n_out = 0, bad_out = 0, first = 0, leaf_bad = 0, leaf_special = 0;
+  for (uint32_t k = 0; k < 256u; k++) {
+    const uint32_t b = tid * 256u + k;
+    const float x = __uint_as_float(b);
+    const uint32_t w = __float_as_uint(1.0f / x), g = __float_as_uint(rcp_exact(x));
+    const bool w_nan = (w & 0x7FFFFFFFu) > 0x7F800000u, g_nan = (g & 0x7FFFFFFFu) > 0x7F800000u;
+    const bool same = w_nan ? g_nan : (g == w);
+    if (rcp_exact_outside(x)) { n_out += 1; bad_out += same ? 0u : 1u; }
+    else if (!same) { bad_in += 1; if (!first) first = b + 1u; }
+    const uint32_t l = __float_as_uint(rcp_leaf(x)), mag = b & 0x7FFFFFFFu;
+    const bool l_nan = (l & 0x7FFFFFFFu) > 0x7F800000u;
+    if (mag == 0u || mag >= 0x7F800000u) leaf_special += l_nan ? 0u : 1u;
+    else if (!rcp_exact_outside(x)) leaf_bad += (l == w) ? 0u : 1u;
+  }
+  if (leaf_bad) atomicAdd(&counts[4], (unsigned long long)leaf_bad);
+  if (leaf_special) atomicAdd(&counts[5], (unsigned long long)leaf_special);
+  if (bad_in) atomicAdd(&counts[0], (unsigned long long)bad_in);
+  if (n_out) atomicAdd(&counts[1], (unsigned long long)n_out);
+  if (bad_out) atomicAdd(&counts[2], (unsigned long long)bad_out);
+  if (first) atomicMax(&counts[3], (unsigned long long)first);
+}
+
+// accum_quantize_dev(x) against rt_accum_quantize(x) for all 2^32 bit patterns: counts[0] = patterns that differ,
+// counts[1] = first differing pattern + 1.
+__global__ void rt_test_quantize_sweep_kernel(unsigned long long *counts) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad = 0, first = 0;
+  for (uint32_t k = 0; k < 256u; k++) {
+    const uint32_t b = tid * 256u + k;
+    const float x = __uint_as_float(b);
+    if (accum_quantize_dev(x) != (unsigned long long)rt_accum_quantize(x)) { bad += 1; if (!first) first = b + 1u; }
+  }
+  if (bad) atomicAdd(&counts[0], (unsigned long long)bad);
+  if (first) atomicMax(&counts[1], (unsigned long long)first);
+}
+
+// srgb_to_linear_tex1(x) against rt_srgb_to_linear1(x) for every float in [0, 2] and in [-0.046875, -0.03125]: counts[0] =
+// patterns compared (2^30 + 2^22), counts[1] = patterns that differ, counts[2] = first differing pattern + 1.
+__global__ void rt_test_srgb_sweep_kernel(unsigned long long *counts) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;       // 2^22 threads x 256 patterns = [0, 0x40000000)
+  uint32_t n = 0, bad = 0, first = 0;
+  for (uint32_t k = 0; k < 257u; k++) {
+    uint32_t b = tid * 256u + k;
+    if (k == 256u) b = tid == 0 ? 0x40000000u : 0xBD000000u + tid - 1u;        // 2.0, and 2^22 - 1 negative values from -0.03125 down
+    const float x = __uint_as_float(b);
+    const uint32_t w = __float_as_uint(rt_srgb_to_linear1(x)), g = __float_as_uint(srgb_to_linear_tex1(x));
+    n += 1;
+    if (w != g) { bad += 1; if (!first) first = b + 1u; }
+  }
+  atomicAdd(&counts[0], (unsigned long long)n);
+  if (bad) atomicAdd(&counts[1], (unsigned long long)bad);
+  if (first) atomicMax(&counts[2], (unsigned long long)first);
+}
+
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_trace_kernel(RT_KParams P, int n, const float *rays,
+                                                                         float *out_t, int *out_tri, float *out_uv) {
+  __shared__ uint32_t s_perm[RT_BLOCK_WAVES][RT_MAX_DEPTH * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  LaneCounters cn;
+  cn.rays = cn.nodes = cn.leaves = cn.shades = cn.bgs = cn.textured = cn.paths = 0;
+  if (i >= n) return;
+  Ray3 r;
+  ray_setup(r, rt_v3_make(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]),
+            rt_v3_make(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]));
+  HitRec hit;
+  if (r.fast) trace_ray<true>(P, r, hit, s_perm[wave], lane, cn);
+  else trace_ray<false>(P, r, hit, s_perm[wave], lane, cn);
+  out_t[i] = hit.t;
+  out_tri[i] = hit.tri;
+  out_uv[i * 2 + 0] = hit.u;
+  out_uv[i * 2 + 1] = hit.v;
+}
+
+__global__ void rt_test_texture_kernel(RT_KParams P, int tex, int n, const float *uv, float *out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rt_v3 c = tex_bilinear(P, tex, uv[i * 2], uv[i * 2 + 1]);
+  out[i * 3 + 0] = c.x;
+  out[i * 3 + 1] = c.y;
+  out[i * 3 + 2] = c.z;
+}
+
+// Arbitrary rays through the PRODUCTION traversal: traversal_blocks() -- the NODE / LEAF / pop code of the path kernels --
+// in the path kernel's workgroup geometry (16 waves, tree in LDS, per-wave perm stacks), lanes refilled from the ray list
+// as they finish, blocks mixed exactly as a frame mixes them.  With a pyramid (`pyr`: 4 outward plane normals at
+// [4 q .. 4 q + 2], the common ray origin at [16 .. 18]) every ray counts as a camera ray of one tile: node blocks take
+// the culled form (pyramid_cull_mask, node_enter_few) whenever the path kernel would.  visits[0 / 1] += node / leaf
+// visits (raytracer.c:452 / :476 calls).  Compared with oracle_trace_rays_counted() by tests/test_gpu_trace_stream.py.
+template <bool SHORT_DIV, bool PYRAMID>
+__global__ __launch_bounds__(16 * 64, 1) void rt_test_trace_stream_kernel(RT_KParams P, int n, const float *rays, const float *pyr_in,
+                                                                         int exit_lanes, float *out_t, int *out_tri, float *out_uv,
+                                                                         unsigned long long *visits) {
+  extern __shared__ float4 smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int n_lds = P.n_lds_nodes;
+  const float4 *lds_nodes = smem;
+  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
+  uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * (perm_f4 + 96));
+  const int pyr_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4 - 16) * 16;
+  {
+    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
+    for (int i = threadIdx.x; i < n_lds * 12; i += 16 * 64) {
+      int nd = i / 12, q = i - nd * 12;
+      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
+    }
+    __syncthreads();
+  }
+  if (PYRAMID) {
+    float *pyr = lds_at(smem, pyr_off);
+    if (lane < 19) pyr[lane] = pyr_in[lane];
+    if (lane < 40) reinterpret_cast<uint32_t *>(pyr)[24 + lane] = 0u;
+  }
+  const int leaf_level = P.depth - 1;
+  const int n_waves = (int)gridDim.x * 16, wave_id = (int)blockIdx.x * 16 + wave;
+  const int per_wave = (n + n_waves - 1) / n_waves;
+  int next = wave_id * per_wave;                                   // this wave's slice of the ray list
+  const int end = next + per_wave < n ? next + per_wave : n;
+
+  int   phase = PH_NEED, idx = 0;
+  Ray3  ray;
+  ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
+  int   level = -1, node = 0, child = 0;
+  uint32_t cur = 0, dirty = 0, live = 0, w_nodes = 0, w_leaves = 0;
+  HitRec hit;
+  hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+  for (;;) {
+    if (phase == PH_HIT || phase == PH_MISS) {
+      out_t[idx] = hit.t;
+      out_tri[idx] = hit.tri;
+      out_uv[idx * 2 + 0] = hit.u;
+      out_uv[idx * 2 + 1] = hit.v;
+      phase = PH_NEED;
+    }
+    if (next < end) {
+      const unsigned long long need = __ballot(phase == PH_NEED);
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+      if (phase == PH_NEED && next + rank < end) {
+        idx = next + rank;
+        const float *r = rays + (size_t)idx * 6;
+        ray_setup<SHORT_DIV>(ray, rt_v3_make(r[0], r[1], r[2]), rt_v3_make(r[3], r[4], r[5]));
+        hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+        dirty = 0; live = 0; cur = 0; level = -1; node = 0;
+        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
+        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+      }
+      next += (int)__popcll(need);
+    }
+    const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+    if (n_trav0 == 0) {
+      if (next >= end) break;
+      continue;
+    }
+    traversal_blocks<true, SHORT_DIV, PYRAMID>(P, smem, lds_nodes, perm, lane, n_lds, PYRAMID ? P.pyr_nodes : 0, pyr_off, leaf_level,
+                                               next < end ? exit_lanes : 1, n_trav0, ray, true, phase, level, node, child, cur, dirty,
+                                               live, hit, w_nodes, w_leaves);
+  }
+  if (lane == 0) {
+    atomicAdd(visits + 0, (unsigned long long)w_nodes);
+    atomicAdd(visits + 1, (unsigned long long)w_leaves);
+  }
+}
+
+extern "C" int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, const float *pyr, int exit_lanes, int n_blocks,
+                                           int smem_bytes, float *out_t, int *out_tri, float *out_uv, unsigned long long *visits,
+                                           hipStream_t stream) {
+#define RT_TTS(SD, PY)                                                                                                          \
+  do {                                                                                                                          \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_test_trace_stream_kernel<SD, PY>),                    \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                 \
+    if (e != hipSuccess) return (int)e;                                                                                         \
+    hipLaunchKernelGGL((rt_test_trace_stream_kernel<SD, PY>), dim3(n_blocks), dim3(16 * 64), smem_bytes, stream, *P, n, rays,  \
+                       pyr, exit_lanes, out_t, out_tri, out_uv, visits);                                                        \
+  } while (0)
+  if (P->short_div) { if (pyr) RT_TTS(true, true); else RT_TTS(true, false); }
+  else { if (pyr) RT_TTS(false, true); else RT_TTS(false, false); }
+#undef RT_TTS
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_math(int op, int n, const float *x, const float *y, float *out, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_math_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, x, y, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_rcp_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_quantize_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_srgb_sweep(unsigned long long *counts, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_srgb_sweep_kernel, dim3(16384), dim3(256), 0, stream, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_trace(const RT_KParams *P, int n, const float *rays, float *out_t, int *out_tri,
+                                    float *out_uv, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_trace_kernel, dim3((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS),
+                     dim3(RT_BLOCK_THREADS), 0, stream, *P, n, rays, out_t, out_tri, out_uv);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const float *uv, float *out,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_texture_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *P, tex, n, uv, out);
+  return (int)hipGetLastError();
+}

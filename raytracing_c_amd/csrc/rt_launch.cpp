@@ -26,6 +26,24 @@ int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const 
   return 0;
 }
 
+// The size limit of one launch, unchanged since a launch was cut into (tile x block of samples) items counted in 32 bits: blocks
+// of p->slab samples, or by default the largest of 32 / 16 / 8 that leaves 24 items per wave of a full grid.  No kernel counts
+// such items any more, but the limit still decides which launches are refused: check_params / check_views bound pixels and
+// tiles, not samples (1024 x 1024 pixels at 2^23 samples pass them and are refused here).
+static int check_launch_size(const Device &D, int tiles_per_view, int n_views, int n_samples, int slab) {
+  if (slab <= 0) {
+    slab = 8;
+    for (int cand = 32; cand > 8; cand >>= 1)
+      if ((int64_t)tiles_per_view * ((n_samples + cand - 1) / cand) >= (int64_t)24 * D.num_cus * 16) { slab = cand; break; }
+  }
+  int shift = 0;
+  while ((1 << shift) < slab && (1 << shift) < n_samples) shift++;
+  const int64_t items = (int64_t)tiles_per_view * ((n_samples + (1 << shift) - 1) >> shift) * n_views;
+  if (items > 0x7fffffff) return rt_fail("too many work items (%lld)", (long long)items);
+  return 0;
+}
+
+// Scene, camera, frame, partition and sample range of the launch; what depends on the launch state comes later.
 static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
                         void *d_accum, ViewBatch const *batch) {
   const int nv = batch ? batch->n : 1;
@@ -57,32 +75,114 @@ static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera con
   }
   K->sample_first = p->sample_first;
   K->sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
-  int n_samples = K->sample_end - K->sample_first;
-  // (work items of the diagnostic kernel generations: samples per item = the largest of 32 / 16 / 8 that still leaves 24
-  // items per wave)
-  int slab = p->slab;
-  if (slab <= 0) {
-    slab = 8;
-    for (int cand = 32; cand > 8; cand >>= 1) {
-      int64_t items = (int64_t)K->n_local_chunks * 16 * ((n_samples + cand - 1) / cand);
-      if (items >= (int64_t)24 * D.num_cus * 16) { slab = cand; break; }
-    }
-  }
-  int shift = 0;
-  while ((1 << shift) < slab && (1 << shift) < n_samples) shift++;
-  K->slab_shift = shift;
-  K->n_slabs = (n_samples + (1 << shift) - 1) >> shift;
-  int64_t n_work = (int64_t)K->n_local_chunks * 16 * K->n_slabs * nv;
-  if (n_work > 0x7fffffff) return rt_fail("too many work items (%lld)", (long long)n_work);
-  K->n_work = (int32_t)n_work;
+  K->n_tiles = K->n_local_chunks * 16 * nv;      // (a batch: the tiles of view v are [v * tiles_per_view, (v + 1) * tiles_per_view))
+  if (check_launch_size(D, K->n_local_chunks * 16, nv, K->sample_end - K->sample_first, p->slab) != 0) return -1;
   K->accum = (unsigned long long *)d_accum;
-  K->counters = d->ls[0].counters;      // (render_accumulate_locked puts the launch state it was asked for)
-  K->work_head = d->ls[0].work_head;
   if (batch) {
     K->n_views = nv;
     K->tiles_per_view = K->n_local_chunks * 16;
     K->pixels_per_view = p->width * p->height;
   }
+  return 0;
+}
+
+// ---- launch geometry: waves per workgroup, BVH nodes in LDS, dynamic LDS per workgroup ----
+static void launch_geometry(const Device &D, const RT_Device_Scene *d, RT_KParams &K, int *wg_waves, int *smem) {
+  // Workgroup size by the size of the launch (round 5, profiles/r05_small_launch.md section 3).  A launch ends with every wave
+  // running the bounce chains of its last paths on thinning lanes, and at four waves per SIMD those thin waves are ISSUE-bound:
+  // with two waves per SIMD a bounce of such a chain takes half the time.  A launch with little work per wave slot is mostly
+  // that tail -- config #1: 0.58 ms with 16-wave workgroups, 0.41 with 8 -- one with much work needs all four waves per SIMD
+  // for its body (the driver's default frame: 2.60 / 2.89 / 3.48 ms with 16 / 12 / 8).  One workgroup per CU either way (the
+  // tree fills the LDS).  Measured crossovers, in wave-fulls of paths per slot of the 16-wave grid: tower 640x360x16 (14) 0.91 /
+  // 0.76 / 0.69 ms, spheres 512^2 x 16 (16) 0.83 / 0.74 / 0.75, helmet 512^2 x 16 (16) 1.23 / 1.17 / 1.41, 64 and more: 16 wins.
+  const int64_t paths = (int64_t)K.n_tiles * 64 * (int64_t)(K.sample_end - K.sample_first);
+  int64_t per_slot = paths / ((int64_t)D.num_cus * 16 * 64);
+  // (a depth-0 scene -- one leaf group, no node blocks -- traces a ray in a quarter of the instructions: its launches are as
+  //  short as launches a quarter their size; quad 256^2 / 512^2 / 768^2 / 1024^2 x 64 spp: best with 8 / 12 / 12 / 16 waves,
+  //  0.43 / 0.90 / 1.62 / 2.43 ms against 0.59 / 0.99 / 1.67 / 2.43 with 16)
+  if (K.depth == 0) per_slot /= 4;
+  *wg_waves = per_slot < 12 ? 8 : (per_slot < 40 ? 12 : 16);
+  int v = knob_int("RT_WG_WAVES", 0);
+  if (v == 8 || v == 12 || v == 16) *wg_waves = v;
+  // dynamic LDS per workgroup: per wave (perm stack: depth x 256 B, accumulator tile: 1536 B) and as many leading BVH
+  // nodes (level order) as fit in the 160 KB of a CU at 208 B each
+  const int lds_limit = 160 * 1024 - 64;      // (- the kernel's static LDS: the 32-byte sRGB scale table, rt_dev.hip.h rt_pow24_lds)
+  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
+  int room = (lds_limit - *wg_waves * per_wave) / 208;
+  if (room < 0) room = 0;
+  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
+  if (!d->boxes_ordered) K.n_lds_nodes = 0;      // (the kernel's LDS node blocks assume min <= max)
+  v = knob_int("RT_LDS_NODES", K.n_lds_nodes);
+  if (v >= 0 && v < K.n_lds_nodes) K.n_lds_nodes = v;
+  *smem = K.n_lds_nodes * 208 + *wg_waves * per_wave;
+}
+
+// ---- schedule feedback: visit expensive tiles first (costs = rays per tile of the previous launch of this view) ----
+// Sets K.order / K.tile_cost; *cost_prev = the costs the preparation kernel sorts into L.order (NULL: none that fit this launch).
+static int schedule_feedback(LaunchState &L, RT_KParams &K, const uint32_t **cost_prev) {
+  K.order = nullptr;
+  K.tile_cost = nullptr;
+  *cost_prev = nullptr;
+  if (knob_is("RT_ORDER", "identity") || K.n_tiles <= 0) return 0;
+  const int n_tiles = K.n_tiles;
+  // the costs of a launch are reusable by a launch of the same frame shape, partition and bounce limit -- NOT only of the same
+  // view: for a camera that moves between frames the previous view's costs are still a better guide than none (helmet, a rotation
+  // of 0.5 / 2 / 10 degrees per frame: -0.7 / -0.8 / -0.2 % kernel time at 256 spp, -2.3 % at 1024^2 x 64 spp against the identity
+  // order, tools/exp_moving.py, profiles/r05_experiments.md section 4), and an order is only ever a schedule, never a pixel
+  uint64_t key = 1469598103934665603ull;
+  auto mix = [&key](const void *ptr, size_t n) {
+    const unsigned char *b = (const unsigned char *)ptr;
+    for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; }
+  };
+  int32_t ids[6] = {K.width, K.height, K.rank, K.world, K.max_bounces, n_tiles};
+  mix(ids, sizeof ids);
+  if (L.sched_tiles != n_tiles) {
+    (void)hipFree(L.cost[0]); (void)hipFree(L.cost[1]); (void)hipFree(L.order);
+    L.cost[0] = L.cost[1] = L.order = nullptr;
+    L.sched_tiles = 0;
+    L.sched_valid = false;
+    HIP_TRY(hipMalloc(&L.cost[0], (size_t)n_tiles * 4));
+    HIP_TRY(hipMalloc(&L.cost[1], (size_t)n_tiles * 4));
+    HIP_TRY(hipMalloc(&L.order, (size_t)n_tiles * 4));
+    L.sched_tiles = n_tiles;
+  }
+  if (L.sched_valid && L.sched_key == key) {
+    *cost_prev = L.cost[L.sched_cur ^ 1];
+    K.order = L.order;
+  }
+  K.tile_cost = L.cost[L.sched_cur];
+  L.sched_cur ^= 1;                // after this launch, cost[sched_cur ^ 1] is the buffer just written
+  L.sched_key = key;
+  L.sched_valid = true;
+  return 0;
+}
+
+// ---- a batch: the view table, on the launch's stream.  The pinned copy is rewritten only once the previous table's copy is done
+// (which waits for the launches queued before it on that stream, at most one launch ahead of this one) ----
+static int upload_view_table(LaunchState &L, RT_KParams &K, ViewBatch const *batch, hipStream_t stream) {
+  const int nv = batch->n;
+  if (L.views_cap < nv) {
+    (void)hipFree(L.views);
+    if (L.views_host) (void)hipHostFree(L.views_host);
+    L.views = L.views_host = nullptr;
+    L.views_cap = 0;
+    HIP_TRY(hipMalloc(&L.views, (size_t)nv * sizeof(RT_KView)));
+    HIP_TRY(hipHostMalloc(&L.views_host, (size_t)nv * sizeof(RT_KView), hipHostMallocDefault));
+    L.views_cap = nv;
+  }
+  if (!L.views_copied) HIP_TRY(hipEventCreateWithFlags(&L.views_copied, hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(L.views_copied));
+  for (int v = 0; v < nv; v++) {
+    RT_KView &r = L.views_host[v];
+    memset(&r, 0, sizeof r);
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 4; j++) r.cam[i][j] = batch->views[v].camera.view_matrix.rows[i][j];
+    r.focal_length = batch->views[v].camera.focal_length;
+    r.seed = batch->views[v].seed;
+  }
+  HIP_TRY(hipMemcpyAsync(L.views, L.views_host, (size_t)nv * sizeof(RT_KView), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(L.views_copied, stream));
+  K.views = L.views;
   return 0;
 }
 
@@ -105,208 +205,100 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   K.counters = L.counters;
   K.work_head = L.work_head;
   D.last_counters = L.counters;
-  // 5 = the tile-stream kernel (the product's only generation); 1-4 exist in the diagnostic build
-  int variant = knob_int("RT_KERNEL", 5);
-  if (variant < 1 || variant > 5) variant = 5;
   bool wavefront = false;
 #ifdef RT_DIAG_VARIANTS
-  wavefront = (g_pipeline.load() == 1 || knob_is("RT_PIPELINE", "wf")) && variant == 5;
+  wavefront = g_pipeline.load() == 1 || knob_is("RT_PIPELINE", "wf");
 #endif
-  if (batch && (variant != 5 || wavefront))
-    return rt_fail("view batch: a batch of views needs the tile-stream path kernel (%s is set)",
-                   wavefront ? "the wavefront pipeline" : "another kernel generation, RT_KERNEL");
+  if (batch && wavefront) return rt_fail("view batch: a batch of views needs the tile-stream path kernel (the wavefront pipeline is set)");
 
-  // persistent grid: 16 waves per CU (4 per SIMD at <= 128 VGPRs), never more waves than work items
+  // persistent grid, one workgroup of wg_waves waves per CU (RT_WAVES_PER_CU: another number of waves per CU)
+  int wg_waves, smem;
+  launch_geometry(D, d, K, &wg_waves, &smem);
   int waves_per_cu = knob_int("RT_WAVES_PER_CU", 0);
-  const bool waves_per_cu_default = waves_per_cu <= 0;
-  if (waves_per_cu_default) waves_per_cu = 16;
-  int wg_waves = 16;                 // waves per workgroup of the tile-stream kernel: 8 / 12 / 16, chosen below
-  int n_waves = D.num_cus * waves_per_cu;
-  if (n_waves > K.n_work && K.n_work > 0) n_waves = K.n_work;
+  if (waves_per_cu <= 0) waves_per_cu = wg_waves;
   K.sched_thresh = knob_int("RT_SCHED_THRESH", 48);
   if (K.sched_thresh < 1 || K.sched_thresh > 64) K.sched_thresh = 48;
-  // dynamic LDS per workgroup: per wave (perm stack: depth x 256 B, accumulator tile: 1536 B) and as many leading BVH
-  // nodes (level order) as fit in the 160 KB of a CU at 208 B each
-  const int lds_limit = 160 * 1024 - 64;      // (- the kernel's static LDS: the 32-byte sRGB scale table, rt_dev.hip.h rt_pow24_lds)
-  int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
-  int smem = 0;
-  K.n_lds_nodes = 0;
-  if (variant == 2) {
-    smem = 4 * per_wave;
-  } else if (variant != 1) {
-    // Workgroup size by the size of the launch (round 5, profiles/r05_small_launch.md section 3).  A launch ends with every wave
-    // running the bounce chains of its last paths on thinning lanes, and at four waves per SIMD those thin waves are ISSUE-bound:
-    // with two waves per SIMD a bounce of such a chain takes half the time.  A launch with little work per wave slot is mostly
-    // that tail -- config #1: 0.58 ms with 16-wave workgroups, 0.41 with 8 -- one with much work needs all four waves per SIMD
-    // for its body (the driver's default frame: 2.60 / 2.89 / 3.48 ms with 16 / 12 / 8).  One workgroup per CU either way (the
-    // tree fills the LDS).  Measured crossovers, in wave-fulls of paths per slot of the 16-wave grid: tower 640x360x16 (14) 0.91 /
-    // 0.76 / 0.69 ms, spheres 512^2 x 16 (16) 0.83 / 0.74 / 0.75, helmet 512^2 x 16 (16) 1.23 / 1.17 / 1.41, 64 and more: 16 wins.
-    int waves_per_block = 16;
-    if (variant == 5) {
-      const int64_t paths = (int64_t)K.n_local_chunks * 1024 * (int64_t)(K.sample_end - K.sample_first) * nv;
-      int64_t per_slot = paths / ((int64_t)D.num_cus * 16 * 64);
-      // (a depth-0 scene -- one leaf group, no node blocks -- traces a ray in a quarter of the instructions: its launches are as
-      //  short as launches a quarter their size; quad 256^2 / 512^2 / 768^2 / 1024^2 x 64 spp: best with 8 / 12 / 12 / 16 waves,
-      //  0.43 / 0.90 / 1.62 / 2.43 ms against 0.59 / 0.99 / 1.67 / 2.43 with 16, gpurun_out/r05s/wg.md)
-      if (K.depth == 0) per_slot /= 4;
-      waves_per_block = per_slot < 12 ? 8 : (per_slot < 40 ? 12 : 16);
-      const int v = knob_int("RT_WG_WAVES", 0);
-      if (v == 8 || v == 12 || v == 16) waves_per_block = v;
-      if (waves_per_cu_default) waves_per_cu = waves_per_block;
-      n_waves = D.num_cus * waves_per_cu;
-      if (n_waves > K.n_work && K.n_work > 0) n_waves = K.n_work;
-    }
-    wg_waves = waves_per_block;
-    int room = (lds_limit - waves_per_block * per_wave) / 208;
-    if (room < 0) room = 0;
-    K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
-    if (variant == 5 && !d->boxes_ordered) K.n_lds_nodes = 0;      // (the tile-stream kernel's LDS node blocks assume min <= max)
-    int v = knob_int("RT_LDS_NODES", K.n_lds_nodes);
-    if (v >= 0 && v < K.n_lds_nodes) K.n_lds_nodes = v;
-    smem = K.n_lds_nodes * 208 + waves_per_block * per_wave;
-  }
+  K.drain_thresh = knob_int("RT_DRAIN_THRESH", K.sched_thresh);
+  if (K.drain_thresh < 1 || K.drain_thresh > 64) K.drain_thresh = K.sched_thresh;
 
-  // ---- schedule feedback: visit expensive tiles first (costs = rays per tile of the previous launch of this view) ----
-  K.order = nullptr;
-  K.tile_cost = nullptr;
-  K.n_tiles = K.n_local_chunks * 16 * nv;      // (a batch: the tiles of view v are [v * tiles_per_view, (v + 1) * tiles_per_view))
   const uint32_t *cost_prev = nullptr;
-  if (variant != 1 && !knob_is("RT_ORDER", "identity") && K.n_tiles > 0) {
-    const int n_tiles = K.n_tiles;
-    // the costs of a launch are reusable by a launch of the same frame shape, partition and bounce limit -- NOT only of the same
-    // view: for a camera that moves between frames the previous view's costs are still a better guide than none (helmet, a rotation
-    // of 0.5 / 2 / 10 degrees per frame: -0.7 / -0.8 / -0.2 % kernel time at 256 spp, -2.3 % at 1024^2 x 64 spp against the identity
-    // order, tools/exp_moving.py, profiles/r05_experiments.md section 4), and an order is only ever a schedule, never a pixel
-    uint64_t key = 1469598103934665603ull;
-    auto mix = [&key](const void *ptr, size_t n) {
-      const unsigned char *b = (const unsigned char *)ptr;
-      for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; }
-    };
-    int32_t ids[6] = {K.width, K.height, K.rank, K.world, K.max_bounces, n_tiles};
-    mix(ids, sizeof ids);
-    if (L.sched_tiles != n_tiles) {
-      (void)hipFree(L.cost[0]); (void)hipFree(L.cost[1]); (void)hipFree(L.order);
-      L.cost[0] = L.cost[1] = L.order = nullptr;
-      L.sched_tiles = 0;
-      L.sched_valid = false;
-      HIP_TRY(hipMalloc(&L.cost[0], (size_t)n_tiles * 4));
-      HIP_TRY(hipMalloc(&L.cost[1], (size_t)n_tiles * 4));
-      HIP_TRY(hipMalloc(&L.order, (size_t)n_tiles * 4));
-      L.sched_tiles = n_tiles;
-    }
-    if (L.sched_valid && L.sched_key == key) {
-      cost_prev = L.cost[L.sched_cur ^ 1];
-      K.order = L.order;
-    }
-    K.tile_cost = L.cost[L.sched_cur];
-    L.sched_cur ^= 1;                // after this launch, cost[sched_cur ^ 1] is the buffer just written
-    L.sched_key = key;
-    L.sched_valid = true;
-  }
+  if (schedule_feedback(L, K, &cost_prev) != 0) return -1;
 
-  if (variant == 5) {
-    // unit = 2 neighbouring pixels x `slab` samples, default 64 (128 paths, pixel-major: the 64 lanes of a wave sit on one
-    // pixel, then on its neighbour); it is also the granularity at which waves share a tile at the end of a launch.
-    // Measured, helmet frame / rank 0 of 8: 32 samples 36.9 / 5.39 ms, 64 36.15 / 5.31, 128 36.6.
-    const int n_samples = K.sample_end - K.sample_first;
-    int cs = p->slab > 0 ? p->slab : 64;
-    int cshift = 0;
-    while ((1 << cshift) < cs && (1 << cshift) < n_samples) cshift++;
-    K.chunk_shift = cshift;
-    K.n_sample_blocks = (n_samples + (1 << cshift) - 1) >> cshift;
-    K.n_chunks_tile = 32 * K.n_sample_blocks;          // units: 8 rows x sample blocks x 4 pixel pairs
-    K.drain_thresh = knob_int("RT_DRAIN_THRESH", K.sched_thresh);
-    if (K.drain_thresh < 1 || K.drain_thresh > 64) K.drain_thresh = K.sched_thresh;
-    if (L.tile_next_n < K.n_tiles) {
-      (void)hipFree(L.tile_next);
-      L.tile_next = nullptr;
-      L.tile_next_n = 0;
-      // [n_tiles] chunk counters, then [ceil(n_tiles / 64)] open-tile counts of the groups
-      HIP_TRY(hipMalloc(&L.tile_next, ((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)) * 4));
-      L.tile_next_n = K.n_tiles;
-    }
-    K.tile_next = L.tile_next;
-    K.open_groups = L.tile_next + L.tile_next_n;
-    int64_t chunks = (int64_t)K.n_tiles * K.n_chunks_tile;
-    n_waves = D.num_cus * waves_per_cu;
-    if ((int64_t)n_waves > chunks) n_waves = (int)chunks;
-    // units per atomic: 1 unit of 128 paths (what a wave still holds when the launch runs dry is its tail); smaller
-    // units (few samples) are taken in pairs.  Measured with units of 128 paths: frame 1 -> 36.25 ms, 2 -> 36.4, 4 -> 37.2.
-    K.grab_max = (cshift >= 6 || (int64_t)K.n_tiles < (int64_t)2 * n_waves) ? 1 : 2;
-    {
-      int v = knob_int("RT_GRAB", 0);
-      if (v == 1 || v == 2 || v == 4) K.grab_max = v;
-    }
-    K.pyr_nodes = knob_int("RT_PYRAMID", 1) ? K.n_lds_nodes : 0;
-    // Leaf blocks with the short reciprocal (rcp_exact, rt_dev.hip.h): equal to the IEEE division while every triangle
-    // determinant |e1 . (d x e2)| <= 6 D E^2 stays below 2^102.  E = largest edge component of the scene; D = largest
-    // component of a ray direction: <= 3 max|view matrix entry| for camera rays (the direction is normalised before the
-    // matrix is applied), < 2 for the normalised directions that shading emits.  E <= 2^38 and matrix entries <= 2^16
-    // give 6 D E^2 < 2^97.  Anything else -- or a NaN -- renders with the kernel that divides.
-    float cam_max = 0.0f;
-    for (int v = 0; v < nv; v++)                 // (a batch: over the cameras of all views)
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          float m = fabsf(batch ? batch->views[v].camera.view_matrix.rows[i][j] : K.cam[i][j]);
-          if (!(m <= cam_max)) cam_max = m;
-        }
-    K.short_div = (d->max_edge <= 0x1p38f && cam_max <= 0x1p16f) ? 1 : 0;
-    if (knob_int("RT_SHORT_DIV", 1) == 0) K.short_div = 0;
-    // hits parked until a dense shade block can be made of them: RT_PARK_RECORD_DWORDS = 18 fields x 128 records per wave
-    K.park = nullptr;
-    if (!wavefront && knob_int("RT_PARK", 1) != 0 && K.max_bounces < (1 << 26)) {      // (a parked record keeps the bounce count in 26 bits)
-      const int grid_waves = (n_waves + wg_waves - 1) / wg_waves * wg_waves;         // whole workgroups are launched
-      if (L.park_waves < grid_waves) {
-        (void)hipFree(L.park);
-        L.park = nullptr;
-        L.park_waves = 0;
-        const size_t slice_bytes = (size_t)RT_PARK_RECORD_DWORDS * 4;      // a wave's slice: 18 fields x 128 records (rt_device.h)
-        HIP_TRY(hipMalloc(&L.park, (size_t)grid_waves * slice_bytes));
-        L.park_waves = grid_waves;
+  // unit = 2 neighbouring pixels x `slab` samples, default 64 (128 paths, pixel-major: the 64 lanes of a wave sit on one
+  // pixel, then on its neighbour); it is also the granularity at which waves share a tile at the end of a launch.
+  // Measured, helmet frame / rank 0 of 8: 32 samples 36.9 / 5.39 ms, 64 36.15 / 5.31, 128 36.6.
+  const int n_samples = K.sample_end - K.sample_first;
+  const int cs = p->slab > 0 ? p->slab : 64;
+  int cshift = 0;
+  while ((1 << cshift) < cs && (1 << cshift) < n_samples) cshift++;
+  K.chunk_shift = cshift;
+  K.n_sample_blocks = (n_samples + (1 << cshift) - 1) >> cshift;
+  K.n_chunks_tile = 32 * K.n_sample_blocks;          // units: 8 rows x sample blocks x 4 pixel pairs
+  if (L.tile_next_n < K.n_tiles) {
+    (void)hipFree(L.tile_next);
+    L.tile_next = nullptr;
+    L.tile_next_n = 0;
+    // [n_tiles] chunk counters, then [ceil(n_tiles / 64)] open-tile counts of the groups
+    HIP_TRY(hipMalloc(&L.tile_next, ((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)) * 4));
+    L.tile_next_n = K.n_tiles;
+  }
+  K.tile_next = L.tile_next;
+  K.open_groups = L.tile_next + L.tile_next_n;
+  // never more waves than units
+  const int64_t n_units = (int64_t)K.n_tiles * K.n_chunks_tile;
+  int n_waves = D.num_cus * waves_per_cu;
+  if ((int64_t)n_waves > n_units) n_waves = (int)n_units;
+  // units per atomic: 1 unit of 128 paths (what a wave still holds when the launch runs dry is its tail); smaller
+  // units (few samples) are taken in pairs.  Measured with units of 128 paths: frame 1 -> 36.25 ms, 2 -> 36.4, 4 -> 37.2.
+  K.grab_max = (cshift >= 6 || (int64_t)K.n_tiles < (int64_t)2 * n_waves) ? 1 : 2;
+  {
+    int v = knob_int("RT_GRAB", 0);
+    if (v == 1 || v == 2 || v == 4) K.grab_max = v;
+  }
+  K.pyr_nodes = knob_int("RT_PYRAMID", 1) ? K.n_lds_nodes : 0;
+  // Leaf blocks with the short reciprocal (rcp_exact, rt_dev.hip.h): equal to the IEEE division while every triangle
+  // determinant |e1 . (d x e2)| <= 6 D E^2 stays below 2^102.  E = largest edge component of the scene; D = largest
+  // component of a ray direction: <= 3 max|view matrix entry| for camera rays (the direction is normalised before the
+  // matrix is applied), < 2 for the normalised directions that shading emits.  E <= 2^38 and matrix entries <= 2^16
+  // give 6 D E^2 < 2^97.  Anything else -- or a NaN -- renders with the kernel that divides.
+  float cam_max = 0.0f;
+  for (int v = 0; v < nv; v++)                 // (a batch: over the cameras of all views)
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        float m = fabsf(batch ? batch->views[v].camera.view_matrix.rows[i][j] : K.cam[i][j]);
+        if (!(m <= cam_max)) cam_max = m;
       }
-      K.park = L.park;
+  K.short_div = (d->max_edge <= 0x1p38f && cam_max <= 0x1p16f) ? 1 : 0;
+  if (knob_int("RT_SHORT_DIV", 1) == 0) K.short_div = 0;
+  // hits parked until a dense shade block can be made of them: RT_PARK_RECORD_DWORDS = 18 fields x 128 records per wave
+  K.park = nullptr;
+  if (!wavefront && knob_int("RT_PARK", 1) != 0 && K.max_bounces < (1 << 26)) {      // (a parked record keeps the bounce count in 26 bits)
+    const int grid_waves = (n_waves + wg_waves - 1) / wg_waves * wg_waves;         // whole workgroups are launched
+    if (L.park_waves < grid_waves) {
+      (void)hipFree(L.park);
+      L.park = nullptr;
+      L.park_waves = 0;
+      const size_t slice_bytes = (size_t)RT_PARK_RECORD_DWORDS * 4;      // a wave's slice: 18 fields x 128 records (rt_device.h)
+      HIP_TRY(hipMalloc(&L.park, (size_t)grid_waves * slice_bytes));
+      L.park_waves = grid_waves;
     }
+    K.park = L.park;
   }
 
-  // ---- a batch: the view table, on the launch's stream.  The pinned copy is rewritten only once the previous table's copy is done
-  // (which waits for the launches queued before it on that stream, at most one launch ahead of this one) ----
   K.views = nullptr;
-  if (batch) {
-    if (L.views_cap < nv) {
-      (void)hipFree(L.views);
-      if (L.views_host) (void)hipHostFree(L.views_host);
-      L.views = L.views_host = nullptr;
-      L.views_cap = 0;
-      HIP_TRY(hipMalloc(&L.views, (size_t)nv * sizeof(RT_KView)));
-      HIP_TRY(hipHostMalloc(&L.views_host, (size_t)nv * sizeof(RT_KView), hipHostMallocDefault));
-      L.views_cap = nv;
-    }
-    if (!L.views_copied) HIP_TRY(hipEventCreateWithFlags(&L.views_copied, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(L.views_copied));
-    for (int v = 0; v < nv; v++) {
-      RT_KView &r = L.views_host[v];
-      memset(&r, 0, sizeof r);
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 4; j++) r.cam[i][j] = batch->views[v].camera.view_matrix.rows[i][j];
-      r.focal_length = batch->views[v].camera.focal_length;
-      r.seed = batch->views[v].seed;
-    }
-    HIP_TRY(hipMemcpyAsync(L.views, L.views_host, (size_t)nv * sizeof(RT_KView), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(L.views_copied, stream));
-    K.views = L.views;
-  }
+  if (batch && upload_view_table(L, K, batch, stream) != 0) return -1;
 
   // ---- ONE preparation launch: counters, work head, tile / unit counters, this launch's cost buffer, tile order ----
   {
-    int rc2 = rt_launch_prepare(K.n_tiles, variant == 5 ? K.tile_next : nullptr, variant == 5 ? K.open_groups : nullptr, L.counters,
-                                L.work_head, K.tile_cost, cost_prev, cost_prev ? L.order : nullptr, stream);
+    int rc2 = rt_launch_prepare(K.n_tiles, K.tile_next, K.open_groups, L.counters, L.work_head, K.tile_cost, cost_prev,
+                                cost_prev ? L.order : nullptr, stream);
     if (rc2 != 0) return rt_fail("prepare kernel launch failed: %s", hipGetErrorString((hipError_t)rc2));
   }
   if (ev_prep) HIP_TRY(hipEventRecord(ev_prep, stream));
-  if (K.n_work == 0) return 0;
+  if (n_units == 0) return 0;      // nothing to render: this rank owns no chunk, or the sample range is empty
 
   K.wave_times = nullptr;
-  if (variant == 4 || (variant == 5 && knob_set("RT_WAVE_TIMES"))) {      // wave timeline (tools/exp_waves.py)
+  if (knob_set("RT_WAVE_TIMES")) {      // wave timeline (tools/exp_waves.py)
     if (!D.ws.wave_times) HIP_TRY(hipMalloc(&D.ws.wave_times, (size_t)65536 * 3 * 8));
     HIP_TRY(hipMemsetAsync(D.ws.wave_times, 0, (size_t)65536 * 3 * 8, stream));
     K.wave_times = D.ws.wave_times;
@@ -329,7 +321,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   } else
 #endif
   {
-    int rc = rt_launch_path_kernel(&K, n_waves, variant, smem, wg_waves, stream);
+    int rc = rt_launch_path_kernel(&K, n_waves, smem, wg_waves, stream);
     if (rc != 0) return rt_fail("path kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
   }
   HIP_TRY(hipEventRecord(D.ws.ev1[slot], stream));

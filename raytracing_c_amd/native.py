@@ -173,7 +173,6 @@ def _declare_diag(d):
     d.rt_get_pipeline.restype = C.c_int32
     d.rt_set_wavefront_capacity.argtypes = [C.c_int64]
     d.rt_set_wavefront_capacity.restype = None
-    d.rt_get_sched_stats.argtypes = [vp]
     d.rt_get_wave_times.argtypes = [vp, C.c_int32]
     d.rt_get_ledger.argtypes = [vp, C.c_int32]
     d.rt_diag_multi_fault.argtypes = [C.c_int32, C.c_int32]

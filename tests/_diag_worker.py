@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Worker of tests/test_gpu_diag.py and tests/test_gpu_contract_v1.py: runs in its OWN process with RT_LIB_PATH = librt_hip_diag.so
-(or librt_hip_v1.so, the product under numeric contract v1) -- the diagnostic build carries the
-superseded kernel generations and reads the RT_* experiment knobs from the environment at every launch) and renders a
-list of jobs.  stdin: JSON list of {config, w, h, s, b, env: {...}, slabs: [...]}; stdout: one JSON line per job with the
+(or librt_hip_v1.so, the product under numeric contract v1) -- the diagnostic build reads the RT_* experiment knobs from
+the environment at every launch -- and renders a list of jobs.  stdin: JSON list of {config, w, h, s, b, env: {...}, slabs: [...]}; stdout: one JSON line per job with the
 sha256 of the radiance sums per slab and the counters of the last launch."""
 import ctypes as C
 import hashlib

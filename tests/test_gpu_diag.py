@@ -1,6 +1,6 @@
-"""The diagnostic build (librt_hip_diag.so, `make -C raytracing_c_amd/csrc diag`): the superseded kernel generations
-(RT_KERNEL=1..4) and the RT_* scheduling knobs exist ONLY there -- the product library librt_hip.so has one path kernel and
-reads no such variable -- and every one of them must still give the oracle's radiance sums and counters bit for bit.
+"""The diagnostic build (librt_hip_diag.so, `make -C raytracing_c_amd/csrc diag`): it links the product's kernel object, and the
+RT_* scheduling knobs exist ONLY there -- the product library librt_hip.so reads no such variable -- and every one of them must
+still give the oracle's radiance sums and counters bit for bit.  Neither library has another path kernel than the tile-stream one.
 The diagnostic library is loaded in a process of its own (tests/_diag_worker.py, RT_LIB_PATH)."""
 import hashlib
 import json
@@ -15,11 +15,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIAG = os.path.join(ROOT, "raytracing_c_amd", "librt_hip_diag.so")
 
-VARIANT_JOBS = [dict(config=name, w=w, h=h, s=s, b=b, env={"RT_KERNEL": str(v)}, slabs=[0])
-                for v in (1, 2, 3, 5) for (name, w, h, s, b) in (("helmet", 96, 54, 6, 8), ("quad", 40, 40, 4, 3))]
+# the path kernel with no knob set (ids k5-*: it was generation 5 while generations 1-3 still had jobs here)
+VARIANT_JOBS = [dict(config=name, w=w, h=h, s=s, b=b, env={}, slabs=[0])
+                for (name, w, h, s, b) in (("helmet", 96, 54, 6, 8), ("quad", 40, 40, 4, 3))]
 KNOBS = [{"RT_SCHED_THRESH": "1"}, {"RT_SCHED_THRESH": "64"}, {"RT_LDS_NODES": "9"}, {"RT_LDS_NODES": "0"}, {"RT_WAVES_PER_CU": "1"},
          {"RT_ORDER": "identity"}, {"RT_GRAB": "1"}, {"RT_GRAB": "4"}, {"RT_DRAIN_THRESH": "1"}, {"RT_PYRAMID": "0"},
-         {"RT_SHORT_DIV": "0"}, {"RT_PARK": "0"}, {"RT_KERNEL": "3", "RT_SCHED_THRESH": "16"},
+         {"RT_SHORT_DIV": "0"}, {"RT_PARK": "0"},
          {"RT_WG_WAVES": "8"}, {"RT_WG_WAVES": "12"}, {"RT_WG_WAVES": "16"},      # the three workgroup sizes the product picks from by launch size
          {"RT_PIPELINE": "wf"}, {"RT_PIPELINE": "wf", "RT_WF_GEOMETRY": "1"}, {"RT_PIPELINE": "wf", "RT_WF_GEOMETRY": "2", "RT_LDS_NODES": "40"}]
 KNOB_JOBS = [dict(config="helmet", w=80, h=45, s=5, b=8, env=k, slabs=[0, 1, 4, 64]) for k in KNOBS]
@@ -50,9 +51,9 @@ def _want(job):
     return hashlib.sha256(want["accum"].tobytes()).hexdigest(), [want["counters"][k] for k in ("rays", "node_visits", "leaf_visits", "shades")]
 
 
-@pytest.mark.parametrize("job", VARIANT_JOBS, ids=[f"k{j['env']['RT_KERNEL']}-{j['config']}" for j in VARIANT_JOBS])
+@pytest.mark.parametrize("job", VARIANT_JOBS, ids=[f"k5-{j['config']}" for j in VARIANT_JOBS])
 def test_every_kernel_generation_is_bit_exact(oracle, diag_results, job):
-    """RT_KERNEL=1 plain while-while kernel, 2 phase-scheduled, 3 phase-scheduled + BVH top in LDS, 5 tile streams (the product's)."""
+    """The tile-stream kernel through the diagnostic library, no knob set: the oracle's radiance sums and counters."""
     got = diag_results[json.dumps(job, sort_keys=True)]
     assert got["error"] is None, got["error"]
     digest, counters = _want(job)
@@ -87,3 +88,10 @@ def test_product_library_ignores_the_experiment_knobs(oracle, monkeypatch):
         monkeypatch.setenv(k, v)
     got = rt.render_frame(hs, 64, 36, 4, 8, want_accum=True)
     assert np.array_equal(got["accum"], want["accum"])
+
+
+def test_diagnostic_library_has_no_other_path_kernel():
+    """The superseded kernel generations and their switch are gone from the diagnostic library too."""
+    raw = open(DIAG, "rb").read()
+    for name in (b"RT_KERNEL", b"rt_path_kernel_sched"):
+        assert name not in raw, name

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """GPU experiment: A/B of kernel variants / knobs in ONE process on one box (interleaved, so box-to-box and clock
-differences cancel).  Each arm = a label and environment settings read per launch by librt_hip.so (RT_KERNEL, ...).
+differences cancel).  Each arm = a label and environment settings read per launch by the diagnostic library (RT_SCHED_THRESH, RT_WG_WAVES, ...).
 Prints the mean kernel time of the whole helmet frame (config #3), of ranks 0,3,5 of the 8-GPU partition, and the
 sha256 of the accumulation buffer (every arm must print the same one).
-    python tools/exp_kernels.py "k3:RT_KERNEL=3" "k5:RT_KERNEL=5" ...      [RT_EXP_REPS=4] [RT_EXP_SPP=256]"""
+    python tools/exp_kernels.py "t48:RT_SCHED_THRESH=48" "t56:RT_SCHED_THRESH=56" ...      [RT_EXP_REPS=4] [RT_EXP_SPP=256]"""
 import ctypes as C
 import hashlib
 import os

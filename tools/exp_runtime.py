@@ -38,15 +38,6 @@ def main():
     if "auto" in knobs:     # the library's own choice of the item size (what bench.py runs); used by tools/exp_ab.sh
         print(f"slab auto: {run(0, 4):8.3f} ms", flush=True)
         print(f"slab auto: {run(0, 4):8.3f} ms", flush=True)
-    if "kernel" in knobs:
-        for kv in (1, 2, 3):
-            os.environ["RT_KERNEL"] = str(kv)
-            for th in ((32,) if kv == 1 else (32, 40, 48, 56)):
-                os.environ["RT_SCHED_THRESH"] = str(th)
-                for slab in (8, 16, 32):
-                    print(f"kernel {kv} thresh {th:2d} slab {slab:3d}: {run(slab, 4):8.3f} ms", flush=True)
-        os.environ.pop("RT_KERNEL")
-        os.environ.pop("RT_SCHED_THRESH")
     if "thresh" in knobs:   # lanes waiting for the shade / environment / regenerate block that trigger it
         for th in (32, 40, 48, 56):
             os.environ["RT_SCHED_THRESH"] = str(th)
