@@ -17,16 +17,6 @@
 #include "rt_device.h"
 #include "../../include/rt_math.h"
 
-#ifndef RT_SCALAR_TEX
-#define RT_SCALAR_TEX 1
-#endif
-#ifndef RT_SCALAR_MATS
-#define RT_SCALAR_MATS 1
-#endif
-#ifndef RT_LEAF_PAIRS
-#define RT_LEAF_PAIRS 0      // 1: leaf tiles fetched by lane pairs (leaf_test_pair) -- bit-exact, measured slower (profiles/r03_experiments.md)
-#endif
-
 #define RT_BLOCK_WAVES 4
 #define RT_BLOCK_THREADS (RT_BLOCK_WAVES * 64)
 
@@ -54,8 +44,6 @@ struct Ray3 {
 __device__ __forceinline__ rt_v3 slab_bias3(const Ray3 &r) {
 #ifdef RT_MATH_NO_FMA
   return rt_v3_make(0.0f, 0.0f, 0.0f);           // contract v1: rt_slab_t_fast() does not read it
-#elif defined(RT_BIAS_PLAIN)
-  return rt_v3_make(rt_slab_bias(r.o.x, r.inv_x), rt_slab_bias(r.o.y, r.inv_y), rt_slab_bias(r.o.z, r.inv_z));
 #else
   float px, py, pz;
   asm volatile("v_mul_f32 %0, %1, %2" : "=v"(px) : "v"(r.o.x), "v"(r.inv_x));
@@ -247,7 +235,7 @@ __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &
   } else if (MODE == NODE_LDS_ORDERED) {
     static_assert(FAST || MODE != NODE_LDS_ORDERED, "the ordered LDS form is for FAST rays only");
     // Near and far plane of every slab picked by ADDRESS from the sign of the reciprocal direction instead of by min / max
-    // of the two distances: with min <= max in every box (checked at upload, rt_api.cpp) and NaN-free operands,
+    // of the two distances: with min <= max in every box (checked at upload, rt_residency.cpp) and NaN-free operands,
     // t(mn) <= t(mx) for inv > 0 and >= for inv < 0 -- rounding is monotonic, for (p - o) * inv and for fma(p, inv, bias)
     // alike -- so the picked distance IS the minimum (maximum); for inv = 0 both are equal.  Six min / max fewer per child.
     const char *nbase = reinterpret_cast<const char *>(lds_nodes + lds_node_f4(node));
@@ -328,15 +316,11 @@ __device__ __forceinline__ float rcp_exact(float x) {
 // u, v or t fails one of the five comparisons or is not below `best`, a NaN t is not below `best`; with inv_det = 0 the
 // distance is 0 < epsilon; with NaN everything is NaN and t < best is false -- so ray_triangles_hit_8's outcome is the same.
 __device__ __forceinline__ float rcp_leaf(float x) {
-#ifdef RT_LEAF_SANITISE
-  return rcp_exact(x);
-#else
   float xs = x * 0x1p24f;
   float y = __builtin_amdgcn_rcpf(xs);
   float e = __builtin_fmaf(-xs, y, 1.0f);
   float z = __builtin_fmaf(e, y, y);
   return z * 0x1p24f;
-#endif
 }
 __device__ __forceinline__ bool rcp_exact_outside(float x) {
   return __builtin_fabsf(x) >= RT_SHORT_DIV_MAX_X && __builtin_fabsf(x) < RT_INF;
@@ -384,7 +368,7 @@ __device__ __forceinline__ float tri_test(const Ray3 &r, float ax, float ay, flo
 }
 
 // leaf_test<false>() with 1 / det by rcp_exact(): same bits as long as every |det| < 2^102, which the host guarantees
-// from the scene's edge lengths and the camera matrix before it selects the kernel built on this (rt_api.cpp).
+// from the scene's edge lengths and the camera matrix before it selects the kernel built on this (rt_launch.cpp).
 __device__ __forceinline__ bool leaf_test_short_div(const RT_KParams &P, const Ray3 &r, int g, HitRec &hit) {
   float best = RT_INF, bu = 0.0f, bv = 0.0f;
   int   bi = 0;
@@ -410,16 +394,10 @@ __device__ __forceinline__ bool leaf_test_short_div(const RT_KParams &P, const R
       float v = inv_det * rt_v3_dot(r.d, sxe1);
       float t = inv_det * rt_v3_dot(edge2, sxe1);
       bool miss = (u < -RT_EPS) || (u > 1.0f + RT_EPS) || (v < -RT_EPS) || (u + v > 1.0f + RT_EPS) || (t < RT_EPS);
-#ifdef RT_LEAF_SANITISE
-      float dist = miss ? RT_INF : t;
-      dist = (dist > 0.0f) ? dist : RT_INF;          // NaN -> +inf (min_f32x8)
-      if (dist < best) { best = dist; bi = h * 4 + k; bu = u; bv = v; }   // lowest lane wins ties
-#else
       // min_f32x8's sanitising (lanes <= epsilon or NaN -> +inf, raytracer.c:15-32) folded into the comparison: a triangle
       // that is not a miss has t >= epsilon or t NaN, `best` is never NaN, and NaN < best is false like +inf < best --
       // the same triangle wins with the same t, three vector instructions fewer per triangle
       if (!miss && t < best) { best = t; bi = h * 4 + k; bu = u; bv = v; }   // lowest lane wins ties
-#endif
     }
   }
   if (best < hit.t) {
@@ -430,82 +408,6 @@ __device__ __forceinline__ bool leaf_test_short_div(const RT_KParams &P, const R
     return true;
   }
   return false;
-}
-
-__device__ __forceinline__ int lane_now();
-
-// ---- leaf block with the tile fetched by lane PAIRS --------------------------------------------------------------
-// What a vector load costs the CU's memory pipe is set by the number of distinct cache lines its 64 lanes touch -- about
-// 1.24 cycles per line (tools/exp/leaf_fetch_bench.hip: 18 x dwordx4 from a different 288-byte tile per lane hold the
-// pipe for 1 430 cycles, the 650 VALU instructions of the block hold the four SIMDs for 325) -- and every one of a lane's
-// 18 loads touches its own line.  Here lanes 2k and 2k+1 share the work on BOTH their rays: each load instruction takes
-// the two 16-byte halves of one tile row (32 contiguous bytes, one line) for the pair, so an instruction touches 32
-// lines instead of 64 (measured 633 cycles per block); lane 2k tests triangles 0-3 of its own leaf and of its partner's,
-// lane 2k+1 triangles 4-7 of both; the partner's result for my ray comes back through four DPP moves and is merged with
-// the reference's tie rule (lowest triangle index wins, raytracer.c:27-29).  Same 18 loads and 8 triangle tests per
-// lane, + 12 DPP moves and a merge; the arithmetic per triangle is tri_test()'s, bit for bit.
-__device__ __forceinline__ int dpp_swap1_i(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true); }
-__device__ __forceinline__ float dpp_swap1_f(float v) { return as_f(dpp_swap1_i(as_i(v))); }
-
-// best of the 4 triangles of half `h` of leaf group g for the ray (o, d): sanitised distance (+inf: none), u, v, index in the group
-template <bool SHORT_DIV>
-__device__ __forceinline__ void leaf_half_test(const float *leaves, rt_v3 o, rt_v3 d, int g, int h, float &best, float &bu, float &bv, int &bi) {
-  best = RT_INF; bu = 0.0f; bv = 0.0f; bi = 0;
-  const float *lb = leaves + (size_t)g * 72 + h * 4;
-  float4 x0 = ld4(lb, 0), x1 = ld4(lb, 2), x2 = ld4(lb, 4);
-  float4 y0 = ld4(lb, 6), y1 = ld4(lb, 8), y2 = ld4(lb, 10);
-  float4 z0 = ld4(lb, 12), z1 = ld4(lb, 14), z2 = ld4(lb, 16);
-  float ax[4] = {x0.x, x0.y, x0.z, x0.w}, bx[4] = {x1.x, x1.y, x1.z, x1.w}, cx[4] = {x2.x, x2.y, x2.z, x2.w};
-  float ay[4] = {y0.x, y0.y, y0.z, y0.w}, by[4] = {y1.x, y1.y, y1.z, y1.w}, cy[4] = {y2.x, y2.y, y2.z, y2.w};
-  float az[4] = {z0.x, z0.y, z0.z, z0.w}, bz[4] = {z1.x, z1.y, z1.z, z1.w}, cz[4] = {z2.x, z2.y, z2.z, z2.w};
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    rt_v3 edge1 = rt_v3_make(bx[k], by[k], bz[k]), edge2 = rt_v3_make(cx[k], cy[k], cz[k]);
-    rt_v3 rxe2 = rt_v3_cross(d, edge2);
-    float det = rt_v3_dot(edge1, rxe2);
-    float inv_det = SHORT_DIV ? rcp_exact(det) : 1.0f / det;
-    rt_v3 s = rt_v3_sub(o, rt_v3_make(ax[k], ay[k], az[k]));
-    rt_v3 sxe1 = rt_v3_cross(s, edge1);
-    float u = inv_det * rt_v3_dot(s, rxe2);
-    float v = inv_det * rt_v3_dot(d, sxe1);
-    float t = inv_det * rt_v3_dot(edge2, sxe1);
-    bool miss = (u < -RT_EPS) || (u > 1.0f + RT_EPS) || (v < -RT_EPS) || (u + v > 1.0f + RT_EPS) || (t < RT_EPS);
-    float dist = miss ? RT_INF : t;
-    dist = (dist > 0.0f) ? dist : RT_INF;          // NaN -> +inf (min_f32x8)
-    if (dist < best) { best = dist; bi = h * 4 + k; bu = u; bv = v; }   // lowest lane wins ties
-  }
-}
-
-// Called by ALL lanes of the wave (uniform control flow); `in_leaf`: this lane's ray wants leaf group g tested.
-template <bool SHORT_DIV>
-__device__ __forceinline__ bool leaf_test_pair(const RT_KParams &P, const Ray3 &r, int g, bool in_leaf, HitRec &hit) {
-  const int h = lane_now() & 1;
-  // the partner's ray and leaf
-  const bool p_act = dpp_swap1_i(in_leaf ? 1 : 0) != 0;
-  const int  pg = dpp_swap1_i(g);
-  const rt_v3 po = rt_v3_make(dpp_swap1_f(r.o.x), dpp_swap1_f(r.o.y), dpp_swap1_f(r.o.z));
-  const rt_v3 pd = rt_v3_make(dpp_swap1_f(r.d.x), dpp_swap1_f(r.d.y), dpp_swap1_f(r.d.z));
-  float bestA = RT_INF, uA = 0.0f, vA = 0.0f, bestB = RT_INF, uB = 0.0f, vB = 0.0f;
-  int   iA = 0, iB = 0;
-  if (in_leaf) leaf_half_test<SHORT_DIV>(P.leaves, r.o, r.d, g, h, bestA, uA, vA, iA);       // my half of my leaf
-  if (p_act) leaf_half_test<SHORT_DIV>(P.leaves, po, pd, pg, h, bestB, uB, vB, iB);          // my half of the partner's leaf
-  // the partner's half of MY leaf
-  const float bestP = dpp_swap1_f(bestB), uP = dpp_swap1_f(uB), vP = dpp_swap1_f(vB);
-  const int   iP = dpp_swap1_i(iB);
-  bool got = false;
-  if (in_leaf) {
-    // triangles 0-3 (lane 2k's half) come before 4-7 in the reference's scan: on equal distance the lower half wins
-    const bool take_p = h ? (bestP <= bestA) : (bestP < bestA);
-    const float best = take_p ? bestP : bestA;
-    if (best < hit.t) {
-      hit.t = best;
-      hit.tri = g * 8 + (take_p ? iP : iA);
-      hit.u = take_p ? uP : uA;
-      hit.v = take_p ? vP : vA;
-      got = true;
-    }
-  }
-  return got;
 }
 
 template <bool SCALAR>
@@ -646,7 +548,6 @@ __device__ __forceinline__ TexTaps tex_taps(const RT_DTexture &T, float tx, floa
   TexTaps t;
   t.a = px - (float)u;
   t.b = py - (float)v;
-#if RT_TEX_TILED
   // 4 x 4 tiles (rt_device.h): the neighbour to the right is the next texel of the tile, or the first of the tile's row in
   // the next tile (+ 16 - 3); the one below the next row of the tile, or the first row of the tile below; clamp to edge = 0
   const int du = (u + 1 < T.width) ? (((u & 3) == 3) ? 13 : 1) : 0;
@@ -655,14 +556,6 @@ __device__ __forceinline__ TexTaps tex_taps(const RT_DTexture &T, float tx, floa
   t.i10 = t.i00 + du;
   t.i01 = t.i00 + dv;
   t.i11 = t.i00 + du + dv;
-#else
-  int u2 = (u + 1 < T.width) ? u + 1 : u;
-  int v2 = (v + 1 < T.height) ? v + 1 : v;
-  t.i00 = u + T.stride * v;
-  t.i10 = u2 + T.stride * v;
-  t.i01 = u + T.stride * v2;
-  t.i11 = u2 + T.stride * v2;
-#endif
   return t;
 }
 __device__ __forceinline__ TexQuad tex_fetch(const uint32_t *tp, const TexTaps &t) {
@@ -679,21 +572,15 @@ __device__ __forceinline__ rt_v3 tex_combine(const TexQuad &q, const TexTaps &t)
 template <class PT>
 __device__ __forceinline__ rt_v3 tex_bilinear(const PT &P, int tex, float tx, float ty) {
   RT_DTexture T;
-#if RT_SCALAR_TEX
-  {
-    // the descriptor of a texture every lane of the block samples comes through the scalar cache (see shade())
-    const int t0 = __builtin_amdgcn_readfirstlane(tex);
-    if (__ballot(tex != t0) == 0ull) {
-      typedef const RT_DTexture __attribute__((address_space(4))) CT;
-      CT *tp = (CT *)(unsigned long long)(P.textures + t0);
-      T.offset = tp->offset; T.width = tp->width; T.height = tp->height; T.stride = tp->stride;
-    } else {
-      T = P.textures[tex];
-    }
+  // the descriptor of a texture every lane of the block samples comes through the scalar cache (see shade())
+  const int t0 = __builtin_amdgcn_readfirstlane(tex);
+  if (__ballot(tex != t0) == 0ull) {
+    typedef const RT_DTexture __attribute__((address_space(4))) CT;
+    CT *tp = (CT *)(unsigned long long)(P.textures + t0);
+    T.offset = tp->offset; T.width = tp->width; T.height = tp->height; T.stride = tp->stride;
+  } else {
+    T = P.textures[tex];
   }
-#else
-  T = P.textures[tex];
-#endif
   const TexTaps t = tex_taps(T, tx, ty);
   const TexQuad q = tex_fetch(P.texels + T.offset, t);
   return tex_combine(q, t);
@@ -722,9 +609,6 @@ __device__ __forceinline__ void pow24_lds_init(int tid) {        // before a __s
 
 template <bool POW24_LDS = false>
 __device__ __forceinline__ float srgb_to_linear_tex1(float x) {
-#ifdef RT_EXP_SRGB_IEEE
-  return rt_srgb_to_linear1(x);
-#endif
   const float c = 1.0f / 1.055f;
   float a = x + 0.055f;
   float q = a * c;
@@ -739,8 +623,6 @@ __device__ __forceinline__ float srgb_to_linear_tex1(float x) {
   else p = rt_pow24_core(b);
   if (!(b >= 0x1p-5f && b < 2.0f)) p = rt_powf(b, 2.4f);
   return p;
-#elif defined(RT_EXP_POW_PLAIN)
-  return rt_powf(__builtin_fmaf(r, c, q), 2.4f);
 #else
   // rt_powf(b, 2.4f) (rt_math.h) straight-line: its clamp of 2.4 log b to [-87, 87] as ONE v_med3_f32 (two compares and two
   // selects as written; equal for every operand that is not NaN, and log b is not NaN for b > 0), its `b > 0 else 0` as a
@@ -902,7 +784,6 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
                                       LaneCounters &cn) {
   float4 m0, m1, m2, m3, m4;
   RT_DTexture D[4];              // albedo, normal, metal_roughness, emission: embedded in the material record (rt_device.h)
-#if RT_SCALAR_MATS
   // one material for every lane of this block (the helmet has one material, most blocks of any scene have one): the
   // record -- parameters AND the descriptors of its four textures -- comes through the scalar cache in ONE round trip
   // (~100 cycles instead of a vector load's several hundred, and no second dependent load for the descriptors)
@@ -918,9 +799,7 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
     for (int k = 0; k < 4; k++) {
       D[k].offset = (uint32_t)as_i(sb[20 + 4 * k]); D[k].width = as_i(sb[21 + 4 * k]); D[k].height = as_i(sb[22 + 4 * k]); D[k].stride = as_i(sb[23 + 4 * k]);
     }
-  } else
-#endif
-  {
+  } else {
     const float *mb = P.mats + (size_t)mat * RT_MAT_FLOATS;
     m0 = ld4(mb, 0); m1 = ld4(mb, 1); m2 = ld4(mb, 2); m3 = ld4(mb, 3); m4 = ld4(mb, 4);
 #pragma unroll
@@ -932,20 +811,14 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
   int tex_albedo = as_i(m3.x), tex_normal = as_i(m3.y), tex_mr = as_i(m3.z), tex_em = as_i(m3.w);
   int kind = as_i(m4.x);
 
-  // RT_TEX_BATCH: how many of the material's four texture fetches have their loads in flight together.  1 = one after the
-  // other (four dependent round trips of four texels, round 3), 2 = normal + albedo, then metal-roughness + emission,
-  // 4 = all sixteen loads before the first is consumed.  Same arithmetic in every case.
-#ifndef RT_TEX_BATCH
-#define RT_TEX_BATCH 2
-#endif
+  // The material's four texture fetches go out in two batches, the loads of each in flight together: normal + albedo here,
+  // metal-roughness + emission after the debug material's return.
   const bool dbg = kind == RT_MAT_DEBUG;
   const bool ha = tex_albedo >= 0 && !dbg, hn = tex_normal >= 0, hm = tex_mr >= 0 && !dbg, he = tex_em >= 0 && !dbg;
   TexTaps tn, ta, tm, te;
   TexQuad qn, qa, qm, qe;
   if (hn) { tn = tex_taps(D[1], in.uvx, in.uvy); qn = tex_fetch(P.texels + D[1].offset, tn); }
-  if (RT_TEX_BATCH >= 2 && ha) { ta = tex_taps(D[0], in.uvx, in.uvy); qa = tex_fetch(P.texels + D[0].offset, ta); }
-  if (RT_TEX_BATCH >= 4 && hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
-  if (RT_TEX_BATCH >= 4 && he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
+  if (ha) { ta = tex_taps(D[0], in.uvx, in.uvy); qa = tex_fetch(P.texels + D[0].offset, ta); }
 
   rt_v3 normal = normal_map(hn, hn ? tex_combine(qn, tn) : rt_v3_make(0, 0, 0), m2.x, in);
   terminate = false;
@@ -960,14 +833,12 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
 
   if (tex_albedo >= 0 || tex_normal >= 0 || tex_mr >= 0 || tex_em >= 0) cn.textured += 1;
 
-  if (RT_TEX_BATCH < 2 && ha) { ta = tex_taps(D[0], in.uvx, in.uvy); qa = tex_fetch(P.texels + D[0].offset, ta); }
-  if (RT_TEX_BATCH == 2 && hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
-  if (RT_TEX_BATCH == 2 && he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
+  if (hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
+  if (he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
   rt_v3 base_color = rt_v3_make(m0.x, m0.y, m0.z);
   if (ha) base_color = rt_v3_mul(base_color, srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_combine(qa, ta)));
 
   float roughness = m0.w, metalness = m1.w;
-  if (RT_TEX_BATCH < 2 && hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
   if (hm) {
     rt_v3 mr = tex_combine(qm, tm);
     roughness *= mr.y;
@@ -978,7 +849,6 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
   metalness /= 0.9f;
 
   emission = rt_v3_make(m1.x, m1.y, m1.z);
-  if (RT_TEX_BATCH < 2 && he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
   if (he) emission = rt_v3_mul(emission, srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_combine(qe, te)));
 
   // basis(), driver.c:155-164
@@ -1019,7 +889,7 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
 template <class PT>
 __device__ __forceinline__ void primary_ray(const PT &P, int x, int y, int sample, rt_v3 &o, rt_v3 &d) {
   // 1/width, 1/height, width/height (raytracer.c:615-617) are frame constants: the host computes the same
-  // three fp32 divisions once (rt_api.cpp) instead of every lane for every path
+  // three fp32 divisions once (rt_launch.cpp) instead of every lane for every path
   float inv_width = P.inv_width;
   float inv_height = P.inv_height;
   float aspect = P.aspect;
@@ -1037,7 +907,7 @@ __device__ __forceinline__ void primary_ray(const PT &P, int x, int y, int sampl
 }
 
 // SHORT_DIV: the reciprocals by rcp_exact() -- same bits as the division for |component| < 2^102, infinity and NaN.  The
-// tile-stream kernel uses it where the host has bounded the camera matrix (rt_api.cpp): a camera direction is a unit
+// tile-stream kernel uses it where the host has bounded the camera matrix (rt_launch.cpp): a camera direction is a unit
 // vector through that matrix, every other direction comes out of shade() as t o.x + b o.y + n o.z of normalised vectors
 // (components within +-3.1, or infinite / NaN when a normalisation met a zero or non-finite vector).
 template <bool SHORT_DIV = false>
@@ -1120,27 +990,13 @@ __device__ __forceinline__ bool shade_hit(const PT &P, const HitRec &hit, rt_v3 
 #define RT_PARK_FIELDS 18     // hit (t, triangle, u, v), ray origin and direction, tint, emission, rng, pixel of the tile | bounce << 6
 #define RT_PARK_CAP 128       // parked hits per wave (fewer than RT_PARK_DENSE + 64 are ever parked)
 static_assert(RT_PARK_FIELDS * RT_PARK_CAP == RT_PARK_RECORD_DWORDS, "park slice size (rt_device.h) out of step");
-#ifndef RT_PARK_DENSE
 #define RT_PARK_DENSE 48      // lanes that make a shade block worth running while the tile still hands out paths
-#endif
-#ifndef RT_JOIN_CHOICES
-#define RT_JOIN_CHOICES 4    // random open tiles a joining wave looks at; it takes the one with most units left
-#endif
-#ifndef RT_PYR_NUM
-#define RT_PYR_NUM 3       // a pyramid-culled node block needs nG >= nN * RT_PYR_NUM / RT_PYR_DEN camera rays on one node
+#define RT_JOIN_CHOICES 4     // random open tiles a joining wave looks at; it takes the one with most units left
+#define RT_PYR_NUM 3          // a pyramid-culled node block needs nG >= nN * RT_PYR_NUM / RT_PYR_DEN camera rays on one node
 #define RT_PYR_DEN 4
 #define RT_PYR_MIN 8
-#endif
 #define RT_STEAL_TRIES  16        // failed joins in a row before a wave retires
-#ifndef RT_LEAF_TRIP
-#define RT_LEAF_TRIP 1          // triangles whose scalar loads are in flight together in leaf_test_uniform (2: nine more SGPRs, which spill into the sky loop)
-#endif
-#ifndef RT_LEAF_CULL_MAX
 #define RT_LEAF_CULL_MAX 4     // surviving triangles up to which a camera-ray leaf block takes the culled, triangle-by-triangle form
-#endif
-#ifndef RT_PARK_STOP_PATHS
-#define RT_PARK_STOP_PATHS 0      // hits are shaded at once instead of parked when the tile has at most this many paths left to hand out (0: off)
-#endif
 
 // Kernel arguments that are only needed outside the traversal loop (camera, frame and tile bookkeeping, material
 // tables) are read from the kernarg segment WHERE they are used, through a pointer the compiler cannot see through:
@@ -1316,28 +1172,12 @@ __device__ __forceinline__ bool leaf_test_uniform(const RT_KParams &P, const Ray
   float best = RT_INF, bu = 0.0f, bv = 0.0f;
   int   bi = 0;
   cfloat *lb = as_scalar_ptr(P.leaves) + (size_t)g * 72;
-  // RT_LEAF_TRIP 2: two triangles per trip, their eighteen scalar loads in flight together (a tile's pyramid leaves two of a group's
-  // eight triangles on average) -- equal on the helmet, but the nine extra SGPRs cost the sky loop four spill moves per batch (tower
-  // +0.3 %): one per trip is what ships
-  while (surv) {
+  while (surv) {                                                           // one triangle per trip
     const int k0 = (int)__builtin_ctz(surv);
     surv &= surv - 1u;
-#if RT_LEAF_TRIP == 1
-    {
-      cfloat *t0 = lb + k0;
-      tri_test_uniform<SHORT_DIV>(r, rt_v3_make(t0[0], t0[24], t0[48]), rt_v3_make(t0[8], t0[32], t0[56]), rt_v3_make(t0[16], t0[40], t0[64]),
-                                  k0, best, bu, bv, bi);
-      continue;
-    }
-#endif
-    const bool two = surv != 0u;
-    const int k1 = two ? (int)__builtin_ctz(surv) : k0;
-    surv &= surv - 1u;                                                     // (0 & anything = 0)
-    cfloat *t0 = lb + k0, *t1 = lb + k1;
-    const rt_v3 a0 = rt_v3_make(t0[0], t0[24], t0[48]), e10 = rt_v3_make(t0[8], t0[32], t0[56]), e20 = rt_v3_make(t0[16], t0[40], t0[64]);
-    const rt_v3 a1 = rt_v3_make(t1[0], t1[24], t1[48]), e11 = rt_v3_make(t1[8], t1[32], t1[56]), e21 = rt_v3_make(t1[16], t1[40], t1[64]);
-    tri_test_uniform<SHORT_DIV>(r, a0, e10, e20, k0, best, bu, bv, bi);
-    if (two) tri_test_uniform<SHORT_DIV>(r, a1, e11, e21, k1, best, bu, bv, bi);
+    cfloat *t0 = lb + k0;
+    tri_test_uniform<SHORT_DIV>(r, rt_v3_make(t0[0], t0[24], t0[48]), rt_v3_make(t0[8], t0[32], t0[56]), rt_v3_make(t0[16], t0[40], t0[64]),
+                                k0, best, bu, bv, bi);
   }
   if (best < hit.t) {
     hit.t = best;
@@ -1397,7 +1237,6 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
       LG(LG_LEAF_CAM, __popcll(__ballot(phase == PH_LEAF && is_cam)));
 #endif
       w_leaves += (uint32_t)nL;
-#if !RT_LEAF_PAIRS && !defined(RT_NO_LEAF_CULL)
       // camera rays of this tile about to test the same leaf group, (almost) alone in the block: only the triangles their
       // pyramid can touch; the other lanes keep waiting for a leaf block
       bool leaf_done = false;
@@ -1433,23 +1272,12 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
           }
         }
       }
-      if (!leaf_done)
-#endif
-#if RT_LEAF_PAIRS
-      {
-        const bool in_leaf = phase == PH_LEAF;
-        const int  g = child - P.last_row_offset;
-        if (leaf_test_pair<SHORT_DIV>(P, ray, g, in_leaf, hit)) dirty = 0xFFFFFFFFu;
-        if (in_leaf) phase = PH_POP;
-      }
-#else
-      if (phase == PH_LEAF) {
+      if (!leaf_done && phase == PH_LEAF) {
         int  g = child - P.last_row_offset;
         bool got = SHORT_DIV ? leaf_test_short_div(P, ray, g, hit) : leaf_test<false>(P, ray, g, hit);
         if (got) dirty = 0xFFFFFFFFu;
         phase = PH_POP;
       }
-#endif
       LGM("leaf_end");
       LGT1(LG_CYC_LEAF);
     } else {

@@ -56,12 +56,9 @@
  *           load between the material record and the texels (zeros for an absent texture)
  */
 
-/* Texel layout in the pool.  RT_TEX_TILED = 1: 4 x 4-texel tiles of 64 bytes (one cache line), tiles row-major,
- * `stride` = tiles per row: the 2 x 2 footprint of a bilinear fetch lies in ONE line 9 times in 16 instead of never (two
- * rows of a row-major image are two lines).  0: row-major, `stride` = texels per row.  Addressing only: same texels. */
-#ifndef RT_TEX_TILED
-#define RT_TEX_TILED 1
-#endif
+/* Texel layout in the pool: 4 x 4-texel tiles of 64 bytes (one cache line), tiles row-major, `stride` = tiles per row: the
+ * 2 x 2 footprint of a bilinear fetch lies in ONE line 9 times in 16 instead of never (two rows of a row-major image are
+ * two lines).  Addressing only: same texels. */
 typedef struct {
   uint32_t offset;    /* first texel in the pool */
   int32_t  width, height, stride;

@@ -9,8 +9,6 @@
 //   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
 //
-// (Comments in rt_dev.hip.h and rt_wavefront.hip still cite rt_api.cpp, the one file these units were split from.)
-//
 // Nothing on the host side computes a pixel on the CPU: every entry point either
 // drives the gfx950 kernels of rt_kernels.hip (one object, shared by both libraries) / rt_wavefront.hip and rt_kernels_test.hip
 // (diagnostic library only) or fails with rt_last_error().

@@ -313,7 +313,6 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     int  n_parked = 0;                   // hits of this tile waiting in the wave's slice of `park`
     uint32_t *park = cold_args()->park;
 
-#ifndef RT_NO_SKY_LOOP
     // ================= tiles whose pyramid misses every child of the root: a loop of their own =================
     // Every camera ray of such a tile (56 % of the camera paths of config #3: 299 M of 531 M) costs one node visit that finds no candidate and
     // goes to the environment -- no traversal state, no phases, no parking, no RNG draw.  The loop below does exactly that for
@@ -368,6 +367,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         // RT_SKY_PATHS paths per lane and iteration.  Two or three -- independent chains of primary ray -> environment lookup for
         // the scheduler to interleave, in a loop that carries no other state -- measure the same as one (32.50 / 32.65 vs 32.55 ms:
         // profiles/r04o_sky_ab.log): what the loop saves is the phase machine's instructions, scalar and vector, not latency.
+        // (The switch stays although nothing sets it: the same batch written with scalars instead of one-element arrays compiles to
+        // different code -- the lookup's atan2 is no longer if-converted and the whole kernel's register allocation shifts.)
 #ifndef RT_SKY_PATHS
 #define RT_SKY_PATHS 1
 #endif
@@ -419,7 +420,6 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       // counters[CNT_SKIPPED_ROOT]: node visits that are counted but not executed (bench.py's roofline footnote)
       if (n_sky != 0u && lane == 0) atomicAdd(cold_args()->counters + CNT_SKIPPED_ROOT, (unsigned long long)n_sky);
     }
-#endif
 
     for (;;) {
       // ================= S: shade the hits, environment for the misses, start new paths =================
@@ -462,11 +462,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           const int h = (int)__popcll(mHit), f = (int)__popcll(mIdle);
           const int back = n_parked < f ? n_parked : f;                 // parked hits that fit into idle lanes
           uint32_t *pk = park + (size_t)__builtin_amdgcn_readfirstlane(wave_id) * (RT_PARK_FIELDS * RT_PARK_CAP);    // (scalar base)
-          // (the last paths of a tile are not parked: what is parked when the tile closes runs its bounce chain AFTER the chains of
-          // the paths in flight -- the drain of the tile, and of the launch, gets a second chain long; RT_PARK_STOP_PATHS)
-          const bool tile_ending = RT_PARK_STOP_PATHS > 0 &&
-                                   (int)(n_chunks_tile - u_end) * unit_paths + (int)(u_end - u_cur) * unit_paths <= RT_PARK_STOP_PATHS;
-          if (!tile_open || tile_ending || h + back >= RT_PARK_DENSE || n_parked + h > RT_PARK_CAP) {
+          if (!tile_open || h + back >= RT_PARK_DENSE || n_parked + h > RT_PARK_CAP) {
             if (back > 0) {
               LG(LG_PLOAD_X, 1); LG(LG_PLOAD_L, back);
               LGM("pload_begin");
@@ -1071,21 +1067,18 @@ static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipSt
   return (int)hipGetLastError();
 }
 
-#ifndef RT_STREAM_MINW
-#define RT_STREAM_MINW 1     // (experiment builds: 5 caps the kernel at 96 VGPRs, 6 at 80 -- profiles/r03_experiments.md)
-#endif
 extern "C" int rt_math_contract(void) { return RT_MATH_CONTRACT; }      // include/rt_math.h: 2 = explicit FMA, 1 = -DRT_MATH_NO_FMA
 
 template <bool VIEWS>
 static int launch_stream_wg(const RT_KParams *P, int n_waves, int smem_bytes, int wg_waves, hipStream_t stream) {
   if (wg_waves == 8)
-    return P->short_div ? launch_stream<8, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<8, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
+    return P->short_div ? launch_stream<8, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<8, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
   if (wg_waves == 12)
-    return P->short_div ? launch_stream<12, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<12, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
-  return P->short_div ? launch_stream<16, true, RT_STREAM_MINW, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                      : launch_stream<16, true, RT_STREAM_MINW, false, VIEWS>(P, n_waves, smem_bytes, stream);
+    return P->short_div ? launch_stream<12, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<12, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
+  return P->short_div ? launch_stream<16, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
+                      : launch_stream<16, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
 }
 
 // `wg_waves` = waves per workgroup, 8 / 12 / 16 (one workgroup per CU: 2 / 3 / 4 waves per SIMD), chosen by rt_launch.cpp from the
@@ -1113,8 +1106,8 @@ extern "C" int rt_launch_untile(int width, int height, int chunks_x, int n_chunk
   return (int)hipGetLastError();
 }
 
-// raw u8 image rows (stride pixels x comp bytes, comp >= 3) -> RGBA8 words in the pool layout of rt_device.h (4 x 4 tiles, or
-// row-major).  `rows` rows starting at row y0 of a texture `width` wide whose first texel is out[0] (rt_scene_touch packs a
+// raw u8 image rows (stride pixels x comp bytes, comp >= 3) -> RGBA8 words in the pool layout of rt_device.h (4 x 4 tiles).
+// `rows` rows starting at row y0 of a texture `width` wide whose first texel is out[0] (rt_scene_touch packs a
 // few rows of a resident texture again).
 __global__ void rt_pack_texture_kernel(const uint8_t *raw, int width, int rows, int y0, int stride, int comp, uint32_t *out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1122,11 +1115,7 @@ __global__ void rt_pack_texture_kernel(const uint8_t *raw, int width, int rows, 
   int yl = (int)(i / width), x = (int)(i % width);
   const uint8_t *p = raw + ((size_t)yl * stride + x) * comp;
   const int y = y0 + yl;
-#if RT_TEX_TILED
   const size_t o = (size_t)RT_TEX_TILE_INDEX(x, y, (width + 3) >> 2);
-#else
-  const size_t o = (size_t)y * width + x;
-#endif
   out[o] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | 0xFF000000u;
 }
 

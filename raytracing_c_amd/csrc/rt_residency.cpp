@@ -71,13 +71,8 @@ static int texture_index(Image const *img, TexturePool &pool) {
   t.offset = (uint32_t)pool.texels;
   t.width = (int32_t)img->width;
   t.height = (int32_t)img->height;
-#if RT_TEX_TILED
   t.stride = (int32_t)((img->width + 3) / 4);                                  // tiles per row (rt_device.h)
   pool.texels += (size_t)t.stride * (size_t)((img->height + 3) / 4) * 16;
-#else
-  t.stride = (int32_t)img->width;
-  pool.texels += (size_t)img->width * img->height;
-#endif
   int idx = (int)pool.descs.size();
   pool.descs.push_back(t);
   pool.sources.push_back(img);
@@ -645,10 +640,7 @@ static int touch_device_scene(RT_Device_Scene *d, Scene const *scene, const void
     HIP_TRY(stage.alloc((r1 - r0) * row_bytes));
     HIP_TRY(hipMemcpy(stage.p, (const unsigned char *)img->pixels.data + r0 * row_bytes, (r1 - r0) * row_bytes, hipMemcpyHostToDevice));
     uint32_t *tex_base = d->texels + desc.offset;
-#if !RT_TEX_TILED
-    tex_base += r0 * (size_t)desc.width;           // (row-major: the kernel's row 0 is row r0 of the texture)
-#endif
-    int rc = rt_launch_pack_texture(stage.as<uint8_t>(), (int)img->width, (int)(r1 - r0), RT_TEX_TILED ? (int)r0 : 0, (int)img->stride,
+    int rc = rt_launch_pack_texture(stage.as<uint8_t>(), (int)img->width, (int)(r1 - r0), (int)r0, (int)img->stride,
                                     (int)img->components, tex_base, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();
     if (rc != 0) return rt_fail("rt_scene_touch: texture rows: %s", hipGetErrorString((hipError_t)rc));

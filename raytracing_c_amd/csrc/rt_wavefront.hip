@@ -19,7 +19,7 @@
 //
 // One frame = camera kernel, then (shade, trace) per bounce; launches of one stream, so a kernel boundary is the only
 // synchronisation between a producer and its consumer: no polling, no inter-kernel flags, nothing that can deadlock.
-// The queues are sized by the host (rt_api.cpp); when the camera kernel runs into the end of its hit queue its waves
+// The queues are sized by the host (rt_diag.cpp); when the camera kernel runs into the end of its hit queue its waves
 // stop taking units and the host runs the bounces and calls the camera kernel again -- the tile / unit counters keep the
 // position.  Per-lane arithmetic is that of rt_dev.hip.h in every kernel, radiance sums are order-free integers
 // (rt_math.h), so images and counters equal the tile-stream kernel's and the CPU oracle's bit for bit.

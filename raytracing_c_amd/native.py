@@ -11,8 +11,8 @@ from . import ctypes_abi as abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_LIB_PATH: A/B a differently built librt_hip.so (tools/exp_ab.sh); the default is the in-tree build.
 LIB_PATH = os.environ.get("RT_LIB_PATH") or os.path.join(_HERE, "librt_hip.so")
-# The diagnostic build (make diag): unit-test entry points (include/rt_hip_diag.h), the wavefront pipeline, the superseded
-# kernel generations.  Tests and experiments load it BESIDE the product library as `raytracing_c_amd.diag`.
+# The diagnostic build (make diag): unit-test entry points (include/rt_hip_diag.h), the wavefront pipeline, host units
+# that read the RT_* experiment knobs.  Tests and experiments load it BESIDE the product library as `raytracing_c_amd.diag`.
 DIAG_PATH = os.path.join(_HERE, "librt_hip_diag.so")
 
 
