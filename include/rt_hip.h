@@ -220,6 +220,69 @@ extern int rt_render_views(Scene const *scene, i32 n_views, RT_View const *views
 extern int rt_render_accumulate_views(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_views,
                                       RT_View const *views, void *d_accum, void *stream);
 
+/* ---- batch ray queries ------------------------------------------------------------ */
+
+/* ray_scene_hit (reference raytracer.c:443-503) for a batch of rays against a resident scene: which triangle a ray hits, where,
+ * with what normal and texture coordinates -- picking, line of sight, visibility, a host's own ambient-occlusion or probe pass,
+ * collision rays, sensor simulation.  Ray i is (origin, direction) = f32[6], taken AS GIVEN: not normalised, zero components, +-0,
+ * infinities and NaN give whatever the reference's arithmetic gives.  Its query is ray_scene_hit(&ray[i], scene, &hit) with
+ * hit.distance = t_max[i] on entry: the reference's own protocol makes the entry distance the upper bound (raytracer.c:452, :159,
+ * :513), the lower bound is its EPSILON; t_max == NULL means F32_INFINITY for every ray.
+ *   closest hit : RT_Ray_Hit per ray; on a miss triangle = -1, t = the entry t_max[i], u = v = 0
+ *   occlusion   : one byte per ray, 1 exactly when the closest-hit query with the same t_max finds a triangle (the kernel stops a
+ *                 ray at the first triangle it accepts: fewer visits, same answer)
+ *   full record : RT_Device_Hit = the reference's Hit (raytracer.c:159-184) with the Shader pair replaced by the triangle and
+ *                 material indices; on a miss distance = the entry t_max[i], triangle = material = -1, every other field 0
+ * One persistent kernel of its own (rt_query_kernel, csrc/rt_kernels.hip) on the traversal of the path kernel; every result equals
+ * the reference's bit for bit.  Frames, views, lightmaps and their counters are not affected by queries. */
+typedef struct { f32 t; i32 triangle; f32 u, v; } RT_Ray_Hit;                                     /* 16 bytes */
+typedef struct {
+  f32  distance;
+  Vec3 normal, normal_geo, point, tangent, bitangent;
+  Vec2 tex_coords;                                                                                /* as in Hit up to here */
+  i32  triangle, material;                                                                        /* index into scene->triangles.aos, device material id */
+  i32  pad[2];
+} RT_Device_Hit;                                                                                  /* 88 bytes = sizeof(Hit) */
+typedef struct { u64 rays, hits, node_visits, leaf_visits; } RT_Query_Counters;
+
+/* Device level, like rt_render_accumulate(): every pointer is a DEVICE pointer owned by the caller, on the device the scene was
+ * uploaded to; the call only enqueues work on `stream` (NULL = default stream).
+ *   d_rays  : f32[n][6]            d_t_max : f32[n] or NULL
+ *   d_hits  : RT_Ray_Hit[n]        d_full  : RT_Device_Hit[n] or NULL        d_flags : u8[n]
+ * d_rays and d_t_max must be 4-byte aligned, d_hits 16-byte (one 16-byte store per ray), d_full 8-byte (eleven 8-byte stores).
+ * Checked before the GPU is touched: dscene, d_rays, d_hits / d_flags not NULL, 0 < n <= 2^30 (RT_QUERY_MAX_RAYS: the kernel holds
+ * ray indices in 32-bit integers, and its 32-bit work counter ends at n plus one grab of at most 512 rays per wave; byte offsets
+ * are 64-bit).
+ * 0 on success, -1 + rt_last_error(). */
+#define RT_QUERY_MAX_RAYS ((i64)1 << 30)
+extern int rt_query_closest(RT_Device_Scene *dscene, i64 n, void const *d_rays, void const *d_t_max, void *d_hits, void *d_full,
+                            void *stream);
+extern int rt_query_occluded(RT_Device_Scene *dscene, i64 n, void const *d_rays, void const *d_t_max, void *d_flags, void *stream);
+
+/* Host level: batch ray_scene_hit with the reference's in / out protocol, from host memory to host memory.
+ *   rt_scene_hits     : hits[i].distance on entry is ray i's bound.  A hit fills the whole Hit (shader copied on the host from
+ *                       scene->triangles.aos[triangle].shader) and sets triangles[i] (optional) to the triangle's index; a miss leaves
+ *                       hits[i] untouched and sets triangles[i] = -1.
+ *   rt_scene_closest  : hits[i] = (t, triangle, u, v) of ray i under the bound t_max[i] (t_max NULL: infinity), as rt_query_closest
+ *                       writes them: 16 bytes per ray, no attribute kernel, no full records -- the cheap form when the
+ *                       barycentrics or the triangle are all the host needs (the reference's Hit has no place for u, v).
+ *   rt_scene_occluded : flags[i] = 1 when ray i hits anything in [EPSILON, t_max[i]) (t_max NULL: infinity), else 0.
+ * All three use the cached device copy of `scene` and the per-call scene check of rt_render_frame() -- the stamp before the launch, the
+ * full content check while the GPU works (off after rt_scene_set_static) -- so an in-place edit or an rt_scene_touch() is seen by the
+ * next query; they take the library's device lock as frames do and block until the results are in host memory.  n is processed in
+ * slices of 2^20 rays (RT_QUERY_SLICE), which bounds the staging memory on the device (133 bytes per ray of a slice at most) and on
+ * the host (88); the device staging is kept for the next call.  With rt_device_count() > 1 they run on the PRIMARY device only; spreading a batch over devices is not done.
+ * Checked before the GPU is touched: scene, rays, hits / flags not NULL, 0 < n <= 2^30.  0 on success, -1 + rt_last_error(); a
+ * call refused for its arguments or for want of a device leaves hits / triangles / flags untouched. */
+#define RT_QUERY_SLICE ((i64)1 << 20)
+extern int rt_scene_hits(Scene const *scene, i64 n, Ray const *rays, Hit *hits, i32 *triangles);
+extern int rt_scene_closest(Scene const *scene, i64 n, Ray const *rays, f32 const *t_max, RT_Ray_Hit *hits);
+extern int rt_scene_occluded(Scene const *scene, i64 n, Ray const *rays, f32 const *t_max, u8 *flags);
+
+/* Counters of the last query call of this process (device or host level; a host call's slices summed): rays answered, rays with
+ * a hit, 8-box slab tests (raytracer.c:452) and 8-triangle tests (:476).  Synchronises.  rt_get_counters() is not affected. */
+extern int rt_get_query_counters(RT_Query_Counters *out);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

@@ -1206,19 +1206,25 @@ __device__ __forceinline__ RT_KArgs cold_args() {
 // rt_test_trace_stream_kernel (unit-level parity against oracle_trace_rays).
 //   PYRAMID: node blocks whose lanes are camera rays (`is_cam`) of the wave's tile about to enter ONE node test only the
 //            child boxes the tile's pyramid (LDS, pyr_off) can touch (pyramid_cull_mask, node_enter_few).
+//   ANY:     any-hit (rt_query_kernel's occlusion form): a lane whose leaf block ACCEPTED a triangle (t in [epsilon, hit.t)) ends
+//            with PH_HIT there instead of popping.  Same answer to "is there a hit" as the closest-hit traversal: until a triangle
+//            is accepted hit.t is the entry bound, no re-test bit is set and every node block sees the same bound, so the visits up
+//            to the first acceptance ARE the closest-hit traversal's first visits, and that one ends with PH_HIT exactly when it
+//            accepted at least once.
 struct TravState {
   int      phase, level, node, child;
   uint32_t cur, dirty, live;
   HitRec   hit;
 };
 
-template <bool LDSN, bool SHORT_DIV, bool PYRAMID>
+template <bool LDSN, bool SHORT_DIV, bool PYRAMID, bool ANY = false>
 __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *smem, const float4 *lds_nodes, uint32_t *perm,
                                                  const int lane, const int n_lds, const int pyr_nodes, const int pyr_off,
                                                  const int leaf_level, const int exit_lanes, const int n_trav0, const Ray3 &ray,
                                                  const bool is_cam, int &phase, int &level, int &node, int &child, uint32_t &cur,
                                                  uint32_t &dirty, uint32_t &live, HitRec &hit, uint32_t &w_nodes, uint32_t &w_leaves,
                                                  uint32_t *lg = nullptr) {
+  static_assert(!(ANY && PYRAMID), "the pyramid-culled leaf block has no any-hit exit");
   LG(LG_TRAV_CALLS, 1);
   for (;;) {
     LGM("round_begin");
@@ -1276,7 +1282,7 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
         int  g = child - P.last_row_offset;
         bool got = SHORT_DIV ? leaf_test_short_div(P, ray, g, hit) : leaf_test<false>(P, ray, g, hit);
         if (got) dirty = 0xFFFFFFFFu;
-        phase = PH_POP;
+        phase = (ANY && got) ? PH_HIT : PH_POP;
       }
       LGM("leaf_end");
       LGT1(LG_CYC_LEAF);

@@ -138,6 +138,22 @@ typedef struct {
   int32_t pixels_per_view;     /* width * height: view v accumulates into accum + v * pixels_per_view * 3                    */
 } RT_KParams;
 
+/* Batch ray queries (rt_query_kernel, rt_hit_attributes_kernel; include/rt_hip.h rt_query_closest / rt_query_occluded): what one
+ * launch reads and writes besides the scene fields of RT_KParams. */
+typedef struct {
+  const float *rays;           /* [n][6] origin, direction -- taken as given                                              */
+  const float *t_max;          /* [n] upper bound of ray i (hit.distance on entry, raytracer.c:452), NULL = infinity      */
+  float       *hits;           /* closest hit: [n][4] t, triangle (int bits), u, v                                        */
+  uint8_t     *flags;          /* occlusion: [n], 1 = a triangle in [epsilon, t_max)                                      */
+  uint32_t    *head;           /* rays handed out so far (zero at launch)                                                 */
+  unsigned long long *counters;/* RT_QUERY_COUNTERS: rays, hits, node visits, leaf visits -- added to                     */
+  int32_t      n;
+  int32_t      grab;           /* rays a wave takes per atomic on `head`                                                  */
+  int32_t      exit_lanes;     /* finished lanes that end a traversal call while rays are left to hand out                */
+} RT_QParams;
+#define RT_QUERY_COUNTERS 4
+#define RT_HIT_DWORDS     22   /* RT_Device_Hit (rt_hip.h), 88 bytes */
+
 #define WF_CHUNK        256
 #define WF_HIT0_FIELDS  9      /* direction (3), t, triangle, u, v, pixel (y << 16 | x), sample                         */
 #define WF_HIT_FIELDS   5      /* index of the ray record (chunk * WF_CHUNK + slot), t, triangle, u, v                  */

@@ -7,6 +7,7 @@
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
+//   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
 //
 // Nothing on the host side computes a pixel on the CPU: every entry point either
@@ -55,6 +56,8 @@ int rt_launch_denoise(int width, int height, int src_stride, int src_comp, int d
                       const uint8_t *src, uint8_t *dst, hipStream_t stream);
 int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, int y0, int stride, int comp, uint32_t *out,
                            hipStream_t stream);
+int rt_launch_query(const RT_KParams *P, const RT_QParams *Q, int any, int wg_waves, int n_blocks, int smem_bytes, hipStream_t stream);
+int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, const float *hits, float *out, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -192,6 +195,23 @@ struct FrameLane {
   double      t_begin = 0.0;
 };
 
+// Batch ray queries (rt_query.cpp).  What a query launch writes besides its results -- the work counter and the four counters -- is
+// one 64-byte slot of a ring, so that query calls on several streams can be in flight at once; a slot is taken again only after
+// the event recorded behind its last launch has completed.  The staging buffers serve the host-level calls, one slice at a time;
+// they are kept between calls (at most 133 B x RT_QUERY_SLICE) and given back with the rest when the slot is torn down
+// (release_query_state).
+#define RT_QUERY_SLOTS 64
+struct QueryState {
+  uint8_t   *slots = nullptr;                 // [RT_QUERY_SLOTS][64]: counters u64[4] at +0, work counter u32 at +32
+  hipEvent_t done[RT_QUERY_SLOTS] = {};
+  bool       used[RT_QUERY_SLOTS] = {};
+  unsigned   next = 0;
+  int        last = -1;                       // slot of the most recent query call (rt_get_query_counters)
+  float     *rays = nullptr, *t_max = nullptr, *hits = nullptr, *full = nullptr;
+  uint8_t   *flags = nullptr;
+  size_t     cap_rays = 0, cap_t_max = 0, cap_hits = 0, cap_full = 0, cap_flags = 0;      // rays each staging buffer holds
+};
+
 struct Device {
   int        slot = 0, phys = 0;
   bool       ready = false;
@@ -206,6 +226,7 @@ struct Device {
   std::vector<DevPartition>                            parts;   // guarded by g_partition_mutex
   FrameTiming timing;
   FrameLane  lanes[RT_FRAME_LANES];           // slot 0 only
+  QueryState query;
 };
 
 // Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
@@ -349,6 +370,9 @@ void frame_split(Workspace &W, FrameTiming &T);                                 
 
 // rt_multi.cpp
 int render_frame_multi(Scene const *scene, Image const *image, RT_Render_Params base, int world);   // slot 0's mutex held
+
+// rt_query.cpp
+void release_query_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

@@ -1126,3 +1126,164 @@ extern "C" int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, i
                      comp, out);
   return (int)hipGetLastError();
 }
+
+// ---- batch ray queries (include/rt_hip.h: rt_query_closest, rt_query_occluded) ------------------------------------------------------
+// ray_scene_hit (raytracer.c:443-503) for a list of rays the HOST supplies: which triangle, where (t, u, v) -- or, ANY, only whether
+// there is one (the argument that the two agree: traversal_blocks, rt_dev.hip.h).  A persistent kernel in the path kernel's launch
+// geometry: one workgroup per CU, the leading BVH nodes in LDS, a perm stack per wave, lanes refilled from the list as they finish.
+//
+// Work distribution: ONE counter for the whole launch (Q.head); a wave takes Q.grab consecutive rays per atomic and hands them to
+// its lanes in order, so the 24-byte ray records of a refill are one contiguous read.  The grab size comes from the launch size
+// (rt_query.cpp): what is left over when the counter runs out is at most one grab per wave, so a grab is an eighth of a wave's mean
+// share -- a batch whose rays differ in cost ends with every wave within that eighth -- but never below 64 (one refill of an
+// empty wave, and the atomic stays one in 64 rays) and never above 512.
+//
+// Reciprocals: IEEE division, in ray_setup and in the leaf blocks.  The short forms rcp_exact() / rcp_leaf() equal the division
+// for |x| < 2^102 only (rt_test_rcp_sweep); the path kernel may use them because the HOST bounds every direction it can produce
+// (unit vectors through a bounded camera matrix, shade()'s outputs) and with them every determinant.  A caller's rays carry no
+// bound -- a direction of 2^110 is as legal as one of 2^-30 -- and a bound per batch would cost a pass over the rays before every
+// launch, so this kernel has no short-division instance.
+//
+// No pyramid culling (the rays are no tile's camera rays).  Outputs by plain vector stores: 16 bytes or one byte per ray.
+template <int WAVES, bool ANY>
+__global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, RT_QParams Q) {
+  extern __shared__ float4 smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int n_lds = P.n_lds_nodes;
+  const float4 *lds_nodes = smem;
+  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
+  uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * perm_f4);
+  {
+    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
+    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
+      int nd = i / 12, q = i - nd * 12;
+      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
+    }
+    __syncthreads();
+  }
+  const int leaf_level = P.depth - 1;
+  int  next = 0, end = 0;                                         // the wave's current grab: rays [next, end) are not handed out yet
+  bool drained = false;                                           // the launch's counter has run past the list (wave-uniform)
+
+  int   phase = PH_NEED, idx = 0;
+  Ray3  ray;
+  ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
+  int   level = -1, node = 0, child = 0;
+  uint32_t cur = 0, dirty = 0, live = 0, w_nodes = 0, w_leaves = 0, w_rays = 0, w_hits = 0;
+  HitRec hit;
+  hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+  for (;;) {
+    w_rays += (uint32_t)__popcll(__ballot(phase == PH_HIT || phase == PH_MISS));
+    w_hits += (uint32_t)__popcll(__ballot(phase == PH_HIT));
+    if (phase == PH_HIT || phase == PH_MISS) {
+      // (a miss: t is still the entry bound, triangle -1, u = v = 0 -- nothing was accepted since the refill)
+      if (ANY) Q.flags[idx] = phase == PH_HIT ? 1 : 0;
+      else reinterpret_cast<float4 *>(Q.hits)[idx] = make_float4(hit.t, as_f(hit.tri), hit.u, hit.v);
+      phase = PH_NEED;
+    }
+    // refill: every lane without a ray takes the next one of the wave's grab; a grab that runs out is followed by the next
+    for (;;) {
+      const unsigned long long need = __ballot(phase == PH_NEED);
+      if (need == 0ull || drained) break;
+      if (next >= end) {
+        uint32_t s = 0;
+        if (lane == 0) s = atomicAdd(Q.head, (uint32_t)Q.grab);
+        s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+        if (s >= (uint32_t)Q.n) { drained = true; break; }
+        next = (int)s;
+        end = (Q.n - next < Q.grab) ? Q.n : next + Q.grab;
+      }
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+      if (phase == PH_NEED && next + rank < end) {
+        idx = next + rank;
+        const float *r = Q.rays + (size_t)idx * 6;
+        ray_setup<false>(ray, rt_v3_make(r[0], r[1], r[2]), rt_v3_make(r[3], r[4], r[5]));
+        hit.t = Q.t_max ? Q.t_max[idx] : RT_INF;                  // raytracer.c:452: hit.distance on entry is the upper bound
+        hit.tri = -1; hit.u = 0; hit.v = 0;
+        dirty = 0; live = 0; cur = 0; level = -1; node = 0;
+        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
+        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+      }
+      next += (int)__popcll(need);
+    }
+    const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+    if (n_trav0 == 0) break;                                      // (only a drained wave gets here without a ray in flight)
+    traversal_blocks<true, false, false, ANY>(P, smem, lds_nodes, perm, lane, n_lds, 0, 0, leaf_level, drained ? 64 : Q.exit_lanes,
+                                              n_trav0, ray, false, phase, level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
+  }
+  if (lane == 0) {
+    atomicAdd(Q.counters + 0, (unsigned long long)w_rays);
+    atomicAdd(Q.counters + 1, (unsigned long long)w_hits);
+    atomicAdd(Q.counters + 2, (unsigned long long)w_nodes);
+    atomicAdd(Q.counters + 3, (unsigned long long)w_leaves);
+  }
+}
+
+// (ray, t, triangle, u, v) -> the reference's Hit without the Shader pair (RT_Device_Hit, rt_hip.h): the fill of raytracer.c:159-184
+// from the 28-float triangle record, with the expressions shade_hit() uses.  One thread per ray; a miss gets distance = t (the
+// entry bound), triangle = material = -1 and zeros.  Records are 88 bytes, 8-byte aligned: eleven 8-byte stores.
+__global__ void rt_hit_attributes_kernel(const float *tris, int n, const float *rays, const float *hits, float *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 h = reinterpret_cast<const float4 *>(hits)[i];
+  const int tri = as_i(h.y);
+  float o[RT_HIT_DWORDS];
+#pragma unroll
+  for (int k = 0; k < RT_HIT_DWORDS; k++) o[k] = 0.0f;
+  o[0] = h.x;
+  o[18] = as_f(tri);
+  o[19] = as_f(-1);
+  if (tri >= 0) {
+    const float *r = rays + (size_t)i * 6;
+    const rt_v3 org = rt_v3_make(r[0], r[1], r[2]), dir = rt_v3_make(r[3], r[4], r[5]);
+    const float *tb = tris + (size_t)tri * 28;
+    float4 q0 = ld4(tb, 0), q1 = ld4(tb, 1), q2 = ld4(tb, 2), q3 = ld4(tb, 3);
+    float4 q4 = ld4(tb, 4), q5 = ld4(tb, 5), q6 = ld4(tb, 6);
+    const float t1 = h.z, t2 = h.w;
+    const float t0 = 1.0f - t1 - t2;
+    const rt_v3 point = rt_v3_madd(dir, h.x, org);
+    o[1] = rt_dot3(q1.x, t0, q2.x, t1, q3.x, t2);                 // normal (interpolated, not normalised: raytracer.c:172-174)
+    o[2] = rt_dot3(q1.y, t0, q2.y, t1, q3.y, t2);
+    o[3] = rt_dot3(q1.z, t0, q2.z, t1, q3.z, t2);
+    o[4] = q0.x; o[5] = q0.y; o[6] = q0.z;                        // normal_geo
+    o[7] = point.x; o[8] = point.y; o[9] = point.z;
+    o[10] = q4.x; o[11] = q4.y; o[12] = q4.z;                     // tangent
+    o[13] = q5.x; o[14] = q5.y; o[15] = q5.z;                     // bitangent
+    o[16] = rt_dot3(q1.w, t0, q3.w, t1, q5.w, t2);                // tex_coords
+    o[17] = rt_dot3(q2.w, t0, q4.w, t1, q6.x, t2);
+    o[19] = q0.w;                                                 // material id (int bits)
+  }
+  float2 *dst = reinterpret_cast<float2 *>(out + (size_t)i * RT_HIT_DWORDS);
+#pragma unroll
+  for (int k = 0; k < RT_HIT_DWORDS / 2; k++) dst[k] = make_float2(o[2 * k], o[2 * k + 1]);
+}
+
+template <int WAVES, bool ANY>
+static int launch_query(const RT_KParams *P, const RT_QParams *Q, int n_blocks, int smem_bytes, hipStream_t stream) {
+  static uint32_t attr_devices = 0;           // devices on which this instance's dynamic-LDS limit has been raised
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(&attr_devices, __ATOMIC_RELAXED) & (1u << dev)))) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_query_kernel<WAVES, ANY>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 32) __atomic_fetch_or(&attr_devices, 1u << dev, __ATOMIC_RELAXED);
+  }
+  hipLaunchKernelGGL((rt_query_kernel<WAVES, ANY>), dim3(n_blocks), dim3(WAVES * 64), smem_bytes, stream, *P, *Q);
+  return (int)hipGetLastError();
+}
+
+// `wg_waves` = 8 or 16 waves per workgroup, `any` = the occlusion form (Q->flags) instead of the closest hit (Q->hits)
+extern "C" int rt_launch_query(const RT_KParams *P, const RT_QParams *Q, int any, int wg_waves, int n_blocks, int smem_bytes,
+                               hipStream_t stream) {
+  if (wg_waves == 8)
+    return any ? launch_query<8, true>(P, Q, n_blocks, smem_bytes, stream) : launch_query<8, false>(P, Q, n_blocks, smem_bytes, stream);
+  return any ? launch_query<16, true>(P, Q, n_blocks, smem_bytes, stream) : launch_query<16, false>(P, Q, n_blocks, smem_bytes, stream);
+}
+
+extern "C" int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, const float *hits, float *out,
+                                        hipStream_t stream) {
+  hipLaunchKernelGGL(rt_hit_attributes_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, P->tris, n, rays, hits, out);
+  return (int)hipGetLastError();
+}

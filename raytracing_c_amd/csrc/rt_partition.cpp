@@ -108,6 +108,7 @@ void remap_device_slots() {
       if (D.mstream) { (void)hipStreamDestroy(D.mstream); D.mstream = nullptr; }
       W = Workspace();
       D.last_counters = nullptr;
+      release_query_state(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);

@@ -136,6 +136,32 @@ class RT_View(C.Structure):  # rt_hip.h: one view of rt_render_views / rt_render
     _fields_ = [("camera", Camera), ("seed", C.c_uint32)]
 
 
+class RT_Ray_Hit(C.Structure):  # rt_hip.h: closest hit of one ray (rt_query_closest)
+    _fields_ = [("t", f32), ("triangle", C.c_int32), ("u", f32), ("v", f32)]
+
+
+class RT_Device_Hit(C.Structure):  # rt_hip.h: Hit with the Shader pair replaced by the triangle and material indices
+    _fields_ = [("distance", f32), ("normal", Vec3), ("normal_geo", Vec3), ("point", Vec3),
+                ("tangent", Vec3), ("bitangent", Vec3), ("tex_coords", Vec2),
+                ("triangle", C.c_int32), ("material", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class RT_Query_Counters(C.Structure):  # rt_hip.h
+    _fields_ = [(n, C.c_uint64) for n in ("rays", "hits", "node_visits", "leaf_visits")]
+
+
+# numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
+_HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
+             ("tangent", "<f4", (3,)), ("bitangent", "<f4", (3,)), ("tex_coords", "<f4", (2,))]
+DEVICE_HIT_DTYPE = np.dtype(_HIT_HEAD + [("triangle", "<i4"), ("material", "<i4"), ("pad", "<i4", (2,))])
+HIT_DTYPE = np.dtype(_HIT_HEAD + [("shader_data", "<u8"), ("shader_proc", "<u8")])
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(RT_Ray_Hit) == 16
+assert DEVICE_HIT_DTYPE.itemsize == C.sizeof(RT_Device_Hit) == 88
+assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 88
+RT_QUERY_MAX_RAYS = 1 << 30
+RT_QUERY_SLICE = 1 << 20
+
 assert C.sizeof(BVH_Node) == 192
 assert C.sizeof(Triangle) == 112
 assert C.sizeof(Triangle_AOS) == 112
@@ -163,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_upload", "rt_scene_release", "rt_scene_invalidate", "rt_scene_device_bytes", "rt_set_camera",
     "rt_chunk_count", "rt_chunk_owner", "rt_local_chunk_count", "rt_max_local_chunk_count", "rt_local_chunk_list", "rt_render_accumulate", "rt_resolve", "rt_untile",
     "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_render_views", "rt_render_accumulate_views",
+    "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 

@@ -129,6 +129,13 @@ def _declare(d):
     if hasattr(d, "rt_render_views"):
         d.rt_render_views.argtypes = [P(abi.Scene), C.c_int32, P(abi.RT_View), P(abi.Image), abi.isize, abi.isize, vp, vp]
         d.rt_render_accumulate_views.argtypes = [vp, P(abi.RT_Render_Params), C.c_int32, P(abi.RT_View), vp, vp]
+    if hasattr(d, "rt_query_closest"):
+        d.rt_query_closest.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
+        d.rt_query_occluded.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+        d.rt_scene_hits.argtypes = [P(abi.Scene), C.c_int64, vp, vp, vp]
+        d.rt_scene_closest.argtypes = [P(abi.Scene), C.c_int64, vp, vp, vp]
+        d.rt_scene_occluded.argtypes = [P(abi.Scene), C.c_int64, vp, vp, vp]
+        d.rt_get_query_counters.argtypes = [P(abi.RT_Query_Counters)]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
