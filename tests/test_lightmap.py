@@ -1,4 +1,8 @@
-"""lightmap_bake (reference raytracer.c:722-784): GPU vs oracle, bit-exact."""
+"""lightmap_bake (reference raytracer.c:722-784): GPU vs oracle, bit-exact.
+
+The map stores raw radiance truncated to u8 (oracle.h), so a comparison sees the traced paths only where radiance exceeds
+1: every compared bake first passes tests._lightmap.assert_discriminating on the oracle's output.  The oracle's own
+rasteriser is pinned by tests._lightmap.np_rasterise, a numpy restatement of the reference text."""
 import ctypes as C
 import os
 
@@ -6,8 +10,11 @@ import numpy as np
 import pytest
 
 from raytracing_c_amd.scene import make_image
+from tests import _lightmap as L
 
 ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
+SEED = 0x1234ABCD
+FILL = 7
 
 
 def _emissive_spheres():
@@ -61,3 +68,247 @@ def test_gpu_lightmap_bit_exact(oracle, case):
     assert rt.last_error() == ""
     assert np.array_equal(keep, want)
     assert (keep[..., :3] != 7).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the oracle's rasteriser and bake, pinned on the CPU
+
+@pytest.mark.parametrize("W,H", [(40, 48), (33, 31)])
+def test_oracle_mask_equals_the_reference_text(oracle, W, H):
+    """Which texels the oracle writes == np_rasterise of the reference text, on a soup whose charts overlap, leave gaps,
+    cross every edge of the map and include the degenerate ones; RGBA rows with 5 texels of padding: alpha, padding and
+    unowned texels are never touched."""
+    hs = L.emissive_soup(3, 300, textured=True)
+    owner, count = L.np_rasterise(hs, W, H)
+    mask, a, b = L.written_mask(oracle, hs, H, W, comp=4, stride=W + 5, samples=1)
+    L.assert_discriminating(a[:, :W], owner >= 0, count, label=f"mask {W}x{H}")
+    assert np.array_equal(mask, owner >= 0)
+    for arr, fill in ((a, 7), (b, 200)):
+        assert (arr[:, W:] == fill).all() and (arr[..., 3] == fill).all()
+        assert (arr[:, :W][~mask] == fill).all()
+    slots = L.special_slots(hs)
+    for name in ("zero_area", "collinear", "outside"):
+        assert not (owner == slots[name]).any(), name
+    uv = L.aos_uvs(hs)
+    for name in ("edge_left", "edge_right", "negative", "zero_normal"):
+        assert L.np_rasterise(uv[slots[name]][None].copy(), W, H)[1].any(), name
+    if W % 2 == 0:                      # the shared edge u = 0.5 runs through texel centres: both triangles accept them
+        pair = np.stack([uv[slots["edge_left"]], uv[slots["edge_right"]]])
+        assert (L.np_rasterise(pair, W, H)[1][H // 4 + 1:3 * H // 4, W // 2] == 2).all()
+    zn = owner == slots["zero_normal"]          # no direction agrees with a zero normal: 64 tries, then cos = 0: writes 0
+    assert zn.any() and (a[:, :W, :3][zn] == 0).all()
+
+
+def test_oracle_last_triangle_wins(oracle):
+    """Moving the charts of the slots below m off the map leaves every texel owned by a slot >= m byte-equal (the seed is
+    (texel, owner), the geometry is untouched, untextured materials read no UV), and uncovers what lay beneath the others."""
+    W, H, samples = 40, 48, 2
+    hs = L.emissive_soup(3, 300, textured=False)
+    uv = L.aos_uvs(hs)
+    owner, count = L.np_rasterise(hs, W, H)
+    m = int(np.median(owner[owner >= 0]))
+    a = L.oracle_bake(oracle, hs, H, W, samples=samples, fill=FILL)
+    L.assert_discriminating(a, owner >= 0, count, label="last wins")
+    uv[:m] = np.float32(-5.0)
+    b = L.oracle_bake(oracle, hs, H, W, samples=samples, fill=FILL)
+    owner_b, _ = L.np_rasterise(hs, W, H)
+    keep = owner >= m
+    assert keep.mean() > 0.2 and np.array_equal(a[keep], b[keep])
+    assert np.array_equal(owner_b[keep], owner[keep]) and (owner_b[~keep] < m).all()
+    under = (count >= 2) & (owner >= 0) & (owner < m)
+    assert under.sum() > 50
+    assert (a[under] != b[under]).any(axis=-1).mean() > 0.5         # differ, or fell back to the fill
+    assert ((b[under] == FILL).all(axis=-1) == (owner_b[under] < 0)).all()
+
+
+def _facing_triangle():
+    """One large triangle in the plane z = 0 with the constant normal +z, its chart over most of the map, under a backdrop
+    of 4 x 4 emissive quads of different colours at z = 0.75 (their charts are zero-area points off the map)."""
+    from raytracing_c_amd.background import procedural_background
+    from raytracing_c_amd.loaders import camera_from_trs
+    from raytracing_c_amd.scene import Material, build_scene
+    P = [[[-1, -1, 0], [1, -1, 0], [-1, 1, 0]]]
+    N = [[[0, 0, 1]] * 3]
+    UV = [[(0.05, 0.05), (0.95, 0.05), (0.05, 0.95)]]
+    ids = [0]
+    mats = [Material()]
+    rng = np.random.default_rng(5)
+    for j in range(4):
+        for i in range(4):
+            x0, x1, y0, y1 = -2 + i, -1 + i, -2 + j, -1 + j
+            # wound so that the geometric normal is -z as well: a triangle seen from behind is passed through (raytracer.c:517)
+            P += [[[x0, y0, 0.75], [x1, y1, 0.75], [x1, y0, 0.75]], [[x0, y0, 0.75], [x0, y1, 0.75], [x1, y1, 0.75]]]
+            N += [[[0, 0, -1]] * 3] * 2
+            UV += [[(-5, -5)] * 3] * 2
+            ids += [len(mats)] * 2
+            mats.append(Material(emission=tuple(rng.uniform(40, 250, 3)), roughness=1.0))
+    return build_scene(np.array(P, np.float32), np.array(N, np.float32), np.array(UV, np.float32), ids, mats, [],
+                       camera_from_trs((0, 0, 5)), 0.9, procedural_background(64, 32))
+
+
+def test_oracle_lightmap_interpolates_samples_and_seeds(oracle):
+    W, H = 32, 32
+    hs = _facing_triangle()
+    owner, count = L.np_rasterise(hs, W, H)
+    assert len(np.unique(owner[owner >= 0])) == 1
+    one = L.oracle_bake(oracle, hs, H, W, samples=1)
+    five = L.oracle_bake(oracle, hs, H, W, samples=5)
+    # a single chart: no overlap by construction
+    for lm, label in ((one, "facing s=1"), (five, "facing s=5")):
+        L.assert_discriminating(lm, owner >= 0, count, ("written", "distinct", "zero", "saturated"), label=label)
+    assert np.array_equal(one, L.oracle_bake(oracle, hs, H, W, samples=1))
+    assert np.array_equal(five, L.oracle_bake(oracle, hs, H, W, samples=5))
+    assert (one != five)[owner >= 0].any(axis=-1).mean() > 0.5
+    other = L.oracle_bake(oracle, hs, H, W, samples=5, seed=SEED + 1)
+    assert (other != five)[owner >= 0].any(axis=-1).mean() > 0.5
+    assert np.array_equal((other != FILL).any(axis=-1), owner >= 0)
+    # five samples of cos * radiance under emitters of 40..250: the mean over the map is far from both ends of a u8
+    assert 20 < five[owner >= 0].mean() < 120
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU == oracle, byte for byte, over the whole backing buffer
+
+def _lit_model(asset, builder="reference", v_shift=0.0, offset=0.0):
+    """An asset with every material's emission raised, inside a box of emissive walls three times its size: a ray that
+    leaves the mesh meets a wall instead of the background, whose radiance is below 1 and bakes to 0."""
+    from raytracing_c_amd.background import procedural_background
+    from raytracing_c_amd.loaders import camera_from_trs, load_model_data
+    from raytracing_c_amd.scene import Material, build_scene
+    d = load_model_data(os.path.join(ASSETS, asset))
+    mats = list(d["materials"])
+    for k, m in enumerate(mats):
+        m.emission = (30.0 + 10 * (k % 5), 60.0, 90.0 - 10 * (k % 5))
+    pos = np.asarray(d["positions"], np.float32) + np.float32(offset)      # translated as tests/_far_scene.py does
+    lo, hi = pos.reshape(-1, 3).min(axis=0), pos.reshape(-1, 3).max(axis=0)
+    c, r = (lo + hi) / 2, 3 * (hi - lo).max()
+    P, N, ids = [], [], []
+    for axis, em in enumerate(((120.0, 40.0, 20.0), (30.0, 110.0, 50.0), (25.0, 45.0, 130.0))):
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        for side in (-1.0, 1.0):
+            q = np.zeros((4, 3))
+            q[:, axis] = side
+            q[:, u], q[:, v] = (-1, 1, 1, -1), (-1, -1, 1, 1)
+            q = c + r * q
+            n = np.zeros(3)
+            n[axis] = -side
+            for t in (q[[0, 1, 2]], q[[0, 2, 3]]):          # wound so that the geometric normal points inward: a wall
+                P.append(t if np.dot(np.cross(t[1] - t[0], t[2] - t[0]), n) > 0 else t[[0, 2, 1]])    # seen from behind is passed through
+            N += [[n] * 3] * 2
+            ids += [len(mats)] * 2
+        mats.append(Material(emission=em, roughness=1.0))
+    uvs = np.asarray(d["uvs"], np.float32).reshape(-1, 3, 2).copy()
+    uvs[..., 1] += np.float32(v_shift)
+    cam = d["camera"] or (camera_from_trs((0, 0, 5)), 0.9)
+    return build_scene(np.concatenate([pos.reshape(-1, 3, 3), np.array(P, np.float32)]),
+                       np.concatenate([np.asarray(d["normals"], np.float32).reshape(-1, 3, 3), np.array(N, np.float32)]),
+                       np.concatenate([uvs, np.full((12, 3, 2), -5.0, np.float32)]),
+                       np.concatenate([np.asarray(d["material_ids"]).reshape(-1), ids]), mats, d["images"], cam[0], cam[1],
+                       procedural_background(), builder=builder)
+
+
+def _big_soup():
+    hs = L.emissive_soup(9, 40000, chart=0.012, textured=True)
+    assert hs.depth == 5 and hs.n_nodes == 4681          # more nodes than the LDS copy holds; 262 144 owner-pass blocks
+    return hs
+
+
+def _empty_scene():
+    from tests.test_gpu_edge_cases import _empty_scene as empty
+    return empty()
+
+
+def _edit_64_vertices(hs):
+    """moves vertex a of 64 populated slots, in place, without telling the library (no rt_scene_touch)"""
+    soa = hs.soa_array()                                   # (9, slots): x0 x1 x2 y0 y1 y2 z0 z1 z2
+    used = np.nonzero(np.any(soa != 0, axis=0))[0]
+    pick = used[:: max(1, len(used) // 64)][:64]
+    assert len(pick) == 64
+    soa[np.ix_([0, 3, 6], pick)] += np.random.default_rng(2).normal(size=(3, 64)).astype(np.float32) * np.float32(0.1)
+
+
+def _soup():
+    return L.emissive_soup(3, 300, textured=True)
+
+
+SMALL = ("written", "overlap", "zero", "saturated")       # 64 texels hold too few values to ask for 48 distinct ones
+TINY = ("some",)                                          # 1 and 6 texels: shares mean nothing; something lit is written
+
+# name: scene, W, H, components, stride, samples, vacuity checks[, variants: (tag, seed, edit made before the bake)]
+CASES = {
+    "soup_40x48_stride53": (_soup, 40, 48, 3, 53, 3, L.ALL_CHECKS),          # textured shade_hit, overlap, clipping, padding
+    "soup_33x31_rgba":     (_soup, 33, 31, 4, 33, 4, L.ALL_CHECKS),          # odd sizes, alpha, 1023 texels: a ragged last block
+    "soup_1x64":           (_soup, 1, 64, 3, 1, 3, SMALL),
+    "soup_64x1":           (_soup, 64, 1, 3, 64, 3, SMALL),
+    "soup_1x1":            (_soup, 1, 1, 3, 1, 3, TINY),
+    "soup_3x2":            (_soup, 3, 2, 3, 3, 3, TINY),
+    "samples_1":           (_soup, 24, 24, 3, 24, 1, L.ALL_CHECKS),
+    "samples_17":          (_soup, 24, 24, 3, 24, 17, L.ALL_CHECKS),
+    "far_300":             (lambda: L.emissive_soup(3, 300, textured=True, offset=300.0), 40, 48, 3, 40, 3, L.ALL_CHECKS),
+    "far_1e5":             (lambda: L.emissive_soup(3, 300, emission=100.0, textured=True, offset=1e5), 40, 48, 3, 40, 3, L.ALL_CHECKS),
+    # the soups' hits rarely graze a leaf box, and only there do the two slab forms part (tests/test_oracle_contracts.py, D9): the
+    # spheres do -- with the fused form forced beyond its domain, 11 texels of this map change
+    "far_spheres_1e5":     (lambda: _lit_model("spheres.glb", offset=1e5), 64, 64, 3, 64, 4, L.ALL_CHECKS),
+    "soup_40000":          (_big_soup, 32, 32, 3, 32, 2, L.ALL_CHECKS),
+    "helmet_sah":          (lambda: _lit_model("helmet.glb", "sah", -1.0), 64, 36, 3, 64, 2, L.ALL_CHECKS),
+    "tower_lit":           (lambda: _lit_model("tower.obj"), 96, 96, 3, 96, 2, L.ALL_CHECKS),
+    "empty":               (_empty_scene, 40, 24, 3, 45, 2, ()),              # nothing to see: the map must stay as it was
+    "edit_in_place":       (_soup, 40, 48, 3, 40, 2, L.ALL_CHECKS, (("before", SEED, None), ("after", SEED, _edit_64_vertices))),
+    "two_seeds":           (_soup, 40, 48, 3, 40, 2, L.ALL_CHECKS, (("seed 1", 1, None), ("seed 2", 0xC0FFEE, None))),
+}
+_WANT = {}
+
+
+def _steps(oracle, name):
+    """Yields (scene, seed, the oracle's backing array) for each bake of a case, after the case's edit for that bake was
+    made on a fresh scene.  The oracle's arrays are computed once per process and never written again; each has passed the
+    vacuity conditions of its case, and everything outside the owned texels' RGB still holds the fill."""
+    scene, W, H, comp, stride, samples, checks = CASES[name][:7]
+    variants = CASES[name][7] if len(CASES[name]) > 7 else (("", SEED, None),)
+    hs = scene()
+    for tag, seed, edit in variants:
+        if edit:
+            edit(hs)
+        if (name, tag) not in _WANT:
+            want = L.oracle_bake(oracle, hs, H, W, comp, stride, samples, FILL, seed)
+            owner, count = L.np_rasterise(hs, W, H)
+            L.assert_discriminating(want[:, :W], owner >= 0, count, checks, label=f"{name} {tag}".strip())
+            rest = np.ones(want.shape, bool)
+            rest[:, :W, :3][owner >= 0] = False
+            assert (want[rest] == FILL).all()
+            if name == "empty":
+                assert (want == FILL).all()
+            want.setflags(write=False)
+            _WANT[(name, tag)] = want
+        yield hs, seed, _WANT[(name, tag)]
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_oracle_lightmap_cases_are_discriminating(oracle, name):
+    """Every map the GPU is compared with, baked by the oracle alone: the vacuity numbers are printed (-s) and asserted."""
+    maps = [want for _, _, want in _steps(oracle, name)]
+    if len(maps) == 2:
+        assert (maps[0] != maps[1]).any(axis=-1).mean() > 0.05
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_gpu_lightmap_equals_oracle(oracle, name):
+    import raytracing_c_amd as rt
+    assert rt.lib.rt_init(0) == 0, rt.last_error()
+    _, W, H, comp, stride, samples = CASES[name][:6]
+    maps = []
+    try:
+        for hs, seed, want in _steps(oracle, name):
+            img, got = L.padded_image(H, W, comp, stride, FILL)
+            rt.lib.rt_clear_error()
+            rt.lib.rt_set_seed(seed)
+            rt.lib.lightmap_bake(C.byref(img), C.byref(hs.scene), samples)
+            assert rt.last_error() == ""
+            diff = (got != want)
+            assert not diff.any(), (name, int(diff.sum()), np.argwhere(diff)[:4].tolist())
+            maps.append(want)
+    finally:
+        rt.lib.rt_set_seed(SEED)
+    if len(maps) == 2:
+        assert (maps[0] != maps[1]).any(axis=-1).mean() > 0.05
