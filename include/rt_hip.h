@@ -283,6 +283,42 @@ extern int rt_scene_occluded(Scene const *scene, i64 n, Ray const *rays, f32 con
  * a hit, 8-box slab tests (raytracer.c:452) and 8-triangle tests (:476).  Synchronises.  rt_get_counters() is not affected. */
 extern int rt_get_query_counters(RT_Query_Counters *out);
 
+/* ---- first-hit feature buffers ----------------------------------------------------- */
+
+/* What the camera sees at the first surface, per pixel: coverage, albedo, shading normal and world position -- the inputs of a
+ * feature-guided denoiser, a matte, an edge-aware upscaler, outlines, debug views.  For pixel (x, y) and sample s the ray is the
+ * frame's own primary ray (raytracer.c:641-694) and the loop is cast_ray's (raytracer.c:505-558) for at most max_bounces
+ * iterations: a hit whose geometric or shading normal faces along the ray is passed through and uses up an iteration; the first
+ * hit the reference would hand to a shader is the FEATURE HIT.  A miss or an exhausted loop leaves every channel of the sample 0.
+ *   coverage : 1
+ *   albedo   : PBR_Shader_Data.base_color, times the decoded texture_albedo sample when there is one (driver.c:364-368), for
+ *              disney and debug materials alike
+ *   normal   : debug_shader_proc's emission (driver.c:411-418): the normal-mapped normal * 0.5 + 0.5
+ *   position : Shader_Input.position (world space, signed)
+ * A pixel's value is the mean over its `samples` samples, accumulated order-free in 32.32 fixed point like the frame
+ * (rt_math.h: rt_accum_quantize / rt_accum_resolve; position rt_accum_quantize_signed / rt_accum_resolve_signed): coverage,
+ * albedo and normal are the frame the reference would render if every shader emitted the feature and terminated, under a black
+ * background.  The seed is not read (the jitter is a hash of pixel and sample).  One kernel of its own (rt_features_kernel,
+ * csrc/rt_features.hip) on the traversal of the path kernel; frames, views, queries and their counters are not affected. */
+#define RT_FEATURE_CHANNELS 10   /* coverage, albedo rgb, normal xyz, position xyz -- in this order */
+typedef struct { f32 *coverage, *albedo, *normal, *position; } RT_Features;   /* f32[h][w] / f32[h][w][3]; NULL = not wanted */
+
+/* Device level, like rt_render_accumulate(): d_sums = u64[height][width][RT_FEATURE_CHANNELS] on the device the scene was
+ * uploaded to, zero on entry; the camera is rt_set_camera()'s (rt_scene_upload() captures scene->camera); only enqueues work on
+ * `stream`.  params->sample_first / sample_count are honoured (a buffer can be filled progressively and resolved once), seed is
+ * not read, rank / world other than 0 / 1 are refused.  rt_resolve_features(): sums -> means, planar f32 on the device, NULL =
+ * not wanted (at least one is).  0 on success, -1 + rt_last_error(). */
+extern int rt_render_accumulate_features(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums, void *stream);
+extern int rt_resolve_features(RT_Render_Params const *params, void const *d_sums,
+                               void *d_coverage, void *d_albedo, void *d_normal, void *d_position, void *stream);
+/* Host level: the cached device copy of `scene` with rt_render_frame()'s scene check and device lock, camera = scene->camera;
+ * out (optional) names the planes wanted, sums (optional) = u64[height][width][RT_FEATURE_CHANNELS].  One device only: with
+ * rt_device_count() > 1 the call fails.  Checked before the GPU is touched: scene not NULL, width, height, samples > 0,
+ * max_bounces >= 0, width x height <= 2^28, at least one plane of `out` or `sums` given.  A refused call leaves the outputs
+ * untouched.  Runs on the NULL stream like rt_render_frame(): it overlaps a frame in flight (rt_frame_begin). */
+extern int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
+                              RT_Features const *out, u64 *sums);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

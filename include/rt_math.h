@@ -419,6 +419,22 @@ RT_FN float rt_accum_resolve(uint64_t sum, uint32_t samples) {
   return (float)mean;
 }
 
+/* The same for a SIGNED quantity (a world position, rt_render_features): clamped to +-RT_ACCUM_MAX, times 2^32 in double
+ * (exact: 24 significant bits), truncated towards zero, kept as a two's-complement u64 and summed mod 2^64 -- order-free like
+ * the unsigned sums.  NaN counts as 0. */
+RT_FN uint64_t rt_accum_quantize_signed(float c) {
+  float v = (c == c) ? c : 0.0f;
+  v = (v > RT_ACCUM_MAX) ? RT_ACCUM_MAX : v;
+  v = (v < -RT_ACCUM_MAX) ? -RT_ACCUM_MAX : v;
+  return (uint64_t)(int64_t)((double)v * 4294967296.0);
+}
+
+/* sum of `samples` signed quantised values -> their mean, rounded once */
+RT_FN float rt_accum_resolve_signed(uint64_t sum, uint32_t samples) {
+  double mean = (double)(int64_t)sum / ((double)samples * 4294967296.0);
+  return (float)mean;
+}
+
 /* average -> clamp -> sRGB -> u8, raytracer.c:700-716 */
 RT_FN uint8_t rt_encode_u8(float linear) {
   float c = rt_clampf(linear, 0.0f, 1.0f);

@@ -154,6 +154,21 @@ typedef struct {
 #define RT_QUERY_COUNTERS 4
 #define RT_HIT_DWORDS     22   /* RT_Device_Hit (rt_hip.h), 88 bytes */
 
+/* First-hit feature buffers (rt_features_kernel, rt_features.hip; include/rt_hip.h rt_render_accumulate_features): what one
+ * launch reads and writes besides the scene, camera and frame fields of RT_KParams.  A unit = 64 camera paths of one 8x8 tile:
+ * (64 >> shift) neighbouring pixels of the tile x (1 << shift) samples, pixel-major; unit u -> tile u / units_per_tile, then
+ * pixel group (u % units_per_tile) / n_sample_blocks, sample block u % n_sample_blocks. */
+typedef struct {
+  unsigned long long *sums;    /* [height][width][RT_FEATURE_CHANNELS] 32.32 fixed point (position: two's complement), added to */
+  uint32_t    *head;           /* units handed out so far (zero at launch)                                                */
+  int32_t      n_units;
+  int32_t      grab;           /* units a wave takes per atomic on `head`                                                 */
+  int32_t      tiles_x;        /* ceil(width / 8)                                                                         */
+  int32_t      shift;          /* log2 samples per unit, 0 .. 6                                                           */
+  int32_t      n_sample_blocks;/* ceil(samples of this launch >> shift)                                                   */
+  int32_t      units_per_tile; /* (1 << shift) pixel groups x n_sample_blocks                                             */
+} RT_FParams;
+
 #define WF_CHUNK        256
 #define WF_HIT0_FIELDS  9      /* direction (3), t, triangle, u, v, pixel (y << 16 | x), sample                         */
 #define WF_HIT_FIELDS   5      /* index of the ray record (chunk * WF_CHUNK + slot), t, triangle, u, v                  */

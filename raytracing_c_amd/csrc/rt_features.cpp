@@ -1,0 +1,191 @@
+// rt_features.cpp -- first-hit feature buffers (include/rt_hip.h): coverage, albedo, shading normal and world position of what the
+// camera sees, on the device level (device pointers, one launch on the caller's stream) and on the host level (host arrays, the
+// cached device copy of a Scene with the frame path's scene check).  The work is rt_features_kernel and
+// rt_features_resolve_kernel (rt_features.hip); nothing here computes a feature on the CPU.
+
+#include "rt_host.h"
+
+static_assert(RT_FEATURE_CHANNELS == 10, "coverage, albedo rgb, normal xyz, position xyz");
+
+// What can be checked without the device.  `who` prefixes the messages.
+static int check_feature_params(const char *who, RT_Render_Params const *p) {
+  if (!p) return rt_fail("%s: render params are NULL", who);
+  if (p->width <= 0 || p->height <= 0) return rt_fail("%s: image size %dx%d is invalid", who, p->width, p->height);
+  if ((int64_t)p->width * p->height > (int64_t)1 << 28) return rt_fail("%s: image %dx%d is too large (more than 2^28 pixels)", who, p->width, p->height);
+  if (p->samples <= 0) return rt_fail("%s: samples must be positive (got %d)", who, p->samples);
+  if (p->max_bounces < 0) return rt_fail("%s: max_bounces must be >= 0 (got %d)", who, p->max_bounces);
+  if (p->rank != 0 || p->world != 1) return rt_fail("%s: rank %d / world %d: a feature pass renders the whole image on one device (0 / 1)", who, p->rank, p->world);
+  if (p->sample_first < 0 || p->sample_count < 0 || p->sample_first + p->sample_count > p->samples)
+    return rt_fail("%s: sample range [%d, +%d) outside [0, %d)", who, p->sample_first, p->sample_count, p->samples);
+  return 0;
+}
+
+// Enqueues one launch of the feature kernel on `stream`.  D.mutex held, D's GPU current, every pointer on D.
+static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream) {
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) K.cam[i][j] = cam->view_matrix.rows[i][j];
+  K.focal_length = cam->focal_length;
+  {
+    volatile float fw = (float)p->width, fh = (float)p->height;      // plain IEEE fp32 divisions (raytracer.c:615-617), as for a frame
+    volatile float iw = 1.0f / fw, ih = 1.0f / fh, asp = fw / fh;
+    K.inv_width = iw;
+    K.inv_height = ih;
+    K.aspect = asp;
+  }
+  K.width = p->width;
+  K.height = p->height;
+  K.samples = p->samples;
+  K.max_bounces = p->max_bounces;
+  K.sample_first = p->sample_first;
+  K.sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
+  const int n_samples = K.sample_end - K.sample_first;
+  if (n_samples <= 0 || K.max_bounces == 0) return 0;             // nothing to trace: every sample of the range is 0
+
+  // units: 64 paths of one 8x8 tile = (64 >> shift) pixels x (1 << shift) samples (RT_FParams, rt_device.h)
+  RT_FParams F;
+  memset(&F, 0, sizeof F);
+  int shift = 0;
+  while (shift < 6 && (1 << shift) < n_samples) shift++;
+  F.shift = shift;
+  F.n_sample_blocks = (n_samples + (1 << shift) - 1) >> shift;
+  F.units_per_tile = F.n_sample_blocks << shift;
+  F.tiles_x = (p->width + RT_TILE - 1) / RT_TILE;
+  const int64_t n_units = (int64_t)F.tiles_x * ((p->height + RT_TILE - 1) / RT_TILE) * F.units_per_tile;
+  // (the kernel's 32-bit work counter ends at n_units plus one grab per wave)
+  if (n_units > (int64_t)0x7fff0000) return rt_fail("feature pass: too many work items (%lld)", (long long)n_units);
+  F.n_units = (int)n_units;
+  F.sums = (unsigned long long *)d_sums;
+
+  // launch geometry: the query kernel's (rt_query.cpp) -- one workgroup of 16 waves per CU, the tree fills the LDS
+  const int wg_waves = 16;
+  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256;         // the wave's perm stack
+  const int lds_limit = 160 * 1024 - 64;                          // (- the kernel's static LDS: the 32-byte sRGB scale table)
+  int room = (lds_limit - wg_waves * per_wave) / 208;
+  if (room < 0) room = 0;
+  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
+  if (!d->boxes_ordered) K.n_lds_nodes = 0;                       // (the LDS node blocks assume min <= max)
+  const int smem = K.n_lds_nodes * 208 + wg_waves * per_wave;
+  int64_t blocks = (n_units + wg_waves - 1) / wg_waves;
+  if (blocks > D.num_cus) blocks = D.num_cus;
+  // units per grab: an eighth of a wave's mean share, within [1, 8] -- what is left when the counter runs out is one grab per wave
+  int64_t grab = n_units / (blocks * wg_waves * 8);
+  F.grab = grab < 1 ? 1 : (grab > 8 ? 8 : (int)grab);
+
+  int slot = 0;
+  if (ensure_query_state(D) != 0 || acquire_slot(D, &slot, false) != 0) return -1;
+  uint8_t *sl = D.query.slots + (size_t)slot * 64;
+  F.head = (uint32_t *)(sl + 32);
+  HIP_TRY(hipMemsetAsync(F.head, 0, 4, stream));                  // (the slot's query counters stay: rt_get_query_counters)
+  int rc = rt_launch_features(&K, &F, (int)blocks, smem, stream);
+  if (rc != 0) return rt_fail("feature kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  HIP_TRY(hipEventRecord(D.query.done[slot], stream));
+  return 0;
+}
+
+static int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal,
+                           void *d_position, hipStream_t stream) {
+  int rc = rt_launch_features_resolve(p->width * p->height, p->samples, (const unsigned long long *)d_sums, (float *)d_coverage,
+                                      (float *)d_albedo, (float *)d_normal, (float *)d_position, stream);
+  if (rc != 0) return rt_fail("feature resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- device level -------------------------------------------------------------------------------------------------------------
+extern "C" int rt_render_accumulate_features(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums, void *stream) {
+  const char *who = "rt_render_accumulate_features";
+  // (everything that can be checked without the device is checked before it is touched)
+  if (!dscene) return rt_fail("%s: device scene is NULL", who);
+  if (check_feature_params(who, params) != 0) return -1;
+  if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  auto it = D.cameras.find(dscene);
+  if (it == D.cameras.end()) return rt_fail("%s: no camera set for this scene (rt_set_camera)", who);
+  return enqueue_features(D, dscene, &it->second, params, d_sums, (hipStream_t)stream);
+}
+
+extern "C" int rt_resolve_features(RT_Render_Params const *params, void const *d_sums, void *d_coverage, void *d_albedo,
+                                   void *d_normal, void *d_position, void *stream) {
+  const char *who = "rt_resolve_features";
+  if (check_feature_params(who, params) != 0) return -1;
+  if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if (!d_coverage && !d_albedo && !d_normal && !d_position) return rt_fail("%s: no output is wanted", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_resolve(params, d_sums, d_coverage, d_albedo, d_normal, d_position, (hipStream_t)stream);
+}
+
+// ---- host level ---------------------------------------------------------------------------------------------------------------
+// Gives back the staging of the host-level call.  D.mutex held, D's GPU current, device idle.
+void release_feature_state(Device &D) {
+  (void)hipFree(D.features.sums);
+  (void)hipFree(D.features.planes);
+  D.features = FeatureState();
+}
+
+extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces, RT_Features const *out,
+                                  u64 *sums) {
+  const char *who = "rt_render_features";
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  if (samples > 0x7fffffff || max_bounces > 0x7fffffff) return rt_fail("%s: samples / max_bounces do not fit 32 bits", who);
+  RT_Render_Params p;
+  memset(&p, 0, sizeof p);
+  p.width = width;
+  p.height = height;
+  p.samples = samples < 0 ? -1 : (i32)samples;
+  p.max_bounces = max_bounces < 0 ? -1 : (i32)max_bounces;
+  p.world = 1;
+  if (check_feature_params(who, &p) != 0) return -1;
+  const bool planes = out && (out->coverage || out->albedo || out->normal || out->position);
+  if (!planes && !sums) return rt_fail("%s: no output is wanted (every plane of `out` and `sums` are NULL)", who);
+
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (rt_device_count() > 1)
+    return rt_fail("%s: a feature pass renders on one device, and %d are set (rt_set_devices)", who, rt_device_count());
+  FeatureState &S = D.features;
+  const size_t pixels = (size_t)width * height;
+  if (S.cap_pixels < pixels) {
+    release_feature_state(D);
+    HIP_TRY(hipMalloc(&S.sums, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&S.planes, pixels * RT_FEATURE_CHANNELS * sizeof(float)));
+    S.cap_pixels = pixels;
+  }
+  float *d_cov = S.planes, *d_alb = S.planes + pixels, *d_nrm = S.planes + pixels * 4, *d_pos = S.planes + pixels * 7;
+  hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
+  const bool verify = !scene_is_static(scene);
+  for (int attempt = 0;; attempt++) {
+    float upload_ms = 0.0f;
+    RT_Device_Scene *d = cached_scene_locked(D, scene, nullptr, &upload_ms);      // the sampled stamp; uploads when it differs
+    if (!d) return -1;
+    HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
+    if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream) != 0) return -1;
+    if (planes && enqueue_resolve(&p, S.sums, out->coverage ? d_cov : nullptr, out->albedo ? d_alb : nullptr,
+                                  out->normal ? d_nrm : nullptr, out->position ? d_pos : nullptr, stream) != 0)
+      return -1;
+    // the full content check of the frame path (render_frame_locked), on this thread, while the GPU works: a host scene that no
+    // longer equals the copy is uploaded again and the pass repeated; nothing has been written yet
+    if (!verify || attempt > 0 || upload_ms > 0.0f) break;
+    if (scene_fingerprint(scene) == d->full_fp) break;
+    HIP_TRY(hipStreamSynchronize(stream));
+    free_device_scene(d);
+    D.scene_cache.erase(scene);
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  if (planes) {
+    if (out->coverage) HIP_TRY(hipMemcpy(out->coverage, d_cov, pixels * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->albedo) HIP_TRY(hipMemcpy(out->albedo, d_alb, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->normal) HIP_TRY(hipMemcpy(out->normal, d_nrm, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->position) HIP_TRY(hipMemcpy(out->position, d_pos, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (sums) HIP_TRY(hipMemcpy(sums, S.sums, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return 0;
+}

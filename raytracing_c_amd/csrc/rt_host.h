@@ -8,6 +8,7 @@
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
+//   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
 //
 // Nothing on the host side computes a pixel on the CPU: every entry point either
@@ -58,6 +59,10 @@ int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, int y0, int 
                            hipStream_t stream);
 int rt_launch_query(const RT_KParams *P, const RT_QParams *Q, int any, int wg_waves, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, const float *hits, float *out, hipStream_t stream);
+// ... in rt_features.hip
+int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
+int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo, float *normal,
+                               float *position, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -212,6 +217,15 @@ struct QueryState {
   size_t     cap_rays = 0, cap_t_max = 0, cap_hits = 0, cap_full = 0, cap_flags = 0;      // rays each staging buffer holds
 };
 
+// First-hit feature buffers (rt_features.cpp): the device staging of the host-level call -- the sums and the ten f32 planes of one
+// frame -- kept between calls, given back with the device slot (release_feature_state).  A launch's work counter is a slot of the
+// query ring above.
+struct FeatureState {
+  unsigned long long *sums = nullptr;         // [pixels][RT_FEATURE_CHANNELS]
+  float              *planes = nullptr;       // coverage [pixels], then albedo, normal, position [pixels][3] each
+  size_t              cap_pixels = 0;
+};
+
 struct Device {
   int        slot = 0, phys = 0;
   bool       ready = false;
@@ -227,6 +241,7 @@ struct Device {
   FrameTiming timing;
   FrameLane  lanes[RT_FRAME_LANES];           // slot 0 only
   QueryState query;
+  FeatureState features;
 };
 
 // Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
@@ -373,6 +388,12 @@ int render_frame_multi(Scene const *scene, Image const *image, RT_Render_Params 
 
 // rt_query.cpp
 void release_query_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
+int  ensure_query_state(Device &D);                                                 // D.mutex held, D's GPU current
+// The ring slot of a new launch.  `query`: a query call, the one rt_get_query_counters() reports.  D.mutex held, D's GPU current.
+int  acquire_slot(Device &D, int *slot, bool query = true);
+
+// rt_features.cpp
+void release_feature_state(Device &D);                                              // D.mutex held, D's GPU current, device idle
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

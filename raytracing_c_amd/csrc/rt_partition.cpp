@@ -109,6 +109,7 @@ void remap_device_slots() {
       W = Workspace();
       D.last_counters = nullptr;
       release_query_state(D);
+      release_feature_state(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);

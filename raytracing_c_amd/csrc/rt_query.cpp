@@ -44,22 +44,25 @@ static void query_geometry(const Device &D, const RT_Device_Scene *d, int n, RT_
   if (Q.exit_lanes < 1 || Q.exit_lanes > 64) Q.exit_lanes = 16;
 }
 
-static int ensure_query_state(Device &D) {                     // D.mutex held, D's GPU current
+int ensure_query_state(Device &D) {                     // D.mutex held, D's GPU current
   QueryState &S = D.query;
   if (S.slots) return 0;
   HIP_TRY(hipMalloc(&S.slots, RT_QUERY_SLOTS * 64));
   return 0;
 }
 
-// The ring slot of a new query call.  D.mutex held, D's GPU current.
-static int acquire_slot(Device &D, int *slot) {
+// The ring slot of a new launch (`query`: of a query call; a feature pass only borrows the slot's work counter and leaves what
+// rt_get_query_counters() reports alone).  D.mutex held, D's GPU current.
+int acquire_slot(Device &D, int *slot, bool query) {
   QueryState &S = D.query;
   const int s = (int)(S.next++ % RT_QUERY_SLOTS);
   if (!S.done[s]) HIP_TRY(hipEventCreateWithFlags(&S.done[s], hipEventDisableTiming));
   if (S.used[s]) HIP_TRY(hipEventSynchronize(S.done[s]));      // (its launch of RT_QUERY_SLOTS calls ago, long over)
   S.used[s] = true;
-  S.last = s;
-  g_query_dev.store(&D);
+  if (query) {
+    S.last = s;
+    g_query_dev.store(&D);
+  }
   *slot = s;
   return 0;
 }

@@ -150,6 +150,13 @@ class RT_Query_Counters(C.Structure):  # rt_hip.h
     _fields_ = [(n, C.c_uint64) for n in ("rays", "hits", "node_visits", "leaf_visits")]
 
 
+class RT_Features(C.Structure):  # rt_hip.h: the planes rt_render_features fills (NULL = not wanted)
+    _fields_ = [(n, C.POINTER(f32)) for n in ("coverage", "albedo", "normal", "position")]
+
+
+RT_FEATURE_CHANNELS = 10          # coverage, albedo rgb, normal xyz, position xyz
+
+
 # numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
 _HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
@@ -190,6 +197,7 @@ EXPORTED_SYMBOLS = [
     "rt_chunk_count", "rt_chunk_owner", "rt_local_chunk_count", "rt_max_local_chunk_count", "rt_local_chunk_list", "rt_render_accumulate", "rt_resolve", "rt_untile",
     "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_render_views", "rt_render_accumulate_views",
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
+    "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 

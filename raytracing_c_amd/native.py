@@ -136,6 +136,10 @@ def _declare(d):
         d.rt_scene_closest.argtypes = [P(abi.Scene), C.c_int64, vp, vp, vp]
         d.rt_scene_occluded.argtypes = [P(abi.Scene), C.c_int64, vp, vp, vp]
         d.rt_get_query_counters.argtypes = [P(abi.RT_Query_Counters)]
+    if hasattr(d, "rt_render_features"):
+        d.rt_render_accumulate_features.argtypes = [vp, P(abi.RT_Render_Params), vp, vp]
+        d.rt_resolve_features.argtypes = [P(abi.RT_Render_Params), vp, vp, vp, vp, vp, vp]
+        d.rt_render_features.argtypes = [P(abi.Scene), C.c_int32, C.c_int32, abi.isize, abi.isize, P(abi.RT_Features), vp]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
