@@ -218,8 +218,24 @@ __device__ __forceinline__ float slab_entry_child_any(const float *n, const Ray3
 #define NODE_LDS_ORDERED 3   // per-lane reads from the workgroup's LDS copy of the top of the tree, the slab planes picked by address (FAST rays, boxes with min <= max)
 #define RT_LDS_NODE_F4 13 // LDS node stride in float4 (12 data + 1 pad: 13 is odd, so random nodes spread over all 16-byte slots of a bank row)
 
+static_assert(RT_LDS_NODE_F4 * 16 == RT_LDS_NODE_BYTES, "the host splits the LDS by the kernels' node stride (rt_device.h, lds_split)");
+
 // float4 index of LDS node `node`: a 24-bit multiply is full rate, v_mul_lo_u32 a quarter
 __device__ __forceinline__ int lds_node_f4(int node) { return (int)__umul24((unsigned)node, (unsigned)RT_LDS_NODE_F4); }
+
+// Host side of a launcher: more than 48 KB of dynamic LDS need the kernel's limit raised to `limit` bytes (dynamic + static LDS stay
+// within RT_LDS_BYTES), once per device.  `devices`: the caller's own static mask of the devices done -- one per kernel instance:
+// the attribute belongs to the function ON ONE DEVICE (a frame spread over N GPUs launches from N).  Returns a hipError_t.
+static inline int raise_lds_limit(const void *kernel, uint32_t *devices, int smem_bytes, int limit) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(devices, __ATOMIC_RELAXED) & (1u << dev)))) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e != hipSuccess) return (int)e;
+    if (dev < 32) __atomic_fetch_or(devices, 1u << dev, __ATOMIC_RELAXED);
+  }
+  return 0;
+}
 
 template <bool FAST, int MODE>
 __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &r, int node, float hit_t,

@@ -25,6 +25,14 @@
 #define RT_MAT_FLOATS 36
 #define RT_MAX_DEPTH  8      /* perm-stack levels in LDS  */
 
+/* LDS of a workgroup of the kernels on traversal_blocks(): the leading BVH nodes (level order), then per wave a perm stack of one
+ * level per tree level (at least one) and what else the kernel keeps per wave.  Split by lds_split (rt_launch.cpp). */
+#define RT_LDS_BYTES            (160 * 1024)   /* LDS of a CU                                                              */
+#define RT_LDS_NODE_BYTES       208            /* a node in LDS: 12 float4 of data + 1 of padding                          */
+#define RT_LDS_TABLE_BYTES      64             /* static LDS of a kernel with the sRGB scale table (32 bytes, rounded up)   */
+#define RT_LDS_PERM_LEVEL_BYTES 256            /* one level of a wave's perm stack                                         */
+#define RT_LDS_ACC_TILE_BYTES   1536           /* path kernel, wavefront kernels: a wave's 8x8-pixel accumulator tile      */
+
 #define RT_MAT_DISNEY 0
 #define RT_MAT_DEBUG  1
 

@@ -83,28 +83,20 @@ int launch_wavefront(Device &D, RT_Device_Scene *d, RT_KParams &K, hipStream_t s
   if (geometry < 0 || geometry > 2) geometry = 0;
   int geometry_cam = knob_int("RT_WF_GEOMETRY_CAM", geometry);
   if (geometry_cam < 0 || geometry_cam > 2) geometry_cam = 0;
-  const int lds_limit = 160 * 1024;
   static const int wpb_of[3] = {16, 12, 10}, bpc_of[3] = {1, 2, 2};
   const int wpb_cam = wpb_of[geometry_cam], bpc_cam = bpc_of[geometry_cam], wpb_tr = wpb_of[geometry], bpc_tr = bpc_of[geometry];
-  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;                   // perm stack + accumulator tile
   const int cam_blocks = D.num_cus * bpc_cam, cam_waves = cam_blocks * wpb_cam;
   const int tr_blocks = D.num_cus * bpc_tr, tr_waves = tr_blocks * wpb_tr;
   int shade_blocks_per_cu = knob_int("RT_WF_SHADE_BLOCKS", 5);
   if (shade_blocks_per_cu < 1 || shade_blocks_per_cu > 8) shade_blocks_per_cu = 5;
   const int shade_blocks = D.num_cus * shade_blocks_per_cu, shade_waves = shade_blocks * 4;
   const int max_waves = std::max(std::max(cam_waves, tr_waves), shade_waves);
-  auto lds_nodes_for = [&](int waves_per_block, int blocks_per_cu) {
-    int room = (lds_limit / blocks_per_cu - waves_per_block * per_wave) / 208;
-    if (room < 0) room = 0;
-    int n = d->n_nodes < room ? d->n_nodes : room;
-    if (!d->boxes_ordered) n = 0;
-    int v = knob_int("RT_LDS_NODES", n);
-    if (v >= 0 && v < n) n = v;
-    return n;
-  };
-  const int n_lds_cam = lds_nodes_for(wpb_cam, bpc_cam), n_lds_trace = lds_nodes_for(wpb_tr, bpc_tr);
-  const int smem_cam = n_lds_cam * 208 + wpb_cam * per_wave;
-  const int smem_trace = n_lds_trace * 208 + wpb_tr * per_wave;
+  // per wave the perm stack and the accumulator tile; the CU's whole LDS is shared out (these launches never counted the table)
+  LdsSplit S_cam = lds_split(d, K.depth, wpb_cam, RT_LDS_ACC_TILE_BYTES, bpc_cam, false);
+  LdsSplit S_trace = lds_split(d, K.depth, wpb_tr, RT_LDS_ACC_TILE_BYTES, bpc_tr, false);
+  S_cam.cap(knob_int("RT_LDS_NODES", -1));
+  S_trace.cap(knob_int("RT_LDS_NODES", -1));
+  const int n_lds_cam = S_cam.n_lds_nodes, n_lds_trace = S_trace.n_lds_nodes, smem_cam = S_cam.smem, smem_trace = S_trace.smem;
 
   const int64_t paths = (int64_t)K.n_tiles * 64 * (K.sample_end - K.sample_first);
   if (wavefront_ensure_queues(d, paths, cam_waves, max_waves) != 0) return -1;
@@ -301,10 +293,9 @@ extern "C" int rt_test_trace_stream(RT_Device_Scene *d, i32 n, f32 const *rays, 
   if (ensure_device(D) != 0) return -1;
   RT_KParams K;
   scene_only_kparams(&K, d);
-  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
-  int room = (160 * 1024 - 16 * per_wave) / 208;
-  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
-  if (!d->boxes_ordered || mode == 2) K.n_lds_nodes = 0;
+  LdsSplit S = lds_split(d, K.depth, 16, RT_LDS_ACC_TILE_BYTES, 1, false);      // the path kernel's geometry, without its table
+  if (mode == 2) S.cap(0);
+  K.n_lds_nodes = S.n_lds_nodes;
   K.pyr_nodes = K.n_lds_nodes;
   // the short reciprocal is valid while |det| < 2^102: edges <= 2^38 (as for frames) and, here, ray directions <= 2^16
   float dir_max = 0.0f;
@@ -314,7 +305,6 @@ extern "C" int rt_test_trace_stream(RT_Device_Scene *d, i32 n, f32 const *rays, 
       if (!(m <= dir_max)) dir_max = m;
     }
   K.short_div = (mode != 1 && d->max_edge <= 0x1p38f && dir_max <= 0x1p16f) ? 1 : 0;
-  const int smem = K.n_lds_nodes * 208 + 16 * per_wave;
   int n_blocks = (n + 16 * 64 * 4 - 1) / (16 * 64 * 4);                 // ~4 rays per lane
   if (n_blocks > D.num_cus) n_blocks = D.num_cus;
   if (n_blocks < 1) n_blocks = 1;
@@ -328,7 +318,7 @@ extern "C" int rt_test_trace_stream(RT_Device_Scene *d, i32 n, f32 const *rays, 
   HIP_TRY(hipMemcpy(br.p, rays, (size_t)n * 24, hipMemcpyHostToDevice));
   if (pyramid) HIP_TRY(hipMemcpy(bp.p, pyramid, 19 * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(bv.p, 0, 16));
-  int rc = rt_launch_test_trace_stream(&K, n, br.as<float>(), pyramid ? bp.as<float>() : nullptr, exit_lanes, n_blocks, smem,
+  int rc = rt_launch_test_trace_stream(&K, n, br.as<float>(), pyramid ? bp.as<float>() : nullptr, exit_lanes, n_blocks, S.smem,
                                        bt.as<float>(), btri.as<int>(), buv.as<float>(), bv.as<unsigned long long>(), nullptr);
   if (rc == 0) rc = (int)hipMemcpy(out_t, bt.p, (size_t)n * 4, hipMemcpyDeviceToHost);
   if (rc == 0) rc = (int)hipMemcpy(out_tri, btri.p, (size_t)n * 4, hipMemcpyDeviceToHost);

@@ -1,6 +1,6 @@
 // rt_features.cpp -- first-hit feature buffers (include/rt_hip.h): coverage, albedo, shading normal and world position of what the
 // camera sees, on the device level (device pointers, one launch on the caller's stream) and on the host level (host arrays, the
-// cached device copy of a Scene with the frame path's scene check).  The work is rt_features_kernel and
+// cached device copy of a Scene through scene_checked, rt_residency.cpp).  The work is rt_features_kernel and
 // rt_features_resolve_kernel (rt_features.hip); nothing here computes a feature on the CPU.
 
 #include "rt_host.h"
@@ -24,22 +24,7 @@ static int check_feature_params(const char *who, RT_Render_Params const *p) {
 static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream) {
   RT_KParams K;
   scene_only_kparams(&K, d);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 4; j++) K.cam[i][j] = cam->view_matrix.rows[i][j];
-  K.focal_length = cam->focal_length;
-  {
-    volatile float fw = (float)p->width, fh = (float)p->height;      // plain IEEE fp32 divisions (raytracer.c:615-617), as for a frame
-    volatile float iw = 1.0f / fw, ih = 1.0f / fh, asp = fw / fh;
-    K.inv_width = iw;
-    K.inv_height = ih;
-    K.aspect = asp;
-  }
-  K.width = p->width;
-  K.height = p->height;
-  K.samples = p->samples;
-  K.max_bounces = p->max_bounces;
-  K.sample_first = p->sample_first;
-  K.sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
+  camera_frame_kparams(&K, cam, p);
   const int n_samples = K.sample_end - K.sample_first;
   if (n_samples <= 0 || K.max_bounces == 0) return 0;             // nothing to trace: every sample of the range is 0
 
@@ -58,15 +43,11 @@ static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT
   F.n_units = (int)n_units;
   F.sums = (unsigned long long *)d_sums;
 
-  // launch geometry: the query kernel's (rt_query.cpp) -- one workgroup of 16 waves per CU, the tree fills the LDS
+  // launch geometry: the query kernel's (rt_query.cpp) -- one workgroup of 16 waves per CU, the tree fills the LDS beside the waves'
+  // perm stacks and the kernel's static sRGB scale table
   const int wg_waves = 16;
-  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256;         // the wave's perm stack
-  const int lds_limit = 160 * 1024 - 64;                          // (- the kernel's static LDS: the 32-byte sRGB scale table)
-  int room = (lds_limit - wg_waves * per_wave) / 208;
-  if (room < 0) room = 0;
-  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
-  if (!d->boxes_ordered) K.n_lds_nodes = 0;                       // (the LDS node blocks assume min <= max)
-  const int smem = K.n_lds_nodes * 208 + wg_waves * per_wave;
+  const LdsSplit S = lds_split(d, K.depth, wg_waves, 0, 1, true);
+  K.n_lds_nodes = S.n_lds_nodes;
   int64_t blocks = (n_units + wg_waves - 1) / wg_waves;
   if (blocks > D.num_cus) blocks = D.num_cus;
   // units per grab: an eighth of a wave's mean share, within [1, 8] -- what is left when the counter runs out is one grab per wave
@@ -78,7 +59,7 @@ static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT
   uint8_t *sl = D.query.slots + (size_t)slot * 64;
   F.head = (uint32_t *)(sl + 32);
   HIP_TRY(hipMemsetAsync(F.head, 0, 4, stream));                  // (the slot's query counters stay: rt_get_query_counters)
-  int rc = rt_launch_features(&K, &F, (int)blocks, smem, stream);
+  int rc = rt_launch_features(&K, &F, (int)blocks, S.smem, stream);
   if (rc != 0) return rt_fail("feature kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
   HIP_TRY(hipEventRecord(D.query.done[slot], stream));
   return 0;
@@ -160,24 +141,15 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   }
   float *d_cov = S.planes, *d_alb = S.planes + pixels, *d_nrm = S.planes + pixels * 4, *d_pos = S.planes + pixels * 7;
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
-  const bool verify = !scene_is_static(scene);
-  for (int attempt = 0;; attempt++) {
-    float upload_ms = 0.0f;
-    RT_Device_Scene *d = cached_scene_locked(D, scene, nullptr, &upload_ms);      // the sampled stamp; uploads when it differs
-    if (!d) return -1;
+  auto pass = [&](RT_Device_Scene *d) -> int {
     HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
     if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream) != 0) return -1;
     if (planes && enqueue_resolve(&p, S.sums, out->coverage ? d_cov : nullptr, out->albedo ? d_alb : nullptr,
                                   out->normal ? d_nrm : nullptr, out->position ? d_pos : nullptr, stream) != 0)
       return -1;
-    // the full content check of the frame path (render_frame_locked), on this thread, while the GPU works: a host scene that no
-    // longer equals the copy is uploaded again and the pass repeated; nothing has been written yet
-    if (!verify || attempt > 0 || upload_ms > 0.0f) break;
-    if (scene_fingerprint(scene) == d->full_fp) break;
-    HIP_TRY(hipStreamSynchronize(stream));
-    free_device_scene(d);
-    D.scene_cache.erase(scene);
-  }
+    return 0;
+  };
+  if (!scene_checked(D, scene, stream, nullptr, pass)) return -1;      // (a scene edited since the copy: uploaded and traced again)
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
   if (planes) {

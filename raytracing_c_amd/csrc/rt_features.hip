@@ -214,18 +214,12 @@ __global__ void rt_features_resolve_kernel(int n_pixels, int samples, const unsi
   }
 }
 
-// `n_blocks` workgroups of 16 waves; smem_bytes = LDS nodes x 208 + 16 perm stacks (rt_features.cpp, features_geometry)
+// `n_blocks` workgroups of 16 waves; smem_bytes = the LDS nodes + 16 perm stacks (lds_split as rt_features.cpp, enqueue_features, calls it)
 extern "C" int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream) {
-  static uint32_t attr_devices = 0;           // devices on which the kernel's dynamic-LDS limit has been raised
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(&attr_devices, __ATOMIC_RELAXED) & (1u << dev)))) {
-    // (dynamic + the kernel's 32 static bytes, rt_pow24_lds, must stay within the 160 KB of a CU)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_features_kernel<16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 32) __atomic_fetch_or(&attr_devices, 1u << dev, __ATOMIC_RELAXED);
-  }
+  static uint32_t attr_devices = 0;
+  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_features_kernel<16>), &attr_devices, smem_bytes,
+                               RT_LDS_BYTES - RT_LDS_TABLE_BYTES))      // (the kernel has the sRGB scale table)
+    return rc;
   hipLaunchKernelGGL((rt_features_kernel<16>), dim3(n_blocks), dim3(16 * 64), smem_bytes, stream, *P, *F);
   return (int)hipGetLastError();
 }

@@ -69,29 +69,11 @@ static int render_frame_locked(Scene const *scene, Image const *image, isize sam
   Workspace &W = D.ws;
   size_t pixels = (size_t)p.width * p.height;
   hipStream_t stream = nullptr;
-  const bool verify = !scene_is_static(scene);
-  for (int attempt = 0;; attempt++) {
-    float stamp_ms = 0.0f, upload_ms = 0.0f;
-    RT_Device_Scene *d = cached_scene_locked(D, scene, &stamp_ms, &upload_ms);
-    if (!d) return -1;
-    T.stamp_ms += stamp_ms;
-    T.upload_ms += upload_ms;
-    const double t_enq = now_ms();
-    if (enqueue_frame(D, d, camera ? camera : &scene->camera, &p, W, stream, batch ? RT_VIEWS_STATE : 0, nullptr, W.image,
-                      linear ? W.linear : nullptr, batch) != 0)
-      return -1;
-    T.enqueue_ms = (float)(now_ms() - t_enq);
-    // the full content check of the host scene, on this thread, while the GPU renders (see rt_scene_touch): a frame of an
-    // unchanged scene waits for max(kernel, check) instead of kernel + check; a changed scene is uploaded and rendered again
-    if (!verify || attempt > 0 || upload_ms > 0.0f) break;
-    const double t_v = now_ms();
-    const bool same = scene_fingerprint(scene) == d->full_fp;
-    T.verify_ms = (float)(now_ms() - t_v);
-    if (same) break;
-    HIP_TRY(hipStreamSynchronize(stream));
-    free_device_scene(d);
-    D.scene_cache.erase(scene);
-  }
+  auto frame = [&](RT_Device_Scene *d) -> int {
+    return enqueue_frame(D, d, camera ? camera : &scene->camera, &p, W, stream, batch ? RT_VIEWS_STATE : 0, nullptr, W.image,
+                         linear ? W.linear : nullptr, batch);
+  };
+  if (!scene_checked(D, scene, stream, &T, frame)) return -1;      // (a scene edited since the copy: uploaded and rendered again)
 
   for (int v = 0; v < nv; v++)
     if (copy_image_out(&image[v], W.image + v * pixels * 3, p.width, p.height, stream) != 0) return -1;

@@ -1,9 +1,12 @@
 // rt_host.h -- internal header of the host side of librt_hip.so: the reference's render entry points
 // (raytracer.h:51-56) and the device-control calls of include/rt_hip.h, in one unit per concern:
 //   rt_host.cpp       errors, configuration, device slots, seed, material / background tokens
-//   rt_residency.cpp  scene upload, fingerprints and stamps, rt_scene_touch / verify / invalidate / set_static, the per-device cache
+//   rt_residency.cpp  scene upload, fingerprints and stamps, rt_scene_touch / verify / invalidate / set_static, the per-device cache,
+//                     the scene-checked call every host-level entry point runs its work through (scene_checked)
 //   rt_partition.cpp  chunk counts and owners, partition tables, device chunk lists
-//   rt_launch.cpp     launch set-up (fill_kparams, render_accumulate_locked), resolve / untile, workspace buffers, counters, kernel timing
+//   rt_launch.cpp     launch set-up (fill_kparams, render_accumulate_locked), the LDS split and the camera / frame fields every
+//                     kernel on traversal_blocks() is launched with (lds_split, camera_frame_kparams), resolve / untile, workspace
+//                     buffers, counters, kernel timing
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
@@ -351,6 +354,17 @@ bool             scene_is_static(Scene const *scene);               // takes g_s
 int              drop_stale_copies(Scene const *scene, uint64_t now, int first_slot);   // takes each slot's mutex; returns copies dropped
 void             scene_only_kparams(RT_KParams *K, RT_Device_Scene *d);
 RT_Device_Scene *cached_scene_locked(Device &D, Scene const *scene, float *stamp_ms, float *upload_ms);   // D.mutex held
+// What lets a host edit a Scene in place: take the cached copy (sampled stamp; uploads when it differs), run enqueue(ctx, copy) on
+// `stream`, fingerprint the whole host scene on this thread while the GPU works; when it differs from the copy, wait for the stream,
+// drop the copy and do it all once more.  Returns the copy the work finally ran from, nullptr after a failure.  T (optional):
+// stamp_ms and upload_ms are added to, enqueue_ms (the last attempt) and verify_ms set.  D.mutex held, D's GPU current.
+RT_Device_Scene *scene_checked_call(Device &D, Scene const *scene, hipStream_t stream, FrameTiming *T,
+                                    int (*enqueue)(void *ctx, RT_Device_Scene *d), void *ctx);
+// ... with any callable `int enqueue(RT_Device_Scene *)`, called in place: nothing is allocated per call
+template <typename F>
+static inline RT_Device_Scene *scene_checked(Device &D, Scene const *scene, hipStream_t stream, FrameTiming *T, F &enqueue) {
+  return scene_checked_call(D, scene, stream, T, [](void *f, RT_Device_Scene *d) { return (*static_cast<F *>(f))(d); }, &enqueue);
+}
 
 // rt_partition.cpp
 void remap_device_slots();                                                          // takes slot 0's mutex, then each slot's
@@ -361,6 +375,17 @@ int  device_owner_table(Device &D, int width, int height, int world, const int32
 // rt_launch.cpp
 int check_params(RT_Render_Params const *p);
 int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who);   // the batch's sizes; no device needed
+// How a workgroup's LDS is split (rt_device.h): as many leading BVH nodes as fit beside `wg_waves` perm stacks of `depth` levels and
+// `wave_extra_bytes` more per wave, when `wgs_per_cu` workgroups share a CU and -- `static_table` -- the kernel's sRGB table takes
+// RT_LDS_TABLE_BYTES of it (launches that never counted the table say false).  No node when a child box has min > max (the LDS
+// node blocks assume min <= max).  smem = the launch's dynamic LDS in bytes.  cap(n): at most n nodes (n < 0: as many as fit).
+struct LdsSplit {
+  int n_lds_nodes, smem;
+  void cap(int n) { if (n >= 0 && n < n_lds_nodes) { smem -= (n_lds_nodes - n) * RT_LDS_NODE_BYTES; n_lds_nodes = n; } }
+};
+LdsSplit lds_split(const RT_Device_Scene *d, int depth, int wg_waves, int wave_extra_bytes, int wgs_per_cu, bool static_table);
+void camera_rows(float dst[3][4], Camera const *cam);                                // rows 0..2 of the view matrix
+void camera_frame_kparams(RT_KParams *K, Camera const *cam, RT_Render_Params const *p);   // the camera and frame fields of K
 // Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
 // ev_prep (optional): recorded between the per-launch preparation and the path kernel.  batch (optional): K views in one launch
 // (cam and p->seed are ignored; d_accum holds K images).

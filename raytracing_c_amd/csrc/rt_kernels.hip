@@ -1039,17 +1039,10 @@ extern "C" int rt_launch_prepare(int n_tiles, uint32_t *tile_next, uint32_t *ope
 
 template <int WAVES, bool LDSN, int MINW, bool SHORT_DIV, bool VIEWS>
 static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipStream_t stream) {
-  // (the attribute belongs to the kernel ON ONE DEVICE: a frame spread over N GPUs launches from N devices)
-  static unsigned attr_devices = 0;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(&attr_devices, __ATOMIC_RELAXED) & (1u << dev)))) {
-    // (dynamic + the kernel's 32 static bytes, rt_pow24_lds, must stay within the 160 KB of a CU)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 32) __atomic_fetch_or(&attr_devices, 1u << dev, __ATOMIC_RELAXED);
-  }
+  static uint32_t attr_devices = 0;
+  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>), &attr_devices,
+                               smem_bytes, RT_LDS_BYTES - RT_LDS_TABLE_BYTES))      // (the kernel has the sRGB scale table)
+    return rc;
 #ifdef RT_LEDGER
   {
     void *sym = nullptr;
@@ -1261,15 +1254,9 @@ __global__ void rt_hit_attributes_kernel(const float *tris, int n, const float *
 
 template <int WAVES, bool ANY>
 static int launch_query(const RT_KParams *P, const RT_QParams *Q, int n_blocks, int smem_bytes, hipStream_t stream) {
-  static uint32_t attr_devices = 0;           // devices on which this instance's dynamic-LDS limit has been raised
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (smem_bytes > 48 * 1024 && (dev >= 32 || !(__atomic_load_n(&attr_devices, __ATOMIC_RELAXED) & (1u << dev)))) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_query_kernel<WAVES, ANY>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    if (dev < 32) __atomic_fetch_or(&attr_devices, 1u << dev, __ATOMIC_RELAXED);
-  }
+  static uint32_t attr_devices = 0;
+  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_query_kernel<WAVES, ANY>), &attr_devices, smem_bytes, RT_LDS_BYTES))
+    return rc;
   hipLaunchKernelGGL((rt_query_kernel<WAVES, ANY>), dim3(n_blocks), dim3(WAVES * 64), smem_bytes, stream, *P, *Q);
   return (int)hipGetLastError();
 }

@@ -206,9 +206,10 @@ extern "C" int rt_launch_test_trace_stream(const RT_KParams *P, int n, const flo
                                            hipStream_t stream) {
 #define RT_TTS(SD, PY)                                                                                                          \
   do {                                                                                                                          \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rt_test_trace_stream_kernel<SD, PY>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                 \
-    if (e != hipSuccess) return (int)e;                                                                                         \
+    static uint32_t attr_devices = 0;                                                                                           \
+    if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_test_trace_stream_kernel<SD, PY>), &attr_devices, smem_bytes, \
+                                 RT_LDS_BYTES))                                                                                 \
+      return rc;                                                                                                                \
     hipLaunchKernelGGL((rt_test_trace_stream_kernel<SD, PY>), dim3(n_blocks), dim3(16 * 64), smem_bytes, stream, *P, n, rays,  \
                        pyr, exit_lanes, out_t, out_tri, out_uv, visits);                                                        \
   } while (0)

@@ -43,17 +43,16 @@ static int check_launch_size(const Device &D, int tiles_per_view, int n_views, i
   return 0;
 }
 
-// Scene, camera, frame, partition and sample range of the launch; what depends on the launch state comes later.
-static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
-                        void *d_accum, ViewBatch const *batch) {
-  const int nv = batch ? batch->n : 1;
-  if (batch) cam = &batch->views[0].camera;      // (the kernel reads every view's camera from the view table)
-  scene_only_kparams(K, d);
+void camera_rows(float dst[3][4], Camera const *cam) {
   for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 4; j++) K->cam[i][j] = cam->view_matrix.rows[i][j];
+    for (int j = 0; j < 4; j++) dst[i][j] = cam->view_matrix.rows[i][j];
+}
+
+void camera_frame_kparams(RT_KParams *K, Camera const *cam, RT_Render_Params const *p) {
+  camera_rows(K->cam, cam);
   K->focal_length = cam->focal_length;
   {
-    volatile float fw = (float)p->width, fh = (float)p->height;      // plain IEEE fp32 divisions, as the kernel used to do
+    volatile float fw = (float)p->width, fh = (float)p->height;      // plain IEEE fp32 divisions (raytracer.c:615-617), as the kernel used to do
     volatile float iw = 1.0f / fw, ih = 1.0f / fh, asp = fw / fh;
     K->inv_width = iw;
     K->inv_height = ih;
@@ -63,6 +62,27 @@ static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera con
   K->height = p->height;
   K->samples = p->samples;
   K->max_bounces = p->max_bounces;
+  K->sample_first = p->sample_first;
+  K->sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
+}
+
+LdsSplit lds_split(const RT_Device_Scene *d, int depth, int wg_waves, int wave_extra_bytes, int wgs_per_cu, bool static_table) {
+  const int per_wave = (depth > 0 ? depth : 1) * RT_LDS_PERM_LEVEL_BYTES + wave_extra_bytes;
+  const int budget = (RT_LDS_BYTES - (static_table ? RT_LDS_TABLE_BYTES : 0)) / wgs_per_cu;
+  int room = (budget - wg_waves * per_wave) / RT_LDS_NODE_BYTES;
+  if (room < 0) room = 0;
+  int n = d->n_nodes < room ? d->n_nodes : room;
+  if (!d->boxes_ordered) n = 0;
+  return {n, n * RT_LDS_NODE_BYTES + wg_waves * per_wave};
+}
+
+// Scene, camera, frame, partition and sample range of the launch; what depends on the launch state comes later.
+static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
+                        void *d_accum, ViewBatch const *batch) {
+  const int nv = batch ? batch->n : 1;
+  if (batch) cam = &batch->views[0].camera;      // (the kernel reads every view's camera from the view table)
+  scene_only_kparams(K, d);
+  camera_frame_kparams(K, cam, p);
   K->seed = p->seed;
   K->chunks_x = (p->width + RT_CHUNK_SIZE - 1) / RT_CHUNK_SIZE;
   K->n_chunks = rt_chunk_count(p->width, p->height);
@@ -73,8 +93,6 @@ static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera con
     if (device_chunk_list(D, p->width, p->height, p->rank, p->world, &K->local_chunks, &n_local) != 0) return -1;
     K->n_local_chunks = n_local;
   }
-  K->sample_first = p->sample_first;
-  K->sample_end = p->sample_count > 0 ? p->sample_first + p->sample_count : p->samples;
   K->n_tiles = K->n_local_chunks * 16 * nv;      // (a batch: the tiles of view v are [v * tiles_per_view, (v + 1) * tiles_per_view))
   if (check_launch_size(D, K->n_local_chunks * 16, nv, K->sample_end - K->sample_first, p->slab) != 0) return -1;
   K->accum = (unsigned long long *)d_accum;
@@ -104,17 +122,11 @@ static void launch_geometry(const Device &D, const RT_Device_Scene *d, RT_KParam
   *wg_waves = per_slot < 12 ? 8 : (per_slot < 40 ? 12 : 16);
   int v = knob_int("RT_WG_WAVES", 0);
   if (v == 8 || v == 12 || v == 16) *wg_waves = v;
-  // dynamic LDS per workgroup: per wave (perm stack: depth x 256 B, accumulator tile: 1536 B) and as many leading BVH
-  // nodes (level order) as fit in the 160 KB of a CU at 208 B each
-  const int lds_limit = 160 * 1024 - 64;      // (- the kernel's static LDS: the 32-byte sRGB scale table, rt_dev.hip.h rt_pow24_lds)
-  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256 + 1536;
-  int room = (lds_limit - *wg_waves * per_wave) / 208;
-  if (room < 0) room = 0;
-  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
-  if (!d->boxes_ordered) K.n_lds_nodes = 0;      // (the kernel's LDS node blocks assume min <= max)
-  v = knob_int("RT_LDS_NODES", K.n_lds_nodes);
-  if (v >= 0 && v < K.n_lds_nodes) K.n_lds_nodes = v;
-  *smem = K.n_lds_nodes * 208 + *wg_waves * per_wave;
+  // dynamic LDS: per wave the perm stack and the accumulator tile, the leading BVH nodes that fit beside them and the static sRGB table
+  LdsSplit S = lds_split(d, K.depth, *wg_waves, RT_LDS_ACC_TILE_BYTES, 1, true);
+  S.cap(knob_int("RT_LDS_NODES", -1));
+  K.n_lds_nodes = S.n_lds_nodes;
+  *smem = S.smem;
 }
 
 // ---- schedule feedback: visit expensive tiles first (costs = rays per tile of the previous launch of this view) ----
@@ -175,8 +187,7 @@ static int upload_view_table(LaunchState &L, RT_KParams &K, ViewBatch const *bat
   for (int v = 0; v < nv; v++) {
     RT_KView &r = L.views_host[v];
     memset(&r, 0, sizeof r);
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 4; j++) r.cam[i][j] = batch->views[v].camera.view_matrix.rows[i][j];
+    camera_rows(r.cam, &batch->views[v].camera);
     r.focal_length = batch->views[v].camera.focal_length;
     r.seed = batch->views[v].seed;
   }

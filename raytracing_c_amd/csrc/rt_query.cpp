@@ -1,6 +1,6 @@
 // rt_query.cpp -- batch ray queries (include/rt_hip.h): closest hit, occlusion and full hit records for rays the host supplies,
 // on the device level (device pointers, one launch on the caller's stream) and on the host level (host arrays, the cached device
-// copy of a Scene with the frame path's scene check, slices of RT_QUERY_SLICE rays).  The work is rt_query_kernel and
+// copy of a Scene through scene_checked, rt_residency.cpp, slices of RT_QUERY_SLICE rays).  The work is rt_query_kernel and
 // rt_hit_attributes_kernel (rt_kernels.hip); nothing here computes a hit on the CPU.
 
 #include "rt_host.h"
@@ -24,12 +24,9 @@ static void query_geometry(const Device &D, const RT_Device_Scene *d, int n, RT_
   *wg_waves = (int64_t)n <= (int64_t)D.num_cus * 8 * 64 ? 8 : 16;
   int v = knob_int("RT_QUERY_WG_WAVES", 0);
   if (v == 8 || v == 16) *wg_waves = v;
-  const int per_wave = (K.depth > 0 ? K.depth : 1) * 256;      // the wave's perm stack
-  int room = (160 * 1024 - *wg_waves * per_wave) / 208;
-  if (room < 0) room = 0;
-  K.n_lds_nodes = d->n_nodes < room ? d->n_nodes : room;
-  if (!d->boxes_ordered) K.n_lds_nodes = 0;                    // (the LDS node blocks assume min <= max)
-  *smem = K.n_lds_nodes * 208 + *wg_waves * per_wave;
+  const LdsSplit S = lds_split(d, K.depth, *wg_waves, 0, 1, false);      // nodes beside the waves' perm stacks; no static table
+  K.n_lds_nodes = S.n_lds_nodes;
+  *smem = S.smem;
   const int wg_lanes = *wg_waves * 64;
   int blocks = (n + wg_lanes - 1) / wg_lanes;
   if (blocks > D.num_cus) blocks = D.num_cus;
@@ -132,6 +129,8 @@ extern "C" int rt_query_occluded(RT_Device_Scene *dscene, i64 n, void const *d_r
 }
 
 // ---- host level ---------------------------------------------------------------------------------------------------------------
+template void std::vector<f32>::resize(size_t);      // (in the library's export list, like unordered_map::erase in rt_residency.cpp)
+
 template <typename T> static int grow(T **p, size_t *cap, size_t want, size_t elem_bytes) {
   if (*cap >= want) return 0;
   (void)hipFree(*p);
@@ -173,7 +172,6 @@ static int query_host(Scene const *scene, i64 n, Ray const *rays, f32 const *t_m
   int slot = 0;
   if (acquire_slot(D, &slot) != 0) return -1;
   hipStream_t stream = nullptr;
-  const bool verify = !scene_is_static(scene);
   std::vector<f32> bounds;
   std::vector<RT_Device_Hit> records;
   RT_Device_Scene *d = nullptr;
@@ -185,25 +183,15 @@ static int query_host(Scene const *scene, i64 n, Ray const *rays, f32 const *t_m
       for (int i = 0; i < m; i++) bounds[(size_t)i] = hits[base + i].distance;
       bound = bounds.data();
     }
-    for (int attempt = 0;; attempt++) {
-      float upload_ms = 0.0f;
-      if (base == 0) {
-        d = cached_scene_locked(D, scene, nullptr, &upload_ms);     // the sampled stamp; uploads when it differs
-        if (!d) return -1;
-      }
+    auto trace_slice = [&](RT_Device_Scene *ds) -> int {
       HIP_TRY(hipMemcpy(S.rays, rays + base, (size_t)m * 24, hipMemcpyHostToDevice));
       if (bound) HIP_TRY(hipMemcpy(S.t_max, bound, (size_t)m * 4, hipMemcpyHostToDevice));
-      if (enqueue_query(D, d, m, S.rays, bound ? S.t_max : nullptr, any ? nullptr : S.hits, hits ? S.full : nullptr,
-                        any ? S.flags : nullptr, stream, slot, base == 0) != 0)
-        return -1;
-      // the full content check of the frame path (render_frame_locked), on this thread, while the GPU works on the first slice:
-      // a host scene that no longer equals the copy is uploaded again and the slice traced again; nothing has been written yet
-      if (base != 0 || !verify || attempt > 0 || upload_ms > 0.0f) break;
-      if (scene_fingerprint(scene) == d->full_fp) break;
-      HIP_TRY(hipStreamSynchronize(stream));
-      free_device_scene(d);
-      D.scene_cache.erase(scene);
-    }
+      return enqueue_query(D, ds, m, S.rays, bound ? S.t_max : nullptr, any ? nullptr : S.hits, hits ? S.full : nullptr,
+                           any ? S.flags : nullptr, stream, slot, base == 0);
+    };
+    // the scene is checked behind the first slice (edited since the copy: uploaded, traced again); later slices use that slice's copy
+    if (base == 0) d = scene_checked(D, scene, stream, nullptr, trace_slice);
+    if (!d || (base != 0 && trace_slice(d) != 0)) return -1;
     if (any) {
       HIP_TRY(hipMemcpy(flags + base, S.flags, (size_t)m, hipMemcpyDeviceToHost));
     } else if (records_out) {

@@ -758,3 +758,34 @@ RT_Device_Scene *cached_scene_locked(Device &D, Scene const *scene, float *stamp
   if (upload_ms) *upload_ms = (float)(now_ms() - t1);
   return d;
 }
+
+// (in the library's export list while the callers' copies of the check left it out of line: instantiated, so that the list stays)
+template size_t std::unordered_map<const Scene *, RT_Device_Scene *>::erase(const Scene *const &);
+
+RT_Device_Scene *scene_checked_call(Device &D, Scene const *scene, hipStream_t stream, FrameTiming *T,
+                                    int (*enqueue)(void *ctx, RT_Device_Scene *d), void *ctx) {
+  const bool verify = scene && !scene_is_static(scene);
+  for (int attempt = 0;; attempt++) {
+    float stamp_ms = 0.0f, upload_ms = 0.0f;
+    RT_Device_Scene *d = cached_scene_locked(D, scene, T ? &stamp_ms : nullptr, &upload_ms);
+    if (!d) return nullptr;
+    const double t_enq = now_ms();
+    if (enqueue(ctx, d) != 0) return nullptr;
+    if (T) {
+      T->stamp_ms += stamp_ms;
+      T->upload_ms += upload_ms;
+      T->enqueue_ms = (float)(now_ms() - t_enq);
+    }
+    // the full content check of the host scene, on this thread, while the GPU works (see rt_scene_touch): work on an unchanged
+    // scene waits for max(kernel, check) instead of kernel + check.  A copy made for this call IS the host scene.
+    if (!verify || attempt > 0 || upload_ms > 0.0f) return d;
+    const double t_v = now_ms();
+    const bool same = scene_fingerprint(scene) == d->full_fp;
+    if (T) T->verify_ms = (float)(now_ms() - t_v);
+    if (same) return d;
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { rt_fail("%s failed: %s", "hipStreamSynchronize(stream)", hipGetErrorString(e)); return nullptr; }
+    free_device_scene(d);
+    D.scene_cache.erase(scene);
+  }
+}

@@ -772,25 +772,17 @@ __global__ __launch_bounds__(256, 4) void rt_wf_shade_kernel(RT_KParams P) {
 // =====================================================================================================================
 // launchers
 // =====================================================================================================================
-template <typename K>
-static int wf_set_lds(K kernel, int smem_bytes) {
-  if (smem_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
-
 // geometry: 0 = one 16-wave workgroup per CU (4 waves per SIMD, the whole tree in LDS when it fits); 1 = two 12-wave
 // workgroups per CU (6 per SIMD at <= 80 VGPRs); 2 = two 10-wave workgroups (5 per SIMD at <= 96 VGPRs).  With two
 // workgroups per CU each holds as much of the top of the tree as half the LDS allows.
 #define WF_LAUNCH(KERNEL, W, M)                                                                                          \
   do {                                                                                                                   \
+    static uint32_t attr_devices[2] = {0, 0};      /* (one mask per instance) */                                         \
     if (P->short_div) {                                                                                                  \
-      if ((rc = wf_set_lds(KERNEL<W, true, M, true>, smem_bytes))) return rc;                                            \
+      if ((rc = raise_lds_limit((const void *)&KERNEL<W, true, M, true>, &attr_devices[1], smem_bytes, RT_LDS_BYTES))) return rc;  \
       hipLaunchKernelGGL((KERNEL<W, true, M, true>), dim3(n_blocks), dim3(W * 64), smem_bytes, stream, *P);              \
     } else {                                                                                                             \
-      if ((rc = wf_set_lds(KERNEL<W, true, M, false>, smem_bytes))) return rc;                                           \
+      if ((rc = raise_lds_limit((const void *)&KERNEL<W, true, M, false>, &attr_devices[0], smem_bytes, RT_LDS_BYTES))) return rc; \
       hipLaunchKernelGGL((KERNEL<W, true, M, false>), dim3(n_blocks), dim3(W * 64), smem_bytes, stream, *P);             \
     }                                                                                                                    \
   } while (0)

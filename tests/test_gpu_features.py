@@ -182,3 +182,47 @@ def test_python_wrapper_equals_the_c_entry_point(rt, oracle, passthrough):
     sums = np.zeros((h, w, 10), np.uint64)
     assert rt.lib.rt_render_features(C.byref(hs.scene), w, h, s, b, None, sums.ctypes.data) == 0, rt.last_error()
     assert np.array_equal(sums, py["sums"]) and np.array_equal(sums, want["sums"])
+
+
+def test_an_edit_nobody_reported_is_seen_by_the_next_pass(rt, oracle):
+    """rt_render_features runs through the frame path's scene check: vertices moved in place without rt_scene_touch -- outside the
+    few bytes the per-call stamp samples (8 runs of 512 bytes per block, rt_hip.h "a bounded sample") -- are found by the full
+    content check behind the pass, which is then traced again from a fresh copy."""
+    from raytracing_c_amd.configs import load_config
+    from tests import _features as F
+    from tests.test_gpu_query import _bbox, _oracle_trace
+    hs, _ = load_config("spheres")
+    w, h, s, b = 64, 48, 4, 4
+    sc = C.byref(hs.scene)
+    first = F.expected(hs, w, h, s, b)["sums"]
+    _same(rt.render_features(hs, w, h, s, b), first, s)
+    # triangles the camera sees: the oracle's first hits of rays through a grid on the image plane
+    m = hs.scene.camera.view_matrix.rows
+    M = np.array([[m[i][j] for j in range(4)] for i in range(3)], np.float64)
+    gx, gy = np.meshgrid(np.linspace(-0.4, 0.4, 96), np.linspace(-0.3, 0.3, 72))
+    d = np.stack([gx.ravel(), gy.ravel(), -np.full(gx.size, float(hs.scene.camera.focal_length))], 1)
+    rays = np.zeros((len(d), 6), np.float32)
+    rays[:, :3] = M[:, 3]
+    rays[:, 3:] = d @ M[:, :3].T
+    seen, _ = _oracle_trace(oracle, hs, np.ascontiguousarray(rays))
+    ids = np.unique(seen["triangle"][seen["triangle"] >= 0])
+    assert len(ids) > 100
+    T = hs.scene.triangles
+    n = int(T.len)
+    zs = [np.ctypeslib.as_array(T.z[k], (n,)) for k in range(3)]
+    saved = [z.copy() for z in zs]
+    lo, hi = _bbox(hs)
+    shift = np.float32(0.25 * (hi[2] - lo[2]))
+    runs = [((n * 4 - 512) * k // 7 & ~7) // 4 for k in range(8)]
+    k0 = next(int(i) for i in ids[len(ids) // 4:] if all(i + 64 <= r or i >= r + 128 for r in runs))
+    try:
+        for z in zs:
+            z[k0:k0 + 64] += shift
+        edited = F.expected(hs, w, h, s, b)["sums"]
+        assert int((edited != first).any(axis=2).sum()) >= 20, "the edit must change what the camera sees"
+        _same(rt.render_features(hs, w, h, s, b), edited, s)                # no rt_scene_touch
+    finally:
+        for k in range(3):
+            zs[k][:] = saved[k]
+            assert rt.lib.rt_scene_touch(sc, zs[k].ctypes.data, n * 4) in (0, 1), rt.last_error()
+    _same(rt.render_features(hs, w, h, s, b), first, s)
