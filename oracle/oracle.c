@@ -1,6 +1,6 @@
 /* oracle.c -- CPU restatement of the reference render path.  TEST INFRASTRUCTURE,
- * see oracle.h for who may use it, the "parity unpinned" statement and the list
- * of deviations D1-D9.  Every function names the reference lines it follows.
+ * see oracle.h for who may use it, how parity with the reference is pinned and the list
+ * of deviations D1-D10.  Every function names the reference lines it follows.
  *
  * Build: see oracle/Makefile (-O2 -ffp-contract=off, no fast-math: the results
  * must be bit-identical to the gfx950 kernels, which share include/rt_math.h).
@@ -455,6 +455,8 @@ static rt_v3 fresnel_schlick_vec3(rt_v3 f0, f32 f90, f32 theta) {
 static f32 distribution_GGX(f32 roughness, f32 NoH) {   /* k == 2 at every call site */
   f32 a2 = roughness * roughness;
   f32 d  = rt_madd(NoH * NoH, rt_madd(a2, a2, -1.0f), 1.0f);
+  /* driver.c:214 `a2 / (PI * pow_f32(..))` with a double PI: product and quotient in double, rounded once (D8) */
+  if (tl_literal) return (f32)((double)a2 / (PI_D * (double)(d * d)));
   return a2 / (RT_PI * (d * d));
 }
 
@@ -516,6 +518,8 @@ static rt_v3 disney_eval_diffuse(rt_v3 base_color, f32 NoL, f32 NoV, f32 LoH, f3
   f32 FD90 = rt_madd(2.0f * roughness * LoH, LoH, 0.5f);
   f32 a = fresnel_schlick_f32(1.0f, FD90, NoL);
   f32 b = fresnel_schlick_f32(1.0f, FD90, NoV);
+  /* driver.c:263 `a * b / PI`: the float product over a double PI, rounded once (D8) */
+  if (tl_literal) return rt_v3_scale(base_color, (f32)((double)(a * b) / PI_D));
   return rt_v3_scale(base_color, (a * b / RT_PI));
 }
 
@@ -559,7 +563,7 @@ static void sample_disney_BRDF(Disney_BRDF_Data const *data, rt_v3 in_dir, rt_v3
     f32 NoV = in_dir.z;
     if (NoL <= 0.0f || NoV <= 0.0f) return;
     f32 LoH = rt_v3_dot(*out_dir, micro_normal);
-    f32 pdf = NoL / RT_PI;
+    f32 pdf = tl_literal ? (f32)((double)NoL / PI_D) : NoL / RT_PI;     /* driver.c:313 `NoL / PI` (D8) */
 
     rt_v3 diff = rt_v3_mul(disney_eval_diffuse(data->base_color, NoL, NoV, LoH, data->roughness),
                            rt_v3_sub(rt_v3_make(1, 1, 1), fresnel));
@@ -1001,6 +1005,29 @@ void oracle_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out) {
 
 u8 oracle_encode_u8(f32 linear) { return rt_encode_u8(linear); }
 
+/* Test-only switch (tests/test_reference_pin.py): the unit-level entry points above run with the default semantics
+ * (oracle_render resets the flag); 1 makes the CALLING thread evaluate the D8 sites as ORACLE_LITERAL does, until it is set
+ * back or oracle_render runs.  Returns the previous mode. */
+int oracle_set_literal(int on) {
+  int was = tl_literal ? 1 : 0;
+  tl_literal = on != 0;
+  return was;
+}
+
+/* raytracer.c:505-558 from a given ray and RNG state, in the mode oracle_set_literal selected */
+void oracle_cast_ray(Scene const *scene, Oracle_Config const *config, Ray const *ray, isize max_bounces, u32 *state, f32 rgb[3]) {
+  random_state = *state;
+  rt_v3 c = cast_ray(scene, config, *ray, max_bounces);
+  *state = random_state;
+  rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+}
+
+/* driver.c:411-418 on its own */
+void oracle_debug_shade(PBR_Shader_Data const *data, Shader_Input const *in, Shader_Output *out) {
+  memset(out, 0, sizeof *out);
+  oracle_debug_shader_proc((rawptr)data, in, out);
+}
+
 /* ------------------------------------------------------------------------- */
 /* denoiser.c:13-153  (SURVEY.md section 8f #3).  Single threaded: every output pixel depends only on
  * the source image, so the reference's chunked threading (denoiser.c:51-129) does not affect results. */
@@ -1077,7 +1104,8 @@ static rt_v3 rand_vec3(void) {
     p.y = rand_f32_range(-1.0f, 1.0f);
     p.z = rand_f32_range(-1.0f, 1.0f);
     f32 lensq = rt_v3_dot(p, p);
-    if (RT_EPS < lensq && lensq <= 1.0f) return rt_v3_scale(p, 1.0f / rt_sqrtf(lensq));
+    /* common.h:39 `1.0 / sqrt_f32(lensq)`: a double quotient, rounded once (D8) */
+    if (RT_EPS < lensq && lensq <= 1.0f) return rt_v3_scale(p, tl_literal ? (f32)(1.0 / (double)rt_sqrtf(lensq)) : 1.0f / rt_sqrtf(lensq));
   }
 }
 
@@ -1086,6 +1114,10 @@ static f32 max3(f32 a, f32 b, f32 c) { f32 m = b > c ? b : c; return a > m ? a :
 
 void oracle_lightmap_bake(Image const *lightmap, Scene const *scene, isize samples, Oracle_Config const *cfg) {
   memset(&tl_counters, 0, sizeof tl_counters);
+  /* ORACLE_LITERAL: ONE RNG stream, seeded once with cfg->seed, runs on across samples, texels and triangles as the
+   * reference's thread-local state does (common.h:13); the D8 sites are evaluated in double */
+  tl_literal = cfg->literal != 0;
+  if (tl_literal) random_state = cfg->seed;
   f32 lw = (f32)lightmap->width, lh = (f32)lightmap->height;
   Triangles const *T = &scene->triangles;
   for (isize i = 0; i < T->len; i++) {
@@ -1118,7 +1150,7 @@ void oracle_lightmap_bake(Image const *lightmap, Scene const *scene, isize sampl
           Ray r;
           r.position = U(rt_v3_add(position, rt_v3_scale(normal, RT_EPS)));
           r.direction = U(rt_v3_make(0, 0, 0));
-          random_state = rt_path_seed(cfg->seed, (u32)(x + y * (i32)lightmap->width), (u32)i);
+          if (!tl_literal) random_state = rt_path_seed(cfg->seed, (u32)(x + y * (i32)lightmap->width), (u32)i);   /* D1 */
           for (isize s = 0; s < samples; s++) {
             f32 cosv;
             i32 guard = 0;
@@ -1133,11 +1165,12 @@ void oracle_lightmap_bake(Image const *lightmap, Scene const *scene, isize sampl
           f32 v[3] = { accumulated.x / (f32)samples, accumulated.y / (f32)samples, accumulated.z / (f32)samples };
           for (int c = 0; c < 3; c++) {
             f32 q = v[c] > 0.0f ? v[c] : 0.0f;          /* NaN and negatives -> 0 */
-            q = q > 255.0f ? 255.0f : q;
+            q = q > 255.0f ? 255.0f : q;                /* D10: the reference converts unclamped */
             lightmap->pixels.data[(x + y * lightmap->stride) * lightmap->components + c] = (u8)q;
           }
         }
       }
     }
   }
+  tl_literal = false;
 }

@@ -3,11 +3,17 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
  * load liboracle.so; nothing under raytracing_c_amd/ links, imports or calls it.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for
- * this path and cannot be compiled here (every file includes the absent,
- * unversioned third-party library "codin": common.h:3-4, raytracer.c:3-7,
- * scene.c:1-6, driver.c:1-8).  The oracle is therefore a by-hand restatement,
- * function by function, of common.h:13-92, raytracer.c:15-32,84-230,443-720 and
+ * PARITY: PINNED TO THE REFERENCE'S OWN TEXT, compiled against a codin stand-in.  The reference includes the absent,
+ * unversioned third-party library "codin" everywhere (common.h:3-4, raytracer.c:3-7, scene.c:1-6), but its hot path uses
+ * only about forty codin names; oracle/codin_shim/ restates those (each header lists its assumptions about the real codin
+ * with the reference lines that use them), and `make -C oracle ref` compiles raytracer.c, scene.c, denoiser.c and the
+ * shading stretch of driver.c UNCHANGED into oracle/_ref/libref.so (oracle/ref_harness.c).  tests/test_reference_pin.py
+ * compares this oracle with it bit for bit under numeric contract v1 -- box and leaf tests, traversal, builder, sampler,
+ * background, BRDF, shader procs, cast_ray, whole frames, denoiser, whole lightmaps -- and tests/golden/ref/ carries the
+ * reference's hits and built scenes to the GPU (tests/test_gpu_reference_pin.py).  What STAYS UNPINNED: the semantics of
+ * the real codin (the stand-in's assumption lists are the checklist for a maintainer who has it), libm (D5), and the
+ * non-literal deviations D1, D2 and D6, which ORACLE_LITERAL switches off for the comparison.
+ * The oracle is a restatement, function by function, of common.h:13-92, raytracer.c:15-32,84-230,443-720 and
  * driver.c:49-104,118-418, with these documented deviations:
  *   D1 per-path RNG seeding rt_path_seed() instead of wall clock per thread;
  *   D2 exact 1/sqrt instead of _mm256_rsqrt_ps for primary directions;
@@ -23,18 +29,22 @@
  *      stepwise in fp32: driver.c:220 `(2.0 * NDotV) / (...)` (smith_G), driver.c:238 `2.0 * PI * rand_f32()`,
  *      :242 `(1.0 - s) * sqrt_f32(1.0 - t1 * t1) + s * t2` (one rounding in the reference, three here),
  *      :246 `max(0.0, 1.0 - t1 * t1 - t2 * t2)`, driver.c:119 `rand_f32() * 2 * PI` and :96-97 `1.0f / PI`
- *      (if codin's PI is a double), common.h:37 `1.0 / sqrt_f32(lensq)` (lightmap only).  driver.c:133 `2.0`,
+ *      (if codin's PI is a double), likewise driver.c:214 `a2 / (PI * pow_f32(..))`, :263 `a * b / PI` and :313 `NoL / PI`,
+ *      common.h:37 `1.0 / sqrt_f32(lensq)` (lightmap only).  driver.c:133 `2.0`,
  *      :241 `0.5 * (1.0 + Vh.z)`, :416 `0.5` and common.h:84 `2.4` give the same f32 either way.  The GPU kernels
  *      have no fp64 on the path; the difference is below 1 ulp per expression.
  *   D9 (contract v2 on) the slab distances of a NaN-free ray whose origin components are all below 256 are
  *      fma(plane, inv, -(o * inv)) instead of (plane - o) * inv (raytracer.c:203-208): rt_slab_fast(), rt_math.h, shared
  *      with the kernels; the origin bound (round 5) keeps the fused form's plane placement error below 0.153 EPSILON.
+ *   D10 (lightmap) a texel is stored as (u8) of the mean clamped to [0, 255], NaN as 0; the reference converts the raw
+ *      float (raytracer.c:777-779), which C leaves undefined outside [0, 256).  Inside that range the two are the same
+ *      conversion, and tests/test_reference_pin.py compares whole lightmaps there.
  *
  * ORACLE_LITERAL (Oracle_Config.literal = 1) switches D1, D2, D6 and D8 back to the reference's literal semantics:
  * ONE thread whose RNG state is seeded once (frame seed in place of time_now(), raytracer.c:597) and runs on across
  * pixels in chunk order, `_mm256_rsqrt_ps` for the primary directions (:663), fp32 running sum in sample order
- * (:695-700), double intermediates at the D8 sites.  It cannot be bit-compared with anything (different random
- * numbers per path); tests/test_oracle_literal.py checks that it and the default oracle are the same estimator:
+ * (:695-700), double intermediates at the D8 sites.  In this mode the oracle equals libref.so bit for bit, whole frames
+ * included (tests/test_reference_pin.py); tests/test_oracle_literal.py checks that it and the default oracle are the same estimator:
  * per-block means agree within the Monte-Carlo noise, with no bias.
  */
 #ifndef ORACLE_H
@@ -112,12 +122,20 @@ void oracle_disney_shade(PBR_Shader_Data const *data, Shader_Input const *in, u3
 /* rt_math.h wrappers: op 0 log,1 exp,2 pow(x,y),3 sin,4 cos,5 atan2(x=y,y=x),6 asin,7 srgb_to_linear,8 linear_to_srgb,9 sqrt, 10 1/x */
 void oracle_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out);
 u8   oracle_encode_u8(f32 linear);
+/* test-only: 1 = the calling thread's unit-level entry points evaluate the D8 sites as ORACLE_LITERAL does (they default
+ * to 0, and oracle_render sets 0 again); returns the previous mode */
+int  oracle_set_literal(int on);
+/* raytracer.c:505-558 from a given ray and RNG state, in the mode oracle_set_literal selected */
+void oracle_cast_ray(Scene const *scene, Oracle_Config const *config, Ray const *ray, isize max_bounces, u32 *state, f32 rgb[3]);
+/* driver.c:411-418 */
+void oracle_debug_shade(PBR_Shader_Data const *data, Shader_Input const *in, Shader_Output *out);
 
 /* raytracer.c:722-784: UV-space light baking.  Texels covered by several triangles
  * keep the LAST triangle's value (the reference's loop order); texels outside the image are skipped (the
  * reference would write out of bounds); per-texel RNG seeding rt_path_seed(seed, x + y*width, triangle)
- * replaces the reference's running thread-local stream; the f32 -> u8 store is the reference's plain
- * conversion (no *255), clamped to [0, 255]. */
+ * replaces the reference's running thread-local stream (D1; config->literal = 1 restores the ONE running stream,
+ * seeded with config->seed, and the double intermediates of D8); the f32 -> u8 store is the reference's plain
+ * conversion (no *255), clamped to [0, 255] (D10). */
 void oracle_lightmap_bake(Image const *lightmap, Scene const *scene, isize samples, Oracle_Config const *config);
 
 /* denoiser.c:51-153: 3x3 luminance-sorted median blended by neighbourhood noisiness; src and dst are
