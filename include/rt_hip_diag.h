@@ -37,6 +37,9 @@ extern int rt_get_ledger(u64 *out, i32 n);
 /* RT_WAVE_TIMES set in the environment: per wave of the last launch (start tick, end tick, (tick of its last grab - start) << 16
  * | tiles it owned); ticks are 10 ns.  Returns the wave count (-1: no such launch). */
 extern int rt_get_wave_times(u64 *out, i32 max_waves);
+/* Device bytes the library's host side holds right now, on all devices: scene copies, launch states, workspaces, staging.  Exact
+ * (counted at every allocation and release of the library's own), so a test can assert that a sequence leaks nothing. */
+extern i64 rt_diag_device_bytes_live(void);
 
 /* ---- unit-level device entry points (parity tests call the same device
  * functions the render kernel uses) ------------------------------------------ */

@@ -57,20 +57,18 @@ static int wavefront_ensure_queues(RT_Device_Scene *d, int64_t paths, int cam_wa
   const int64_t fill = WF_CHUNK - 63;
   const int64_t soft = (want + fill - 1) / fill + cam_waves + 1;
   if (d->wf_ctl && d->wf_soft0 >= soft && d->wf_waves >= max_waves) return 0;
-  (void)hipFree(d->wf_hit0); (void)hipFree(d->wf_hit); (void)hipFree(d->wf_ray[0]); (void)hipFree(d->wf_ray[1]);
-  (void)hipFree(d->wf_cnt); (void)hipFree(d->wf_ctl);
-  d->wf_hit0 = d->wf_hit = d->wf_ray[0] = d->wf_ray[1] = d->wf_cnt = d->wf_ctl = nullptr;
+  d->wf_hit0.reset(); d->wf_hit.reset(); d->wf_ray[0].reset(); d->wf_ray[1].reset(); d->wf_cnt.reset(); d->wf_ctl.reset();
   d->wf_soft0 = 0;
   const int64_t hard = soft + 2 * (int64_t)cam_waves + 8;                      // a stopped wave closes at most two more chunks
   const int64_t ray_chunks = (hard * WF_CHUNK + fill - 1) / fill + max_waves + 8;   // rays <= hits
   const int64_t hit_chunks = (ray_chunks * WF_CHUNK + fill - 1) / fill + max_waves + 8;   // hits <= rays
-  HIP_TRY(hipMalloc(&d->wf_hit0, (size_t)hard * WF_HIT0_FIELDS * WF_CHUNK * 4));
-  HIP_TRY(hipMalloc(&d->wf_hit, (size_t)hit_chunks * WF_HIT_FIELDS * WF_CHUNK * 4));
-  HIP_TRY(hipMalloc(&d->wf_ray[0], (size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK * 4));
-  HIP_TRY(hipMalloc(&d->wf_ray[1], (size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK * 4));
-  HIP_TRY(hipMalloc(&d->wf_cnt, (size_t)(hard + hit_chunks + 2 * ray_chunks) * 4));
-  HIP_TRY(hipMalloc(&d->wf_ctl, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4));
-  if (!d->wf_ctl_host) HIP_TRY(hipHostMalloc((void **)&d->wf_ctl_host, (size_t)WF_N_CTL * WF_CTL_STRIDE * 4, hipHostMallocDefault));
+  HIP_TRY(d->wf_hit0.grow((size_t)hard * WF_HIT0_FIELDS * WF_CHUNK));
+  HIP_TRY(d->wf_hit.grow((size_t)hit_chunks * WF_HIT_FIELDS * WF_CHUNK));
+  HIP_TRY(d->wf_ray[0].grow((size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK));
+  HIP_TRY(d->wf_ray[1].grow((size_t)ray_chunks * WF_RAY_FIELDS * WF_CHUNK));
+  HIP_TRY(d->wf_cnt.grow((size_t)(hard + hit_chunks + 2 * ray_chunks)));
+  HIP_TRY(d->wf_ctl.grow((size_t)WF_N_CTL * WF_CTL_STRIDE));
+  HIP_TRY(d->wf_ctl_host.grow((size_t)WF_N_CTL * WF_CTL_STRIDE));
   d->wf_soft0 = soft; d->wf_hard0 = hard; d->wf_ray_chunks = ray_chunks; d->wf_hit_chunks = hit_chunks;
   d->wf_waves = max_waves;
   return 0;
@@ -175,6 +173,9 @@ extern "C" int rt_get_wave_times(u64 *out, i32 max_waves) {
   return n;
 }
 
+// Device bytes the library's owners hold right now (rt_mem.h): what a test compares before and after to see a leak exactly.
+extern "C" int64_t rt_diag_device_bytes_live(void) { return g_device_bytes_live.load(); }
+
 // ---------------------------------------------------------------------------------
 // unit-level device entry points (include/rt_hip_diag.h; diagnostic library only)
 
@@ -183,15 +184,13 @@ extern "C" int rt_test_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out)
   std::lock_guard<std::mutex> lock(D.mutex);
   if (ensure_device(D) != 0) return -1;
   if (n <= 0 || !x || !out) return rt_fail("rt_test_math: bad arguments");
-  DevBuf bx, by, bout;
+  DevMem<float> dx, dy, dout;
   size_t bytes = (size_t)n * sizeof(float);
-  HIP_TRY(bx.alloc(bytes));
-  HIP_TRY(bout.alloc(bytes));
-  float *dx = bx.as<float>(), *dy = nullptr, *dout = bout.as<float>();
+  HIP_TRY(dx.grow((size_t)n));
+  HIP_TRY(dout.grow((size_t)n));
   HIP_TRY(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
   if (y) {
-    HIP_TRY(by.alloc(bytes));
-    dy = by.as<float>();
+    HIP_TRY(dy.grow((size_t)n));
     HIP_TRY(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
   }
   int rc = rt_launch_test_math(op, n, dx, dy, dout, nullptr);
@@ -205,11 +204,11 @@ static int run_sweep(int (*launch)(unsigned long long *, hipStream_t), const cha
   std::lock_guard<std::mutex> lock(D.mutex);
   if (ensure_device(D) != 0) return -1;
   if (!out) return rt_fail("%s: NULL", name);
-  DevBuf b;
-  HIP_TRY(b.alloc((size_t)n_out * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(b.p, 0, (size_t)n_out * sizeof(unsigned long long)));
-  int rc = launch(b.as<unsigned long long>(), nullptr);
-  if (rc == 0) rc = (int)hipMemcpy(out, b.p, (size_t)n_out * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  DevMem<unsigned long long> b;
+  HIP_TRY(b.grow((size_t)n_out));
+  HIP_TRY(hipMemset(b, 0, (size_t)n_out * sizeof(unsigned long long)));
+  int rc = launch(b, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, b, (size_t)n_out * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   if (rc != 0) return rt_fail("%s failed: %s", name, hipGetErrorString((hipError_t)rc));
   return 0;
 }
@@ -235,18 +234,18 @@ extern "C" int rt_test_tile_order(i32 n_tiles, u32 const *cost, u32 *order) {
   std::lock_guard<std::mutex> lock(D.mutex);
   if (ensure_device(D) != 0) return -1;
   if (n_tiles <= 0 || !cost || !order) return rt_fail("rt_test_tile_order: bad arguments");
-  DevBuf bc, bo, bn, bk, bw, bz;
-  HIP_TRY(bc.alloc((size_t)n_tiles * 4));
-  HIP_TRY(bo.alloc((size_t)n_tiles * 4));
-  HIP_TRY(bn.alloc(((size_t)n_tiles + (size_t)(n_tiles + 63) / 64) * 4));
-  HIP_TRY(bk.alloc(RT_N_COUNTERS * 8));
-  HIP_TRY(bw.alloc(64));
-  HIP_TRY(bz.alloc((size_t)n_tiles * 4));
-  HIP_TRY(hipMemcpy(bc.p, cost, (size_t)n_tiles * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(bo.p, 0xFF, (size_t)n_tiles * 4));
-  int rc = rt_launch_prepare(n_tiles, bn.as<uint32_t>(), bn.as<uint32_t>() + n_tiles, bk.as<unsigned long long>(), bw.as<uint32_t>(),
-                             bz.as<uint32_t>(), bc.as<uint32_t>(), bo.as<uint32_t>(), nullptr);
-  if (rc == 0) rc = (int)hipMemcpy(order, bo.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
+  DevMem<uint32_t> bc, bo, bn, bw, bz;
+  DevMem<unsigned long long> bk;
+  HIP_TRY(bc.grow((size_t)n_tiles));
+  HIP_TRY(bo.grow((size_t)n_tiles));
+  HIP_TRY(bn.grow((size_t)n_tiles + (size_t)(n_tiles + 63) / 64));
+  HIP_TRY(bk.grow(RT_N_COUNTERS));
+  HIP_TRY(bw.grow(16));
+  HIP_TRY(bz.grow((size_t)n_tiles));
+  HIP_TRY(hipMemcpy(bc, cost, (size_t)n_tiles * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(bo, 0xFF, (size_t)n_tiles * 4));
+  int rc = rt_launch_prepare(n_tiles, bn, bn + n_tiles, bk, bw, bz, bc, bo, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(order, bo, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
   if (rc != 0) return rt_fail("rt_test_tile_order failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
@@ -259,13 +258,12 @@ extern "C" int rt_test_trace(RT_Device_Scene *d, i32 n, f32 const *rays, f32 *ou
   if (ensure_device(D) != 0) return -1;
   RT_KParams K;
   scene_only_kparams(&K, d);
-  DevBuf br, bt, btri, buv;
-  HIP_TRY(br.alloc((size_t)n * 24));
-  HIP_TRY(bt.alloc((size_t)n * 4));
-  HIP_TRY(btri.alloc((size_t)n * 4));
-  HIP_TRY(buv.alloc((size_t)n * 8));
-  float *dr = br.as<float>(), *dt = bt.as<float>(), *duv = buv.as<float>();
-  int   *dtri = btri.as<int>();
+  DevMem<float> dr, dt, duv;
+  DevMem<int>   dtri;
+  HIP_TRY(dr.grow((size_t)n * 6));
+  HIP_TRY(dt.grow((size_t)n));
+  HIP_TRY(dtri.grow((size_t)n));
+  HIP_TRY(duv.grow((size_t)n * 2));
   HIP_TRY(hipMemcpy(dr, rays, (size_t)n * 24, hipMemcpyHostToDevice));
   int rc = rt_launch_test_trace(&K, n, dr, dt, dtri, duv, nullptr);
   if (rc == 0) rc = (int)hipMemcpy(out_t, dt, (size_t)n * 4, hipMemcpyDeviceToHost);
@@ -308,22 +306,23 @@ extern "C" int rt_test_trace_stream(RT_Device_Scene *d, i32 n, f32 const *rays, 
   int n_blocks = (n + 16 * 64 * 4 - 1) / (16 * 64 * 4);                 // ~4 rays per lane
   if (n_blocks > D.num_cus) n_blocks = D.num_cus;
   if (n_blocks < 1) n_blocks = 1;
-  DevBuf br, bp, bt, btri, buv, bv;
-  HIP_TRY(br.alloc((size_t)n * 24));
-  HIP_TRY(bp.alloc(19 * 4));
-  HIP_TRY(bt.alloc((size_t)n * 4));
-  HIP_TRY(btri.alloc((size_t)n * 4));
-  HIP_TRY(buv.alloc((size_t)n * 8));
-  HIP_TRY(bv.alloc(16));
-  HIP_TRY(hipMemcpy(br.p, rays, (size_t)n * 24, hipMemcpyHostToDevice));
-  if (pyramid) HIP_TRY(hipMemcpy(bp.p, pyramid, 19 * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(bv.p, 0, 16));
-  int rc = rt_launch_test_trace_stream(&K, n, br.as<float>(), pyramid ? bp.as<float>() : nullptr, exit_lanes, n_blocks, S.smem,
-                                       bt.as<float>(), btri.as<int>(), buv.as<float>(), bv.as<unsigned long long>(), nullptr);
-  if (rc == 0) rc = (int)hipMemcpy(out_t, bt.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (rc == 0) rc = (int)hipMemcpy(out_tri, btri.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (rc == 0) rc = (int)hipMemcpy(out_uv, buv.p, (size_t)n * 8, hipMemcpyDeviceToHost);
-  if (rc == 0) rc = (int)hipMemcpy(visits, bv.p, 16, hipMemcpyDeviceToHost);
+  DevMem<float> br, bp, bt, buv;
+  DevMem<int>   btri;
+  DevMem<unsigned long long> bv;
+  HIP_TRY(br.grow((size_t)n * 6));
+  HIP_TRY(bp.grow(19));
+  HIP_TRY(bt.grow((size_t)n));
+  HIP_TRY(btri.grow((size_t)n));
+  HIP_TRY(buv.grow((size_t)n * 2));
+  HIP_TRY(bv.grow(2));
+  HIP_TRY(hipMemcpy(br, rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  if (pyramid) HIP_TRY(hipMemcpy(bp, pyramid, 19 * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(bv, 0, 16));
+  int rc = rt_launch_test_trace_stream(&K, n, br, pyramid ? bp.get() : nullptr, exit_lanes, n_blocks, S.smem, bt, btri, buv, bv, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out_t, bt, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_tri, btri, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_uv, buv, (size_t)n * 8, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(visits, bv, 16, hipMemcpyDeviceToHost);
   if (rc != 0) return rt_fail("rt_test_trace_stream failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
@@ -338,10 +337,9 @@ extern "C" int rt_test_texture(RT_Device_Scene *d, i32 tex, i32 n, f32 const *uv
   if (tex >= d->n_textures) return rt_fail("rt_test_texture: texture %d of %d", tex, d->n_textures);
   RT_KParams K;
   scene_only_kparams(&K, d);
-  DevBuf buv, bout;
-  HIP_TRY(buv.alloc((size_t)n * 8));
-  HIP_TRY(bout.alloc((size_t)n * 12));
-  float *duv = buv.as<float>(), *dout = bout.as<float>();
+  DevMem<float> duv, dout;
+  HIP_TRY(duv.grow((size_t)n * 2));
+  HIP_TRY(dout.grow((size_t)n * 3));
   HIP_TRY(hipMemcpy(duv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
   int rc = rt_launch_test_texture(&K, tex, n, duv, dout, nullptr);
   if (rc == 0) rc = (int)hipMemcpy(out_rgb, dout, (size_t)n * 12, hipMemcpyDeviceToHost);

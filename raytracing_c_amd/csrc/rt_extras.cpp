@@ -26,13 +26,12 @@ static int lightmap_bake_locked(Device &D, Image const *lightmap, Scene const *s
     }
   size_t pb = (size_t)lightmap->stride * lightmap->height * lightmap->components;
   size_t ob = (size_t)lightmap->width * lightmap->height * sizeof(int);
-  DevBuf b_verts, b_owner, b_pixels;
-  HIP_TRY(b_verts.alloc(verts.size() * sizeof(float)));
-  HIP_TRY(b_owner.alloc(ob));
-  HIP_TRY(b_pixels.alloc(pb));
-  float *dv = b_verts.as<float>();
-  int *dow = b_owner.as<int>();
-  uint8_t *dp = b_pixels.as<uint8_t>();
+  DevMem<float>   dv;
+  DevMem<int>     dow;
+  DevMem<uint8_t> dp;
+  HIP_TRY(dv.grow(verts.size()));
+  HIP_TRY(dow.grow((size_t)lightmap->width * lightmap->height));
+  HIP_TRY(dp.grow(pb));
   HIP_TRY(hipMemcpy(dv, verts.data(), verts.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(dow, 0xFF, ob));                                        // owner = -1
   HIP_TRY(hipMemcpy(dp, lightmap->pixels.data, pb, hipMemcpyHostToDevice));   // untouched texels keep their value
@@ -112,10 +111,9 @@ static int denoise_host(Image const *src, Image const *dst) {
     return rt_fail("denoise_image: bad layout");
   size_t sb = (size_t)src->stride * src->height * src->components;
   size_t db = (size_t)dst->stride * dst->height * dst->components;
-  DevBuf b_src, b_dst;
-  HIP_TRY(b_src.alloc(sb));
-  HIP_TRY(b_dst.alloc(db));
-  uint8_t *ds = b_src.as<uint8_t>(), *dd = b_dst.as<uint8_t>();
+  DevMem<uint8_t> ds, dd;
+  HIP_TRY(ds.grow(sb));
+  HIP_TRY(dd.grow(db));
   HIP_TRY(hipMemcpy(ds, src->pixels.data, sb, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dd, dst->pixels.data, db, hipMemcpyHostToDevice));     // components beyond 3 keep their values
   int rc = rt_launch_denoise((int)src->width, (int)src->height, (int)src->stride, (int)src->components,

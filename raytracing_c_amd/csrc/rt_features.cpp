@@ -104,11 +104,7 @@ extern "C" int rt_resolve_features(RT_Render_Params const *params, void const *d
 
 // ---- host level ---------------------------------------------------------------------------------------------------------------
 // Gives back the staging of the host-level call.  D.mutex held, D's GPU current, device idle.
-void release_feature_state(Device &D) {
-  (void)hipFree(D.features.sums);
-  (void)hipFree(D.features.planes);
-  D.features = FeatureState();
-}
+void release_feature_state(Device &D) { D.features = FeatureState(); }
 
 extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces, RT_Features const *out,
                                   u64 *sums) {
@@ -133,12 +129,8 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
     return rt_fail("%s: a feature pass renders on one device, and %d are set (rt_set_devices)", who, rt_device_count());
   FeatureState &S = D.features;
   const size_t pixels = (size_t)width * height;
-  if (S.cap_pixels < pixels) {
-    release_feature_state(D);
-    HIP_TRY(hipMalloc(&S.sums, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&S.planes, pixels * RT_FEATURE_CHANNELS * sizeof(float)));
-    S.cap_pixels = pixels;
-  }
+  HIP_TRY(S.sums.grow(pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(S.planes.grow(pixels * RT_FEATURE_CHANNELS));
   float *d_cov = S.planes, *d_alb = S.planes + pixels, *d_nrm = S.planes + pixels * 4, *d_pos = S.planes + pixels * 7;
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
   auto pass = [&](RT_Device_Scene *d) -> int {

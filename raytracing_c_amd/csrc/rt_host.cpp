@@ -60,7 +60,7 @@ extern "C" int rt_set_devices(i32 n_devices, i32 rehearse) {
 // ---------------------------------------------------------------------------------
 // per-device state
 
-Device           g_devs[RT_MAX_DEVICES];
+Device *const    g_devs = new Device[RT_MAX_DEVICES];   // never destroyed: no HIP call from static destruction (rt_host.h)
 int              g_primary = 0;                   // physical device of slot 0
 static bool      g_primary_fixed = false;         // slot 0 has been initialised (rt_init can no longer move it)
 std::atomic<u32> g_seed{0x1234ABCDu};

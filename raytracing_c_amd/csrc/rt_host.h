@@ -13,6 +13,8 @@
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
+//   rt_mem.h          the owners of device memory, pinned memory and events (DevMem, PinnedMem, DevEvent): what a struct below
+//                     holds is given back when the struct is destroyed or assigned over, never by a hand-kept list
 //
 // Nothing on the host side computes a pixel on the CPU: every entry point either
 // drives the gfx950 kernels of rt_kernels.hip (one object, shared by both libraries) / rt_wavefront.hip and rt_kernels_test.hip
@@ -24,6 +26,11 @@
 // experiment knobs exist only in the host units of the diagnostic build (-DRT_DIAG_VARIANTS, librt_hip_diag.so).
 //
 // Lock order everywhere: slot 0's Device::mutex -> slot r's -> g_partition_mutex (rt_partition.cpp).
+//
+// No HIP call from static destruction: at process exit the HIP runtime may be gone already and the device threads of rt_multi.cpp
+// are still parked.  So NO object of static storage duration has an owner of rt_mem.h as a member, at any depth: the device slots
+// (g_devs), the retired partition tables (rt_partition.cpp) and the workers (rt_multi.cpp) are allocated once with `new` and never
+// destroyed.  Nothing is freed at exit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +50,7 @@
 
 #include "../../include/rt_hip.h"
 #include "rt_device.h"
+#include "rt_mem.h"
 
 // launchers in rt_kernels.hip, rt_denoise.hip
 extern "C" {
@@ -76,17 +84,6 @@ int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long lo
     hipError_t e_ = (expr);                                                                   \
     if (e_ != hipSuccess) return rt_fail("%s failed: %s", #expr, hipGetErrorString(e_));      \
   } while (0)
-
-// Temporary device buffer that is released on every exit path (HIP_TRY returns early).
-struct DevBuf {
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T> T *as() const { return (T *)p; }
-};
 
 static inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -154,32 +151,30 @@ struct ViewBatch {
   RT_View const *views = nullptr;
 };
 
+// (hidden, here and at LaunchState: the structs made of owners have destructors and move assignments now, and none of them joins
+//  the libraries' export lists)
+#pragma GCC visibility push(hidden)
 struct Workspace {
-  unsigned long long *accum = nullptr;
-  size_t              accum_elems = 0;
-  uint8_t            *image = nullptr;
-  float              *linear = nullptr;
-  size_t              image_pixels = 0;
-  uint8_t            *tiles = nullptr;        // multi-device frames: this device's compact tiles
-  size_t              tiles_bytes = 0;
-  uint8_t            *all_tiles = nullptr;    // slot 0: the tiles of every device, rank-major
-  size_t              all_tiles_bytes = 0;
-  uint8_t            *tiles_host = nullptr;   // pinned: a device without peer access to slot 0 stages its tiles here
-  size_t              tiles_host_bytes = 0;
-  unsigned long long *counters_host = nullptr;   // pinned: ray counters of a multi-device frame, copied asynchronously
+  DevMem<unsigned long long>    accum;        // [pixels][3]
+  DevMem<uint8_t>               image;        // [pixels][3]
+  DevMem<float>                 linear;       // [pixels][3] (a frame lane has none)
+  DevMem<uint8_t>               tiles;        // multi-device frames: this device's compact tiles
+  DevMem<uint8_t>               all_tiles;    // slot 0: the tiles of every device, rank-major
+  PinnedMem<uint8_t>            tiles_host;   // a device without peer access to slot 0 stages its tiles here
+  PinnedMem<unsigned long long> counters_host;   // ray counters of a multi-device frame, copied asynchronously
   // HIP event pairs around every path-kernel launch since the last timing reset
-  std::vector<hipEvent_t> ev0, ev1;
-  size_t              n_timed = 0;
-  hipEvent_t          ev_frame[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // frame start, prep done, path done, resolve done, copy done
-  unsigned long long *wave_times = nullptr;   // RT_WAVE_TIMES (diagnostic library): the wave timeline of the last launch
-  int                 wave_times_n = 0;
+  std::vector<DevEvent>         ev0, ev1;
+  size_t                        n_timed = 0;
+  DevEvent                      ev_frame[5];  // frame start, prep done, path done, resolve done, copy done
+  DevMem<unsigned long long>    wave_times;   // RT_WAVE_TIMES (diagnostic library): the wave timeline of the last launch
+  int                           wave_times_n = 0;
 };
 #define RT_MAX_TIMED 256
 
 struct DevPartition {
   const Partition        *host = nullptr;
-  std::vector<int32_t *>  d_lists;            // device copies of the ranks' chunk lists, uploaded on first use
-  int32_t                *d_owner_slot = nullptr;
+  std::vector<DevMem<int32_t>> d_lists;       // device copies of the ranks' chunk lists, uploaded on first use
+  DevMem<int32_t>         d_owner_slot;
 };
 
 // A frame in flight behind rt_frame_begin() / rt_frame_end() (slot 0): its own stream, accumulators and image buffer, and launch
@@ -207,27 +202,27 @@ struct FrameLane {
 // one 64-byte slot of a ring, so that query calls on several streams can be in flight at once; a slot is taken again only after
 // the event recorded behind its last launch has completed.  The staging buffers serve the host-level calls, one slice at a time;
 // they are kept between calls (at most 133 B x RT_QUERY_SLICE) and given back with the rest when the slot is torn down
-// (release_query_state).
+// (release_query_state).  The staging buffers are counted in f32 (a ray is 6, a hit record 4, a full record RT_HIT_DWORDS).
 #define RT_QUERY_SLOTS 64
 struct QueryState {
-  uint8_t   *slots = nullptr;                 // [RT_QUERY_SLOTS][64]: counters u64[4] at +0, work counter u32 at +32
-  hipEvent_t done[RT_QUERY_SLOTS] = {};
+  DevMem<uint8_t> slots;                      // [RT_QUERY_SLOTS][64]: counters u64[4] at +0, work counter u32 at +32
+  DevEvent   done[RT_QUERY_SLOTS];
   bool       used[RT_QUERY_SLOTS] = {};
   unsigned   next = 0;
   int        last = -1;                       // slot of the most recent query call (rt_get_query_counters)
-  float     *rays = nullptr, *t_max = nullptr, *hits = nullptr, *full = nullptr;
-  uint8_t   *flags = nullptr;
-  size_t     cap_rays = 0, cap_t_max = 0, cap_hits = 0, cap_full = 0, cap_flags = 0;      // rays each staging buffer holds
+  DevMem<float>   rays, t_max, hits, full;
+  DevMem<uint8_t> flags;
 };
 
 // First-hit feature buffers (rt_features.cpp): the device staging of the host-level call -- the sums and the ten f32 planes of one
 // frame -- kept between calls, given back with the device slot (release_feature_state).  A launch's work counter is a slot of the
 // query ring above.
 struct FeatureState {
-  unsigned long long *sums = nullptr;         // [pixels][RT_FEATURE_CHANNELS]
-  float              *planes = nullptr;       // coverage [pixels], then albedo, normal, position [pixels][3] each
-  size_t              cap_pixels = 0;
+  DevMem<unsigned long long> sums;            // [pixels][RT_FEATURE_CHANNELS]
+  DevMem<float>              planes;          // coverage [pixels], then albedo, normal, position [pixels][3] each
 };
+
+#pragma GCC visibility pop
 
 struct Device {
   int        slot = 0, phys = 0;
@@ -266,36 +261,34 @@ struct FpBlock {            // one block of a host scene's full fingerprint (sce
   uint64_t    h;
 };
 
+#pragma GCC visibility push(hidden)
 // What ONE launch of the path kernel writes besides the accumulators: counters, work head, the tiles' unit counters, parked hits,
 // the schedule feedback.  A device scene owns several (RT_Device_Scene::ls), allocated on first use.
 struct LaunchState {
-  unsigned long long *counters = nullptr;      // RT_N_COUNTERS
-  uint32_t           *work_head = nullptr;
-  uint32_t           *tile_next = nullptr;     // tile-stream kernel: chunks handed out per tile
-  int32_t             tile_next_n = 0;
-  uint32_t           *park = nullptr;          // tile-stream kernel: parked hits, [waves][18][128]
-  int32_t             park_waves = 0;
+  DevMem<unsigned long long> counters;         // RT_N_COUNTERS
+  DevMem<uint32_t>    work_head;               // one 64-byte line
+  DevMem<uint32_t>    tile_next;               // tile-stream kernel: chunks handed out per tile, then the groups' open-tile counts
+  int32_t             tile_next_n = 0;         // tiles it was sized for: the groups' counts begin at tile_next + tile_next_n
+  DevMem<uint32_t>    park;                    // tile-stream kernel: parked hits, [waves][18][128]
   // schedule feedback: rays per 8x8 tile of the previous launch of the same frame shape -> visiting order of the next
-  uint32_t    *cost[2] = {nullptr, nullptr};   // [cur] is written by the running launch, [cur^1] is last launch's
-  uint32_t    *order = nullptr;
+  DevMem<uint32_t>    cost[2];                 // [cur] is written by the running launch, [cur^1] is last launch's
+  DevMem<uint32_t>    order;
   int32_t      sched_tiles = 0, sched_cur = 0;
   bool         sched_valid = false;            // cost[cur^1] holds the costs of a launch with sched_key
   uint64_t     sched_key = 0;
   // view batches: the device view table of the launch, filled from a pinned copy on the launch's stream
-  RT_KView    *views = nullptr;
-  RT_KView    *views_host = nullptr;
-  int32_t      views_cap = 0;
-  hipEvent_t   views_copied = nullptr;         // recorded after the table's copy: views_host may be rewritten once it completed
+  DevMem<RT_KView>    views;
+  PinnedMem<RT_KView> views_host;
+  DevEvent            views_copied;            // recorded after the table's copy: views_host may be rewritten once it completed
 };
+
+#pragma GCC visibility pop
 
 struct RT_Device_Scene {
   Device      *dev = nullptr;
-  float       *nodes = nullptr;
-  float       *leaves = nullptr;
-  float       *tris = nullptr;
-  float       *mats = nullptr;
-  RT_DTexture *textures = nullptr;
-  uint32_t    *texels = nullptr;
+  DevMem<float>       nodes, leaves, tris, mats;
+  DevMem<RT_DTexture> textures;
+  DevMem<uint32_t>    texels;
   int32_t      depth = 0, last_row_offset = 0, bg_texture = -1, n_nodes = 0;
   int32_t      n_triangles = 0, n_materials = 0, n_textures = 0;
   int64_t      bytes = 0;
@@ -319,17 +312,17 @@ struct RT_Device_Scene {
   // of single frames and of batches from replacing each other)
   LaunchState ls[RT_LAUNCH_STATES + 1];
   // wavefront pipeline (rt_wavefront.hip): record queues between the camera / shade / trace kernels
-  uint32_t           *wf_hit0 = nullptr, *wf_hit = nullptr, *wf_ray[2] = {nullptr, nullptr};
-  uint32_t           *wf_cnt = nullptr;        // records per chunk: hit0 | hit | ray[0] | ray[1]
-  uint32_t           *wf_ctl = nullptr;        // WF_N_CTL control words, one per 64-byte line
-  uint32_t           *wf_ctl_host = nullptr;   // pinned copy the host reads after a pass
+  DevMem<uint32_t>    wf_hit0, wf_hit, wf_ray[2];
+  DevMem<uint32_t>    wf_cnt;                  // records per chunk: hit0 | hit | ray[0] | ray[1]
+  DevMem<uint32_t>    wf_ctl;                  // WF_N_CTL control words, one per 64-byte line
+  PinnedMem<uint32_t> wf_ctl_host;             // the copy the host reads after a pass
   int64_t             wf_soft0 = 0, wf_hard0 = 0, wf_ray_chunks = 0, wf_hit_chunks = 0;   // capacities in chunks
   int32_t             wf_waves = 0;            // waves the capacities were sized for
 };
 
 // ---------------------------------------------------------------------------------
 // what one unit defines and another calls.  Hidden: none of it is exported from the library (the types above keep default
-// visibility, so the library's export list is what it was).
+// visibility, the structs made of owners aside, so the library's export list is what it was).
 
 #pragma GCC visibility push(hidden)
 
@@ -337,7 +330,7 @@ struct RT_Device_Scene {
 int    rt_fail(const char *fmt, ...);                   // sets rt_last_error(), returns -1
 Config config();
 int    ensure_device(Device &D);                        // D.mutex held (or single-threaded start-up); makes D's GPU current
-extern Device           g_devs[RT_MAX_DEVICES];
+extern Device *const    g_devs;                         // [RT_MAX_DEVICES], allocated once and never destroyed (see the top)
 extern int              g_primary;                      // physical device of slot 0
 extern std::atomic<u32> g_seed;
 extern std::mutex       g_multi_mutex;                  // counters of the last multi-device frame
@@ -348,7 +341,7 @@ extern Background_Proc  g_tok_background;               // ... and the device ba
 static inline Device &dev0() { return g_devs[0]; }
 
 // rt_residency.cpp
-void             free_device_scene(RT_Device_Scene *d);            // d->dev->mutex held, d's device current
+void             free_device_scene(RT_Device_Scene *d);            // d->dev->mutex held, d's device current; waits for the lanes that render from d
 uint64_t         scene_fingerprint(Scene const *scene);
 bool             scene_is_static(Scene const *scene);               // takes g_static_mutex
 int              drop_stale_copies(Scene const *scene, uint64_t now, int first_slot);   // takes each slot's mutex; returns copies dropped

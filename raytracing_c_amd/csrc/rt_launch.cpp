@@ -148,14 +148,13 @@ static int schedule_feedback(LaunchState &L, RT_KParams &K, const uint32_t **cos
   };
   int32_t ids[6] = {K.width, K.height, K.rank, K.world, K.max_bounces, n_tiles};
   mix(ids, sizeof ids);
-  if (L.sched_tiles != n_tiles) {
-    (void)hipFree(L.cost[0]); (void)hipFree(L.cost[1]); (void)hipFree(L.order);
-    L.cost[0] = L.cost[1] = L.order = nullptr;
+  if (L.sched_tiles != n_tiles) {      // (another size, not only a larger one: the costs kept are those of n_tiles tiles)
+    L.cost[0].reset(); L.cost[1].reset(); L.order.reset();
     L.sched_tiles = 0;
     L.sched_valid = false;
-    HIP_TRY(hipMalloc(&L.cost[0], (size_t)n_tiles * 4));
-    HIP_TRY(hipMalloc(&L.cost[1], (size_t)n_tiles * 4));
-    HIP_TRY(hipMalloc(&L.order, (size_t)n_tiles * 4));
+    HIP_TRY(L.cost[0].grow((size_t)n_tiles));
+    HIP_TRY(L.cost[1].grow((size_t)n_tiles));
+    HIP_TRY(L.order.grow((size_t)n_tiles));
     L.sched_tiles = n_tiles;
   }
   if (L.sched_valid && L.sched_key == key) {
@@ -173,16 +172,9 @@ static int schedule_feedback(LaunchState &L, RT_KParams &K, const uint32_t **cos
 // (which waits for the launches queued before it on that stream, at most one launch ahead of this one) ----
 static int upload_view_table(LaunchState &L, RT_KParams &K, ViewBatch const *batch, hipStream_t stream) {
   const int nv = batch->n;
-  if (L.views_cap < nv) {
-    (void)hipFree(L.views);
-    if (L.views_host) (void)hipHostFree(L.views_host);
-    L.views = L.views_host = nullptr;
-    L.views_cap = 0;
-    HIP_TRY(hipMalloc(&L.views, (size_t)nv * sizeof(RT_KView)));
-    HIP_TRY(hipHostMalloc(&L.views_host, (size_t)nv * sizeof(RT_KView), hipHostMallocDefault));
-    L.views_cap = nv;
-  }
-  if (!L.views_copied) HIP_TRY(hipEventCreateWithFlags(&L.views_copied, hipEventDisableTiming));
+  HIP_TRY(L.views.grow((size_t)nv));
+  HIP_TRY(L.views_host.grow((size_t)nv));
+  if (!L.views_copied) HIP_TRY(L.views_copied.ensure(hipEventDisableTiming));
   else HIP_TRY(hipEventSynchronize(L.views_copied));
   for (int v = 0; v < nv; v++) {
     RT_KView &r = L.views_host[v];
@@ -211,8 +203,8 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   if (fill_kparams(D, &K, d, cam, p, d_accum, batch) != 0) return -1;
   if (launch_state < 0 || launch_state > RT_VIEWS_STATE) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
   LaunchState &L = d->ls[launch_state];
-  if (!L.counters) HIP_TRY(hipMalloc((void **)&L.counters, RT_N_COUNTERS * sizeof(unsigned long long)));
-  if (!L.work_head) HIP_TRY(hipMalloc((void **)&L.work_head, 64));
+  HIP_TRY(L.counters.grow(RT_N_COUNTERS));
+  HIP_TRY(L.work_head.grow(16));
   K.counters = L.counters;
   K.work_head = L.work_head;
   D.last_counters = L.counters;
@@ -246,11 +238,9 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   K.n_sample_blocks = (n_samples + (1 << cshift) - 1) >> cshift;
   K.n_chunks_tile = 32 * K.n_sample_blocks;          // units: 8 rows x sample blocks x 4 pixel pairs
   if (L.tile_next_n < K.n_tiles) {
-    (void)hipFree(L.tile_next);
-    L.tile_next = nullptr;
     L.tile_next_n = 0;
     // [n_tiles] chunk counters, then [ceil(n_tiles / 64)] open-tile counts of the groups
-    HIP_TRY(hipMalloc(&L.tile_next, ((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)) * 4));
+    HIP_TRY(L.tile_next.grow((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)));
     L.tile_next_n = K.n_tiles;
   }
   K.tile_next = L.tile_next;
@@ -285,14 +275,8 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   K.park = nullptr;
   if (!wavefront && knob_int("RT_PARK", 1) != 0 && K.max_bounces < (1 << 26)) {      // (a parked record keeps the bounce count in 26 bits)
     const int grid_waves = (n_waves + wg_waves - 1) / wg_waves * wg_waves;         // whole workgroups are launched
-    if (L.park_waves < grid_waves) {
-      (void)hipFree(L.park);
-      L.park = nullptr;
-      L.park_waves = 0;
-      const size_t slice_bytes = (size_t)RT_PARK_RECORD_DWORDS * 4;      // a wave's slice: 18 fields x 128 records (rt_device.h)
-      HIP_TRY(hipMalloc(&L.park, (size_t)grid_waves * slice_bytes));
-      L.park_waves = grid_waves;
-    }
+    const size_t slice_dwords = RT_PARK_RECORD_DWORDS;                            // a wave's slice: 18 fields x 128 records (rt_device.h)
+    HIP_TRY(L.park.grow((size_t)grid_waves * slice_dwords));
     K.park = L.park;
   }
 
@@ -310,7 +294,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
 
   K.wave_times = nullptr;
   if (knob_set("RT_WAVE_TIMES")) {      // wave timeline (tools/exp_waves.py)
-    if (!D.ws.wave_times) HIP_TRY(hipMalloc(&D.ws.wave_times, (size_t)65536 * 3 * 8));
+    HIP_TRY(D.ws.wave_times.grow((size_t)65536 * 3));
     HIP_TRY(hipMemsetAsync(D.ws.wave_times, 0, (size_t)65536 * 3 * 8, stream));
     K.wave_times = D.ws.wave_times;
     if (n_waves > 65536) n_waves = 65536;          // the diagnostic buffer holds that many waves
@@ -319,12 +303,11 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
 
   size_t slot = D.ws.n_timed % RT_MAX_TIMED;
   if (slot >= D.ws.ev0.size()) {
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
-    D.ws.ev0.push_back(a);
-    D.ws.ev1.push_back(b);
+    D.ws.ev0.emplace_back();
+    D.ws.ev1.emplace_back();
   }
+  HIP_TRY(D.ws.ev0[slot].ensure());
+  HIP_TRY(D.ws.ev1[slot].ensure());
   HIP_TRY(hipEventRecord(D.ws.ev0[slot], stream));
 #ifdef RT_DIAG_VARIANTS
   if (wavefront) {
@@ -424,40 +407,13 @@ extern "C" int rt_untile(i32 width, i32 height, i32 world, void const *d_all_til
 }
 
 int ensure_ws_buffers(Workspace &W, int width, int height, size_t tiles_bytes, size_t all_tiles_bytes, bool want_linear) {
-  size_t pixels = (size_t)width * height;
-  if (W.accum_elems < pixels * 3) {
-    (void)hipFree(W.accum);
-    W.accum = nullptr;
-    W.accum_elems = 0;
-    HIP_TRY(hipMalloc(&W.accum, pixels * 3 * sizeof(unsigned long long)));
-    W.accum_elems = pixels * 3;
-  }
-  if (W.image_pixels < pixels) {
-    (void)hipFree(W.image);
-    (void)hipFree(W.linear);
-    W.image = nullptr;
-    W.linear = nullptr;
-    W.image_pixels = 0;
-    HIP_TRY(hipMalloc(&W.image, pixels * 3));
-    if (want_linear) HIP_TRY(hipMalloc(&W.linear, pixels * 3 * sizeof(float)));      // (a frame lane has no fp32 output)
-    W.image_pixels = pixels;
-  }
-  if (W.tiles_bytes < tiles_bytes) {
-    (void)hipFree(W.tiles);
-    W.tiles = nullptr;
-    W.tiles_bytes = 0;
-    HIP_TRY(hipMalloc(&W.tiles, tiles_bytes));
-    W.tiles_bytes = tiles_bytes;
-  }
-  if (W.all_tiles_bytes < all_tiles_bytes) {
-    (void)hipFree(W.all_tiles);
-    W.all_tiles = nullptr;
-    W.all_tiles_bytes = 0;
-    HIP_TRY(hipMalloc(&W.all_tiles, all_tiles_bytes));
-    W.all_tiles_bytes = all_tiles_bytes;
-  }
-  for (int i = 0; i < 5; i++)
-    if (!W.ev_frame[i]) HIP_TRY(hipEventCreate(&W.ev_frame[i]));
+  const size_t pixels = (size_t)width * height;
+  HIP_TRY(W.accum.grow(pixels * 3));
+  HIP_TRY(W.image.grow(pixels * 3));
+  if (want_linear) HIP_TRY(W.linear.grow(pixels * 3));                  // (a frame lane has no fp32 output)
+  if (tiles_bytes) HIP_TRY(W.tiles.grow(tiles_bytes));                  // (multi-device frames only: a request for none would yield a pointer)
+  if (all_tiles_bytes) HIP_TRY(W.all_tiles.grow(all_tiles_bytes));
+  for (DevEvent &e : W.ev_frame) HIP_TRY(e.ensure());
   return 0;
 }
 

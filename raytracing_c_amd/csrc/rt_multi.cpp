@@ -68,17 +68,10 @@ static void enqueue_device_frame(MultiFrame &J, int r) {
   const double t_enq = now_ms();
   Workspace &W = D.ws;
   if (ensure_ws_buffers(W, J.w, J.h, J.tiles_bytes, r == 0 ? J.tiles_bytes * (size_t)J.world : 0) != 0) { device_fail(J, r, rt_last_error()); return; }
-  if (!W.counters_host && hipHostMalloc((void **)&W.counters_host, RT_N_COUNTERS * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-    device_fail(J, r, "pinned counter buffer"); return;
-  }
+  if (W.counters_host.grow(RT_N_COUNTERS) != hipSuccess) { device_fail(J, r, "pinned counter buffer"); return; }
   const bool same_gpu = D.phys == D0.phys;
   const bool direct = same_gpu || (D.peer_ok && !fault_no_peer());
-  if (!direct && W.tiles_host_bytes < J.tiles_bytes) {
-    if (W.tiles_host) (void)hipHostFree(W.tiles_host);
-    W.tiles_host = nullptr; W.tiles_host_bytes = 0;
-    if (hipHostMalloc((void **)&W.tiles_host, J.tiles_bytes, hipHostMallocDefault) != hipSuccess) { device_fail(J, r, "pinned tile buffer"); return; }
-    W.tiles_host_bytes = J.tiles_bytes;
-  }
+  if (!direct && W.tiles_host.grow(J.tiles_bytes) != hipSuccess) { device_fail(J, r, "pinned tile buffer"); return; }
   RT_Render_Params p = J.base;
   p.rank = r;
   p.world = J.world;

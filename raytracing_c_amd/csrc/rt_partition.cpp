@@ -50,14 +50,16 @@ static std::mutex               g_partition_mutex;   // the host tables and ever
 // pointers and release g_partition_mutex before the kernel that reads them is enqueued (under the device's own mutex), and
 // another thread's 17th distinct (width, height, world) may evict in between.  They are RETIRED and freed by the eviction
 // after the next one -- every frame synchronises before it returns, so whatever read them has long finished by then.
-struct RetiredBuffer { int phys; void *ptr; };
-static std::vector<RetiredBuffer> g_retired[2];                 // [0]: retired by the latest eviction, [1]: by the one before
+namespace { struct RetiredTables { int phys; DevPartition tables; }; }
+// [0]: retired by the latest eviction, [1]: by the one before; never destroyed (no HIP call from static destruction, rt_host.h)
+static std::vector<RetiredTables> *const g_retired = new std::vector<RetiredTables>[2];
+static void retire(Device &D, DevPartition &&dp) { g_retired[0].push_back({D.phys, std::move(dp)}); }      // g_partition_mutex held
 static void drop_device_partitions(const Partition *q) {        // g_partition_mutex held
-  for (const RetiredBuffer &rb : g_retired[1]) {
+  for (RetiredTables &rb : g_retired[1]) {                      // freed with their device current
     int prev = -1;
     (void)hipGetDevice(&prev);
     if (prev != rb.phys) (void)hipSetDevice(rb.phys);
-    (void)hipFree(rb.ptr);
+    rb.tables = DevPartition();
     if (prev >= 0 && prev != rb.phys) (void)hipSetDevice(prev);
   }
   g_retired[1].swap(g_retired[0]);
@@ -66,8 +68,7 @@ static void drop_device_partitions(const Partition *q) {        // g_partition_m
     Device &D = g_devs[i];
     for (size_t k = 0; k < D.parts.size(); k++) {
       if (D.parts[k].host != q) continue;
-      for (int32_t *ptr : D.parts[k].d_lists) if (ptr) g_retired[0].push_back({D.phys, ptr});
-      if (D.parts[k].d_owner_slot) g_retired[0].push_back({D.phys, D.parts[k].d_owner_slot});
+      retire(D, std::move(D.parts[k]));
       D.parts.erase(D.parts.begin() + (long)k);
       break;
     }
@@ -97,26 +98,15 @@ void remap_device_slots() {
       for (auto &kv : D.scene_cache) free_device_scene(kv.second);
       D.scene_cache.clear();
       D.cameras.clear();
-      Workspace &W = D.ws;
-      (void)hipFree(W.accum); (void)hipFree(W.image); (void)hipFree(W.linear); (void)hipFree(W.tiles); (void)hipFree(W.all_tiles);
-      if (W.tiles_host) (void)hipHostFree(W.tiles_host);
-      if (W.counters_host) (void)hipHostFree(W.counters_host);
-      (void)hipFree(W.wave_times);
-      for (hipEvent_t e : W.ev0) (void)hipEventDestroy(e);
-      for (hipEvent_t e : W.ev1) (void)hipEventDestroy(e);
-      for (int i = 0; i < 5; i++) if (W.ev_frame[i]) (void)hipEventDestroy(W.ev_frame[i]);
+      D.ws = Workspace();
       if (D.mstream) { (void)hipStreamDestroy(D.mstream); D.mstream = nullptr; }
-      W = Workspace();
       D.last_counters = nullptr;
       release_query_state(D);
       release_feature_state(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);
-      for (DevPartition &dp : D.parts) {
-        for (int32_t *ptr : dp.d_lists) if (ptr) g_retired[0].push_back({D.phys, ptr});
-        if (dp.d_owner_slot) g_retired[0].push_back({D.phys, dp.d_owner_slot});
-      }
+      for (DevPartition &dp : D.parts) retire(D, std::move(dp));
       D.parts.clear();
     }
     D.ready = false;
@@ -172,10 +162,9 @@ extern "C" i32 rt_local_chunk_list(i32 width, i32 height, i32 rank, i32 world, i
 static DevPartition &device_partition(Device &D, const Partition *q) {     // g_partition_mutex held
   for (DevPartition &dp : D.parts)
     if (dp.host == q) return dp;
-  DevPartition dp;
-  dp.host = q;
-  dp.d_lists.assign((size_t)q->world, nullptr);
-  D.parts.push_back(dp);
+  D.parts.emplace_back();
+  D.parts.back().host = q;
+  D.parts.back().d_lists.resize((size_t)q->world);
   return D.parts.back();
 }
 
@@ -185,13 +174,14 @@ int device_chunk_list(Device &D, int width, int height, int rank, int world, con
   Partition *q = get_partition(width, height, world);
   DevPartition &dp = device_partition(D, q);
   const std::vector<int32_t> &l = q->lists[(size_t)rank];
-  if (!dp.d_lists[(size_t)rank]) {
-    int32_t *ptr = nullptr;
-    HIP_TRY(hipMalloc((void **)&ptr, l.empty() ? 16 : l.size() * 4));
-    if (!l.empty()) HIP_TRY(hipMemcpy(ptr, l.data(), l.size() * 4, hipMemcpyHostToDevice));
-    dp.d_lists[(size_t)rank] = ptr;
+  DevMem<int32_t> &list = dp.d_lists[(size_t)rank];
+  if (!list) {
+    DevMem<int32_t> fresh;                       // (kept only once it is filled)
+    HIP_TRY(fresh.grow(l.size()));
+    if (!l.empty()) HIP_TRY(hipMemcpy(fresh, l.data(), l.size() * 4, hipMemcpyHostToDevice));
+    list = std::move(fresh);
   }
-  *d_list = dp.d_lists[(size_t)rank];
+  *d_list = list;
   *n_local = (int)l.size();
   return 0;
 }
@@ -201,8 +191,10 @@ int device_owner_table(Device &D, int width, int height, int world, const int32_
   Partition *q = get_partition(width, height, world);
   DevPartition &dp = device_partition(D, q);
   if (!dp.d_owner_slot) {
-    HIP_TRY(hipMalloc((void **)&dp.d_owner_slot, q->owner_slot.size() * 4));
-    HIP_TRY(hipMemcpy(dp.d_owner_slot, q->owner_slot.data(), q->owner_slot.size() * 4, hipMemcpyHostToDevice));
+    DevMem<int32_t> fresh;
+    HIP_TRY(fresh.grow(q->owner_slot.size()));
+    HIP_TRY(hipMemcpy(fresh, q->owner_slot.data(), q->owner_slot.size() * 4, hipMemcpyHostToDevice));
+    dp.d_owner_slot = std::move(fresh);
   }
   *d_table = dp.d_owner_slot;
   *n_chunks = q->n_chunks;

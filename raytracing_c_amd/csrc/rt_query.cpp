@@ -42,9 +42,7 @@ static void query_geometry(const Device &D, const RT_Device_Scene *d, int n, RT_
 }
 
 int ensure_query_state(Device &D) {                     // D.mutex held, D's GPU current
-  QueryState &S = D.query;
-  if (S.slots) return 0;
-  HIP_TRY(hipMalloc(&S.slots, RT_QUERY_SLOTS * 64));
+  HIP_TRY(D.query.slots.grow(RT_QUERY_SLOTS * 64));
   return 0;
 }
 
@@ -53,7 +51,7 @@ int ensure_query_state(Device &D) {                     // D.mutex held, D's GPU
 int acquire_slot(Device &D, int *slot, bool query) {
   QueryState &S = D.query;
   const int s = (int)(S.next++ % RT_QUERY_SLOTS);
-  if (!S.done[s]) HIP_TRY(hipEventCreateWithFlags(&S.done[s], hipEventDisableTiming));
+  HIP_TRY(S.done[s].ensure(hipEventDisableTiming));
   if (S.used[s]) HIP_TRY(hipEventSynchronize(S.done[s]));      // (its launch of RT_QUERY_SLOTS calls ago, long over)
   S.used[s] = true;
   if (query) {
@@ -131,22 +129,9 @@ extern "C" int rt_query_occluded(RT_Device_Scene *dscene, i64 n, void const *d_r
 // ---- host level ---------------------------------------------------------------------------------------------------------------
 template void std::vector<f32>::resize(size_t);      // (in the library's export list, like unordered_map::erase in rt_residency.cpp)
 
-template <typename T> static int grow(T **p, size_t *cap, size_t want, size_t elem_bytes) {
-  if (*cap >= want) return 0;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc(p, want * elem_bytes));
-  *cap = want;
-  return 0;
-}
-
 // Gives back what a device's query state holds (ring, events, staging).  D.mutex held, D's GPU current, device idle.
 void release_query_state(Device &D) {
-  QueryState &S = D.query;
-  (void)hipFree(S.slots); (void)hipFree(S.rays); (void)hipFree(S.t_max); (void)hipFree(S.hits); (void)hipFree(S.full); (void)hipFree(S.flags);
-  for (hipEvent_t e : S.done) if (e) (void)hipEventDestroy(e);
-  S = QueryState();
+  D.query = QueryState();
   Device *self = &D;
   g_query_dev.compare_exchange_strong(self, nullptr);
 }
@@ -165,10 +150,11 @@ static int query_host(Scene const *scene, i64 n, Ray const *rays, f32 const *t_m
   const size_t slice = (size_t)(n < RT_QUERY_SLICE ? n : RT_QUERY_SLICE);
   // staging on the device, kept for the next call: rays 24 + t_max 4 B per ray of a slice, then flags 1, or hit records 16 and --
   // rt_scene_hits only -- full records 88
-  if (grow(&S.rays, &S.cap_rays, slice, 24) != 0 || grow(&S.t_max, &S.cap_t_max, slice, 4) != 0) return -1;
-  if (any && grow(&S.flags, &S.cap_flags, slice, 1) != 0) return -1;
-  if (!any && grow(&S.hits, &S.cap_hits, slice, 16) != 0) return -1;
-  if (hits && grow(&S.full, &S.cap_full, slice, sizeof(RT_Device_Hit)) != 0) return -1;
+  HIP_TRY(S.rays.grow(slice * 6));
+  HIP_TRY(S.t_max.grow(slice));
+  if (any) HIP_TRY(S.flags.grow(slice));
+  if (!any) HIP_TRY(S.hits.grow(slice * 4));
+  if (hits) HIP_TRY(S.full.grow(slice * RT_HIT_DWORDS));
   int slot = 0;
   if (acquire_slot(D, &slot) != 0) return -1;
   hipStream_t stream = nullptr;

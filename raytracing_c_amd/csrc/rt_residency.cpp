@@ -4,48 +4,23 @@
 
 void free_device_scene(RT_Device_Scene *d) {      // d->dev->mutex held, d's device current
   if (!d) return;
-  if (d->dev)
+  if (d->dev) {
     for (FrameLane &F : d->dev->lanes)        // a frame in flight renders from this copy: let it finish (its pixels are in the lane's buffer)
       if (F.busy && F.d == d) {
         if (F.stream) (void)hipStreamSynchronize(F.stream);
         F.d = nullptr;
       }
-  (void)hipFree(d->nodes);
-  (void)hipFree(d->leaves);
-  (void)hipFree(d->tris);
-  (void)hipFree(d->mats);
-  (void)hipFree(d->textures);
-  (void)hipFree(d->texels);
-  for (LaunchState &L : d->ls) {
-    if (d->dev && L.counters && d->dev->last_counters == L.counters) d->dev->last_counters = nullptr;
-    (void)hipFree(L.counters);
-    (void)hipFree(L.work_head);
-    (void)hipFree(L.tile_next);
-    (void)hipFree(L.park);
-    (void)hipFree(L.cost[0]);
-    (void)hipFree(L.cost[1]);
-    (void)hipFree(L.order);
-    (void)hipFree(L.views);
-    if (L.views_host) (void)hipHostFree(L.views_host);
-    if (L.views_copied) (void)hipEventDestroy(L.views_copied);
+    for (LaunchState &L : d->ls)
+      if (L.counters && d->dev->last_counters == L.counters) d->dev->last_counters = nullptr;
   }
-  (void)hipFree(d->wf_hit0);
-  (void)hipFree(d->wf_hit);
-  (void)hipFree(d->wf_ray[0]);
-  (void)hipFree(d->wf_ray[1]);
-  (void)hipFree(d->wf_cnt);
-  (void)hipFree(d->wf_ctl);
-  if (d->wf_ctl_host) (void)hipHostFree(d->wf_ctl_host);
-  delete d;
+  delete d;                                   // (its members own what it holds on the device, rt_mem.h)
 }
 
 template <typename T>
-static int upload(T **dst, const std::vector<T> &src, int64_t *bytes) {
-  size_t n = src.size() * sizeof(T);
-  if (n == 0) n = 16;
-  HIP_TRY(hipMalloc((void **)dst, n));
-  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  *bytes += (int64_t)n;
+static int upload(DevMem<T> &dst, const std::vector<T> &src, int64_t *bytes) {
+  HIP_TRY(dst.grow(src.size()));
+  if (!src.empty()) HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  *bytes += (int64_t)dst.bytes();
   return 0;
 }
 
@@ -80,26 +55,24 @@ static int texture_index(Image const *img, TexturePool &pool) {
   return idx;
 }
 
-static int upload_textures(const TexturePool &pool, uint32_t **d_texels, int64_t *bytes) {
-  size_t n = pool.texels ? pool.texels * 4 : 16;
-  HIP_TRY(hipMalloc((void **)d_texels, n));
-  *bytes += (int64_t)n;
+static int upload_textures(const TexturePool &pool, DevMem<uint32_t> &d_texels, int64_t *bytes) {
+  HIP_TRY(d_texels.grow(pool.texels));
+  *bytes += (int64_t)d_texels.bytes();
   size_t max_raw = 0;
   for (const Image *img : pool.sources) {
     size_t raw = (size_t)img->stride * img->height * img->components;
     if (raw > max_raw) max_raw = raw;
   }
   if (max_raw == 0) return 0;
-  DevBuf stage_buf;
-  HIP_TRY(stage_buf.alloc(max_raw));
-  uint8_t *stage = stage_buf.as<uint8_t>();
+  DevMem<uint8_t> stage;
+  HIP_TRY(stage.grow(max_raw));
   int rc = 0;
   for (size_t k = 0; k < pool.sources.size() && rc == 0; k++) {
     const Image *img = pool.sources[k];
     size_t raw = (size_t)img->stride * img->height * img->components;
     rc = (int)hipMemcpy(stage, img->pixels.data, raw, hipMemcpyHostToDevice);
     if (rc == 0) rc = rt_launch_pack_texture(stage, (int)img->width, (int)img->height, 0, (int)img->stride, (int)img->components,
-                                             *d_texels + pool.descs[k].offset, nullptr);
+                                             d_texels + pool.descs[k].offset, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();        // the staging buffer is reused by the next texture
   }
   if (rc != 0) return rt_fail("texture upload failed: %s", hipGetErrorString((hipError_t)rc));
@@ -453,15 +426,14 @@ static RT_Device_Scene *upload_scene_locked(Device &D, Scene const *scene) {
 
   RT_Device_Scene *d = new RT_Device_Scene();
   d->dev = &D;
-  if (hipMalloc((void **)&d->ls[0].counters, RT_N_COUNTERS * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void **)&d->ls[0].work_head, 64) != hipSuccess) {
+  if (d->ls[0].counters.grow(RT_N_COUNTERS) != hipSuccess || d->ls[0].work_head.grow(16) != hipSuccess) {
     rt_fail("rt_scene_upload: out of device memory");
     free_device_scene(d);
     return nullptr;
   }
-  if (upload(&d->nodes, nodes, &d->bytes) || upload(&d->leaves, leaves, &d->bytes) ||
-      upload(&d->tris, tris, &d->bytes) || upload(&d->mats, mats, &d->bytes) ||
-      upload(&d->textures, pool.descs, &d->bytes) || upload_textures(pool, &d->texels, &d->bytes)) {
+  if (upload(d->nodes, nodes, &d->bytes) || upload(d->leaves, leaves, &d->bytes) ||
+      upload(d->tris, tris, &d->bytes) || upload(d->mats, mats, &d->bytes) ||
+      upload(d->textures, pool.descs, &d->bytes) || upload_textures(pool, d->texels, &d->bytes)) {
     free_device_scene(d);
     return nullptr;
   }
@@ -636,11 +608,11 @@ static int touch_device_scene(RT_Device_Scene *d, Scene const *scene, const void
     const size_t row_bytes = (size_t)img->stride * img->components;
     if (!range_in(begin, bytes, img->pixels.data, row_bytes * img->height, &off)) continue;
     const size_t r0 = off / row_bytes, r1 = (off + bytes + row_bytes - 1) / row_bytes;
-    DevBuf stage;
-    HIP_TRY(stage.alloc((r1 - r0) * row_bytes));
-    HIP_TRY(hipMemcpy(stage.p, (const unsigned char *)img->pixels.data + r0 * row_bytes, (r1 - r0) * row_bytes, hipMemcpyHostToDevice));
+    DevMem<uint8_t> stage;
+    HIP_TRY(stage.grow((r1 - r0) * row_bytes));
+    HIP_TRY(hipMemcpy(stage, (const unsigned char *)img->pixels.data + r0 * row_bytes, (r1 - r0) * row_bytes, hipMemcpyHostToDevice));
     uint32_t *tex_base = d->texels + desc.offset;
-    int rc = rt_launch_pack_texture(stage.as<uint8_t>(), (int)img->width, (int)(r1 - r0), (int)r0, (int)img->stride,
+    int rc = rt_launch_pack_texture(stage, (int)img->width, (int)(r1 - r0), (int)r0, (int)img->stride,
                                     (int)img->components, tex_base, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();
     if (rc != 0) return rt_fail("rt_scene_touch: texture rows: %s", hipGetErrorString((hipError_t)rc));

@@ -205,6 +205,7 @@ EXPORTED_SYMBOLS = [
 # NOT carry them (tests/test_abi.py)
 DIAG_ONLY_SYMBOLS = [
     "rt_diag_set_tokens", "rt_diag_multi_fault", "rt_set_pipeline", "rt_get_pipeline", "rt_set_wavefront_capacity", "rt_get_wave_times", "rt_get_ledger",
+    "rt_diag_device_bytes_live",
     "rt_test_math", "rt_test_rcp_sweep", "rt_test_srgb_sweep", "rt_test_quantize_sweep", "rt_test_trace", "rt_test_trace_stream",
     "rt_test_tile_order", "rt_test_texture",
 ]

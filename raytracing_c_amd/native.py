@@ -186,6 +186,8 @@ def _declare_diag(d):
     d.rt_set_wavefront_capacity.restype = None
     d.rt_get_wave_times.argtypes = [vp, C.c_int32]
     d.rt_get_ledger.argtypes = [vp, C.c_int32]
+    d.rt_diag_device_bytes_live.argtypes = []
+    d.rt_diag_device_bytes_live.restype = C.c_int64
     d.rt_diag_multi_fault.argtypes = [C.c_int32, C.c_int32]
     d.rt_diag_multi_fault.restype = None
     d.rt_diag_set_tokens.argtypes = [vp, vp, vp]
