@@ -319,6 +319,74 @@ extern int rt_resolve_features(RT_Render_Params const *params, void const *d_sum
 extern int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
                               RT_Features const *out, u64 *sums);
 
+/* ---- guided denoiser ------------------------------------------------------------------ */
+
+/* An edge-stopping a-trous filter (Dammertz et al. 2010) of the linear frame, steered by the feature buffers above: what turns the
+ * reference driver's default 16 spp frame into a usable picture.  Two kernels of their own (rt_guided_pack_kernel,
+ * rt_guided_filter_kernel, csrc/rt_guided.hip); frames, views, queries, feature passes and their counters are not affected.
+ *
+ * THE FILTER.  Only + - * / , comparisons and selects in f32, every operation rounded on its own (no fused multiply-add, no exp,
+ * sqrt or reciprocal), a fixed tap order: a float32 restatement on the CPU is equal bit for bit (tests/_guided.py).
+ *   Inputs (all finite): color f32[h][w][3] the linear mean radiance; coverage f32[h][w]; albedo, normal, position f32[h][w][3];
+ *     normal is the encoded n * 0.5 + 0.5 mean exactly as rt_resolve_features writes it.
+ *   Parameters: iterations 1 .. 8; every sigma > 0 and not NaN, +inf switches that term off; demodulate 0 or 1.  The host
+ *     computes k_c = 1.0f / (sigma_color * sigma_color), k_n and k_p likewise, in f32.
+ *   Per pixel p, once:
+ *     N_p = normal_p * 2.0f - coverage_p per component: the mean of the unit normals over the samples that hit, 0 for sky
+ *     m_p = albedo_p + ((1.0f - coverage_p) + 1e-3f) per channel when demodulate is set, otherwise 1
+ *     c_p = color_p / m_p
+ *   Iteration i = 0 .. iterations - 1, step s = 1 << i, kc_i = k_c * (float)(1u << (2 * i)) (the colour sigma halves every time):
+ *     L = c.r * 0.2126f + c.g * 0.7152f + c.b * 0.0722f, evaluated left to right
+ *     taps t = 0 .. 24 in this order: dy = t / 5 - 2 (outer), dx = t % 5 - 2 (inner), q = (x + s dx, y + s dy); a tap outside the
+ *     image is skipped, not clamped
+ *       dn = N_p - N_q;  dn2 = dn.x * dn.x + dn.y * dn.y + dn.z * dn.z
+ *       dcov = cov_p - cov_q
+ *       e = P_q - P_p;  pl = N_p.x * e.x + N_p.y * e.y + N_p.z * e.z      (the distance of q from p's tangent plane)
+ *       dl = L_p - L_q
+ *       D = dn2 * k_n + dcov * dcov * k_n + pl * pl * k_p + dl * dl * kc_i, evaluated left to right
+ *       r = 1.0f / (1.0f + D)
+ *       wgt = ((H[|dy|] * H[|dx|]) * r) * r,  H = {0.375f, 0.25f, 0.0625f}
+ *       sum_c = sum_c + wgt * c_q per channel;  sum_w = sum_w + wgt
+ *     c'_p = sum_c / sum_w (the centre tap has wgt = 0.140625, so sum_w > 0)
+ *     a pixel with coverage_p == 0 keeps c_p: sky is not noisy, and the features say nothing about it
+ *   Output: out_p = c_p * m_p; where coverage_p == 0, out_p = color_p bit for bit.  The u8 image is rt_encode_u8(out) per channel
+ *     (rt_math.h), under the library's numeric contract like rt_resolve's.
+ * Not done: variance-guided weights (SVGF), temporal reuse, several devices, view batches. */
+typedef struct {
+  i32 iterations;
+  f32 sigma_color, sigma_normal, sigma_position;
+  i32 demodulate;
+} RT_Guided_Params;                                                                              /* 20 bytes */
+
+/* Device level, like rt_render_accumulate_features(): every pointer is a DEVICE pointer owned by the caller, the call only
+ * enqueues work on `stream` (a pack launch, then one filter launch per iteration).
+ *   d_out   : f32[h][w][3] or NULL        d_image : u8[h][w][3] or NULL        (at least one of them)
+ *   d_work  : rt_guided_work_bytes(width, height) bytes of scratch, 16-byte aligned: 64 B per pixel -- two ping-pong colour
+ *             buffers of float4 (r, g, b, L) and the guide planes float4 (N, cov) and (P, 0)
+ * d_out == d_color is allowed: every input is packed into d_work before anything is written (the last launch reads a pixel's own
+ * colour and albedo once more, to write that pixel).  d_albedo may be NULL only when demodulate == 0.
+ * Host level: rt_guided_denoise_host() from host memory to host memory through library-owned staging (kept between calls); it
+ * takes the library's device lock and runs on the NULL stream like rt_render_features().  planes: all four (albedo may be NULL
+ * when demodulate == 0); out f32[h][w][3] and / or image u8[h][w][3].
+ * Checked before the GPU is touched, by all of them: NULL pointers, width, height > 0, width x height <= 2^28, iterations in
+ * 1 .. 8, sigmas > 0 and not NaN, demodulate 0 or 1, at least one output.  0 on success, -1 + rt_last_error() (rt_guided_work_bytes:
+ * the size, -1 + rt_last_error()); a refused call leaves its outputs untouched. */
+extern i64 rt_guided_work_bytes(i32 width, i32 height);
+extern int rt_guided_denoise(i32 width, i32 height, RT_Guided_Params const *params, void const *d_color, void const *d_coverage,
+                             void const *d_albedo, void const *d_normal, void const *d_position, void *d_out, void *d_image,
+                             void *d_work, void *stream);
+extern int rt_guided_denoise_host(i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
+                                  RT_Features const *planes, f32 *out, u8 *image);
+/* A denoised frame in one call: rt_render_frame()'s frame sequence, the feature pass of the same frame shape and the filter, in
+ * ONE scene-checked call (the scene check and the device lock are rt_render_frame()'s; seed and camera are read as it reads
+ * them).  The Image receives the encoded DENOISED frame with rt_render_frame()'s layout rules (stride >= width, >= 3 components;
+ * pixels.data may be NULL when linear_denoised is given); linear_noisy (optional) = what rt_render_frame() returns as `linear`,
+ * linear_denoised (optional) = the filter's f32 output, f32[h][w][3] each.  rt_get_counters() afterwards describes the frame;
+ * rt_get_frame_timing()'s gpu_copy_ms then also covers the feature pass and the filter.  One device only: with
+ * rt_device_count() > 1 the call fails. */
+extern int rt_render_denoised(Scene const *scene, Image const *image, isize samples, isize max_bounces,
+                              RT_Guided_Params const *params, f32 *linear_noisy, f32 *linear_denoised);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

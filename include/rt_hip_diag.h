@@ -40,6 +40,10 @@ extern int rt_get_wave_times(u64 *out, i32 max_waves);
 /* Device bytes the library's host side holds right now, on all devices: scene copies, launch states, workspaces, staging.  Exact
  * (counted at every allocation and release of the library's own), so a test can assert that a sequence leaks nothing. */
 extern i64 rt_diag_device_bytes_live(void);
+/* Gives back the staging the host-level calls keep on the primary device -- query, feature and guided-denoiser buffers -- the way
+ * a device slot's teardown does (rt_set_devices remaps slots >= 1 only): waits for the device, then releases.  The next call
+ * that needs staging allocates it again.  Not while a frame is in flight.  0 on success. */
+extern int rt_diag_release_staging(void);
 
 /* ---- unit-level device entry points (parity tests call the same device
  * functions the render kernel uses) ------------------------------------------ */

@@ -11,3 +11,4 @@ from .loaders import load_model, default_camera, camera_from_trs   # noqa: F401
 from .render import render_frame, render_views, render_context, frame_begin, frame_end, Counters   # noqa: F401
 from .query import closest_hits, occluded, closest_hits_device, occluded_device, get_query_counters, QueryCounters   # noqa: F401
 from .features import render_features   # noqa: F401
+from .guided import guided_denoise, render_denoised   # noqa: F401

@@ -176,6 +176,18 @@ extern "C" int rt_get_wave_times(u64 *out, i32 max_waves) {
 // Device bytes the library's owners hold right now (rt_mem.h): what a test compares before and after to see a leak exactly.
 extern "C" int64_t rt_diag_device_bytes_live(void) { return g_device_bytes_live.load(); }
 
+// The staging part of a slot's teardown (remap_device_slots, rt_partition.cpp) on slot 0, which is never torn down.
+extern "C" int rt_diag_release_staging(void) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  HIP_TRY(hipDeviceSynchronize());
+  release_query_state(D);
+  release_feature_state(D);
+  release_guided_state(D);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------
 // unit-level device entry points (include/rt_hip_diag.h; diagnostic library only)
 

@@ -21,7 +21,7 @@ static int check_feature_params(const char *who, RT_Render_Params const *p) {
 }
 
 // Enqueues one launch of the feature kernel on `stream`.  D.mutex held, D's GPU current, every pointer on D.
-static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream) {
+int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream) {
   RT_KParams K;
   scene_only_kparams(&K, d);
   camera_frame_kparams(&K, cam, p);
@@ -65,8 +65,8 @@ static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT
   return 0;
 }
 
-static int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal,
-                           void *d_position, hipStream_t stream) {
+int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal,
+                    void *d_position, hipStream_t stream) {
   int rc = rt_launch_features_resolve(p->width * p->height, p->samples, (const unsigned long long *)d_sums, (float *)d_coverage,
                                       (float *)d_albedo, (float *)d_normal, (float *)d_position, stream);
   if (rc != 0) return rt_fail("feature resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));

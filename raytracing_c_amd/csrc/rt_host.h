@@ -9,7 +9,8 @@
 //                     buffers, counters, kernel timing
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
-//   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser
+//   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser; guided denoiser: the a-trous filter over the feature buffers (device
+//                     level, host level, behind a frame)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -74,6 +75,12 @@ int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, cons
 int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo, float *normal,
                                float *position, hipStream_t stream);
+// ... in rt_guided.hip
+int rt_launch_guided_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
+                          const float *normal, const float *position, void *c0, void *g0, void *g1, hipStream_t stream);
+int rt_launch_guided_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate, const void *src,
+                            void *dst, const void *g0, const void *g1, const float *color, const float *albedo, float *out,
+                            uint8_t *image, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -222,6 +229,15 @@ struct FeatureState {
   DevMem<float>              planes;          // coverage [pixels], then albedo, normal, position [pixels][3] each
 };
 
+// Guided denoiser (rt_extras.cpp): the device staging of the host-level calls, kept between calls, given back with the device slot
+// (release_guided_state).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes: it uses work and out.
+struct GuidedState {
+  DevMem<float>   in;                         // rt_guided_denoise_host: color [pixels][3], coverage [pixels], albedo, normal, position [pixels][3]
+  DevMem<float>   out;                        // [pixels][3]
+  DevMem<uint8_t> image;                      // [pixels][3]
+  DevMem<uint8_t> work;                       // rt_guided_work_bytes()
+};
+
 #pragma GCC visibility pop
 
 struct Device {
@@ -240,6 +256,7 @@ struct Device {
   FrameLane  lanes[RT_FRAME_LANES];           // slot 0 only
   QueryState query;
   FeatureState features;
+  GuidedState guided;
 };
 
 // Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
@@ -412,6 +429,14 @@ int  acquire_slot(Device &D, int *slot, bool query = true);
 
 // rt_features.cpp
 void release_feature_state(Device &D);                                              // D.mutex held, D's GPU current, device idle
+// One launch of the feature kernel / of its resolve on `stream` (what rt_render_features runs; rt_render_denoised runs them behind
+// a frame).  D.mutex held, D's GPU current, every pointer on D.
+int  enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream);
+int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal, void *d_position,
+                     hipStream_t stream);
+
+// rt_extras.cpp
+void release_guided_state(Device &D);                                               // D.mutex held, D's GPU current, device idle
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

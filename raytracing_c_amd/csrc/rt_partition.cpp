@@ -103,6 +103,7 @@ void remap_device_slots() {
       D.last_counters = nullptr;
       release_query_state(D);
       release_feature_state(D);
+      release_guided_state(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);

@@ -157,6 +157,14 @@ class RT_Features(C.Structure):  # rt_hip.h: the planes rt_render_features fills
 RT_FEATURE_CHANNELS = 10          # coverage, albedo rgb, normal xyz, position xyz
 
 
+class RT_Guided_Params(C.Structure):  # rt_hip.h: the guided denoiser's parameters
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", f32), ("sigma_normal", f32), ("sigma_position", f32),
+                ("demodulate", C.c_int32)]
+
+
+assert C.sizeof(RT_Guided_Params) == 20
+
+
 # numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
 _HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
@@ -198,6 +206,7 @@ EXPORTED_SYMBOLS = [
     "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_render_views", "rt_render_accumulate_views",
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
+    "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 
@@ -205,7 +214,7 @@ EXPORTED_SYMBOLS = [
 # NOT carry them (tests/test_abi.py)
 DIAG_ONLY_SYMBOLS = [
     "rt_diag_set_tokens", "rt_diag_multi_fault", "rt_set_pipeline", "rt_get_pipeline", "rt_set_wavefront_capacity", "rt_get_wave_times", "rt_get_ledger",
-    "rt_diag_device_bytes_live",
+    "rt_diag_device_bytes_live", "rt_diag_release_staging",
     "rt_test_math", "rt_test_rcp_sweep", "rt_test_srgb_sweep", "rt_test_quantize_sweep", "rt_test_trace", "rt_test_trace_stream",
     "rt_test_tile_order", "rt_test_texture",
 ]

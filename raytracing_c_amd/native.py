@@ -140,6 +140,12 @@ def _declare(d):
         d.rt_render_accumulate_features.argtypes = [vp, P(abi.RT_Render_Params), vp, vp]
         d.rt_resolve_features.argtypes = [P(abi.RT_Render_Params), vp, vp, vp, vp, vp, vp]
         d.rt_render_features.argtypes = [P(abi.Scene), C.c_int32, C.c_int32, abi.isize, abi.isize, P(abi.RT_Features), vp]
+    if hasattr(d, "rt_guided_denoise"):
+        d.rt_guided_work_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_guided_work_bytes.restype = C.c_int64
+        d.rt_guided_denoise.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params)] + [vp] * 9
+        d.rt_guided_denoise_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params), vp, P(abi.RT_Features), vp, vp]
+        d.rt_render_denoised.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, P(abi.RT_Guided_Params), vp, vp]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
@@ -188,6 +194,7 @@ def _declare_diag(d):
     d.rt_get_ledger.argtypes = [vp, C.c_int32]
     d.rt_diag_device_bytes_live.argtypes = []
     d.rt_diag_device_bytes_live.restype = C.c_int64
+    d.rt_diag_release_staging.argtypes = []
     d.rt_diag_multi_fault.argtypes = [C.c_int32, C.c_int32]
     d.rt_diag_multi_fault.restype = None
     d.rt_diag_set_tokens.argtypes = [vp, vp, vp]

@@ -1,0 +1,83 @@
+"""What the guided denoiser must return: the contract of include/rt_hip.h ("THE FILTER") restated in numpy float32, one rounded
+operation per numpy call, the 25 taps in the contract's order as shifted arrays with validity masks.  TEST INFRASTRUCTURE ONLY;
+written from the contract's text, not from the kernel's.
+"""
+import math
+
+import numpy as np
+
+F = np.float32
+H = (F(0.375), F(0.25), F(0.0625))
+
+
+def _shifted(a, ox, oy):
+    """(a[y + oy, x + ox] where that is inside the image, else 0; the inside mask (h, w)) -- None when no pixel has the tap."""
+    h, w = a.shape[:2]
+    y0, y1, x0, x1 = max(0, -oy), min(h, h - oy), max(0, -ox), min(w, w - ox)
+    if y0 >= y1 or x0 >= x1:
+        return None
+    q = np.zeros_like(a)
+    q[y0:y1, x0:x1] = a[y0 + oy:y1 + oy, x0 + ox:x1 + ox]
+    return q
+
+
+def luminance(c):
+    return c[..., 0] * F(0.2126) + c[..., 1] * F(0.7152) + c[..., 2] * F(0.0722)
+
+
+def guided(color, coverage, albedo, normal, position, iterations=4, sigma_color=1.0, sigma_normal=0.2, sigma_position=1.0,
+           demodulate=True):
+    """out f32 (h, w, 3)."""
+    color, cov, normal, P = [np.ascontiguousarray(a, F) for a in (color, coverage, normal, position)]
+    h, w = cov.shape
+    with np.errstate(all="ignore"):
+        k_c, k_n, k_p = [F(1.0) / (F(s) * F(s)) for s in (sigma_color, sigma_normal, sigma_position)]
+        N = normal * F(2.0) - cov[..., None]
+        m = np.ascontiguousarray(albedo, F) + ((F(1.0) - cov) + F(1e-3))[..., None] if demodulate else np.ones_like(color)
+        c = color / m
+        inside = np.ones((h, w), bool)
+        for i in range(iterations):
+            s = 1 << i
+            kc = k_c * F(1 << (2 * i))
+            L = luminance(c)
+            sum_c, sum_w = np.zeros((h, w, 3), F), np.zeros((h, w), F)
+            for t in range(25):
+                dy, dx = t // 5 - 2, t % 5 - 2
+                valid = _shifted(inside, s * dx, s * dy)
+                if valid is None:
+                    continue
+                Nq, covq, Pq, Lq, cq = [_shifted(a, s * dx, s * dy) for a in (N, cov, P, L, c)]
+                dn = N - Nq
+                dn2 = dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1] + dn[..., 2] * dn[..., 2]
+                dcov = cov - covq
+                e = Pq - P
+                pl = N[..., 0] * e[..., 0] + N[..., 1] * e[..., 1] + N[..., 2] * e[..., 2]
+                dl = L - Lq
+                D = dn2 * k_n + dcov * dcov * k_n + pl * pl * k_p + dl * dl * kc
+                r = F(1.0) / (F(1.0) + D)
+                wgt = ((H[abs(dy)] * H[abs(dx)]) * r) * r
+                sum_c = np.where(valid[..., None], sum_c + wgt[..., None] * cq, sum_c)
+                sum_w = np.where(valid, sum_w + wgt, sum_w)
+            c = np.where((cov == 0)[..., None], c, sum_c / sum_w[..., None])
+        out = np.where((cov == 0)[..., None], color, c * m)
+    assert out.dtype == F
+    return out
+
+
+def encode_u8(x):
+    """rt_encode_u8 per element (rt_math.h): clamp, the oracle's rt_linear_to_srgb, x 255.999, truncate."""
+    from tests import _oracle
+    x = np.ascontiguousarray(x, F)
+    c = np.where(x < 0, F(0.0), np.where(x > 1, F(1.0), x)).astype(F)
+    return (_oracle.math(8, c) * F(255.999)).astype(np.uint8)
+
+
+def sigma_position(position, coverage):
+    """The default: 0.02 x the diagonal of the bounding box of position over coverage == 1, 1.0 when there is no such pixel."""
+    full = np.asarray(coverage) == 1.0
+    if not full.any():
+        return 1.0
+    pts = np.asarray(position, np.float64)[full]
+    d = pts.max(axis=0) - pts.min(axis=0)
+    diag = math.sqrt(float(d[0]) * float(d[0]) + float(d[1]) * float(d[1]) + float(d[2]) * float(d[2]))
+    return 0.02 * diag if diag > 0.0 else 1.0
