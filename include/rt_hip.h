@@ -394,6 +394,10 @@ extern int rt_get_counters(RT_Counters *out);
  * ONE root visit of every camera path whose 8x8 tile's pixel pyramid misses every child box of the root (raytracer.c:459-472
  * finds no candidate for any of them; the kernel proves that per tile and skips the block).  The oracle counts them too. */
 extern int rt_get_skipped_root_visits(u64 *out);
+/* Camera paths of the last rt_render_accumulate launch (single device) that the path kernel's leafless loop served: paths of 8x8
+ * tiles whose pixel pyramid, pruned through the tree from the root, reaches no leaf group.  Their node visits ARE executed (and
+ * are not among the skipped root visits); what they skip is the traversal state machine.  For tests and profile notes. */
+extern int rt_get_leafless_paths(u64 *out);
 
 /* Where the time of the last frame behind render_thread_proc / render / rt_render_frame went, in milliseconds.
  * Host clock: stamp = the per-frame scene check, upload = the scene upload when one was needed, enqueue = launching the

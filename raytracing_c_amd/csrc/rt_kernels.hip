@@ -42,7 +42,8 @@
 //    reaches an exit (bounded scans), there is no inter-wave dependency and no grid barrier.
 //  * Camera rays of a tile whose pixel pyramid misses every child box of the root skip the root block (below); node blocks
 //    whose lanes are (mostly) camera rays about to enter ONE node test only the child boxes that pyramid can touch
-//    (pyramid_cull_mask, node_enter_few; the mask of a (tile, node) is cached in LDS).
+//    (pyramid_cull_mask, node_enter_few; the mask of a (tile, node) is cached in LDS).  Tiles whose pyramid, pruned through the
+//    tree from the root, reaches no leaf group never enter the traversal: a batch loop counts their rays' node visits.
 //  * Hits are parked -- path state to memory, lane to a new path -- while a shade block would run sparse, and shaded
 //    together when 48 lanes can be filled (`park`, S block).
 //  * The traversal blocks run in an inner loop of their own; shading / environment / regeneration run in the outer
@@ -285,6 +286,42 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       }
       tile_root_miss = __ballot(may_hit) == 0ull;
     }
+    // ---- does the pyramid, pruned through the tree, reach a leaf group at all? ----
+    // Breadth-first from the root with the node blocks' own plane test (pyramid_cull_mask on the LDS nodes): the surviving
+    // children of a listed node join the list; a surviving child that is a leaf group ends the walk.  A tile whose walk ends
+    // without one is LEAFLESS: every child box that a NaN-free camera ray of the tile can enter is a listed node, none of them
+    // leads to a triangle, so the ray's outcome is known -- no hit -- and only its node visits remain to be counted (the
+    // leafless form of the batch loop below).  Caps: RT_LEAFLESS_MAX listed nodes, 4 survivors per node (node_enter_few's
+    // limit), every listed node LDS resident; a tile over a cap is an ordinary tile.  The list lives in row 0 of the wave's perm
+    // stack, which is free while no lane of the wave traverses: entry i >= 1 at [i] = byte offset of (parent node, child slot) in
+    // the LDS node image | index of the parent in the list << 20 | 1 << 31 (marks an entry), the node itself at [RT_LEAFLESS_MAX + i].
+#define RT_LEAFLESS_MAX 8
+    int n_list = 0;                       // listed nodes of a leafless tile (the root counts); 0: not leafless
+    // (the launch constants through empty asm: tests and offsets formed from them here are not hoisted out of the tile loop into
+    //  scalar registers that live, and spill, for the whole kernel)
+    int ll_levels = leaf_level, ll_nodes = pyr_nodes, ll_leaf0 = P.last_row_offset;
+    asm volatile("" : "+s"(ll_levels), "+s"(ll_nodes), "+s"(ll_leaf0));
+    if (ll_levels >= 1 && ll_nodes > 0 && !tile_root_miss) {
+      const float *pyr = lds_at(smem, pyr_off);
+      uint32_t *list = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off) - ll_levels * (RT_LDS_PERM_LEVEL_BYTES / 4));      // row 0 of `perm`
+      n_list = 1;
+      for (int head = 0; head < n_list; head++) {
+        const int nd = head ? __builtin_amdgcn_readfirstlane((int)list[RT_LEAFLESS_MAX + head]) : 0;
+        const uint32_t surv = 0xFFu & ~pyramid_cull_mask(lds_nodes, pyr, nd);
+        if (surv) {
+          const int ns = (int)__popc(surv);
+          // children that are leaf groups, or nodes outside the LDS image (its last node's children at the most), or a cap
+          if (8 * nd + 1 >= ll_leaf0 || 8 * nd + 8 >= ll_nodes || ns > 4 || n_list + ns > RT_LEAFLESS_MAX) { n_list = 0; break; }
+          const int k = lane_now();             // lane k < 8: child k
+          if (k < 8 && ((surv >> k) & 1u)) {
+            const int at = n_list + (int)__popc(surv & ((1u << k) - 1u));
+            list[at] = (uint32_t)(nd * RT_LDS_NODE_BYTES + k * 4) | ((uint32_t)head << 20) | 0x80000000u;
+            list[RT_LEAFLESS_MAX + at] = (uint32_t)(8 * nd + 1 + k);
+          }
+          n_list += ns;
+        }
+      }
+    }
     const uint32_t rays_before = w_rays;
     LG(LG_TILE_X, 1);
     LGM("tile_end");
@@ -319,7 +356,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     // batches of up to 64 paths: primary ray, environment lookup, sample into the LDS tile; same arithmetic, same counters as
     // the general loop, which takes over at once -- from the same unit, nothing consumed -- should a ray turn up that is not
     // NaN-free (such a ray does not take the shortcut: its root visit must be computed, see tile_root_miss).
-    if (tile_root_miss && cold_args()->max_bounces > 0) {
+    //
+    // LEAFLESS tiles (n_list > 0, see the tile set-up: 19 % of the camera paths of config #3, 100 M) take the same loop.  Their rays
+    // do enter nodes, but no leaf group: per batch, a wave-uniform pass over the listed nodes gives every lane the set of listed
+    // nodes its ray enters -- node i when the ray entered i's parent and the slab test of i's box, the arithmetic of node_enter_few
+    // with t_max = infinity (no hit is ever recorded, so every candidate child is visited whatever the near-first order), finds a
+    // candidate -- and the number of those nodes is the ray's node visits.  These visits are executed, not skipped.
+    if ((tile_root_miss || n_list > 0) && cold_args()->max_bounces > 0) {
       RT_KArgs A = cold_args();
       typename CamSrc<VIEWS>::type S;
       if constexpr (VIEWS) S = vrec; else S = A;
@@ -336,6 +379,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       SP.bg_texture = A->bg_texture; SP.max_bounces = A->max_bounces;
       uint32_t *tile_next = A->tile_next, *open_groups = A->open_groups;
       uint32_t n_sky = 0;                 // paths served here: their root visit is COUNTED (like the oracle's) but not executed
+      // lane i: entry i of the tile's node list, 0 past its end (the pass below stops there: no count in a scalar register)
+      const uint32_t *list = reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off)) - ll_levels * (RT_LDS_PERM_LEVEL_BYTES / 4);
+      const uint32_t list_entry = (n_list > 1 && lane_now() < n_list) ? list[lane_now() & (RT_LEAFLESS_MAX - 1)] : 0u;
       for (;;) {
         if (c_next >= c_end) {
           if (u_cur + 1u < u_end) {
@@ -380,6 +426,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         bool valid[RT_SKY_PATHS];
         int  pxs[RT_SKY_PATHS];
         rt_v3 dirs[RT_SKY_PATHS];
+        Ray3 rs[RT_SKY_PATHS];
         bool slow = false;
 #pragma unroll
         for (int q = 0; q < RT_SKY_PATHS; q++) {
@@ -391,13 +438,35 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           valid[q] = kq < take && x < width && sm < sample_end;
           rt_v3 o = rt_v3_make(0, 0, 0);
           dirs[q] = rt_v3_make(0, 0, 1);
-          Ray3 r;
           if (valid[q]) primary_ray(PP, x, c_y, sm, o, dirs[q]);
-          ray_setup<SHORT_DIV>(r, o, dirs[q]);
-          slow = slow || (valid[q] && !r.fast);
+          ray_setup<SHORT_DIV>(rs[q], o, dirs[q]);
+          slow = slow || (valid[q] && !rs[q].fast);
         }
         if (__ballot(slow) != 0ull) break;          // the general loop redoes this batch, and the rest of the tile
         uint32_t nv = 0;
+        // (leafless tiles; every lane runs every test -- nothing to save under a lane mask, and no mask to keep in scalar registers;
+        //  a sky tile pays one readlane and a branch per batch)
+        uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)list_entry, 1);
+        if ((int)e < 0) {
+#pragma unroll
+          for (int q = 0; q < RT_SKY_PATHS; q++) {
+            const Ray3 &r = rs[q];
+            const int nx = (as_i(r.inv_x) >> 31) & 96, ny = (as_i(r.inv_y) >> 31) & 96, nz = (as_i(r.inv_z) >> 31) & 96;
+            const rt_v3 bs = slab_bias3(r);
+            uint32_t entered = valid[q] ? 1u : 0u;                // bit i: the ray enters listed node i
+            int i = 1;
+            if (q > 0) e = (uint32_t)__builtin_amdgcn_readlane((int)list_entry, 1);
+            do {
+              const char *cb = reinterpret_cast<const char *>(lds_nodes) + (e & 0xFFFFFu);
+              const float t = slab_entry_ordered(r, bs, cb, 0, nx, ny, nz, RT_INF);
+              const uint32_t in = ((entered >> ((e >> 20) & 7u)) & 1u) & (t < RT_INF ? 1u : 0u);
+              entered |= in << i;
+              w_nodes += (uint32_t)__popcll(__ballot(in != 0u));    // a visit of a listed node below the root
+              i += 1;
+              e = (uint32_t)__builtin_amdgcn_readlane((int)list_entry, i);
+            } while ((int)e < 0);
+          }
+        }
 #pragma unroll
         for (int q = 0; q < RT_SKY_PATHS; q++) {
           if (valid[q]) {
@@ -418,7 +487,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         LGM("sky_end");
       }
       // counters[CNT_SKIPPED_ROOT]: node visits that are counted but not executed (bench.py's roofline footnote)
-      if (n_sky != 0u && lane == 0) atomicAdd(cold_args()->counters + CNT_SKIPPED_ROOT, (unsigned long long)n_sky);
+      // counters[RT_CNT_LEAFLESS]: paths of leafless tiles served here; their root visits are executed, not skipped
+      if (n_sky != 0u && lane == 0) atomicAdd(cold_args()->counters + (tile_root_miss ? CNT_SKIPPED_ROOT : RT_CNT_LEAFLESS), (unsigned long long)n_sky);
     }
 
     for (;;) {

@@ -448,6 +448,18 @@ extern "C" int rt_get_skipped_root_visits(u64 *out) {
   return 0;
 }
 
+// Camera paths of the last rt_render_accumulate launch that the leafless loop of the path kernel served (rt_kernels.hip).
+extern "C" int rt_get_leafless_paths(u64 *out) {
+  if (!out) return rt_fail("rt_get_leafless_paths: NULL");
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  unsigned long long c[RT_N_COUNTERS];
+  if (read_counters(D, c) != 0) return -1;
+  *out = c[RT_CNT_LEAFLESS];
+  return 0;
+}
+
 int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]) {
   HIP_TRY(hipDeviceSynchronize());
   if (!D.last_counters) { memset(c, 0, RT_N_COUNTERS * sizeof(unsigned long long)); return 0; }

@@ -207,7 +207,7 @@ EXPORTED_SYMBOLS = [
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
-    "rt_get_counters", "rt_get_skipped_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
+    "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 
 # include/rt_hip_diag.h: exported by librt_hip_diag.so only (which also exports everything above); the product library must
