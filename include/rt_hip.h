@@ -95,6 +95,22 @@ extern int rt_set_camera(RT_Device_Scene *dscene, Camera const *camera);
  * csrc/rt_build.hip).  Host memory comes from `allocator` as in scene_init.  0 on success. */
 extern int scene_init_gpu(Scene *scene, Triangle_Slice src_triangles, Allocator allocator);
 
+/* scene_refit() (rt_scene.h) by GPU kernels, on the primary device's cached copy of `scene`, which is updated IN PLACE
+ * (csrc/rt_refit.hip): same contract, same validation -- on the host, before anything is launched -- and the same bytes
+ * in the host Scene afterwards, which stays the truth for the per-frame check.  One lane per slot writes the slot's
+ * record, shading record and leaf-tile column and the wave writes the node above its eight leaf groups; the levels above
+ * follow in at most `depth` more launches.  The nodes and the triangle block are copied back into the host Scene (the
+ * textures and materials never move), the copy's edge bound is recomputed exactly and its stamps are refreshed: the next
+ * frame, query, feature pass or lightmap uploads nothing and renders the moved geometry.  Without a cached copy one is
+ * made first by the ordinary upload.  Copies on other device slots are dropped; those devices upload on their next frame.
+ * A `src` with a NaN position is refitted by scene_refit itself (the copies are dropped, 0 is returned).  So is a scene whose
+ * materials, texels or background were edited in place since the copy was made without rt_scene_touch: the refit takes the host
+ * bytes as the copy's new reference, and must not absorb an edit nobody reported -- the next frame uploads the scene as it is.
+ * Like rt_scene_touch, not to be called between rt_frame_begin and rt_frame_end of a frame on this scene: the device is
+ * synchronised before the kernels write the copy, but a frame begun on the old geometry is checked against the host
+ * Scene when it ends.  0 on success, -1 with rt_last_error() otherwise (nothing written after a failed validation). */
+extern int scene_refit_gpu(Scene *scene, Triangle_Slice src_triangles, i32 const *slot_of_source);
+
 /* ---- rendering -------------------------------------------------------------- */
 
 typedef struct {

@@ -169,6 +169,28 @@ extern void scene_init_sah(Scene *scene, Triangle_Slice src_triangles, Allocator
  * Allocator and scenes that alias a file buffer are left alone) and drops the device copy of the scene. */
 extern void rt_scene_free(Scene *scene);
 
+/* ---- refit: the mesh deforms, the topology stays (raytracing_c_amd/csrc/rt_scene_refit.c; the reference has none) ----
+ *
+ * slot_of_source[i] = the slot of scene->triangles that holds src.data[i].  Works on any Scene whose populated slots
+ * (Shader.proc != NULL) are exactly the triangles of `src` (scene_init, scene_init_sah, scene_init_gpu, a loaded .scene
+ * file): matched on the BYTES of positions, vertex normals, tex_coords and Shader, in expected O(n).  The map is one to
+ * one; of byte-identical triangles the k-th in source order gets the k-th matching slot in slot order.  Returns src.len,
+ * or -1 (nothing written) when some triangle of src has no slot of its own or the scene has a different number of
+ * populated slots. */
+extern isize rt_scene_slot_map(Scene const *scene, Triangle_Slice src, i32 *slot_of_source);
+
+/* Same topology, new geometry: writes src.data[i] into slot slot_of_source[i] -- the nine coordinates and the
+ * Triangle_AOS record, exactly as scene_init does -- and recomputes every child box bottom-up: the boxes of the last
+ * internal level from the populated slots of their leaf group, each level above as the union over the populated
+ * children; unpopulated children stay all-zero boxes, padding slots stay all zero.  With unmoved triangles this is the
+ * identity on a scene_init / scene_init_sah scene.  The tree keeps its shape, so its quality follows the deformation:
+ * rebuild when the boxes have grown too loose.
+ * Validates first and writes nothing on failure (-1, rt_last_error()): src.len must equal the number of populated
+ * slots, the map must be in range and one to one onto them, and src.data[i].shader must equal the slot's Shader byte
+ * for byte (a refit keeps the materials).  Drops the device copies of `scene` (rt_scene_invalidate); scene_refit_gpu
+ * (rt_hip.h) is the refit that updates the device copy in place.  0 on success. */
+extern int scene_refit(Scene *scene, Triangle_Slice src, i32 const *slot_of_source);
+
 /* The `.scene` cache file, reference scene.h:99-100 / scene.c:13-76: a 96-byte header
  * {i32 version, n_nodes, n_triangles, bvh_depth; Camera}, the BVH nodes, then the triangle allocation (nine f32
  * arrays + Triangle_AOS records), all raw.  scene_load_bytes has the reference's signature and semantics: the

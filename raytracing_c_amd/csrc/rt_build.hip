@@ -34,8 +34,7 @@
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "../../include/rt_scene.h"
-#include "../../include/rt_math.h"
+#include "rt_triangle_record.h"
 
 namespace {
 
@@ -191,47 +190,15 @@ __global__ __launch_bounds__(256) void child_box_kernel(int n, const Fin *fins, 
   }
 }
 
-// triangles_insert of rt_scene_build.c (scene.c:105-155) for the leaf rows: position `pos` of the final order goes to
-// slot `slot_of_pos[pos]` of the triangle block
+// triangles_insert of rt_scene_build.c (scene.c:105-155; rt_triangle_record.h) for the leaf rows: position `pos` of the
+// final order goes to slot `slot_of_pos[pos]` of the triangle block
 __global__ void leaf_insert_kernel(int n, const Triangle *tris, const uint32_t *idx, const int *slot_of_pos, int len, float *block) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const Triangle &t = tris[idx[p]];
   const int slot = slot_of_pos[p];
-  float *x[3], *y[3], *z[3];
-  for (int k = 0; k < 3; k++) {
-    x[k] = block + (size_t)len * (0 + k);
-    y[k] = block + (size_t)len * (3 + k);
-    z[k] = block + (size_t)len * (6 + k);
-  }
-  Triangle_AOS *aos = reinterpret_cast<Triangle_AOS *>(block + (size_t)len * 9) + slot;
-  for (int k = 0; k < 3; k++) {
-    x[k][slot] = t.positions[k].x;
-    y[k][slot] = t.positions[k].y;
-    z[k][slot] = t.positions[k].z;
-  }
-  rt_v3 p0 = rt_v3_make(t.positions[0].x, t.positions[0].y, t.positions[0].z);
-  rt_v3 p1 = rt_v3_make(t.positions[1].x, t.positions[1].y, t.positions[1].z);
-  rt_v3 p2 = rt_v3_make(t.positions[2].x, t.positions[2].y, t.positions[2].z);
-  rt_v3 edge1 = rt_v3_sub(p1, p0), edge2 = rt_v3_sub(p2, p0);
-  float du1 = t.tex_coords[1].x - t.tex_coords[0].x, dv1 = t.tex_coords[1].y - t.tex_coords[0].y;
-  float du2 = t.tex_coords[2].x - t.tex_coords[0].x, dv2 = t.tex_coords[2].y - t.tex_coords[0].y;
-  float d = du1 * dv2 - du2 * dv1;
-  if (rt_absf(d) < 0.0001f) d = (d < 0) ? -0.0001f : 0.0001f;
-  float inv_d = 1.0f / d;
-  rt_v3 tangent = rt_v3_normalize_plain(rt_v3_scale(rt_v3_sub(rt_v3_scale(edge1, dv2), rt_v3_scale(edge2, dv1)), inv_d));
-  rt_v3 bitangent = rt_v3_normalize_plain(rt_v3_scale(rt_v3_sub(rt_v3_scale(edge2, du1), rt_v3_scale(edge1, du2)), inv_d));
-  rt_v3 fn = rt_v3_normalize_plain(rt_v3_cross_plain(edge1, edge2));
-  aos->shader = t.shader;
-  aos->normal.x = fn.x; aos->normal.y = fn.y; aos->normal.z = fn.z;
-  aos->normal_a = t.normals[0];
-  aos->normal_b = t.normals[1];
-  aos->normal_c = t.normals[2];
-  aos->tex_coords_a = t.tex_coords[0];
-  aos->tex_coords_b = t.tex_coords[1];
-  aos->tex_coords_c = t.tex_coords[2];
-  aos->tangent.x = tangent.x; aos->tangent.y = tangent.y; aos->tangent.z = tangent.z;
-  aos->bitangent.x = bitangent.x; aos->bitangent.y = bitangent.y; aos->bitangent.z = bitangent.z;
+  rt_triangle_coordinates(&t, block, len, slot);
+  rt_triangle_record(&t, reinterpret_cast<Triangle_AOS *>(block + (size_t)len * 9) + slot);
 }
 
 struct DevBuf {

@@ -87,6 +87,96 @@ extern "C" int scene_init_gpu(Scene *scene, Triangle_Slice src, Allocator alloca
 }
 
 // ---------------------------------------------------------------------------------
+// scene_refit on the GPU (csrc/rt_refit.hip): same bytes as scene_refit() in the host Scene, and the primary device's copy of
+// the scene updated in place -- nothing is uploaded by the next frame
+
+void release_refit_state(Device &D) { D.refit = RefitState(); }
+
+// 0 = refitted in place, 1 = the copy may not be kept (the caller refits on the host, which drops it), -1 = error
+static int refit_gpu_locked(Device &D, Scene *scene, Triangle_Slice src, const std::vector<i32> &source_of_slot) {
+  auto cached = D.scene_cache.find(scene);
+  RT_Device_Scene *d = cached != D.scene_cache.end() ? cached->second
+                                                     : cached_scene_locked(D, scene, nullptr, nullptr);   // (the ordinary upload, then the one path)
+  if (!d) return -1;
+  // The refit rewrites nodes and triangle block on both sides and then takes the host bytes as the copy's reference.  That is only
+  // sound while everything ELSE of the host scene -- materials, texels, background -- still is what the copy was made from: an edit
+  // nobody reported (rt_scene_touch) would otherwise be absorbed into the reference and never be seen again.  (The full blocks are
+  // compared, not the sampled stamp of a frame: an existing copy is either kept as it is or dropped, never uploaded again in here.)
+  std::vector<FpBlock> now;
+  if (!refit_may_keep_copy(d, scene, now)) return 1;
+  const Triangles &T = scene->triangles;
+  const int len = (int)T.len, depth = (int)scene->bvh.depth, n_internal = (int)scene->bvh.nodes.len;
+  if (d->n_triangles != len || d->depth != depth || d->n_nodes != n_internal) return rt_fail("scene_refit_gpu: the device copy has another shape");
+  const size_t block_bytes = (size_t)TRIANGLES_ALLOCATION_SIZE(len), src_bytes = (size_t)src.len * sizeof(Triangle);
+  RefitState &R = D.refit;
+  HIP_TRY(R.src.grow(src_bytes));
+  HIP_TRY(R.source_of_slot.grow((size_t)len));
+  HIP_TRY(R.block.grow(block_bytes / 4));
+  HIP_TRY(R.populated.grow((size_t)n_internal + (size_t)len / 8));
+  HIP_TRY(R.max_edge_bits.grow(1));
+  HIP_TRY(hipDeviceSynchronize());                          // whatever still reads the copy finishes before the kernels write it
+  HIP_TRY(hipMemcpy(R.src, src.data, src_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(R.source_of_slot, source_of_slot.data(), (size_t)len * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(R.max_edge_bits, 0, 4));
+  int rc = rt_launch_refit(len, depth, n_internal, R.src, R.source_of_slot, R.block, d->nodes, d->leaves, d->tris, R.populated,
+                           R.max_edge_bits, nullptr);
+  // one copy of the nodes and one of the staging block: the host Scene stays the truth for the oracle and the per-frame check
+  uint32_t edge_bits = 0;
+  if (rc == 0 && n_internal > 0) rc = (int)hipMemcpy(scene->bvh.nodes.data, d->nodes, (size_t)n_internal * sizeof(BVH_Node), hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(T.x[0], R.block, block_bytes, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(&edge_bits, R.max_edge_bits, 4, hipMemcpyDeviceToHost);
+  if (rc != 0) {
+    // the copy (and perhaps part of the host Scene) is half refitted: drop the copy, the caller rebuilds or refits again
+    rt_fail("scene_refit_gpu failed: %s", hipGetErrorString((hipError_t)rc));
+    free_device_scene(d);
+    D.scene_cache.erase(scene);
+    return -1;
+  }
+  memcpy(&d->max_edge, &edge_bits, 4);                      // exact, not "can only grow"
+  d->boxes_ordered = n_internal == 0 || node_boxes_ordered((const float *)scene->bvh.nodes.data, (size_t)n_internal);
+  rehash_geometry_blocks(scene, now);
+  adopt_scene_stamps(d, scene, now);
+  return 0;
+}
+
+extern "C" int scene_refit_gpu(Scene *scene, Triangle_Slice src, i32 const *slot_of_source) {
+  if (!scene) return rt_fail("scene_refit_gpu: scene is NULL");
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  std::vector<i32> source_of_slot((size_t)(scene->triangles.len > 0 ? scene->triangles.len : 0));
+  if (rt_refit_check(scene, src, slot_of_source, source_of_slot.data()) != 0) return -1;
+  // scene_init_gpu's rule: the kernels reduce bounds in another order than the host, which gives the same boxes for numbers
+  // only.  A soup with a NaN position is refitted by scene_refit itself (which drops the device copies).
+  for (isize i = 0; i < src.len; i++)
+    for (int v = 0; v < 3; v++) {
+      const Vec3 &q = src.data[i].positions[v];
+      if (q.x != q.x || q.y != q.y || q.z != q.z) return scene_refit(scene, src, slot_of_source);
+    }
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    DeviceGuard guard(D);
+    rc = refit_gpu_locked(D, scene, src, source_of_slot);
+    // the other device slots hold the old geometry: they upload on their next frame (lock order: slot 0, then slot r)
+    for (int i = 1; i < RT_MAX_DEVICES; i++) {
+      Device &O = g_devs[i];
+      std::lock_guard<std::mutex> other(O.mutex);
+      auto it = O.scene_cache.find(scene);
+      if (it == O.scene_cache.end()) continue;
+      DeviceGuard og(O);
+      (void)hipDeviceSynchronize();
+      free_device_scene(it->second);
+      O.scene_cache.erase(it);
+    }
+  }
+  // an unreported edit outside the geometry: scene_refit drops every copy, and the next frame uploads the scene as it is
+  return rc == 1 ? scene_refit(scene, src, slot_of_source) : rc;
+}
+
+// ---------------------------------------------------------------------------------
 // denoiser (reference denoiser.h / denoiser.c:131-153), SURVEY.md section 8f #3
 
 extern "C" int rt_denoise(i32 width, i32 height, void const *d_src, void *d_dst, void *stream) {

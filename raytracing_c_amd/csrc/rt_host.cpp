@@ -18,6 +18,8 @@ int rt_fail(const char *fmt, ...) {
   return -1;
 }
 
+// rt_fail for the host units written in C (rt_scene_refit.c reaches it through a weak reference)
+extern "C" __attribute__((visibility("hidden"))) void rt_error_message(char const *message) { rt_fail("%s", message); }
 extern "C" char const *rt_last_error(void) { return g_err; }
 extern "C" void rt_clear_error(void) {
   std::lock_guard<std::mutex> lock(g_err_mutex);

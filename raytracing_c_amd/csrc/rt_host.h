@@ -9,7 +9,7 @@
 //                     buffers, counters, kernel timing
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
-//   rt_extras.cpp     lightmap bake, GPU BVH build, denoiser; guided denoiser: the a-trous filter over the feature buffers (device
+//   rt_extras.cpp     lightmap bake, GPU BVH build and refit, denoiser; guided denoiser: the a-trous filter over the feature buffers (device
 //                     level, host level, behind a frame)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
@@ -75,6 +75,11 @@ int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, cons
 int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo, float *normal,
                                float *position, hipStream_t stream);
+// ... in rt_refit.hip
+int rt_launch_refit(int len, int depth, int n_internal, const void *d_src, const int *d_source_of_slot, float *d_block, float *d_nodes,
+                    float *d_leaves, float *d_tris, unsigned char *d_populated, unsigned int *d_max_edge_bits, hipStream_t stream);
+// ... in rt_scene_refit.c: scene_refit's validation alone; source_of_slot (optional, triangles.len entries) receives the inverse map
+int rt_refit_check(Scene const *scene, Triangle_Slice src, i32 const *slot_of_source, i32 *source_of_slot);
 // ... in rt_guided.hip
 int rt_launch_guided_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
                           const float *normal, const float *position, void *c0, void *g0, void *g1, hipStream_t stream);
@@ -238,6 +243,16 @@ struct GuidedState {
   DevMem<uint8_t> work;                       // rt_guided_work_bytes()
 };
 
+// scene_refit_gpu (rt_extras.cpp): the device staging of a refit, kept between calls -- a deforming mesh is refitted every frame --
+// and given back with the device slot (release_refit_state).
+struct RefitState {
+  DevMem<uint8_t>  src;                       // the source triangles, 112 B each
+  DevMem<int32_t>  source_of_slot;            // [slots]
+  DevMem<float>    block;                     // the host-layout triangle block: nine f32 arrays, then the Triangle_AOS records
+  DevMem<uint8_t>  populated;                 // [nodes + leaf groups], indexed like the implicit tree
+  DevMem<uint32_t> max_edge_bits;             // one word
+};
+
 #pragma GCC visibility pop
 
 struct Device {
@@ -257,6 +272,7 @@ struct Device {
   QueryState query;
   FeatureState features;
   GuidedState guided;
+  RefitState refit;
 };
 
 // Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
@@ -364,6 +380,15 @@ bool             scene_is_static(Scene const *scene);               // takes g_s
 int              drop_stale_copies(Scene const *scene, uint64_t now, int first_slot);   // takes each slot's mutex; returns copies dropped
 void             scene_only_kparams(RT_KParams *K, RT_Device_Scene *d);
 RT_Device_Scene *cached_scene_locked(Device &D, Scene const *scene, float *stamp_ms, float *upload_ms);   // D.mutex held
+// After the host scene and the copy `d` were changed together (rt_scene_touch, scene_refit_gpu): d's stamp and full fingerprint
+// become those of `now`, the host scene's blocks -- every one of which the caller knows the copy to match.
+void             adopt_scene_stamps(RT_Device_Scene *d, Scene const *scene, const std::vector<FpBlock> &now);
+// scene_refit_gpu's guard against an edit nobody reported: `now` = the host scene's blocks with the geometry (nodes, coordinates,
+// AoS records: what the refit rewrites on both sides) unhashed; true when the list has the shape of d's and every other block has
+// the hash d was made from.  rehash_geometry_blocks() completes `now` once the host Scene holds the refitted bytes.
+bool             refit_may_keep_copy(const RT_Device_Scene *d, Scene const *scene, std::vector<FpBlock> &now);
+void             rehash_geometry_blocks(Scene const *scene, std::vector<FpBlock> &now);
+bool             node_boxes_ordered(const float *nodes, size_t n_nodes);      // every child box has min <= max on every axis
 // What lets a host edit a Scene in place: take the cached copy (sampled stamp; uploads when it differs), run enqueue(ctx, copy) on
 // `stream`, fingerprint the whole host scene on this thread while the GPU works; when it differs from the copy, wait for the stream,
 // drop the copy and do it all once more.  Returns the copy the work finally ran from, nullptr after a failure.  T (optional):
@@ -437,6 +462,7 @@ int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_cove
 
 // rt_extras.cpp
 void release_guided_state(Device &D);                                               // D.mutex held, D's GPU current, device idle
+void release_refit_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

@@ -91,8 +91,9 @@ static int upload_textures(const TexturePool &pool, DevMem<uint32_t> &d_texels, 
 //  * What it can miss: an IN-PLACE edit of a few vertices or texels inside a large block (the helmet has 5 MB of geometry
 //    and 50 MB of texels; hashing them, even one word in 61, cost 0.5 ms per frame in round 2).  A host that does that
 //    calls rt_scene_invalidate(scene) afterwards; scene_init / scene_init_sah / scene_init_gpu /
-//    scene_load_bytes do so themselves.  scene_fingerprint() -- geometry in full, texels of large images one word in 61 --
-//    is what rt_scene_verify() compares for a host that wants the check anyway.
+//    scene_refit / scene_load_bytes do so themselves (scene_refit_gpu changes the copy along with the host scene).
+//    scene_fingerprint() -- geometry in full, texels of large images one word in 61 -- is what rt_scene_verify() compares for
+//    a host that wants the check anyway.
 static inline uint64_t mix64(uint64_t h, uint64_t v) {
   h ^= v;
   h *= 0x9E3779B97F4A7C15ull;
@@ -147,23 +148,28 @@ static void fp_image(std::vector<FpBlock> &out, Image const *img) {
   out.push_back({n ? img->pixels.data : nullptr, n, hash_image(0x51ED27u, img)});
 }
 
-static void scene_fingerprint_blocks(Scene const *scene, std::vector<FpBlock> &out) {
+static const uint64_t kFpSeed = 0x452821E638D01377ull;
+
+// hash_geometry = false (scene_refit_gpu, before its kernels run): the node array, the coordinate arrays and the AoS records get
+// their ranges but no hash (h = 0); rehash_geometry_blocks() fills them in afterwards
+static void scene_fingerprint_blocks(Scene const *scene, std::vector<FpBlock> &out, bool hash_geometry = true) {
   out.clear();
   const Triangles &T = scene->triangles;
-  const uint64_t h0 = 0x452821E638D01377ull;
+  const uint64_t h0 = kFpSeed;
+  auto geometry = [&](const void *p, size_t n) { out.push_back({p, n, hash_geometry ? hash_bytes(h0, p, n) : 0}); };
   int64_t dims[5] = {(int64_t)scene->bvh.depth, (int64_t)scene->bvh.last_row_offset, (int64_t)scene->bvh.nodes.len,
                      (int64_t)T.len, (int64_t)(uintptr_t)scene->background.proc};
   out.push_back({nullptr, 0, hash_bytes(h0, dims, sizeof dims)});
   if (scene->bvh.nodes.data && scene->bvh.nodes.len > 0) {
     const size_t n = (size_t)scene->bvh.nodes.len * sizeof(BVH_Node);
-    out.push_back({scene->bvh.nodes.data, n, hash_bytes(h0, scene->bvh.nodes.data, n)});
+    geometry(scene->bvh.nodes.data, n);
   }
   if (T.len > 0 && T.x[0] && T.aos) {
     for (int k = 0; k < 3; k++) {                // the nine coordinate arrays (one block in scene_init, but not required to be)
       const float *arrs[3] = {T.x[k], T.y[k], T.z[k]};
-      for (const float *a : arrs) out.push_back({a, (size_t)T.len * 4, hash_bytes(h0, a, (size_t)T.len * 4)});
+      for (const float *a : arrs) geometry(a, (size_t)T.len * 4);
     }
-    out.push_back({T.aos, (size_t)T.len * sizeof(Triangle_AOS), hash_bytes(h0, T.aos, (size_t)T.len * sizeof(Triangle_AOS))});
+    geometry(T.aos, (size_t)T.len * sizeof(Triangle_AOS));
     const void *last = nullptr;                  // distinct material records, in first-use order
     std::vector<const void *> seen;
     for (int i = 0; i < T.len; i++) {
@@ -321,6 +327,13 @@ static void build_material_row(const PBR_Shader_Data *d, int ta, int tn, int tm,
   }
 }
 
+bool node_boxes_ordered(const float *nodes, size_t n_nodes) {
+  for (size_t nd = 0; nd < n_nodes; nd++)
+    for (int k = 0; k < 24; k++)
+      if (!(nodes[nd * 48 + k] <= nodes[nd * 48 + 24 + k])) return false;
+  return true;
+}
+
 static RT_Device_Scene *upload_scene_locked(Device &D, Scene const *scene) {
   if (ensure_device(D) != 0) return nullptr;
   if (!scene) { rt_fail("rt_scene_upload: scene is NULL"); return nullptr; }
@@ -416,9 +429,7 @@ static RT_Device_Scene *upload_scene_locked(Device &D, Scene const *scene) {
     nodes.assign(src, src + (size_t)scene->bvh.nodes.len * 48);
     // the LDS node blocks pick the near / far plane of a slab by the sign of the ray direction: valid for min <= max
     // (what scene_init builds; a Scene from elsewhere is checked, and traverses through the min / max form otherwise)
-    for (size_t nd = 0; nd < (size_t)scene->bvh.nodes.len && boxes_ordered; nd++)
-      for (int k = 0; k < 24; k++)
-        if (!(nodes[nd * 48 + k] <= nodes[nd * 48 + 24 + k])) { boxes_ordered = false; break; }
+    boxes_ordered = node_boxes_ordered(nodes.data(), (size_t)scene->bvh.nodes.len);
   }
 
   int bg = texture_index((Image const *)scene->background.data, pool);
@@ -651,9 +662,7 @@ extern "C" int rt_scene_touch(Scene const *scene, void const *begin, size_t byte
     }
     int rc = unreported ? 0 : touch_device_scene(d, scene, begin, (size_t)bytes);
     if (rc == 1) {
-      d->stamp = scene_stamp(scene, d->mat_ptrs, d->mat_first_tri);
-      d->fp_blocks = now;
-      d->full_fp = fp_fold(now);
+      adopt_scene_stamps(d, scene, now);
     } else {
       free_device_scene(d);
       D.scene_cache.erase(it);
@@ -662,6 +671,45 @@ extern "C" int rt_scene_touch(Scene const *scene, void const *begin, size_t byte
     }
   }
   return dropped ? 1 : 0;
+}
+
+// After the host scene and the copy `d` were changed together: d's stamp and full fingerprint become those of the host bytes
+// as they are now (`now`: their blocks).  Only for blocks the caller KNOWS the copy matches: a block that changed without a word
+// must drop the copy instead, or the unreported edit is hidden from every later check.
+void adopt_scene_stamps(RT_Device_Scene *d, Scene const *scene, const std::vector<FpBlock> &now) {
+  d->stamp = scene_stamp(scene, d->mat_ptrs, d->mat_first_tri);
+  d->fp_blocks = now;
+  d->full_fp = fp_fold(now);
+}
+
+// scene_refit_gpu rewrites the node array and the triangle block on both sides and nothing else.  Is a block one of those?
+static bool is_geometry_block(Scene const *scene, const FpBlock &b) {
+  const Triangles &T = scene->triangles;
+  const uintptr_t p = (uintptr_t)b.begin, n0 = (uintptr_t)scene->bvh.nodes.data, t0 = (uintptr_t)T.x[0];
+  if (!b.begin) return false;
+  if (scene->bvh.nodes.len > 0 && p >= n0 && p < n0 + (size_t)scene->bvh.nodes.len * sizeof(BVH_Node)) return true;
+  return T.len > 0 && p >= t0 && p < t0 + (size_t)TRIANGLES_ALLOCATION_SIZE(T.len);
+}
+
+// Before the refit kernels run: `now` = the host scene's blocks, geometry unhashed.  true when the list has the shape of the
+// one `d` was made from and every block OUTSIDE the geometry -- dimensions, material records, texels, background -- still has the
+// hash it had then.  An unreported edit of the geometry itself is about to be overwritten on both sides, which is harmless.
+bool refit_may_keep_copy(const RT_Device_Scene *d, Scene const *scene, std::vector<FpBlock> &now) {
+  scene_fingerprint_blocks(scene, now, false);
+  if (now.size() != d->fp_blocks.size()) return false;
+  for (size_t k = 0; k < now.size(); k++) {
+    const FpBlock &a = now[k], &b = d->fp_blocks[k];
+    if (a.begin != b.begin || a.bytes != b.bytes) return false;
+    if (!is_geometry_block(scene, a) && a.h != b.h) return false;
+  }
+  return true;
+}
+
+// ... and after them, once the host Scene holds the refitted bytes: the geometry blocks are hashed, the rest keeps the hashes
+// that were just compared
+void rehash_geometry_blocks(Scene const *scene, std::vector<FpBlock> &now) {
+  for (FpBlock &b : now)
+    if (is_geometry_block(scene, b)) b.h = hash_bytes(kFpSeed, b.begin, b.bytes);
 }
 
 // Full content check of the cached device copies of `scene`: 1 = the host scene still equals what every copy was made from

@@ -10,8 +10,7 @@
  * thread each (the reference's 12 builder threads likewise write disjoint node
  * slots, so the result does not depend on threading).
  */
-#include "../../include/rt_scene.h"
-#include "../../include/rt_math.h"
+#include "rt_triangle_record.h"
 
 #include <pthread.h>
 #include <stdlib.h>
@@ -78,44 +77,12 @@ static bool triangles_init(Triangles *triangles, isize len, Allocator allocator)
   return true;
 }
 
-static rt_v3 P(Vec3 v) { return rt_v3_make(v.x, v.y, v.z); }
-static Vec3 Q(rt_v3 v) { Vec3 r; r.x = v.x; r.y = v.y; r.z = v.z; return r; }
-
 /* scene.c:105-155: copy positions to the SoA arrays and precompute the face
- * normal and the UV-aligned tangent frame of every triangle */
+ * normal and the UV-aligned tangent frame of every triangle (rt_triangle_record.h) */
 static void triangles_insert(Triangles *triangles, Triangle const *v, isize count, isize offset) {
   for (isize i = 0; i < count; i++) {
-    Triangle const *t = &v[i];
-    for (int k = 0; k < 3; k++) {
-      triangles->x[k][offset + i] = t->positions[k].x;
-      triangles->y[k][offset + i] = t->positions[k].y;
-      triangles->z[k][offset + i] = t->positions[k].z;
-    }
-
-    rt_v3 edge1 = rt_v3_sub(P(t->positions[1]), P(t->positions[0]));
-    rt_v3 edge2 = rt_v3_sub(P(t->positions[2]), P(t->positions[0]));
-
-    f32 du1 = t->tex_coords[1].x - t->tex_coords[0].x, dv1 = t->tex_coords[1].y - t->tex_coords[0].y;
-    f32 du2 = t->tex_coords[2].x - t->tex_coords[0].x, dv2 = t->tex_coords[2].y - t->tex_coords[0].y;
-
-    f32 d = du1 * dv2 - du2 * dv1;
-    if (rt_absf(d) < 0.0001f) d = (d < 0) ? -0.0001f : 0.0001f;
-    f32 inv_d = 1.0f / d;
-
-    rt_v3 tangent   = rt_v3_normalize_plain(rt_v3_scale(rt_v3_sub(rt_v3_scale(edge1, dv2), rt_v3_scale(edge2, dv1)), inv_d));
-    rt_v3 bitangent = rt_v3_normalize_plain(rt_v3_scale(rt_v3_sub(rt_v3_scale(edge2, du1), rt_v3_scale(edge1, du2)), inv_d));
-
-    Triangle_AOS *aos = &triangles->aos[offset + i];
-    aos->shader       = t->shader;
-    aos->normal       = Q(rt_v3_normalize_plain(rt_v3_cross_plain(edge1, edge2)));
-    aos->normal_a     = t->normals[0];
-    aos->normal_b     = t->normals[1];
-    aos->normal_c     = t->normals[2];
-    aos->tex_coords_a = t->tex_coords[0];
-    aos->tex_coords_b = t->tex_coords[1];
-    aos->tex_coords_c = t->tex_coords[2];
-    aos->tangent      = Q(tangent);
-    aos->bitangent    = Q(bitangent);
+    rt_triangle_coordinates(&v[i], triangles->x[0], triangles->len, offset + i);
+    rt_triangle_record(&v[i], &triangles->aos[offset + i]);
   }
 }
 
@@ -127,14 +94,8 @@ static f32 aabb_surface_area(AABB const *aabb) {
   return 2.0f * (x * y + y * z + z * x);
 }
 
-static f32 min3f(f32 a, f32 b, f32 c) { f32 m = b < c ? b : c; return a < m ? a : m; }
-static f32 max3f(f32 a, f32 b, f32 c) { f32 m = b > c ? b : c; return a > m ? a : m; }
-
 static void aabb_triangle(Triangle const *t, AABB *aabb) {
-  for (int ax = 0; ax < 3; ax++) {
-    aabb->min.data[ax] = min3f(t->positions[0].data[ax], t->positions[1].data[ax], t->positions[2].data[ax]) - RT_EPSILON;
-    aabb->max.data[ax] = max3f(t->positions[0].data[ax], t->positions[1].data[ax], t->positions[2].data[ax]) + RT_EPSILON;
-  }
+  rt_triangle_bounds(t, aabb->min.data, aabb->max.data);
 }
 
 static void aabb_triangle_slice(Triangle const *tris, isize count, AABB *aabb) {

@@ -95,6 +95,11 @@ def _declare(d):
     d.scene_init_sah.argtypes = [P(abi.Scene), abi.Triangle_Slice, abi.Allocator]
     d.scene_init_sah.restype = None
     d.scene_init_gpu.argtypes = [P(abi.Scene), abi.Triangle_Slice, abi.Allocator]
+    if hasattr(d, "scene_refit"):                          # (absent from older builds loaded as A/B partners)
+        d.rt_scene_slot_map.argtypes = [P(abi.Scene), abi.Triangle_Slice, vp]
+        d.rt_scene_slot_map.restype = C.c_ssize_t
+        d.scene_refit.argtypes = [P(abi.Scene), abi.Triangle_Slice, vp]
+        d.scene_refit_gpu.argtypes = [P(abi.Scene), abi.Triangle_Slice, vp]
     d.rt_scene_alloc.argtypes = [P(abi.Scene), abi.isize, abi.Allocator]
     d.rt_scene_alloc.restype = C.c_bool
     d.rt_scene_free.argtypes = [P(abi.Scene)]

@@ -73,6 +73,8 @@ class HostScene:
         self.shader_kind = "disney"
         self._freed = False
         self.scene_init_seconds = 0.0
+        self.source_triangles = None   # the Triangle array (abi.TRIANGLE_DTYPE) the scene was built from, kept up to date by refit()
+        self._slot_map = None
 
     # --- convenience views -------------------------------------------------------------
     @property
@@ -112,6 +114,40 @@ class HostScene:
 
     def set_camera(self, matrix, yfov):
         set_camera(self.scene.camera, matrix, yfov)
+
+    def slot_map(self):
+        """slot_of_source: (n,) int32, the slot of the triangle block that holds source triangle i (rt_scene_slot_map).  A refit
+        keeps every triangle in its slot, so the map is computed once."""
+        if not hasattr(lib, "scene_refit"):
+            raise RuntimeError("the loaded library has no scene_refit / rt_scene_slot_map (an older build loaded through RT_LIB_PATH?)")
+        if self._slot_map is None:
+            tri = self.source_triangles
+            if tri is None:
+                raise RuntimeError("this HostScene does not know the triangles it was built from")
+            out = np.zeros(len(tri), np.int32)
+            if lib.rt_scene_slot_map(C.byref(self.scene), abi.Triangle_Slice(tri.ctypes.data, len(tri)), out.ctypes.data) != len(tri):
+                raise RuntimeError("rt_scene_slot_map: the scene does not hold exactly the source triangles")
+            self._slot_map = out
+        return self._slot_map
+
+    def refit(self, positions=None, normals=None, uvs=None, device="gpu"):
+        """Same topology, new geometry: positions / normals (N,3,3) f32, uvs (N,3,2) f32, None = unchanged.  "gpu":
+        scene_refit_gpu, the device copy is updated in place; "cpu": scene_refit, the device copies are dropped."""
+        if device not in ("gpu", "cpu"):
+            raise ValueError(f"unknown refit device {device!r}")
+        smap = self.slot_map()                   # (before the source changes: the map matches on bytes)
+        tri = self.source_triangles.copy()       # source_triangles follows only a refit that went through
+        n = len(tri)
+        if positions is not None:
+            tri["positions"] = np.asarray(positions, np.float32).reshape(n, 3, 3)
+        if normals is not None:
+            tri["normals"] = np.asarray(normals, np.float32).reshape(n, 3, 3)
+        if uvs is not None:
+            tri["tex_coords"] = np.asarray(uvs, np.float32).reshape(n, 3, 2)
+        fn = lib.scene_refit_gpu if device == "gpu" else lib.scene_refit
+        if fn(C.byref(self.scene), abi.Triangle_Slice(tri.ctypes.data, n), smap.ctypes.data) != 0:
+            raise RuntimeError(("scene_refit_gpu: " if device == "gpu" else "scene_refit: ") + last_error())
+        self.source_triangles[...] = tri
 
     def free(self):
         if not self._freed:
@@ -204,6 +240,7 @@ def build_scene(positions, normals, uvs, material_ids, materials: List[Material]
     else:
         raise ValueError(f"unknown BVH builder {builder!r}")
     hs.builder = builder
+    hs.source_triangles = tri
     hs.scene_init_seconds = time.perf_counter() - t0
     if not hs.scene.triangles.x[0]:
         raise MemoryError("scene_init failed")
