@@ -367,7 +367,7 @@ extern int rt_render_features(Scene const *scene, i32 width, i32 height, isize s
  *     a pixel with coverage_p == 0 keeps c_p: sky is not noisy, and the features say nothing about it
  *   Output: out_p = c_p * m_p; where coverage_p == 0, out_p = color_p bit for bit.  The u8 image is rt_encode_u8(out) per channel
  *     (rt_math.h), under the library's numeric contract like rt_resolve's.
- * Not done: variance-guided weights (SVGF), temporal reuse, several devices, view batches. */
+ * Not done: variance-guided weights (SVGF), several devices, view batches.  (Reuse over time: temporal accumulation below.) */
 typedef struct {
   i32 iterations;
   f32 sigma_color, sigma_normal, sigma_position;
@@ -402,6 +402,127 @@ extern int rt_guided_denoise_host(i32 width, i32 height, RT_Guided_Params const 
  * rt_device_count() > 1 the call fails. */
 extern int rt_render_denoised(Scene const *scene, Image const *image, isize samples, isize max_bounces,
                               RT_Guided_Params const *params, f32 *linear_noisy, f32 *linear_denoised);
+
+/* ---- temporal accumulation -------------------------------------------------------------- */
+
+/* The frame blended with the frames before it: every pixel fetches the accumulated colour from where its surface point WAS in the
+ * previous camera and blends the new frame in with weight 1 / (frames accumulated).  For static geometry under a moving camera
+ * the correspondence is exact and in closed form: the mean world position of a pixel's first hits (the feature buffers above)
+ * is projected into both cameras.  One kernel of its own (rt_temporal_kernel, csrc/rt_temporal.hip); frames, views, queries,
+ * feature passes, the guided filter and their counters are not affected.
+ *
+ * THE ACCUMULATION.  Only + - * / , floorf, int <-> float conversions of exactly representable values, comparisons and selects in
+ * f32; every operation rounded on its own (no fused multiply-add, no reciprocal), sums evaluated left to right as written: a
+ * float32 restatement on the CPU is equal bit for bit (tests/_temporal.py).
+ *   Inputs (all finite): color f32[h][w][3] the linear mean radiance; coverage f32[h][w]; albedo, normal (the encoded n * 0.5 + 0.5
+ *     mean), position f32[h][w][3] exactly as rt_resolve_features writes them; the frame's Camera and the history's Camera; a
+ *     previous HISTORY or none.
+ *   Parameters: alpha in (0, 1]; max_history 1 .. 2^20; both tolerances > 0 and not NaN, +inf switches that test off; demodulate 0
+ *     or 1.  The host computes in f32: tn2 = normal_tolerance * normal_tolerance, tp2 = plane_tolerance * plane_tolerance,
+ *     half_w = (float)w * 0.5f, half_h = (float)h * 0.5f, aspect = (float)w / (float)h.
+ *   A history is 48 B per pixel, three planes of float4 records one after the other ([3][h][w] float4):
+ *     (c.r, c.g, c.b, len)  the accumulated, demodulated colour and the history length in frames
+ *     (N.x, N.y, N.z, cov)  the signed mean normal and the coverage
+ *     (W.x, W.y, W.z, 0)    the mean world position of the first hits
+ *     A call reads one history and writes another; the reads are gathers from neighbouring pixels, so the two must not overlap
+ *     (refused).
+ *   proj(cam, W): R = cam.view_matrix rows[i][0..2], t = rows[i][3].  R IS TAKEN AS ORTHONORMAL: its inverse is its transpose (a
+ *     view matrix with scale or shear is projected wrongly; the guides then reject the taps or the reuse is wrong).
+ *       e  = W - t per component
+ *       cx = R[0][0] * e.x + R[1][0] * e.y + R[2][0] * e.z;  cy, cz likewise with R[.][1], R[.][2]
+ *       front = cz < 0.0f;  d = 0.0f - cz
+ *       ux = ((cx * cam.focal_length) / d) / aspect;  uy = 0.0f - ((cy * cam.focal_length) / d)
+ *       fx = (ux + 1.0f) * half_w;  fy = (uy + 1.0f) * half_h
+ *     the inverse of the frame's primary ray (raytracer.c:641-694): fx = x + jitter - 0.5.
+ *   Per pixel p = (x, y):
+ *     cov = coverage_p;  N_p = normal_p * 2.0f - cov per component (as the guided filter)
+ *     m_p = albedo_p + ((1.0f - cov) + 1e-3f) per channel and c_p = color_p / m_p when demodulate is set; otherwise m_p = 1, c_p = color_p
+ *     cov == 0 (sky is not noisy, and the features say nothing about it): out_p = color_p bit for bit, the history record is
+ *       (color_p, 0), (0, 0, 0, 0), (0, 0, 0, 0), length_p = 0.
+ *     Otherwise:
+ *       W_p = position_p / cov per component            (the mean world position of the samples that hit)
+ *       (front_c, fxc, fyc, .) = proj(camera, W_p);  (front_v, fxv, fyv, dv) = proj(previous camera, W_p)
+ *       hx = (float)x + (fxv - fxc);  hy = (float)y + (fyv - fyc)
+ *         the motion is the difference of two projections of one point, not fxv itself: the mean jitter of a pixel's samples is not
+ *         0.5, and the difference cancels that offset; with equal cameras it is +0 and hx = x exactly
+ *       usable = history given && front_c && front_v && hx >= -1.0f && hx < (float)w && hy >= -1.0f && hy < (float)h
+ *         (every comparison is false for NaN)
+ *       if usable: x0 = (int)floorf(hx), y0 = (int)floorf(hy), ax = hx - (float)x0, ay = hy - (float)y0; taps k = 0 .. 3 in this order
+ *           (x0, y0) b = (1.0f - ax) * (1.0f - ay);  (x0 + 1, y0) b = ax * (1.0f - ay);  (x0, y0 + 1) b = (1.0f - ax) * ay;  (x0 + 1, y0 + 1) b = ax * ay
+ *         a tap q is VALID when it lies inside the image, cov_q > 0 and
+ *           dn = N_p - N_q;  dn.x * dn.x + dn.y * dn.y + dn.z * dn.z <= tn2
+ *           e = W_q - W_p;  pl = N_p.x * e.x + N_p.y * e.y + N_p.z * e.z;  pl * pl <= (tp2 * dv) * dv
+ *           (the distance of the old surface point from p's tangent plane, relative to its depth in the old camera)
+ *         over the valid taps in tap order: sum_w = sum_w + b;  sum_c = sum_c + b * c_q per channel;  sum_n = sum_n + b * len_q
+ *       if usable && sum_w > 0:
+ *           h_c = sum_c / sum_w;  h_n = sum_n / sum_w;  n = h_n < (float)max_history ? h_n : (float)max_history
+ *           a = 1.0f / (n + 1.0f);  if (a < alpha) a = alpha
+ *           c' = h_c + (c_p - h_c) * a;  len' = n + 1.0f
+ *       otherwise c' = c_p, len' = 1.0f
+ *       out_p = c' * m_p (demodulate == 0: c'); the history record is (c', len'), (N_p, cov), (W_p, 0); length_p = len'
+ *     The u8 image is rt_encode_u8(out) per channel (rt_math.h), under the library's numeric contract like rt_resolve's.
+ *   Two consequences.  Equal cameras over an unchanged scene: hx = x, ax = 0, the centre tap has weight 1 and passes both tests with
+ *   0 (the feature pass does not read the seed: old and new guides are the same bits), so the output is the recursion
+ *   h + (c - h) * a bit for bit.  No history (first frame, after a reset): out = c_p * m_p and len = 1.
+ * Out of scope: MOVING GEOMETRY -- after scene_refit_gpu a surface that moved off its old plane fails the plane test and restarts
+ * there, one that slid within its own plane is reused wrongly; a host that deforms the mesh resets the history or accepts that
+ * (per-triangle motion vectors need a triangle-id feature channel).  Variance / moment estimation and SVGF weights, several devices,
+ * view batches, weighting frames by their sample counts. */
+typedef struct {
+  f32 alpha;
+  i32 max_history;
+  f32 normal_tolerance, plane_tolerance;
+  i32 demodulate;
+} RT_Temporal_Params;                                                                            /* 20 bytes */
+
+/* A history as planar host arrays (rt_temporal_accumulate_host): the accumulated colour f32[h][w][3], the length f32[h][w], the
+ * coverage f32[h][w], the signed N and W f32[h][w][3] -- the fields of the three records above, one plane each. */
+typedef struct { f32 *color, *length, *coverage, *normal, *position; } RT_History_Planes;
+
+/* Device level, like rt_guided_denoise(): every pointer is a DEVICE pointer owned by the caller, the call only enqueues one launch
+ * on `stream`.
+ *   d_history_in  : rt_temporal_history_bytes(width, height) bytes, 16-byte aligned, or NULL = no history (then previous_camera is
+ *                   not read and may be NULL)
+ *   d_history_out : as many bytes, 16-byte aligned; receives the new history.  Must not overlap d_history_in.
+ *   d_out f32[h][w][3], d_length f32[h][w], d_image u8[h][w][3] : each optional.  d_out == d_color is allowed: a pixel reads only
+ *                   its own colour.  d_albedo may be NULL only when demodulate == 0.
+ * Host level: rt_temporal_accumulate_host() from host memory to host memory through library-owned staging (kept between calls); it
+ * takes the library's device lock and runs on the NULL stream.  planes: all four (albedo may be NULL when demodulate == 0);
+ * history_in: NULL = none, otherwise all five planes; history_out: NULL = not wanted, otherwise all five planes (which may be
+ * history_in's: the arrays are staged); at least one of history_out, out, length, image.
+ * Checked before the GPU is touched, by all of them: NULL pointers, width, height > 0, width x height <= 2^28, alpha in (0, 1],
+ * max_history in 1 .. 2^20, tolerances > 0 and not NaN, demodulate 0 or 1, alignment, overlapping histories, no output.  0 on
+ * success, -1 + rt_last_error() (rt_temporal_history_bytes: the size, -1 + rt_last_error()); a refused call leaves its outputs
+ * untouched. */
+extern i64 rt_temporal_history_bytes(i32 width, i32 height);
+extern int rt_temporal_accumulate(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                  Camera const *previous_camera, void const *d_color, void const *d_coverage, void const *d_albedo,
+                                  void const *d_normal, void const *d_position, void const *d_history_in, void *d_history_out,
+                                  void *d_out, void *d_length, void *d_image, void *stream);
+extern int rt_temporal_accumulate_host(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                       Camera const *previous_camera, f32 const *color, RT_Features const *planes,
+                                       RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
+                                       f32 *length, u8 *image);
+
+/* The history a host keeps for a sequence: two device histories, ping-ponged, and the camera of the last frame accumulated.  The
+ * memory is allocated on the primary device by the first frame that uses it (rt_history_create touches no device) and belongs
+ * to that device slot's staging: when the slot's staging is given back, the history is empty again and the next frame starts from
+ * nothing, as after rt_history_reset().  rt_history_destroy(NULL) is allowed.  A history serves one thread at a time. */
+typedef struct RT_History RT_History;
+extern RT_History *rt_history_create(i32 width, i32 height);
+extern int         rt_history_reset(RT_History *history);
+extern void        rt_history_destroy(RT_History *history);
+
+/* An accumulated frame in one call: rt_render_frame()'s frame sequence, the feature pass of the same frame shape, the accumulation
+ * against `history` (previous camera = the camera of the last call on this history) and, when guided_params is not NULL, the guided
+ * filter over the accumulated output -- in ONE scene-checked call, as rt_render_denoised() is.  The history keeps the UNFILTERED
+ * accumulation and the camera of this call.  The Image receives the encoding of the last stage with rt_render_frame()'s layout
+ * rules (pixels.data may be NULL when linear_out or length is given); linear_noisy (optional) = what rt_render_frame() returns as
+ * `linear`, linear_out (optional) = the last stage's f32 output, f32[h][w][3] each; length (optional) f32[h][w].  The image size
+ * must be the history's.  One device only: with rt_device_count() > 1 the call fails. */
+extern int rt_render_temporal(Scene const *scene, Image const *image, isize samples, isize max_bounces, RT_History *history,
+                              RT_Temporal_Params const *temporal_params, RT_Guided_Params const *guided_params, f32 *linear_noisy,
+                              f32 *linear_out, f32 *length);
 
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */

@@ -12,3 +12,4 @@ from .render import render_frame, render_views, render_context, frame_begin, fra
 from .query import closest_hits, occluded, closest_hits_device, occluded_device, get_query_counters, QueryCounters   # noqa: F401
 from .features import render_features   # noqa: F401
 from .guided import guided_denoise, render_denoised   # noqa: F401
+from .temporal import temporal_accumulate, render_temporal, History   # noqa: F401

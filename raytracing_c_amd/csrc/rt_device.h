@@ -178,6 +178,25 @@ typedef struct {
   int32_t      units_per_tile; /* (1 << shift) pixel groups x n_sample_blocks                                             */
 } RT_FParams;
 
+/* Temporal accumulation (rt_temporal_kernel, rt_temporal.hip; include/rt_hip.h rt_temporal_accumulate): a camera as proj() of the
+ * contract reads it, and what the host computes once per launch. */
+typedef struct {
+  float r[3][3];               /* view_matrix rows[i][0..2]: camera space -> world space, taken as orthonormal             */
+  float t[3];                  /* rows[i][3]                                                                               */
+  float focal_length;
+} RT_TCamera;
+typedef struct {
+  RT_TCamera cur, prev;        /* the frame's camera, the camera of the history                                            */
+  int32_t width, height;
+  float   half_w, half_h;      /* (float)w * 0.5f, (float)h * 0.5f                                                         */
+  float   aspect;              /* (float)w / (float)h                                                                      */
+  float   tn2, tp2;            /* normal_tolerance^2, plane_tolerance^2                                                    */
+  float   alpha;
+  float   max_history;         /* (float)max_history: at most 2^20, exact                                                  */
+  int32_t demodulate;
+  int32_t tiles_x;             /* ceil(width / 32): block b is tile (b % tiles_x, b / tiles_x) of 32 x 8 pixels            */
+} RT_TParams;
+
 #define WF_CHUNK        256
 #define WF_HIT0_FIELDS  9      /* direction (3), t, triangle, u, v, pixel (y << 16 | x), sample                         */
 #define WF_HIT_FIELDS   5      /* index of the ray record (chunk * WF_CHUNK + slot), t, triangle, u, v                  */

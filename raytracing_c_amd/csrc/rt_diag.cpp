@@ -186,6 +186,7 @@ extern "C" int rt_diag_release_staging(void) {
   release_feature_state(D);
   release_guided_state(D);
   release_refit_state(D);
+  release_temporal_state(D);
   return 0;
 }
 

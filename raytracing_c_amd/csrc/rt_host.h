@@ -10,7 +10,7 @@
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build and refit, denoiser; guided denoiser: the a-trous filter over the feature buffers (device
-//                     level, host level, behind a frame)
+//                     level, host level, behind a frame); temporal accumulation: the reprojected history (the same three levels)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -86,6 +86,13 @@ int rt_launch_guided_pack(int n_pixels, int demodulate, const float *color, cons
 int rt_launch_guided_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate, const void *src,
                             void *dst, const void *g0, const void *g1, const float *color, const float *albedo, float *out,
                             uint8_t *image, hipStream_t stream);
+// ... in rt_temporal.hip
+int rt_launch_temporal(const RT_TParams *P, const float *color, const float *coverage, const float *albedo, const float *normal,
+                       const float *position, const void *hist_in, void *hist_out, float *out, float *length, uint8_t *image,
+                       hipStream_t stream);
+int rt_launch_temporal_pack(int n_pixels, const float *c, const float *len, const float *cov, const float *n, const float *w, void *hist,
+                            hipStream_t stream);
+int rt_launch_temporal_unpack(int n_pixels, const void *hist, float *c, float *len, float *cov, float *n, float *w, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -243,6 +250,20 @@ struct GuidedState {
   DevMem<uint8_t> work;                       // rt_guided_work_bytes()
 };
 
+// Temporal accumulation (rt_extras.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame, a history
+// as 11 planar f32 (staged in, later staged out), the two histories as records -- and the f32 output of rt_render_temporal, kept
+// between calls; and the histories hosts keep (rt_history_create), whose device memory is part of this slot's staging: giving the
+// staging back (release_temporal_state) empties every one of them, so that none points at memory of a slot that was torn down.
+struct TemporalState {
+  DevMem<float>   in;                         // color [pixels][3], coverage [pixels], albedo, normal, position [pixels][3]
+  DevMem<float>   planar;                     // a history as planes: colour [pixels][3], length, coverage [pixels], N, W [pixels][3]
+  DevMem<uint8_t> hist[2];                    // rt_temporal_history_bytes() each: read, written
+  DevMem<float>   out;                        // [pixels][3]
+  DevMem<float>   length;                     // [pixels]
+  DevMem<uint8_t> image;                      // [pixels][3]
+  std::vector<RT_History *> histories;        // every live RT_History (slot 0 only)
+};
+
 // scene_refit_gpu (rt_extras.cpp): the device staging of a refit, kept between calls -- a deforming mesh is refitted every frame --
 // and given back with the device slot (release_refit_state).
 struct RefitState {
@@ -273,7 +294,19 @@ struct Device {
   FeatureState features;
   GuidedState guided;
   RefitState refit;
+  TemporalState temporal;
 };
+
+// rt_history_create's object.  Guarded by slot 0's mutex like the staging it belongs to.
+#pragma GCC visibility push(hidden)
+struct RT_History {
+  i32             width = 0, height = 0;
+  DevMem<uint8_t> buf[2];                     // the two histories; [cur] is the one the last frame wrote
+  int             cur = 0;
+  bool            valid = false;              // buf[cur] holds a history and `camera` its camera
+  Camera          camera;
+};
+#pragma GCC visibility pop
 
 // Makes `D`'s GPU the calling thread's current HIP device for the guard's lifetime.
 struct DeviceGuard {
@@ -463,6 +496,7 @@ int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_cove
 // rt_extras.cpp
 void release_guided_state(Device &D);                                               // D.mutex held, D's GPU current, device idle
 void release_refit_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
+void release_temporal_state(Device &D);                                             // D.mutex held, D's GPU current, device idle
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

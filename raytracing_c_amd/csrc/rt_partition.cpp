@@ -105,6 +105,7 @@ void remap_device_slots() {
       release_feature_state(D);
       release_guided_state(D);
       release_refit_state(D);
+      release_temporal_state(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);

@@ -165,6 +165,19 @@ class RT_Guided_Params(C.Structure):  # rt_hip.h: the guided denoiser's paramete
 assert C.sizeof(RT_Guided_Params) == 20
 
 
+class RT_Temporal_Params(C.Structure):  # rt_hip.h: temporal accumulation's parameters
+    _fields_ = [("alpha", f32), ("max_history", C.c_int32), ("normal_tolerance", f32), ("plane_tolerance", f32),
+                ("demodulate", C.c_int32)]
+
+
+class RT_History_Planes(C.Structure):  # rt_hip.h: a history as planar host arrays
+    _fields_ = [(n, C.POINTER(f32)) for n in ("color", "length", "coverage", "normal", "position")]
+
+
+assert C.sizeof(RT_Temporal_Params) == 20
+RT_TEMPORAL_HISTORY_PER_PIXEL = 48    # three float4 records
+
+
 # numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
 _HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
@@ -208,6 +221,8 @@ EXPORTED_SYMBOLS = [
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
+    "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
+    "rt_history_destroy", "rt_render_temporal",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 

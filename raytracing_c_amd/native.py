@@ -151,6 +151,19 @@ def _declare(d):
         d.rt_guided_denoise.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params)] + [vp] * 9
         d.rt_guided_denoise_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params), vp, P(abi.RT_Features), vp, vp]
         d.rt_render_denoised.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, P(abi.RT_Guided_Params), vp, vp]
+    if hasattr(d, "rt_temporal_accumulate"):
+        d.rt_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_temporal_history_bytes.restype = C.c_int64
+        d.rt_temporal_accumulate.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera)] + [vp] * 11
+        d.rt_temporal_accumulate_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera), vp,
+                                                  P(abi.RT_Features), P(abi.RT_History_Planes), P(abi.RT_History_Planes), vp, vp, vp]
+        d.rt_history_create.argtypes = [C.c_int32, C.c_int32]
+        d.rt_history_create.restype = vp
+        d.rt_history_reset.argtypes = [vp]
+        d.rt_history_destroy.argtypes = [vp]
+        d.rt_history_destroy.restype = None
+        d.rt_render_temporal.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, vp, P(abi.RT_Temporal_Params),
+                                         P(abi.RT_Guided_Params), vp, vp, vp]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
