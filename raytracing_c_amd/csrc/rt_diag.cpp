@@ -182,11 +182,7 @@ extern "C" int rt_diag_release_staging(void) {
   std::lock_guard<std::mutex> lock(D.mutex);
   if (ensure_device(D) != 0) return -1;
   HIP_TRY(hipDeviceSynchronize());
-  release_query_state(D);
-  release_feature_state(D);
-  release_guided_state(D);
-  release_refit_state(D);
-  release_temporal_state(D);
+  release_staging(D);
   return 0;
 }
 

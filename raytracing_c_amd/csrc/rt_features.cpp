@@ -10,8 +10,7 @@ static_assert(RT_FEATURE_CHANNELS == 10, "coverage, albedo rgb, normal xyz, posi
 // What can be checked without the device.  `who` prefixes the messages.
 static int check_feature_params(const char *who, RT_Render_Params const *p) {
   if (!p) return rt_fail("%s: render params are NULL", who);
-  if (p->width <= 0 || p->height <= 0) return rt_fail("%s: image size %dx%d is invalid", who, p->width, p->height);
-  if ((int64_t)p->width * p->height > (int64_t)1 << 28) return rt_fail("%s: image %dx%d is too large (more than 2^28 pixels)", who, p->width, p->height);
+  if (check_image_size(who, p->width, p->height) != 0) return -1;
   if (p->samples <= 0) return rt_fail("%s: samples must be positive (got %d)", who, p->samples);
   if (p->max_bounces < 0) return rt_fail("%s: max_bounces must be >= 0 (got %d)", who, p->max_bounces);
   if (p->rank != 0 || p->world != 1) return rt_fail("%s: rank %d / world %d: a feature pass renders the whole image on one device (0 / 1)", who, p->rank, p->world);
@@ -103,9 +102,6 @@ extern "C" int rt_resolve_features(RT_Render_Params const *params, void const *d
 }
 
 // ---- host level ---------------------------------------------------------------------------------------------------------------
-// Gives back the staging of the host-level call.  D.mutex held, D's GPU current, device idle.
-void release_feature_state(Device &D) { D.features = FeatureState(); }
-
 extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces, RT_Features const *out,
                                   u64 *sums) {
   const char *who = "rt_render_features";
@@ -131,13 +127,13 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   const size_t pixels = (size_t)width * height;
   HIP_TRY(S.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(S.planes.grow(pixels * RT_FEATURE_CHANNELS));
-  float *d_cov = S.planes, *d_alb = S.planes + pixels, *d_nrm = S.planes + pixels * 4, *d_pos = S.planes + pixels * 7;
+  const FeaturePlanes f = split_feature_planes(S.planes, pixels);
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
   auto pass = [&](RT_Device_Scene *d) -> int {
     HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
     if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream) != 0) return -1;
-    if (planes && enqueue_resolve(&p, S.sums, out->coverage ? d_cov : nullptr, out->albedo ? d_alb : nullptr,
-                                  out->normal ? d_nrm : nullptr, out->position ? d_pos : nullptr, stream) != 0)
+    if (planes && enqueue_resolve(&p, S.sums, out->coverage ? f.coverage : nullptr, out->albedo ? f.albedo : nullptr,
+                                  out->normal ? f.normal : nullptr, out->position ? f.position : nullptr, stream) != 0)
       return -1;
     return 0;
   };
@@ -145,10 +141,10 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
   if (planes) {
-    if (out->coverage) HIP_TRY(hipMemcpy(out->coverage, d_cov, pixels * sizeof(float), hipMemcpyDeviceToHost));
-    if (out->albedo) HIP_TRY(hipMemcpy(out->albedo, d_alb, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out->normal) HIP_TRY(hipMemcpy(out->normal, d_nrm, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out->position) HIP_TRY(hipMemcpy(out->position, d_pos, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->coverage) HIP_TRY(hipMemcpy(out->coverage, f.coverage, pixels * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->albedo) HIP_TRY(hipMemcpy(out->albedo, f.albedo, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->normal) HIP_TRY(hipMemcpy(out->normal, f.normal, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->position) HIP_TRY(hipMemcpy(out->position, f.position, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
   }
   if (sums) HIP_TRY(hipMemcpy(sums, S.sums, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;

@@ -7,10 +7,13 @@ void forget_multi_counters() {
   g_multi_counters_valid = false;
 }
 
-// The parameters of a one-device frame into `image` (rank 0 of 1), validated; `who` prefixes the error messages.
-static int frame_params(Image const *image, isize samples, isize max_bounces, u32 seed, const char *who, RT_Render_Params *p) {
+int check_image_layout(Image const *image, const char *who) {
   if (image->pixels.data && image->components < 3) return rt_fail("%s: image needs >= 3 components", who);
   if (image->pixels.data && image->stride < image->width) return rt_fail("%s: image stride < width", who);
+  return 0;
+}
+
+int fill_frame_params(RT_Render_Params *p, Image const *image, isize samples, isize max_bounces, u32 seed) {
   memset(p, 0, sizeof *p);
   p->width = (i32)image->width;
   p->height = (i32)image->height;
@@ -20,6 +23,12 @@ static int frame_params(Image const *image, isize samples, isize max_bounces, u3
   p->rank = 0;
   p->world = 1;
   return check_params(p);
+}
+
+// The parameters of a one-device frame into `image` (rank 0 of 1), validated; `who` prefixes the error messages.
+static int frame_params(Image const *image, isize samples, isize max_bounces, u32 seed, const char *who, RT_Render_Params *p) {
+  if (check_image_layout(image, who) != 0) return -1;
+  return fill_frame_params(p, image, samples, max_bounces, seed);
 }
 
 int enqueue_frame(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, Workspace &W, hipStream_t stream,
@@ -43,6 +52,15 @@ void frame_split(Workspace &W, FrameTiming &T) {
   T.gpu_path_ms = event_ms(W.ev_frame[1], W.ev_frame[2]);
   T.gpu_resolve_ms = event_ms(W.ev_frame[2], W.ev_frame[3]);
   T.gpu_copy_ms = event_ms(W.ev_frame[3], W.ev_frame[4]);
+}
+
+int finish_frame(Device &D, Workspace &W, hipStream_t stream, FrameTiming &T, double t_start) {
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  frame_split(W, T);
+  T.total_ms = (float)(now_ms() - t_start);
+  D.timing = T;
+  return 0;
 }
 
 // batch (rt_render_views): `image` points to batch->n images of one size, linear / accum hold batch->n views one after the other.
@@ -80,12 +98,7 @@ static int render_frame_locked(Scene const *scene, Image const *image, isize sam
   HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
   if (linear) HIP_TRY(hipMemcpy(linear, W.linear, nv * pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
   if (accum) HIP_TRY(hipMemcpy(accum, W.accum, nv * pixels * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(hipGetLastError());
-  frame_split(W, T);
-  T.total_ms = (float)(now_ms() - t_start);
-  D.timing = T;
-  return 0;
+  return finish_frame(D, W, stream, T, t_start);
 }
 
 extern "C" int rt_render_frame(Scene const *scene, Image const *image, isize samples, isize max_bounces, f32 *linear,
@@ -221,14 +234,10 @@ extern "C" int rt_frame_end(int ticket) {
   if (e != hipSuccess) return rt_fail("rt_frame_end: %s", hipGetErrorString(e));
   if (copy_image_out(&F.image, W.image, F.p.width, F.p.height, F.stream) != 0) return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[4], F.stream));
-  HIP_TRY(hipStreamSynchronize(F.stream));
-  HIP_TRY(hipGetLastError());
+  FrameTiming T = F.timing;
+  if (finish_frame(D, W, F.stream, T, F.t_begin) != 0) return -1;
   D.last_counters = F.d ? F.d->ls[1 + ticket].counters : nullptr;       // rt_get_counters() = this frame's
   F.d = nullptr;
-  FrameTiming T = F.timing;
-  frame_split(W, T);
-  T.total_ms = (float)(now_ms() - F.t_begin);
-  D.timing = T;
   return 0;
 }
 

@@ -9,8 +9,9 @@
 //                     buffers, counters, kernel timing
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
-//   rt_extras.cpp     lightmap bake, GPU BVH build and refit, denoiser; guided denoiser: the a-trous filter over the feature buffers (device
-//                     level, host level, behind a frame); temporal accumulation: the reprojected history (the same three levels)
+//   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
+//   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter) and temporal accumulation (the
+//                     reprojected history), each on the device level, on the host level and behind a frame (one pipeline)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -221,7 +222,7 @@ struct FrameLane {
 // one 64-byte slot of a ring, so that query calls on several streams can be in flight at once; a slot is taken again only after
 // the event recorded behind its last launch has completed.  The staging buffers serve the host-level calls, one slice at a time;
 // they are kept between calls (at most 133 B x RT_QUERY_SLICE) and given back with the rest when the slot is torn down
-// (release_query_state).  The staging buffers are counted in f32 (a ray is 6, a hit record 4, a full record RT_HIT_DWORDS).
+// (release_staging).  The staging buffers are counted in f32 (a ray is 6, a hit record 4, a full record RT_HIT_DWORDS).
 #define RT_QUERY_SLOTS 64
 struct QueryState {
   DevMem<uint8_t> slots;                      // [RT_QUERY_SLOTS][64]: counters u64[4] at +0, work counter u32 at +32
@@ -234,28 +235,36 @@ struct QueryState {
 };
 
 // First-hit feature buffers (rt_features.cpp): the device staging of the host-level call -- the sums and the ten f32 planes of one
-// frame -- kept between calls, given back with the device slot (release_feature_state).  A launch's work counter is a slot of the
+// frame -- kept between calls, given back with the device slot (release_staging).  A launch's work counter is a slot of the
 // query ring above.
 struct FeatureState {
   DevMem<unsigned long long> sums;            // [pixels][RT_FEATURE_CHANNELS]
   DevMem<float>              planes;          // coverage [pixels], then albedo, normal, position [pixels][3] each
 };
 
-// Guided denoiser (rt_extras.cpp): the device staging of the host-level calls, kept between calls, given back with the device slot
-// (release_guided_state).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes: it uses work and out.
+// The four planes of such a buffer.
+struct FeaturePlanes {
+  float *coverage, *albedo, *normal, *position;
+};
+static inline FeaturePlanes split_feature_planes(float *planes, size_t pixels) {
+  return {planes, planes + pixels, planes + pixels * 4, planes + pixels * 7};
+}
+
+// Guided denoiser (rt_post.cpp): the device staging of the host-level calls, kept between calls, given back with the device slot
+// (release_staging).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes: it uses work and out.
 struct GuidedState {
-  DevMem<float>   in;                         // rt_guided_denoise_host: color [pixels][3], coverage [pixels], albedo, normal, position [pixels][3]
+  DevMem<float>   in;                         // rt_guided_denoise_host: color [pixels][3], then planes as FeatureState's
   DevMem<float>   out;                        // [pixels][3]
   DevMem<uint8_t> image;                      // [pixels][3]
   DevMem<uint8_t> work;                       // rt_guided_work_bytes()
 };
 
-// Temporal accumulation (rt_extras.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame, a history
+// Temporal accumulation (rt_post.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame, a history
 // as 11 planar f32 (staged in, later staged out), the two histories as records -- and the f32 output of rt_render_temporal, kept
 // between calls; and the histories hosts keep (rt_history_create), whose device memory is part of this slot's staging: giving the
 // staging back (release_temporal_state) empties every one of them, so that none points at memory of a slot that was torn down.
 struct TemporalState {
-  DevMem<float>   in;                         // color [pixels][3], coverage [pixels], albedo, normal, position [pixels][3]
+  DevMem<float>   in;                         // color [pixels][3], then planes as FeatureState's
   DevMem<float>   planar;                     // a history as planes: colour [pixels][3], length, coverage [pixels], N, W [pixels][3]
   DevMem<uint8_t> hist[2];                    // rt_temporal_history_bytes() each: read, written
   DevMem<float>   out;                        // [pixels][3]
@@ -265,7 +274,7 @@ struct TemporalState {
 };
 
 // scene_refit_gpu (rt_extras.cpp): the device staging of a refit, kept between calls -- a deforming mesh is refitted every frame --
-// and given back with the device slot (release_refit_state).
+// and given back with the device slot (release_staging).
 struct RefitState {
   DevMem<uint8_t>  src;                       // the source triangles, 112 B each
   DevMem<int32_t>  source_of_slot;            // [slots]
@@ -436,12 +445,15 @@ static inline RT_Device_Scene *scene_checked(Device &D, Scene const *scene, hipS
 
 // rt_partition.cpp
 void remap_device_slots();                                                          // takes slot 0's mutex, then each slot's
+void release_staging(Device &D);                                                    // D.mutex held, D's GPU current, device idle
 bool partition_args_ok(i32 width, i32 height, i32 world);
 int  device_chunk_list(Device &D, int width, int height, int rank, int world, const int32_t **d_list, int *n_local);   // D's GPU current; takes g_partition_mutex
 int  device_owner_table(Device &D, int width, int height, int world, const int32_t **d_table, int *n_chunks);      // D's GPU current; takes g_partition_mutex
 
 // rt_launch.cpp
+#define RT_MAX_PIXELS ((int64_t)1 << 28)                                            // of one image: pixel and tile indices are 32-bit
 int check_params(RT_Render_Params const *p);
+int check_image_size(const char *who, i32 width, i32 height);                       // `who`: not positive / more than RT_MAX_PIXELS
 int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who);   // the batch's sizes; no device needed
 // How a workgroup's LDS is split (rt_device.h): as many leading BVH nodes as fit beside `wg_waves` perm stacks of `depth` levels and
 // `wave_extra_bytes` more per wave, when `wgs_per_cu` workgroups share a CU and -- `static_table` -- the kernel's sRGB table takes
@@ -475,28 +487,32 @@ void forget_multi_counters();                                                   
 int  enqueue_frame(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, Workspace &W, hipStream_t stream,
                    int launch_state, uint8_t *tiles, uint8_t *image, float *linear, ViewBatch const *batch = nullptr);
 void frame_split(Workspace &W, FrameTiming &T);                                     // the four GPU spans between W's frame events
+// The end of a blocking frame whose event 4 is recorded and whose copies are issued on `stream`: waits for it, and T -- with
+// frame_split and total_ms since t_start -- becomes D's timing.
+int  finish_frame(Device &D, Workspace &W, hipStream_t stream, FrameTiming &T, double t_start);
+// The halves of a one-device frame's parameters (rank 0 of 1) into `image`: the Image's layout, refused with `who` in front; p
+// filled and through check_params.
+int  check_image_layout(Image const *image, const char *who);
+int  fill_frame_params(RT_Render_Params *p, Image const *image, isize samples, isize max_bounces, u32 seed);
 
 // rt_multi.cpp
 int render_frame_multi(Scene const *scene, Image const *image, RT_Render_Params base, int world);   // slot 0's mutex held
 
 // rt_query.cpp
-void release_query_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
+void release_query_state(Device &D);                                                // release_staging()'s part here
 int  ensure_query_state(Device &D);                                                 // D.mutex held, D's GPU current
 // The ring slot of a new launch.  `query`: a query call, the one rt_get_query_counters() reports.  D.mutex held, D's GPU current.
 int  acquire_slot(Device &D, int *slot, bool query = true);
 
 // rt_features.cpp
-void release_feature_state(Device &D);                                              // D.mutex held, D's GPU current, device idle
-// One launch of the feature kernel / of its resolve on `stream` (what rt_render_features runs; rt_render_denoised runs them behind
+// One launch of the feature kernel / of its resolve on `stream` (what rt_render_features runs; rt_post.cpp runs them behind
 // a frame).  D.mutex held, D's GPU current, every pointer on D.
 int  enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream);
 int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal, void *d_position,
                      hipStream_t stream);
 
-// rt_extras.cpp
-void release_guided_state(Device &D);                                               // D.mutex held, D's GPU current, device idle
-void release_refit_state(Device &D);                                                // D.mutex held, D's GPU current, device idle
-void release_temporal_state(Device &D);                                             // D.mutex held, D's GPU current, device idle
+// rt_post.cpp
+void release_temporal_state(Device &D);                                             // release_staging()'s part here
 
 // rt_diag.cpp (diagnostic library only); the product's fault hooks are constant
 #ifdef RT_DIAG_VARIANTS

@@ -14,6 +14,12 @@ int check_params(RT_Render_Params const *p) {
   return 0;
 }
 
+int check_image_size(const char *who, i32 width, i32 height) {
+  if (width <= 0 || height <= 0) return rt_fail("%s: image size %dx%d is invalid", who, width, height);
+  if ((int64_t)width * height > RT_MAX_PIXELS) return rt_fail("%s: image %dx%d is too large (more than 2^28 pixels)", who, width, height);
+  return 0;
+}
+
 int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who) {
   if (n_views <= 0) return rt_fail("%s: n_views must be positive (got %d)", who, n_views);
   if (!views) return rt_fail("%s: views is NULL", who);

@@ -75,6 +75,16 @@ static void drop_device_partitions(const Partition *q) {        // g_partition_m
   }
 }
 
+// Gives back the staging a device keeps between host-level calls: one line per staging struct of Device.  D.mutex held, D's GPU
+// current, device idle.
+void release_staging(Device &D) {
+  release_query_state(D);                       // (also forgets that D was the last device to answer a query)
+  D.features = FeatureState();
+  D.guided = GuidedState();
+  D.refit = RefitState();
+  release_temporal_state(D);                    // (also empties every live RT_History; the list of them stays)
+}
+
 // After rt_set_devices(): slot r >= 1 belongs to GPU (primary + r) mod count, or to the primary GPU when rehearsing.  A slot
 // that was initialised under the other mapping gives back what it holds on the old GPU -- scene copies, frame buffers,
 // events, partition tables -- and is initialised again by its next frame.
@@ -101,11 +111,7 @@ void remap_device_slots() {
       D.ws = Workspace();
       if (D.mstream) { (void)hipStreamDestroy(D.mstream); D.mstream = nullptr; }
       D.last_counters = nullptr;
-      release_query_state(D);
-      release_feature_state(D);
-      release_guided_state(D);
-      release_refit_state(D);
-      release_temporal_state(D);
+      release_staging(D);
     }
     {
       std::lock_guard<std::mutex> pl(g_partition_mutex);

@@ -51,6 +51,27 @@ def _device_plane(t, shape, name, device):
     return t.data_ptr()
 
 
+def _frame(color, coverage, albedo, normal, position, plane):
+    """(colour, coverage, albedo, normal, position), each through plane(array, shape, name); `albedo` may be None and stays None."""
+    h, w = coverage.shape
+    cov = plane(coverage, (h, w), "coverage")
+    col, alb, nrm, pos = [None if a is None else plane(a, (h, w, 3), n)
+                          for a, n in zip((color, albedo, normal, position), ("color", "albedo", "normal", "position"))]
+    return col, cov, alb, nrm, pos
+
+
+def _host_frame(*frame):
+    """Of a frame in numpy arrays: (pointer to the colour, abi.RT_Features, the arrays the two point to)."""
+    arrays = _frame(*frame, _host_plane)
+    fp = C.POINTER(C.c_float)
+    return arrays[0].ctypes.data, abi.RT_Features(*[None if a is None else a.ctypes.data_as(fp) for a in arrays[1:]]), arrays
+
+
+def _device_frame(color, *planes):
+    """Of a frame in torch GPU tensors on the colour's device: the five device pointers, in the C calls' order."""
+    return _frame(color, *planes, lambda t, shape, name: _device_plane(t, shape, name, color.device))
+
+
 def guided_denoise(color, coverage, albedo, normal, position, iterations=4, sigma_color=1.0, sigma_normal=0.2, sigma_position=None,
                    demodulate=True, image=False, lib=None):
     """The filtered frame: float32 (h, w, 3), and with image=True the pair (filtered, its uint8 encoding (h, w, 3)).
@@ -62,22 +83,17 @@ def guided_denoise(color, coverage, albedo, normal, position, iterations=4, sigm
         sigma_position = default_sigma_position(position, coverage)
     params = _params(iterations, sigma_color, sigma_normal, sigma_position, demodulate)
     h, w = coverage.shape
-    names = ("color", "albedo", "normal", "position")
     if isinstance(color, np.ndarray):
-        cov = _host_plane(coverage, (h, w), "coverage")
-        col, alb, nrm, pos = [None if a is None else _host_plane(a, (h, w, 3), n) for a, n in zip((color, albedo, normal, position), names)]
-        fp = C.POINTER(C.c_float)
-        planes = abi.RT_Features(*[None if a is None else a.ctypes.data_as(fp) for a in (cov, alb, nrm, pos)])
+        col, planes, _keep = _host_frame(color, coverage, albedo, normal, position)
         out = np.zeros((h, w, 3), np.float32)
         img = np.zeros((h, w, 3), np.uint8) if image else None
-        if lib.rt_guided_denoise_host(w, h, C.byref(params), col.ctypes.data, C.byref(planes), out.ctypes.data,
+        if lib.rt_guided_denoise_host(w, h, C.byref(params), col, C.byref(planes), out.ctypes.data,
                                       img.ctypes.data if image else None) != 0:
             raise RuntimeError("rt_guided_denoise_host failed: " + last_error(lib))
         return (out, img) if image else out
     import torch
     dev = color.device
-    cov = _device_plane(coverage, (h, w), "coverage", dev)
-    col, alb, nrm, pos = [None if t is None else _device_plane(t, (h, w, 3), n, dev) for t, n in zip((color, albedo, normal, position), names)]
+    frame = _device_frame(color, coverage, albedo, normal, position)
     with torch.cuda.device(dev):
         n_work = lib.rt_guided_work_bytes(w, h)
         if n_work < 0:
@@ -87,8 +103,8 @@ def guided_denoise(color, coverage, albedo, normal, position, iterations=4, sigm
         out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         img = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if image else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if lib.rt_guided_denoise(w, h, C.byref(params), col, cov, alb, nrm, pos, out.data_ptr(), img.data_ptr() if image else None,
-                                 work.data_ptr(), stream) != 0:
+        if lib.rt_guided_denoise(w, h, C.byref(params), *frame, out.data_ptr(), img.data_ptr() if image else None, work.data_ptr(),
+                                 stream) != 0:
             raise RuntimeError("rt_guided_denoise failed: " + last_error(lib))
     return (out, img) if image else out
 

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import ctypes_abi as abi
-from .guided import _device_plane, _host_plane, _params as _guided_params
+from .guided import _device_frame, _device_plane, _host_frame, _host_plane, _params as _guided_params
 from .native import lib as _lib, last_error
 from .scene import HostScene, make_image
 
@@ -55,18 +55,14 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
     cam = as_camera(camera)
     prev = None if previous_camera is None else as_camera(previous_camera)
     h, w = coverage.shape
-    names = ("color", "albedo", "normal", "position")
     if isinstance(color, np.ndarray):
-        cov = _host_plane(coverage, (h, w), "coverage")
-        col, alb, nrm, pos = [None if a is None else _host_plane(a, (h, w, 3), n) for a, n in zip((color, albedo, normal, position), names)]
-        fp = C.POINTER(C.c_float)
-        planes = abi.RT_Features(*[None if a is None else a.ctypes.data_as(fp) for a in (cov, alb, nrm, pos)])
+        col, planes, _keep_frame = _host_frame(color, coverage, albedo, normal, position)
         h_in, _keep = (None, None) if history is None else _history_planes(h, w, history)
         h_out, new = _history_planes(h, w)
         out = np.zeros((h, w, 3), np.float32)
         length = np.zeros((h, w), np.float32)
         img = np.zeros((h, w, 3), np.uint8) if image else None
-        if lib.rt_temporal_accumulate_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col.ctypes.data,
+        if lib.rt_temporal_accumulate_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col,
                                            C.byref(planes), None if h_in is None else C.byref(h_in), C.byref(h_out), out.ctypes.data,
                                            length.ctypes.data, img.ctypes.data if image else None) != 0:
             raise RuntimeError("rt_temporal_accumulate_host failed: " + last_error(lib))
@@ -76,8 +72,7 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
         return res
     import torch
     dev = color.device
-    cov = _device_plane(coverage, (h, w), "coverage", dev)
-    col, alb, nrm, pos = [None if t is None else _device_plane(t, (h, w, 3), n, dev) for t, n in zip((color, albedo, normal, position), names)]
+    frame = _device_frame(color, coverage, albedo, normal, position)
     h_in = None if history is None else _device_plane(history, (3, h, w, 4), "history", dev)
     with torch.cuda.device(dev):
         new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
@@ -85,9 +80,8 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
         length = torch.empty((h, w), dtype=torch.float32, device=dev)
         img = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if image else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if lib.rt_temporal_accumulate(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col, cov, alb, nrm,
-                                      pos, h_in, new.data_ptr(), out.data_ptr(), length.data_ptr(), img.data_ptr() if image else None,
-                                      stream) != 0:
+        if lib.rt_temporal_accumulate(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame, h_in,
+                                      new.data_ptr(), out.data_ptr(), length.data_ptr(), img.data_ptr() if image else None, stream) != 0:
             raise RuntimeError("rt_temporal_accumulate failed: " + last_error(lib))
     res = dict(out=out, length=length, history=new)
     if image:

@@ -3,7 +3,7 @@ rt_temporal.hip) against the numpy float32 restatement of its contract (tests/_t
 output, every plane of the new history, the length and the u8 image; every class of pixel the contract distinguishes; both
 demodulate settings, each tolerance finite and +inf; sizes ragged against the 32 x 8 tile and degenerate ones; through the host call
 and through the device call on a non-default stream; no history; output aliasing the input; every output alone; behind a frame with
-equal and with moving cameras, with and without the guided filter; reset; no effect on frames, queries, feature passes and the
+equal and with moving cameras, with and without the guided filter; a first frame against rt_render_denoised; reset; no effect on frames, queries, feature passes and the
 guided filter; the staging given back and a history used after that."""
 import ctypes as C
 
@@ -351,6 +351,44 @@ def test_reset_gives_first_frame_output_again(rt, oracle):
         again = rt.render_temporal(hs, w, h, s, b, history, seed=5)
         for k in ("image", "linear_noisy", "linear_out", "length"):
             assert again[k].tobytes() == first[k].tobytes(), k
+
+
+def test_a_first_frame_without_demodulation_is_the_denoised_frame(rt, oracle):
+    """rt_render_temporal and rt_render_denoised are one pipeline.  With no usable history and no demodulation the accumulation
+    writes the colour's own bits, so the filter behind it sees what rt_render_denoised's filter sees: the same Image, the same
+    filtered and noisy frames, byte for byte, and a history of one frame wherever something is hit.  Then the other way round
+    and once more, for the filter's buffers, which the two entry points share."""
+    from tests import _guided as G
+    hs = _spheres()
+    w, h, s, b = SHAPE
+    pl = rt.render_features(hs, w, h, s, b)
+    gkw = dict(iterations=3, sigma_color=1.0, sigma_normal=0.2, sigma_position=G.sigma_position(pl["position"], pl["coverage"]),
+               demodulate=True)
+    hit = pl["coverage"] > 0
+    assert hit.sum() >= 100 and (~hit).sum() >= 100
+
+    def temporal():
+        with rt.History(w, h) as history:
+            return rt.render_temporal(hs, w, h, s, b, history, seed=SEEDS[0], demodulate=False, guided=gkw)
+
+    def denoised():
+        return rt.render_denoised(hs, w, h, s, b, seed=SEEDS[0], **gkw)
+
+    def same(t, d, what):
+        assert t["image"].tobytes() == d["image"].tobytes(), what
+        assert t["linear_out"].tobytes() == d["linear_denoised"].tobytes(), what
+        assert t["linear_noisy"].tobytes() == d["linear_noisy"].tobytes(), what
+        assert (t["length"][hit] == 1).all() and (t["length"][~hit] == 0).all(), what
+    t0 = temporal()
+    d0 = denoised()
+    same(t0, d0, "temporal, denoised")
+    assert d0["linear_denoised"].tobytes() != d0["linear_noisy"].tobytes()            # (the filter ran)
+    d1 = denoised()
+    t1 = temporal()
+    d2 = denoised()
+    same(t1, d1, "denoised, temporal")
+    same(t1, d2, "temporal, denoised again")
+    same(t0, d2, "first and last")
 
 
 def test_frames_queries_feature_passes_and_the_filter_are_not_affected(rt, oracle):
