@@ -89,6 +89,31 @@ extern int rt_test_tile_order(i32 n_tiles, u32 const *cost, u32 *order);
  * uploaded scene (index in upload order; -1 = background image). */
 extern int rt_test_texture(RT_Device_Scene *dscene, i32 tex, i32 n, f32 const *uv, f32 *out_rgb);
 
+/* ---- the shade block, item by item (tests/test_gpu_shade.py; the CPU counterparts are oracle_disney_shade, oracle_debug_shade,
+ * oracle_sample_disney_brdf, oracle_sample_background and oracle_primary_ray of oracle/oracle.h).  Host arrays. */
+
+/* shade() -- disney_shader_proc / debug_shader_proc, driver.c:350-418 -- on n inputs a test chooses.
+ *   mode      0 = shade<ShadeParams>, 1 = shade<ShadeParamsLds>: the path kernel's instance, the sRGB scale table in LDS
+ *   tri[n]    triangle slot of the uploaded scene whose MATERIAL is evaluated: float 3 of its 28-float record, as shade_hit()
+ *             reads it.  Nothing else of the triangle is used.
+ *   in        14 floats per item: direction, normal, tangent, bitangent (3 each), texture coordinates (2, finite)
+ *   state_in  RNG state per item; state_out[n] the state afterwards
+ *   out       9 floats per item: outgoing direction, tint, emission; terminate[n] 0 / 1
+ *   textured  per item the increment of the `textured` counter (RT_Counters)
+ * LANE LAYOUT, part of the contract: item i is lane i & 63 of wave i >> 6, and n need not be a multiple of 64 (the last wave
+ * is partial).  A wave whose items all name one material reads the record through the scalar cache, any other wave through
+ * vector loads: the caller decides which by the order of its items. */
+extern int rt_test_shade(RT_Device_Scene *dscene, i32 mode, i32 n, i32 const *tri, f32 const *in, u32 const *state_in,
+                         f32 *out, u32 *state_out, i32 *terminate, i32 *textured);
+/* sample_disney() (driver.c:287-348) on raw parameters: params = 8 floats per item (roughness, metalness, sheen, sheen_tint,
+ * aniso2, base colour), in_dir = 3; out_dir = 3, brdf = 4 per item (rgb and the weight-pdf; <= 0 ends the path) */
+extern int rt_test_brdf(i32 n, f32 const *params, f32 const *in_dir, u32 const *state_in, f32 *out_dir, f32 *brdf, u32 *state_out);
+/* background_lookup() (driver.c:95-104) of n finite directions (3 floats each) on the scene's environment image; mode as above */
+extern int rt_test_background(RT_Device_Scene *dscene, i32 mode, i32 n, f32 const *dir, f32 *rgb);
+/* primary_ray() (raytracer.c:641-694) of n (x, y, sample) triples of a width x height frame, with the frame constants the host
+ * computes for a real frame (1 / width, 1 / height, width / height); rays = 6 floats per item: origin, direction */
+extern int rt_test_primary_ray(Camera const *camera, i32 width, i32 height, i32 n, i32 const *xys, f32 *rays);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1028,6 +1028,16 @@ void oracle_debug_shade(PBR_Shader_Data const *data, Shader_Input const *in, Sha
   oracle_debug_shader_proc((rawptr)data, in, out);
 }
 
+/* raytracer.c:641-694 on its own, always with the default semantics (exact 1/sqrt, D2) */
+void oracle_primary_ray(Camera const *camera, i32 width, i32 height, i32 x, i32 y, i32 sample, f32 out[6]) {
+  bool was = tl_literal;
+  tl_literal = false;
+  Ray r = primary_ray(camera, width, height, x, y, sample);
+  tl_literal = was;
+  out[0] = r.position.x;  out[1] = r.position.y;  out[2] = r.position.z;
+  out[3] = r.direction.x; out[4] = r.direction.y; out[5] = r.direction.z;
+}
+
 /* ------------------------------------------------------------------------- */
 /* denoiser.c:13-153  (SURVEY.md section 8f #3).  Single threaded: every output pixel depends only on
  * the source image, so the reference's chunked threading (denoiser.c:51-129) does not affect results. */

@@ -129,6 +129,9 @@ int  oracle_set_literal(int on);
 void oracle_cast_ray(Scene const *scene, Oracle_Config const *config, Ray const *ray, isize max_bounces, u32 *state, f32 rgb[3]);
 /* driver.c:411-418 */
 void oracle_debug_shade(PBR_Shader_Data const *data, Shader_Input const *in, Shader_Output *out);
+/* raytracer.c:641-694: the primary ray of (x, y, sample) of a width x height frame, out = position, direction; always in the
+ * default (non-literal) mode */
+void oracle_primary_ray(Camera const *camera, i32 width, i32 height, i32 x, i32 y, i32 sample, f32 out[6]);
 
 /* raytracer.c:722-784: UV-space light baking.  Texels covered by several triangles
  * keep the LAST triangle's value (the reference's loop order); texels outside the image are skipped (the

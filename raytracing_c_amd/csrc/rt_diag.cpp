@@ -2,6 +2,8 @@
 
 #include "rt_host.h"
 
+#include <cmath>
+
 #ifndef RT_DIAG_VARIANTS
 #error rt_diag.cpp belongs to the diagnostic library only (-DRT_DIAG_VARIANTS)
 #endif
@@ -18,6 +20,12 @@ int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, c
                                 int smem_bytes, float *out_t, int *out_tri, float *out_uv, unsigned long long *visits,
                                 hipStream_t stream);
 int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const float *uv, float *out, hipStream_t stream);
+int rt_launch_test_shade(const RT_KParams *P, int lds, int n, const int *tri, const float *in, const uint32_t *state_in, float *out,
+                         uint32_t *state_out, int *terminate, int *textured, hipStream_t stream);
+int rt_launch_test_brdf(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir, float *brdf,
+                        uint32_t *state_out, hipStream_t stream);
+int rt_launch_test_background(const RT_KParams *P, int lds, int n, const float *dir, float *rgb, hipStream_t stream);
+int rt_launch_test_primary_ray(const RT_KParams *P, int n, const int *xys, float *rays, hipStream_t stream);
 int rt_wf_launch_camera(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
 int rt_wf_launch_trace(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
 int rt_wf_launch_shade(const RT_KParams *P, int n_blocks, int first, hipStream_t stream);
@@ -354,5 +362,117 @@ extern "C" int rt_test_texture(RT_Device_Scene *d, i32 tex, i32 n, f32 const *uv
   int rc = rt_launch_test_texture(&K, tex, n, duv, dout, nullptr);
   if (rc == 0) rc = (int)hipMemcpy(out_rgb, dout, (size_t)n * 12, hipMemcpyDeviceToHost);
   if (rc != 0) return rt_fail("rt_test_texture failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- the shade block, the BRDF sampler, the environment lookup and the camera rays on inputs a test chooses ----------
+// (include/rt_hip_diag.h; compared with the oracle's unit functions by tests/test_gpu_shade.py)
+
+static bool all_finite(f32 const *v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+extern "C" int rt_test_shade(RT_Device_Scene *d, i32 mode, i32 n, i32 const *tri, f32 const *in, u32 const *state_in, f32 *out,
+                             u32 *state_out, i32 *terminate, i32 *textured) {
+  if (!d || n <= 0 || !tri || !in || !state_in || !out || !state_out || !terminate || !textured) return rt_fail("rt_test_shade: bad arguments");
+  if (mode != 0 && mode != 1) return rt_fail("rt_test_shade: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds)", mode);
+  for (i32 i = 0; i < n; i++) {
+    if (tri[i] < 0 || tri[i] >= d->n_triangles) return rt_fail("rt_test_shade: item %d names triangle slot %d of %d", i, tri[i], d->n_triangles);
+    // texture coordinates index texels: finite only (a NaN converts to an index differently on the two sides)
+    if (!all_finite(in + (size_t)i * 14 + 12, 2)) return rt_fail("rt_test_shade: item %d has non-finite texture coordinates", i);
+  }
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  DevMem<int> dtri, dterm, dtex;
+  DevMem<float> din, dout;
+  DevMem<uint32_t> ds0, ds1;
+  HIP_TRY(dtri.grow((size_t)n));
+  HIP_TRY(dterm.grow((size_t)n));
+  HIP_TRY(dtex.grow((size_t)n));
+  HIP_TRY(din.grow((size_t)n * 14));
+  HIP_TRY(dout.grow((size_t)n * 9));
+  HIP_TRY(ds0.grow((size_t)n));
+  HIP_TRY(ds1.grow((size_t)n));
+  HIP_TRY(hipMemcpy(dtri, tri, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(din, in, (size_t)n * 56, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ds0, state_in, (size_t)n * 4, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_shade(&K, mode, n, dtri, din, ds0, dout, ds1, dterm, dtex, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, (size_t)n * 36, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(state_out, ds1, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(terminate, dterm, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(textured, dtex, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_shade failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_brdf(i32 n, f32 const *params, f32 const *in_dir, u32 const *state_in, f32 *out_dir, f32 *brdf, u32 *state_out) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (n <= 0 || !params || !in_dir || !state_in || !out_dir || !brdf || !state_out) return rt_fail("rt_test_brdf: bad arguments");
+  DevMem<float> dp, di, dout, db;
+  DevMem<uint32_t> ds0, ds1;
+  HIP_TRY(dp.grow((size_t)n * 8));
+  HIP_TRY(di.grow((size_t)n * 3));
+  HIP_TRY(dout.grow((size_t)n * 3));
+  HIP_TRY(db.grow((size_t)n * 4));
+  HIP_TRY(ds0.grow((size_t)n));
+  HIP_TRY(ds1.grow((size_t)n));
+  HIP_TRY(hipMemcpy(dp, params, (size_t)n * 32, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(di, in_dir, (size_t)n * 12, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ds0, state_in, (size_t)n * 4, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_brdf(n, dp, di, ds0, dout, db, ds1, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out_dir, dout, (size_t)n * 12, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(brdf, db, (size_t)n * 16, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(state_out, ds1, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_brdf failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_background(RT_Device_Scene *d, i32 mode, i32 n, f32 const *dir, f32 *rgb) {
+  if (!d || n <= 0 || !dir || !rgb) return rt_fail("rt_test_background: bad arguments");
+  if (mode != 0 && mode != 1) return rt_fail("rt_test_background: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds)", mode);
+  if (!all_finite(dir, (size_t)n * 3)) return rt_fail("rt_test_background: non-finite direction");
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  DevMem<float> dd, dout;
+  HIP_TRY(dd.grow((size_t)n * 3));
+  HIP_TRY(dout.grow((size_t)n * 3));
+  HIP_TRY(hipMemcpy(dd, dir, (size_t)n * 12, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_background(&K, mode, n, dd, dout, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(rgb, dout, (size_t)n * 12, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_background failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_primary_ray(Camera const *camera, i32 width, i32 height, i32 n, i32 const *xys, f32 *rays) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (!camera || width < 1 || height < 1 || n <= 0 || !xys || !rays) return rt_fail("rt_test_primary_ray: bad arguments");
+  RT_KParams K;
+  memset(&K, 0, sizeof K);
+  RT_Render_Params p;
+  memset(&p, 0, sizeof p);
+  p.width = width; p.height = height; p.samples = 1; p.max_bounces = 1;
+  camera_frame_kparams(&K, camera, &p);          // the host's own three divisions, not a copy of them
+  DevMem<int> dx;
+  DevMem<float> dr;
+  HIP_TRY(dx.grow((size_t)n * 3));
+  HIP_TRY(dr.grow((size_t)n * 6));
+  HIP_TRY(hipMemcpy(dx, xys, (size_t)n * 12, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_primary_ray(&K, n, dx, dr, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(rays, dr, (size_t)n * 24, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_primary_ray failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }

@@ -120,6 +120,98 @@ __global__ void rt_test_texture_kernel(RT_KParams P, int tex, int n, const float
   out[i * 3 + 2] = c.z;
 }
 
+// The shade block on inputs a test chooses: shade() (disney_shader_proc / debug_shader_proc) on the material of triangle
+// tri[i] -- float 3 of its 28-float record, as shade_hit() reads it -- with the 14 floats of in[] as direction, normal,
+// tangent, bitangent, uv.  Item i is lane i & 63 of wave i >> 6 (the block is four whole waves), so the caller decides which
+// waves are material-uniform and read the record through the scalar cache; the lanes past n of the last wave have left
+// before shade(), as the lanes of a partial block of the path kernel have.  SP = ShadeParamsLds: the sRGB scale table in LDS,
+// filled before the barrier as the path kernel does.
+template <class SP>
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_shade_kernel(RT_KParams P, int n, const int *tri, const float *in,
+                                                                         const uint32_t *state_in, float *out, uint32_t *state_out,
+                                                                         int *terminate, int *textured) {
+  if (Pow24InLds<SP>::value) {
+    pow24_lds_init((int)threadIdx.x);
+    __syncthreads();
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SP S;
+  S.tris = P.tris; S.mats = P.mats; S.textures = P.textures; S.texels = P.texels;
+  S.bg_texture = P.bg_texture; S.max_bounces = 0;
+  const float4 q0 = ld4(S.tris + (size_t)tri[i] * 28, 0);
+  const float *f = in + (size_t)i * 14;
+  ShadeIn si;
+  si.direction = rt_v3_make(f[0], f[1], f[2]);
+  si.normal = rt_v3_make(f[3], f[4], f[5]);
+  si.tangent = rt_v3_make(f[6], f[7], f[8]);
+  si.bitangent = rt_v3_make(f[9], f[10], f[11]);
+  si.uvx = f[12];
+  si.uvy = f[13];
+  LaneCounters cn;
+  cn.rays = cn.nodes = cn.leaves = cn.shades = cn.bgs = cn.textured = cn.paths = 0;
+  uint32_t rng = state_in[i];
+  rt_v3 out_dir, tint, emission;
+  bool term;
+  shade(S, as_i(q0.w), si, rng, out_dir, tint, emission, term, cn);
+  float *o = out + (size_t)i * 9;
+  o[0] = out_dir.x; o[1] = out_dir.y; o[2] = out_dir.z;
+  o[3] = tint.x; o[4] = tint.y; o[5] = tint.z;
+  o[6] = emission.x; o[7] = emission.y; o[8] = emission.z;
+  state_out[i] = rng;
+  terminate[i] = term ? 1 : 0;
+  textured[i] = (int)cn.textured;
+}
+
+// sample_disney() on a raw BrdfIn: params = roughness, metalness, sheen, sheen_tint, aniso2, base colour
+__global__ void rt_test_brdf_kernel(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir,
+                                    float *brdf, uint32_t *state_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *p = params + (size_t)i * 8;
+  BrdfIn m;
+  m.roughness = p[0]; m.metalness = p[1]; m.sheen = p[2]; m.sheen_tint = p[3]; m.aniso2 = p[4];
+  m.base_color = rt_v3_make(p[5], p[6], p[7]);
+  uint32_t rng = state_in[i];
+  rt_v3 o, rgb;
+  float a;
+  sample_disney(m, rt_v3_make(in_dir[i * 3 + 0], in_dir[i * 3 + 1], in_dir[i * 3 + 2]), rng, o, rgb, a);
+  out_dir[i * 3 + 0] = o.x; out_dir[i * 3 + 1] = o.y; out_dir[i * 3 + 2] = o.z;
+  brdf[i * 4 + 0] = rgb.x; brdf[i * 4 + 1] = rgb.y; brdf[i * 4 + 2] = rgb.z; brdf[i * 4 + 3] = a;
+  state_out[i] = rng;
+}
+
+template <class SP>
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_background_kernel(RT_KParams P, int n, const float *dir, float *rgb) {
+  if (Pow24InLds<SP>::value) {
+    pow24_lds_init((int)threadIdx.x);
+    __syncthreads();
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SP S;
+  S.tris = nullptr; S.mats = nullptr; S.textures = P.textures; S.texels = P.texels;
+  S.bg_texture = P.bg_texture; S.max_bounces = 0;
+  const rt_v3 c = background_lookup(S, rt_v3_make(dir[i * 3 + 0], dir[i * 3 + 1], dir[i * 3 + 2]));
+  rgb[i * 3 + 0] = c.x; rgb[i * 3 + 1] = c.y; rgb[i * 3 + 2] = c.z;
+}
+
+// primary_ray() of (x, y, sample) with the frame constants the host computed (camera_frame_kparams)
+__global__ void rt_test_primary_ray_kernel(RT_KParams P, int n, const int *xys, float *rays) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  PrimaryParams PP;
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 4; c++) PP.cam[r][c] = P.cam[r][c];
+  PP.focal_length = P.focal_length; PP.inv_width = P.inv_width; PP.inv_height = P.inv_height; PP.aspect = P.aspect;
+  rt_v3 o, d;
+  primary_ray(PP, xys[i * 3 + 0], xys[i * 3 + 1], xys[i * 3 + 2], o, d);
+  float *r = rays + (size_t)i * 6;
+  r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+
 // Arbitrary rays through the PRODUCTION traversal: traversal_blocks() -- the NODE / LEAF / pop code of the path kernels --
 // in the path kernel's workgroup geometry (16 waves, tree in LDS, per-wave perm stacks), lanes refilled from the ray list
 // as they finish, blocks mixed exactly as a frame mixes them.  With a pyramid (`pyr`: 4 outward plane normals at
@@ -249,5 +341,32 @@ extern "C" int rt_launch_test_trace(const RT_KParams *P, int n, const float *ray
 extern "C" int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const float *uv, float *out,
                                       hipStream_t stream) {
   hipLaunchKernelGGL(rt_test_texture_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *P, tex, n, uv, out);
+  return (int)hipGetLastError();
+}
+
+// lds: 0 = ShadeParams, 1 = ShadeParamsLds (the instance of the path kernel)
+extern "C" int rt_launch_test_shade(const RT_KParams *P, int lds, int n, const int *tri, const float *in, const uint32_t *state_in,
+                                    float *out, uint32_t *state_out, int *terminate, int *textured, hipStream_t stream) {
+  const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
+  if (lds) hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+  else hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_brdf(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir,
+                                   float *brdf, uint32_t *state_out, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_brdf_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, params, in_dir, state_in, out_dir, brdf, state_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_background(const RT_KParams *P, int lds, int n, const float *dir, float *rgb, hipStream_t stream) {
+  const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
+  if (lds) hipLaunchKernelGGL(rt_test_background_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, dir, rgb);
+  else hipLaunchKernelGGL(rt_test_background_kernel<ShadeParams>, grid, block, 0, stream, *P, n, dir, rgb);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_primary_ray(const RT_KParams *P, int n, const int *xys, float *rays, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_primary_ray_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *P, n, xys, rays);
   return (int)hipGetLastError();
 }

@@ -204,6 +204,10 @@ def _declare_diag(d):
     d.rt_test_quantize_sweep.argtypes = [vp]
     d.rt_test_trace.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     d.rt_test_texture.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    d.rt_test_shade.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 7
+    d.rt_test_brdf.argtypes = [C.c_int32] + [vp] * 6
+    d.rt_test_background.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    d.rt_test_primary_ray.argtypes = [C.POINTER(abi.Camera), C.c_int32, C.c_int32, C.c_int32, vp, vp]
     d.rt_test_trace_stream.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
     d.rt_test_tile_order.argtypes = [C.c_int32, vp, vp]
     d.rt_set_pipeline.argtypes = [C.c_int32]

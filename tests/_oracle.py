@@ -68,6 +68,10 @@ def load(path=None):
     d.oracle_sample_disney_brdf.restype = None
     d.oracle_disney_shade.argtypes = [P(abi.PBR_Shader_Data), P(abi.Shader_Input), P(C.c_uint32), P(abi.Shader_Output)]
     d.oracle_disney_shade.restype = None
+    d.oracle_debug_shade.argtypes = [P(abi.PBR_Shader_Data), P(abi.Shader_Input), P(abi.Shader_Output)]
+    d.oracle_debug_shade.restype = None
+    d.oracle_primary_ray.argtypes = [P(abi.Camera)] + [C.c_int32] * 5 + [vp]
+    d.oracle_primary_ray.restype = None
     d.oracle_math.argtypes = [C.c_int32, C.c_int32, vp, vp, vp]
     d.oracle_math.restype = None
     d.oracle_lightmap_bake.argtypes = [P(abi.Image), P(abi.Scene), abi.isize, P(Oracle_Config)]
