@@ -535,6 +535,11 @@ extern int rt_get_skipped_root_visits(u64 *out);
  * tiles whose pixel pyramid, pruned through the tree from the root, reaches no leaf group.  Their node visits ARE executed (and
  * are not among the skipped root visits); what they skip is the traversal state machine.  For tests and profile notes. */
 extern int rt_get_leafless_paths(u64 *out);
+/* Rays of the last rt_render_accumulate launch (single device) whose root visit the path kernel ran at the top of a traversal call,
+ * in front of the traversal rounds, over the populated children of the root only (at most four of them; a root with more, a tree of
+ * depth 0 and rays that are not NaN-free take the node block as before: 0 for such a frame).  The visits are executed and counted;
+ * what they skip is a traversal round.  Equals rays - skipped root visits - leafless paths when every ray is NaN-free.  For tests. */
+extern int rt_get_fused_root_visits(u64 *out);
 
 /* Where the time of the last frame behind render_thread_proc / render / rt_render_frame went, in milliseconds.
  * Host clock: stamp = the per-frame scene check, upload = the scene upload when one was needed, enqueue = launching the

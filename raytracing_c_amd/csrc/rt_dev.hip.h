@@ -85,9 +85,13 @@ enum {
   // small-launch ledger (round 5, tools/exp_small.py): the workgroup's copy of the tree into LDS, the join scans, and the DRAIN of a
   // tile -- from the moment its last unit is handed out to this wave until the wave's last path of it has ended (RT_LEDGER >= 2)
   LG_CYC_COPY, LG_CYC_JOIN, LG_CYC_DRAIN, LG_DRAIN_X, LG_DRAIN_L, LG_CYC_FLUSH,
+  // root visits (round 7, profiles/r07_root_visits.md): node rounds in which every lane of the block enters the root -- in the full
+  // form, in the culled form, and full-form ones that directly follow a culled one in the same traversal call (the bounce rays the
+  // culled block left waiting) -- and the root visits that run in front of the traversal call instead
+  LG_ROOT_FULL_X, LG_ROOT_FULL_L, LG_ROOT_CULL_X, LG_ROOT_CULL_L, LG_ROOT_LEFT_X, LG_ROOT_LEFT_L, LG_ROOTF_X, LG_ROOTF_L,
   LG_N
 };
-#define RT_LEDGER_ROW 128      /* dwords per wave in g_ledger (LG_N <= 128 = RT_N_COUNTERS - 8) */
+#define RT_LEDGER_ROW 128      /* dwords per wave in g_ledger (LG_N <= 128: slots 8..135 of the counters, rt_device.h) */
 // The counters live in MEMORY, one row of 64 dwords per wave (g_ledger, rt_kernels.hip), bumped by lane 0 with atomics that
 // return nothing: as scalar registers they did not fit beside the kernel's own (59 of them: 286 spilled VGPRs; even a
 // dozen: 50-80), which would have measured a different kernel.  -DRT_LEDGER=1 counts blocks and lanes, =2 adds the
@@ -1075,6 +1079,9 @@ __device__ __forceinline__ float slab_entry_ordered(const Ray3 &r, const rt_v3 &
 
 // node_enter() for a node of which only the children in `surv` (1 to 4 of them, wave-uniform) can be entered: the
 // same word -- the other children are misses, which rank behind every candidate and are never read.
+// (AT_ROOT: the copy in front of the traversal call of the path kernel; it only names the ledger's ISA markers apart)
+#define LGM_FEW(name) do { if (AT_ROOT) LGM("rfew_" name); else LGM("nfew_" name); } while (0)
+template <bool AT_ROOT = false>
 __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *lds_nodes, int node, uint32_t surv,
                                                    float hit_t) {
   const char *nbase = reinterpret_cast<const char *>(lds_nodes + lds_node_f4(node));
@@ -1084,33 +1091,33 @@ __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *
   const int k0 = (int)__builtin_ctz(surv);
   const int e0 = as_i(slab_entry_ordered(r, bs, nbase, k0, nx, ny, nz, hit_t));
   const uint32_t f0 = 1u - (((uint32_t)e0 + 0x00800000u) >> 31);                   // 1 iff e0 is finite (a candidate)
-  LGM("nfew_ret1");
+  LGM_FEW("ret1");
   if (n == 1) return (uint32_t)k0 | (f0 << 24);
   surv &= surv - 1u;
   const int k1 = (int)__builtin_ctz(surv);
   const int e1 = as_i(slab_entry_ordered(r, bs, nbase, k1, nx, ny, nz, hit_t));
   const uint32_t f1 = 1u - (((uint32_t)e1 + 0x00800000u) >> 31);
-  LGM("nfew_two");
+  LGM_FEW("two");
   if (n == 2) {
     const bool swap = e1 < e0;                                                     // ties: lowest index first
     const uint32_t first = swap ? (uint32_t)k1 : (uint32_t)k0, second = swap ? (uint32_t)k0 : (uint32_t)k1;
     return first | (second << 3) | ((f0 + f1) << 24);
   }
-  LGM("nfew_ret2");
+  LGM_FEW("ret2");
   surv &= surv - 1u;
   const int k2 = (int)__builtin_ctz(surv);
   const int e2 = as_i(slab_entry_ordered(r, bs, nbase, k2, nx, ny, nz, hit_t));
   const uint32_t f2 = 1u - (((uint32_t)e2 + 0x00800000u) >> 31);
   int e3 = 0x7F800000, k3 = 0;
   uint32_t f3 = 0;
-  LGM("nfew_four_begin");
+  LGM_FEW("four_begin");
   if (n == 4) {
     surv &= surv - 1u;
     k3 = (int)__builtin_ctz(surv);
       e3 = as_i(slab_entry_ordered(r, bs, nbase, k3, nx, ny, nz, hit_t));
     f3 = 1u - (((uint32_t)e3 + 0x00800000u) >> 31);
   }
-  LGM("nfew_four_end");
+  LGM_FEW("four_end");
   const int e[4] = {e0, e1, e2, e3};
   const int kk[4] = {k0, k1, k2, k3};
   int rank[4] = {0, 1, 2, 3};
@@ -1128,6 +1135,7 @@ __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *
   for (int j = 0; j < 4; j++) w |= (uint32_t)kk[j] << (3 * rank[j]);
   return w | ((f0 + f1 + f2 + f3) << 24);
 }
+#undef LGM_FEW
 
 // ---- pyramid culling of leaf blocks (tile-stream kernel) ----
 // The camera rays of a wave sit on one or two pixels: most leaf blocks that hold camera rays hold (almost) nothing else, all
@@ -1242,6 +1250,9 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
                                                  uint32_t *lg = nullptr) {
   static_assert(!(ANY && PYRAMID), "the pyramid-culled leaf block has no any-hit exit");
   LG(LG_TRAV_CALLS, 1);
+#ifdef RT_LEDGER
+  bool lg_after_root_cull = false;      // the round before this one was a culled root round
+#endif
   for (;;) {
     LGM("round_begin");
     const unsigned long long maskN = __ballot(phase == PH_NODE);
@@ -1256,6 +1267,7 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
       LGM("leaf_begin");
       LG(LG_LEAF_X, 1); LG(LG_LEAF_L, nL);
 #ifdef RT_LEDGER
+      lg_after_root_cull = false;
       LG(LG_LEAF_CAM, __popcll(__ballot(phase == PH_LEAF && is_cam)));
 #endif
       w_leaves += (uint32_t)nL;
@@ -1350,6 +1362,18 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
           }
         }
       }
+#ifdef RT_LEDGER
+      {
+        const unsigned long long mb = __ballot(in_blk);
+        const int nb = (int)__popcll(mb);
+        const bool root_blk = mb != 0ull && (mb & __ballot(child != 0)) == 0ull;
+        const bool culled = PYRAMID && surv <= 0xFFu;
+        LG(LG_ROOT_CULL_X, root_blk && culled); LG(LG_ROOT_CULL_L, root_blk && culled ? nb : 0);
+        LG(LG_ROOT_FULL_X, root_blk && !culled); LG(LG_ROOT_FULL_L, root_blk && !culled ? nb : 0);
+        LG(LG_ROOT_LEFT_X, root_blk && !culled && lg_after_root_cull); LG(LG_ROOT_LEFT_L, root_blk && !culled && lg_after_root_cull ? nb : 0);
+        lg_after_root_cull = root_blk && culled;
+      }
+#endif
       if (in_blk) {
         if (level >= 0) {
           perm[level * 64 + lane] = cur;

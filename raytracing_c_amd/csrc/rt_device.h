@@ -40,9 +40,11 @@
 #define RT_TILE_PIX  64
 
 #define RT_PARK_RECORD_DWORDS (18 * 128)   /* a wave's slice of RT_KParams.park: RT_PARK_FIELDS x RT_PARK_CAP (rt_dev.hip.h) */
-#define RT_N_COUNTERS 137    /* 0..6 ray counters, 7 skipped root visits; 8..135 the block ledger of the path kernel (-DRT_LEDGER
-                              * builds, LG_* slots in rt_dev.hip.h); 136 camera paths served by the leafless loop */
+#define RT_N_COUNTERS 138    /* 0..6 ray counters, 7 skipped root visits; 8..135 the block ledger of the path kernel (-DRT_LEDGER
+                              * builds, LG_* slots in rt_dev.hip.h); 136 camera paths served by the leafless loop; 137 rays whose
+                              * root visit ran in front of the traversal rounds (rt_kernels.hip) */
 #define RT_CNT_LEAFLESS 136
+#define RT_CNT_FUSED_ROOT 137
 
 /* triangle record, 28 floats:
  *  [0..2] face normal      [3]  material id (int bits)

@@ -84,8 +84,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   // tile's camera-ray pyramid
   const int acc_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4) * 16;
   const int pyr_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4 - 16) * 16;
-  // (the pyramid: planes and origin in floats 0..18, 8 cache entries of leaf masks at 24..31 (0x800000 | group) << 8 | cull mask, then 128
-  //  bytes: 32 cache entries of node masks, direct mapped by node: (node + 1) << 8 | cull mask)
+  // (the pyramid: planes and origin in floats 0..18, the root's populated children at 19 (per wave, not per tile) and the root visits the
+  //  wave ran in front of its traversal calls at 20 (flushed with the tile), 8 cache entries of leaf masks at 24..31 (0x800000 | group) << 8 | cull mask, then 128 bytes: 32 cache
+  //  entries of node masks, direct mapped by node: (node + 1) << 8 | cull mask)
 
 #ifdef RT_LEDGER
   uint32_t *lg = g_ledger + (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + wave) * RT_LEDGER_ROW;
@@ -111,6 +112,27 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   acc[lane] = 0ull;
   acc[lane + 64] = 0ull;
   acc[lane + 128] = 0ull;
+
+  // ---- the root's populated children: the only ones a ray's root visit has to test (in front of the traversal call, below) ----
+  // The reference builder fills a tree of fixed capacity, so the root of a small scene has children without a triangle below them:
+  // all-zero boxes, whose near and far distance coincide per axis and which are therefore never a candidate for a NaN-free ray
+  // (pyramid_cull_mask's `empty`).  Read from the LDS node image of THIS launch, not kept on the host: a refit rewrites the boxes on
+  // the device.  0 = the root visit is left to the node blocks: more than four populated children (node_enter_few's
+  // limit), no root in LDS, a tree of depth 0.  A word of the wave's LDS slice, read where it is used, not a scalar register.
+  if (LDSN) {
+    uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
+    bool populated = false;
+    if (lane_now() < 8 && cold_args()->n_lds_nodes > 0 && cold_args()->depth > 0) {
+      const float *nb = lds_at(smem, 0) + lane_now();      // child `lane` of node 0: rows are 8 floats apart
+      populated = !(nb[0] == 0.0f && nb[8] == 0.0f && nb[16] == 0.0f && nb[24] == 0.0f && nb[32] == 0.0f && nb[40] == 0.0f);
+    }
+    const uint32_t pm = (uint32_t)__ballot(populated) & 0xFFu;
+#ifdef RT_ROOT_AT_NODE_BLOCKS      /* (ledger builds that count the root rounds of the node blocks: profiles/r07_root_visits.md) */
+    if (lane_now() == 0) { pw[19] = 0u; pw[20] = 0u; }
+#else
+    if (lane_now() == 0) { pw[19] = __popc(pm) <= 4 ? pm : 0u; pw[20] = 0u; }
+#endif
+  }
 
   // wave-level counters (scalar registers)
   uint32_t w_paths = 0, w_rays = 0, w_nodes = 0, w_leaves = 0, w_shades = 0, w_bgs = 0, w_tex = 0;
@@ -308,6 +330,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       for (int head = 0; head < n_list; head++) {
         const int nd = head ? __builtin_amdgcn_readfirstlane((int)list[RT_LEAFLESS_MAX + head]) : 0;
         const uint32_t surv = 0xFFu & ~pyramid_cull_mask(lds_nodes, pyr, nd);
+        // into the (tile, node) mask cache of the node blocks: the root visit in front of the traversal finds the root's there
+        if (lane_now() == 0) reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off))[32 + (nd & 31)] = ((uint32_t)(nd + 1) << 8) | (0xFFu & ~surv);
         if (surv) {
           const int ns = (int)__popc(surv);
           // children that are leaf groups, or nodes outside the LDS image (its last node's children at the most), or a cap
@@ -719,7 +743,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
           dirty = 0;
           live = 0;
-          cur = 0;
+          // (at level -1 the word holds no children yet: 1 tells the root visit below that it serves this ray -- the ray is NaN-free and
+          //  the root has one to four populated children (pyr[19]); the LDS read hides behind the ray set-up here, and a scene whose
+          //  root the visit does not serve pays one ballot per traversal call for it, no LDS round trip)
+          cur = (LDSN && ray.fast && reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off))[19] != 0u) ? 1u : 0u;
           level = -1;
           node = 0;
           child = (leaf_level >= 0) ? 0 : P.last_row_offset;
@@ -745,6 +772,55 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         if (n_parked > 0 || __any(phase == PH_HIT)) continue;      // parked hits come back in the next S block
         if (!tile_open) break;            // every path of the tile that this wave took has ended
         continue;                         // (nothing started, e.g. pixels outside the image: pull more)
+      }
+
+      // ================= the root visit of the rays that the S block started =================
+      // Every such ray sits at the root (level -1, PH_NODE) and would take the first traversal round for it, camera rays in a culled
+      // block of their own and bounce rays in a full one: 8 slab tests and the rank order of 8, where only the root's POPULATED
+      // children can be candidates.  With at most four of those (the word at pyr[19]) the visit runs here, for camera and bounce
+      // rays together, as node_enter_few() over a wave-uniform set: the populated children, less those the tile's pyramid cannot
+      // touch when every ray at the root is a camera ray of the tile (the root's entry of the (tile, node) mask cache, written by
+      // the tile set-up; a child the pyramid culls is a miss for a camera ray anyway).  Same word as the node block's, same state
+      // after it: the first child and PH_NODE / PH_LEAF, or PH_MISS at level -1 where the pop would end -- a lane that traversed
+      // and has finished, for the exit rule below.  Rays that are not NaN-free, and roots left to the node blocks (pyr[19] == 0),
+      // keep child = 0, PH_NODE.
+      if (LDSN) {
+        const bool at_root = phase == PH_NODE && level < 0 && cur != 0u;      // (`cur`: set where the ray starts; ray.fast itself is in scratch here)
+        const int n_root = (int)__popcll(__ballot(at_root));
+        if (n_root != 0) {
+          LGM("root_begin");
+          LG(LG_ROOTF_X, 1); LG(LG_ROOTF_L, n_root);
+          // (both words in one LDS round trip; this glue runs once per traversal call and waits for whatever it reads)
+          uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
+          const uint32_t w_pop = pw[19], w_cull = pw[32];
+          uint32_t rsurv = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_pop);      // (not 0: `cur`)
+          w_nodes += (uint32_t)n_root;
+          // The count: one LDS add that returns nothing, by lane 0.  Written as the instruction itself: the atomic built-in compiles
+          // to the same ds_add_u32 behind a wave-aggregation prologue (a lane count, a multiply) that this one-lane add has no use
+          // for -- measured 0.03 ms per step of config #3 (profiles/r07_root_visits.md); same registers either way.  The address is
+          // the pointer cast to the LDS address space, i.e. its 32-bit offset.
+          if (lane_now() == 0) {
+            const uint32_t at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(pw + 20);
+            asm volatile("ds_add_u32 %0, %1" : : "v"(at), "v"((uint32_t)n_root) : "memory");
+          }
+          if (__ballot(at_root && bounce != 0) == 0ull) {
+            const uint32_t ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_cull);
+            if ((ce >> 8) == 1u) rsurv &= ~ce;
+          }
+          if (at_root) {
+            level = 0;
+            cur = rsurv ? node_enter_few<true>(ray, lds_nodes, 0, rsurv, RT_INF) : 0u;
+            if (cur >> 24) {
+              child = 1 + (int)(cur & 7u);
+              cur = ((cur >> 3) & 0x1FFFFFu) | (((cur >> 24) - 1u) << 24);
+              phase = (leaf_level == 0) ? PH_LEAF : PH_NODE;
+            } else {
+              level = -1;
+              phase = PH_MISS;
+            }
+          }
+          LGM("root_end");
+        }
       }
 
       // ================= traversal: NODE / LEAF blocks until `thresh` lanes wait for S =================
@@ -779,6 +855,12 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       }
       uint32_t *tile_cost = A->tile_cost;
       if (tile_cost && lane == 0) atomicAdd(&tile_cost[tile_idx], w_rays - rays_before);
+      if (LDSN && lane == 0) {            // counters[RT_CNT_FUSED_ROOT]: the root visits this wave ran in front of its traversal calls
+        uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
+        const uint32_t n_fused = pw[20];
+        pw[20] = 0u;
+        if (n_fused != 0u) atomicAdd(A->counters + RT_CNT_FUSED_ROOT, (unsigned long long)n_fused);
+      }
       steal_tries = 0;                    // joined (or owned) a tile that had work: keep looking for more
       n_tiles_done += 1;
       LGT1(LG_CYC_FLUSH);

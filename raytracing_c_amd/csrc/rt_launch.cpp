@@ -466,6 +466,20 @@ extern "C" int rt_get_leafless_paths(u64 *out) {
   return 0;
 }
 
+// Rays of the last rt_render_accumulate launch whose root visit ran at the top of a traversal call, in front of the traversal
+// rounds (rt_kernels.hip): every NaN-free ray that the sky / leafless loop does not serve, when the root has at most four populated
+// children.
+extern "C" int rt_get_fused_root_visits(u64 *out) {
+  if (!out) return rt_fail("rt_get_fused_root_visits: NULL");
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  unsigned long long c[RT_N_COUNTERS];
+  if (read_counters(D, c) != 0) return -1;
+  *out = c[RT_CNT_FUSED_ROOT];
+  return 0;
+}
+
 int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]) {
   HIP_TRY(hipDeviceSynchronize());
   if (!D.last_counters) { memset(c, 0, RT_N_COUNTERS * sizeof(unsigned long long)); return 0; }

@@ -223,7 +223,7 @@ EXPORTED_SYMBOLS = [
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
     "rt_history_destroy", "rt_render_temporal",
-    "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
+    "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_fused_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 
 # include/rt_hip_diag.h: exported by librt_hip_diag.so only (which also exports everything above); the product library must

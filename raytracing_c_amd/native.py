@@ -169,6 +169,8 @@ def _declare(d):
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
     if hasattr(d, "rt_get_leafless_paths"):
         d.rt_get_leafless_paths.argtypes = [P(C.c_uint64)]
+    if hasattr(d, "rt_get_fused_root_visits"):
+        d.rt_get_fused_root_visits.argtypes = [P(C.c_uint64)]
     d.rt_math_contract.restype = C.c_int
     d.rt_last_kernel_ms.restype = C.c_float
     d.rt_kernel_timing_reset.restype = None

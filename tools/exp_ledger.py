@@ -25,6 +25,10 @@ LG_NAMES = ["S_ITER", "ENV_X", "ENV_L", "SHADE_X", "SHADE_L", "PSTORE_X", "PSTOR
             "NFEW0_X", "NFEW1_X", "NFEW2_X", "NFEW3_X", "NFEW4_X", "NFEW0_L", "NFEW1_L", "NFEW2_L", "NFEW3_L", "NFEW4_L",
             "LEAF_X", "LEAF_L", "LEAF_CAM", "POP_X", "POP_L", "POP_UP_L", "POP_RETEST_L", "POP_CAM", "POP_UP_X", "POP_RETEST_X", "POP_DONE_L",
             "CYC_S", "CYC_NODE", "CYC_LEAF", "CYC_POP", "CYC_WAVE", "CYC_TILE", "SKY_X", "SKY_L", "CYC_SKY"]
+# the slots behind them (csrc/rt_dev.hip.h): the small-launch ledger's (tools/exp_small.py reads those itself), then the root visits of
+# profiles/r07_root_visits.md; RT_LEDGER_ROOT=1 adds the latter to every line
+LG_TAIL = ["CYC_COPY", "CYC_JOIN", "CYC_DRAIN", "DRAIN_X", "DRAIN_L", "CYC_FLUSH"]
+LG_ROOT = ["ROOT_FULL_X", "ROOT_FULL_L", "ROOT_CULL_X", "ROOT_CULL_L", "ROOT_LEFT_X", "ROOT_LEFT_L", "ROOTF_X", "ROOTF_L"]
 
 # (config, shader, width, height, spp, bounces): a spread of block mixes -- no nodes at all (quad), environment-dominated
 # (tower), deep bounce chains (helmet at 16 bounces), primary rays only (1 bounce, debug shader), small frames whose launch
@@ -53,6 +57,8 @@ def main():
     has_ledger = hasattr(rt.lib, "rt_get_ledger")
     scenes = {}
     jobs = JOBS[:int(os.environ.get("RT_LEDGER_JOBS", len(JOBS)))]
+    if os.environ.get("RT_LEDGER_PICK"):                    # e.g. "0,12": those entries of the list only
+        jobs = [JOBS[int(i)] for i in os.environ["RT_LEDGER_PICK"].split(",")]
     for (name, shader, w, h, s, b) in jobs:
         key = (name, shader)
         if key not in scenes:
@@ -75,6 +81,11 @@ def main():
             buf = (C.c_uint64 * len(LG_NAMES))()
             assert rt.lib.rt_get_ledger(buf, len(LG_NAMES)) == 0, rt.last_error()
             out["ledger"] = {n: int(v) for n, v in zip(LG_NAMES, buf)}
+            if os.environ.get("RT_LEDGER_ROOT"):
+                names = LG_NAMES + LG_TAIL + LG_ROOT
+                buf = (C.c_uint64 * len(names))()
+                assert rt.lib.rt_get_ledger(buf, len(names)) == 0, rt.last_error()
+                out["root"] = {n: int(v) for n, v in zip(names, buf) if n in LG_ROOT}
         print(json.dumps(out), flush=True)
 
 

@@ -4,6 +4,16 @@
 #   cycles.jsonl   the same for the headline frame with shader-clock cycles per kind of block (-DRT_LEDGER=2)
 #   pmc.csv        SQ_INSTS_VALU ... per dispatch of the PRODUCT library over the same job list (rocprofv3 --pmc)
 #   ta.txt         TA-side counters of the headline frame, two per pass
+# The libraries it loads are built on the build machine beforehand (tools/build_variant.sh):
+#   DIAG=1 tools/build_variant.sh ledger  -DRT_LEDGER=1          -> tools/exp/librt_ledger.so
+#   DIAG=1 tools/build_variant.sh ledger2 -DRT_LEDGER=2          -> tools/exp/librt_ledger2.so
+# The root-visit count of profiles/r07_root_visits.md section 0 (ROOT_FULL / ROOT_CULL / ROOT_LEFT: root rounds of the node blocks)
+# needs a build that leaves the root visit to the node blocks, -DRT_ROOT_AT_NODE_BLOCKS (rt_kernels.hip), beside the ordinary one
+# (ROOTF: the visit in front of the traversal call):
+#   DIAG=1 tools/build_variant.sh ledger_rootnb -DRT_LEDGER=1 -DRT_ROOT_AT_NODE_BLOCKS
+#   RT_LIB_PATH=tools/exp/librt_ledger_rootnb.so RT_LEDGER_ROOT=1 RT_LEDGER_PICK=0,12 python3 tools/exp_ledger.py
+#   RT_LIB_PATH=tools/exp/librt_ledger.so        RT_LEDGER_ROOT=1 RT_LEDGER_PICK=0,12 python3 tools/exp_ledger.py
+# (RT_LEDGER_PICK: entries of exp_ledger.py's job list, here config #3 and the tower; RT_LEDGER_ROOT adds the "root" slots to a line.)
 set -u
 TAG=${1:-ledger}
 R=${GRAFT_REPO_ROOT:-$(pwd)}

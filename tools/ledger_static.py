@@ -125,7 +125,15 @@ def regions(blocks):
     r["regen_iter"] = q("regen_begin", ["regen_end"])
     r["s_total"] = q("s_begin", ["s_end"])
     r["s_overhead"] = r["s_total"] - sum(q(n + "_begin", [n + "_end"]) for n in inner_s)
-    r["s_to_traversal"] = q("s_end", ["round_begin", "tile_begin", "flush_begin", "s_begin"])
+    r["s_to_traversal"] = q("s_end", ["root_begin", "round_begin", "tile_begin", "flush_begin", "s_begin"])
+    # the root visit in front of the traversal call (round 7): its glue, then node_enter_few's arms as for the node block below
+    r["root_head"] = q("root_begin", ["rfew_ret1", "root_end"])
+    r["root_second_child"] = q("rfew_ret1", ["rfew_two", "root_end"])
+    r["root_2_merge"] = q("rfew_two", ["rfew_ret2", "root_end"])
+    r["root_third_child"] = q("rfew_ret2", ["rfew_four_begin", "root_end"])
+    r["root_fourth_child"] = q("rfew_four_begin", ["rfew_four_end"])
+    r["root_rank4"] = q("rfew_four_end", ["root_end"])
+    r["root_to_traversal"] = q("root_end", ["round_begin", "tile_begin", "flush_begin", "s_begin"])
     r["round"] = q("round_begin", ["leaf_begin", "node_begin", "s_begin", "flush_begin", "pop_begin"])
     stops_node = ["cullmask_begin", "nfull_begin", "nglob_begin", "nexact_begin", "nfew_begin", "node_entered", "node_end"]
     r["node_head"] = q("node_begin", stops_node)
