@@ -7,7 +7,7 @@ import os
 import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_dev.hip.h", "csrc/rt_device.h", "../include/rt_math.h")
+KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_dev.hip.h", "csrc/rt_tile.hip.h", "csrc/rt_device.h", "../include/rt_math.h")
 
 
 def hipflags():

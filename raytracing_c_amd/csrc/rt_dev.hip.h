@@ -20,16 +20,6 @@
 #define RT_BLOCK_WAVES 4
 #define RT_BLOCK_THREADS (RT_BLOCK_WAVES * 64)
 
-// counters slots
-#define CNT_PATHS 0
-#define CNT_RAYS 1
-#define CNT_NODES 2
-#define CNT_LEAVES 3
-#define CNT_SHADES 4
-#define CNT_BG 5
-#define CNT_TEXTURED 6
-#define CNT_SKIPPED_ROOT 7   // of CNT_NODES: root visits of camera paths whose tile's pyramid misses the root -- counted, not executed
-
 struct Ray3 {
   rt_v3 o, d;
   float inv_x, inv_y, inv_z;
@@ -91,7 +81,7 @@ enum {
   LG_ROOT_FULL_X, LG_ROOT_FULL_L, LG_ROOT_CULL_X, LG_ROOT_CULL_L, LG_ROOT_LEFT_X, LG_ROOT_LEFT_L, LG_ROOTF_X, LG_ROOTF_L,
   LG_N
 };
-#define RT_LEDGER_ROW 128      /* dwords per wave in g_ledger (LG_N <= 128: slots 8..135 of the counters, rt_device.h) */
+#define RT_LEDGER_ROW 128      /* dwords per wave in g_ledger (LG_N <= 128: RT_CNT_LEDGER_SLOTS of the counters, rt_device.h) */
 // The counters live in MEMORY, one row of 64 dwords per wave (g_ledger, rt_kernels.hip), bumped by lane 0 with atomics that
 // return nothing: as scalar registers they did not fit beside the kernel's own (59 of them: 286 spilled VGPRs; even a
 // dozen: 50-80), which would have measured a different kernel.  -DRT_LEDGER=1 counts blocks and lanes, =2 adds the
@@ -99,7 +89,8 @@ enum {
 #ifdef RT_LEDGER
 __device__ __forceinline__ int lane_now();
 __device__ __forceinline__ void lg_add(uint32_t *lg, int slot, uint32_t n) {
-  if (lane_now() == 0 && n != 0u) __hip_atomic_fetch_add(lg + slot, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // (lg == nullptr: a kernel without a ledger row -- the wavefront and test kernels of a ledger build of the diagnostic library)
+  if (lg && lane_now() == 0 && n != 0u) __hip_atomic_fetch_add(lg + slot, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #define LG(slot, n) lg_add(lg, (slot), (uint32_t)(n))
 #define LG_ARG , lg
@@ -1036,20 +1027,69 @@ __device__ __forceinline__ int lane_now() {
   return (int)__builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
 }
 
+// ---- the workgroup's LDS: the leading BVH nodes, then one slice per wave (rt_device.h, lds_split in rt_launch.cpp) ----
+// The node image, by all THREADS threads of the workgroup; the caller's __syncthreads() follows.
+template <int THREADS>
+__device__ __forceinline__ void lds_load_nodes(float4 *smem, const float *nodes, int n_lds) {
+  const float4 *g = reinterpret_cast<const float4 *>(nodes);
+  for (int i = threadIdx.x; i < n_lds * RT_NODE_F4; i += THREADS) {
+    int nd = i / RT_NODE_F4, q = i - nd * RT_NODE_F4;
+    smem[nd * RT_LDS_NODE_F4 + q] = g[i];
+  }
+}
+
+// A wave's slice of the kernels that render tiles (path kernel, wavefront camera and trace kernels): the perm stack, one row of 64
+// words per tree level (at least one), then the 8x8-pixel accumulator tile, 3 x u64 per pixel.  The perm row of the deepest node
+// level is never written (a leaf-level node has no node below it): it is the PYRAMID AREA, the RT_PYR_* words below.  Row 0 is free
+// while no lane of the wave traverses: the tile set-up keeps the node list of a leafless tile there (RT_LL_*, rt_tile.hip.h).
+#define RT_LDS_PERM_LEVEL_F4 (RT_LDS_PERM_LEVEL_BYTES / 16)
+#define RT_LDS_ACC_TILE_F4   (RT_LDS_ACC_TILE_BYTES / 16)
+struct WaveLds {
+  uint32_t *perm;                // the perm stack (per-lane address arithmetic: traversal_blocks)
+  unsigned long long *acc;       // the accumulator tile
+  int acc_off, pyr_off;          // byte offsets of the accumulator tile and the pyramid area from `smem`, wave-uniform: for lds_at()
+};
+__device__ __forceinline__ WaveLds wave_lds(float4 *smem, int n_lds, int depth, int wave) {
+  const int perm_f4 = (depth > 0 ? depth : 1) * RT_LDS_PERM_LEVEL_F4, slice_f4 = perm_f4 + RT_LDS_ACC_TILE_F4;
+  float4 *wave_base = smem + n_lds * RT_LDS_NODE_F4 + wave * slice_f4;
+  const int base_f4 = n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * slice_f4;
+  WaveLds L;
+  L.perm = reinterpret_cast<uint32_t *>(wave_base);
+  L.acc = reinterpret_cast<unsigned long long *>(wave_base + perm_f4);
+  L.acc_off = (base_f4 + perm_f4) * 16;
+  L.pyr_off = (base_f4 + perm_f4 - RT_LDS_PERM_LEVEL_F4) * 16;
+  return L;
+}
+// the pyramid area, as words (floats or uint32_t) from pyr_off
+#define RT_PYR_PLANE      0      // [4 q .. 4 q + 2]: outward normal of side plane q of the tile's camera-ray pyramid
+#define RT_PYR_ORIGIN     16     // [16 .. 18]: the common ray origin
+#define RT_PYR_ROOT_POP   19     // the root's populated children when there are one to four, else 0 (per wave, not per tile)
+#define RT_PYR_ROOT_FUSED 20     // root visits the wave ran in front of its traversal calls since the last tile flush
+#define RT_PYR_LEAF_CACHE 24     // 8 entries of leaf cull masks, by group & 7: (0x800000 | group) << 8 | cull mask
+#define RT_PYR_NODE_CACHE 32     // 32 entries of node cull masks, direct mapped by node & 31: (node + 1) << 8 | cull mask
+#define RT_PYR_CACHE_WORDS 40    // both caches: cleared per tile
+
+// an unpopulated child of a node: the all-zero box, whose near and far distance coincide per axis, so that it is never a
+// candidate for a NaN-free ray.
+__device__ __forceinline__ bool child_box_empty(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) {
+  return mnx == 0.0f && mny == 0.0f && mnz == 0.0f && mxx == 0.0f && mxy == 0.0f && mxz == 0.0f;
+}
+// (`nb`: the child's column of the node; rows are 8 floats apart)
+__device__ __forceinline__ bool child_box_empty(const float *nb) { return child_box_empty(nb[0], nb[8], nb[16], nb[24], nb[32], nb[40]); }
+
 // ---- pyramid culling of node blocks (tile-stream kernel) ----
-// `pyr` (LDS, per wave): outward normals of the four side planes of the tile's camera-ray pyramid at [4 q .. 4 q + 2],
-// the common ray origin at [16 .. 18].  Lane l tests child (l & 7) of LDS node `node` against plane ((l >> 3) & 3);
+// `pyr` (LDS, per wave): the pyramid area of the wave's slice, RT_PYR_PLANE and RT_PYR_ORIGIN.  Lane l tests child (l & 7) of LDS node `node` against plane ((l >> 3) & 3);
 // returns the 8-bit mask of the children that NO ray inside the pyramid can enter (outside one plane by a relative
 // margin of 1e-3, or the all-zero box of an unpopulated child): ray_aabbs_hit_8 reports a miss for each of them
 // (raytracer.c:190-230), whatever the ray's t_max.
 __device__ __forceinline__ uint32_t pyramid_cull_mask(const float4 *lds_nodes, const float *pyr, int node) {
   const int lane = lane_now();
   const float *nb = reinterpret_cast<const float *>(lds_nodes + lds_node_f4(node)) + (lane & 7);
-  const float *pl = pyr + ((lane >> 3) & 3) * 4;
-  const float ox = pyr[16], oy = pyr[17], oz = pyr[18];
+  const float *pl = pyr + RT_PYR_PLANE + ((lane >> 3) & 3) * 4;
+  const float ox = pyr[RT_PYR_ORIGIN], oy = pyr[RT_PYR_ORIGIN + 1], oz = pyr[RT_PYR_ORIGIN + 2];
   const float mnx = nb[0], mny = nb[8], mnz = nb[16], mxx = nb[24], mxy = nb[32], mxz = nb[40];
   const float nx = pl[0], ny = pl[1], nz = pl[2];
-  const bool empty = mnx == 0.0f && mny == 0.0f && mnz == 0.0f && mxx == 0.0f && mxy == 0.0f && mxz == 0.0f;
+  const bool empty = child_box_empty(mnx, mny, mnz, mxx, mxy, mxz);      // (the values read above: a second read of `nb` reorders the block's LDS reads)
   const float lox = nx * (mnx - ox), hix = nx * (mxx - ox), loy = ny * (mny - oy), hiy = ny * (mxy - oy);
   const float loz = nz * (mnz - oz), hiz = nz * (mxz - oz);
   const float nearest = fminf(lox, hix) + fminf(loy, hiy) + fminf(loz, hiz);       // smallest n . (p - o) over the box
@@ -1149,8 +1189,8 @@ __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *
 __device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const float *pyr, int g) {
   const int lane = lane_now();
   const float *tb = leaves + (size_t)g * 72 + (lane & 7);
-  const float *pl = pyr + ((lane >> 3) & 3) * 4;
-  const float ox = pyr[16], oy = pyr[17], oz = pyr[18];
+  const float *pl = pyr + RT_PYR_PLANE + ((lane >> 3) & 3) * 4;
+  const float ox = pyr[RT_PYR_ORIGIN], oy = pyr[RT_PYR_ORIGIN + 1], oz = pyr[RT_PYR_ORIGIN + 2];
   const float nx = pl[0], ny = pl[1], nz = pl[2];
   const float ax = tb[0], e1x = tb[8], e2x = tb[16], ay = tb[24], e1y = tb[32], e2y = tb[40], az = tb[48], e1z = tb[56], e2z = tb[64];
   bool outside = true;
@@ -1283,7 +1323,7 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
           const int g0 = c0 - P.last_row_offset;
           if (nG * RT_PYR_DEN >= nL * RT_PYR_NUM && nG >= RT_PYR_MIN && (uint32_t)g0 < 0x800000u) {
             float *pyr = lds_at(smem, pyr_off);
-            uint32_t *slot = reinterpret_cast<uint32_t *>(pyr) + 24 + (g0 & 7);      // 8 entries of their own, in front of the node masks'
+            uint32_t *slot = reinterpret_cast<uint32_t *>(pyr) + RT_PYR_LEAF_CACHE + (g0 & 7);      // 8 entries of their own, in front of the node masks'
             const uint32_t key = 0x800000u | (uint32_t)g0;
             const uint32_t ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)*slot);
             uint32_t cull;
@@ -1335,7 +1375,7 @@ __device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *sm
           if (c0 < pyr_nodes && nG * RT_PYR_DEN >= nN * RT_PYR_NUM && nG >= RT_PYR_MIN) {
             // the mask depends on (tile, node) only and the tile's camera rays keep coming back to the same nodes
             float *pyr = lds_at(smem, pyr_off);
-            uint32_t *slot = reinterpret_cast<uint32_t *>(pyr) + 32 + (c0 & 31);
+            uint32_t *slot = reinterpret_cast<uint32_t *>(pyr) + RT_PYR_NODE_CACHE + (c0 & 31);
             const uint32_t ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)*slot);
             if ((ce >> 8) == (uint32_t)c0 + 1u) {
               surv = 0xFFu & ~ce;
@@ -1528,5 +1568,7 @@ struct PrimaryParams {          // what primary_ray reads
   float focal_length, inv_width, inv_height, aspect;
 };
 
+
+#include "rt_tile.hip.h"      // the stages of a tile-owning kernel's outer loop
 
 #endif  // RT_DEV_HIP_H

@@ -40,11 +40,16 @@
 #define RT_TILE_PIX  64
 
 #define RT_PARK_RECORD_DWORDS (18 * 128)   /* a wave's slice of RT_KParams.park: RT_PARK_FIELDS x RT_PARK_CAP (rt_dev.hip.h) */
-#define RT_N_COUNTERS 138    /* 0..6 ray counters, 7 skipped root visits; 8..135 the block ledger of the path kernel (-DRT_LEDGER
-                              * builds, LG_* slots in rt_dev.hip.h); 136 camera paths served by the leafless loop; 137 rays whose
-                              * root visit ran in front of the traversal rounds (rt_kernels.hip) */
-#define RT_CNT_LEAFLESS 136
-#define RT_CNT_FUSED_ROOT 137
+/* RT_KParams.counters, one array of u64 per launch: index names for the kernels that add and the host units that read */
+enum {
+  RT_CNT_PATHS = 0, RT_CNT_RAYS, RT_CNT_NODES, RT_CNT_LEAVES, RT_CNT_SHADES, RT_CNT_BG, RT_CNT_TEXTURED,
+  RT_CNT_SKIPPED_ROOT,         /* of RT_CNT_NODES: root visits of camera paths whose tile's pyramid misses the root -- counted, not executed */
+  RT_CNT_LEDGER,               /* .. + RT_CNT_LEDGER_SLOTS: the block ledger of the path kernel (-DRT_LEDGER builds, LG_* slots in rt_dev.hip.h) */
+  RT_CNT_LEAFLESS = 136,       /* camera paths served by the leafless loop (rt_kernels.hip) */
+  RT_CNT_FUSED_ROOT,           /* rays whose root visit ran in front of the traversal rounds (rt_kernels.hip) */
+  RT_N_COUNTERS
+};
+#define RT_CNT_LEDGER_SLOTS (RT_CNT_LEAFLESS - RT_CNT_LEDGER)
 
 /* triangle record, 28 floats:
  *  [0..2] face normal      [3]  material id (int bits)
@@ -162,7 +167,7 @@ typedef struct {
   int32_t      grab;           /* rays a wave takes per atomic on `head`                                                  */
   int32_t      exit_lanes;     /* finished lanes that end a traversal call while rays are left to hand out                */
 } RT_QParams;
-#define RT_QUERY_COUNTERS 4
+enum { RT_QCNT_RAYS = 0, RT_QCNT_HITS, RT_QCNT_NODES, RT_QCNT_LEAVES, RT_QUERY_COUNTERS };      /* RT_QParams.counters */
 #define RT_HIT_DWORDS     22   /* RT_Device_Hit (rt_hip.h), 88 bytes */
 
 /* First-hit feature buffers (rt_features_kernel, rt_features.hip; include/rt_hip.h rt_render_accumulate_features): what one

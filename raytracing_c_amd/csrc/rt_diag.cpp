@@ -158,14 +158,14 @@ extern "C" void rt_diag_multi_fault(i32 no_peer, i32 failing_slot) {
 bool fault_no_peer() { return (g_multi_fault.load() & 1) != 0; }
 bool fault_fails(int slot) { return (g_multi_fault.load() >> 8) == slot + 1; }
 
-// Block ledger of a -DRT_LEDGER build of the tile-stream kernel (LG_* slots, rt_dev.hip.h): out[0 .. n) = counters[8 .. 8 + n).
+// Block ledger of a -DRT_LEDGER build of the tile-stream kernel (LG_* slots, rt_dev.hip.h): out[0 .. n) = counters[RT_CNT_LEDGER .. + n).
 extern "C" int rt_get_ledger(u64 *out, i32 n) {
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
-  if (ensure_device(D) != 0 || !out || n < 0 || n > RT_N_COUNTERS - 8) return -1;
+  if (ensure_device(D) != 0 || !out || n < 0 || n > RT_CNT_LEDGER_SLOTS) return -1;
   unsigned long long c[RT_N_COUNTERS];
   if (read_counters(D, c) != 0) return -1;
-  for (int i = 0; i < n; i++) out[i] = c[8 + i];
+  for (int i = 0; i < n; i++) out[i] = c[RT_CNT_LEDGER + i];
   return 0;
 }
 

@@ -111,14 +111,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_features_kernel(RT_KParams P
   const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
   uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * perm_f4);
   pow24_lds_init((int)threadIdx.x);
-  {
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
-    __syncthreads();
-  }
+  lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
+  __syncthreads();
   const int leaf_level = P.depth - 1;
   const int shift = F.shift;
   uint32_t next = 0, end = 0;                                     // the wave's current grab: units [next, end)

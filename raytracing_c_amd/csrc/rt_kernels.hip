@@ -58,16 +58,9 @@ __global__ void rt_ledger_reduce_kernel(unsigned long long *counters) {
   if (slot >= LG_N || slot >= RT_LEDGER_ROW) return;
   unsigned long long sum = 0ull;
   for (int w = 0; w < RT_LEDGER_WAVES; w++) sum += g_ledger[w * RT_LEDGER_ROW + slot];
-  counters[8 + slot] = sum;
+  counters[RT_CNT_LEDGER + slot] = sum;
 }
 #endif
-
-// Multi-view launches (VIEWS, rt_render_views): the tile list is n_views x n_local_chunks x 16 tiles long, tile t renders view
-// t / tiles_per_view.  A wave keeps only the pointer to its tile's view record (scalar, constant address space) and reads the
-// camera and seed from it where the one-view kernel reads them from the kernel arguments.
-typedef const RT_KView __attribute__((address_space(4))) *RT_KViewP;
-template <bool VIEWS> struct CamSrc { typedef RT_KArgs type; };       // where camera and seed come from
-template <> struct CamSrc<true> { typedef RT_KViewP type; };
 
 template <int WAVES, bool LDSN, int MIN_WAVES_PER_SIMD, bool SHORT_DIV, bool VIEWS>
 __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel_stream(RT_KParams P) {
@@ -76,17 +69,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   const int wave = threadIdx.x >> 6;
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  float4 *wave_base = smem + n_lds * RT_LDS_NODE_F4 + wave * (perm_f4 + 96);
-  uint32_t *perm = reinterpret_cast<uint32_t *>(wave_base);
-  unsigned long long *acc = reinterpret_cast<unsigned long long *>(wave_base + perm_f4);
-  // the perm row of the deepest node level is never written (a leaf-level node has no node below it): it holds the
-  // tile's camera-ray pyramid
-  const int acc_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4) * 16;
-  const int pyr_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4 - 16) * 16;
-  // (the pyramid: planes and origin in floats 0..18, the root's populated children at 19 (per wave, not per tile) and the root visits the
-  //  wave ran in front of its traversal calls at 20 (flushed with the tile), 8 cache entries of leaf masks at 24..31 (0x800000 | group) << 8 | cull mask, then 128 bytes: 32 cache
-  //  entries of node masks, direct mapped by node: (node + 1) << 8 | cull mask)
+  const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the wave's LDS slice: perm stack, pyramid area, accumulator tile
+  uint32_t *perm = L.perm;
+  unsigned long long *acc = L.acc;
+  const int acc_off = L.acc_off, pyr_off = L.pyr_off;
 
 #ifdef RT_LEDGER
   uint32_t *lg = g_ledger + (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + wave) * RT_LEDGER_ROW;
@@ -98,11 +84,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   pow24_lds_init((int)threadIdx.x);
   if (LDSN) {
     LGT0();
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
+    lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
     __syncthreads();          // the only workgroup barrier of the kernel; waves are independent afterwards
     LGT1(LG_CYC_COPY);
   } else {
@@ -115,22 +97,20 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 
   // ---- the root's populated children: the only ones a ray's root visit has to test (in front of the traversal call, below) ----
   // The reference builder fills a tree of fixed capacity, so the root of a small scene has children without a triangle below them:
-  // all-zero boxes, whose near and far distance coincide per axis and which are therefore never a candidate for a NaN-free ray
-  // (pyramid_cull_mask's `empty`).  Read from the LDS node image of THIS launch, not kept on the host: a refit rewrites the boxes on
-  // the device.  0 = the root visit is left to the node blocks: more than four populated children (node_enter_few's
+  // all-zero boxes, never a candidate for a NaN-free ray (child_box_empty).  Read from the LDS node image of THIS launch, not kept
+  // on the host: a refit rewrites the boxes on the device.  0 = the root visit is left to the node blocks: more than four populated children (node_enter_few's
   // limit), no root in LDS, a tree of depth 0.  A word of the wave's LDS slice, read where it is used, not a scalar register.
   if (LDSN) {
     uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
     bool populated = false;
     if (lane_now() < 8 && cold_args()->n_lds_nodes > 0 && cold_args()->depth > 0) {
-      const float *nb = lds_at(smem, 0) + lane_now();      // child `lane` of node 0: rows are 8 floats apart
-      populated = !(nb[0] == 0.0f && nb[8] == 0.0f && nb[16] == 0.0f && nb[24] == 0.0f && nb[32] == 0.0f && nb[40] == 0.0f);
+      populated = !child_box_empty(lds_at(smem, 0) + lane_now());      // child `lane` of node 0
     }
     const uint32_t pm = (uint32_t)__ballot(populated) & 0xFFu;
 #ifdef RT_ROOT_AT_NODE_BLOCKS      /* (ledger builds that count the root rounds of the node blocks: profiles/r07_root_visits.md) */
-    if (lane_now() == 0) { pw[19] = 0u; pw[20] = 0u; }
+    if (lane_now() == 0) { pw[RT_PYR_ROOT_POP] = 0u; pw[RT_PYR_ROOT_FUSED] = 0u; }
 #else
-    if (lane_now() == 0) { pw[19] = __popc(pm) <= 4 ? pm : 0u; pw[20] = 0u; }
+    if (lane_now() == 0) { pw[RT_PYR_ROOT_POP] = __popc(pm) <= 4 ? pm : 0u; pw[RT_PYR_ROOT_FUSED] = 0u; }
 #endif
   }
 
@@ -156,196 +136,32 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     // ---------------- take a tile: own one from the queue, or join one that still has units ----------------
     LGT0();
     LGM("tile_begin");
-    int tile_idx = -1;
-    if (queue_open) {
-      RT_KArgs A = cold_args();
-      uint32_t pos = 0;
-      if (lane == 0) pos = atomicAdd(A->work_head, 1u);
-      pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-      const uint32_t *order = A->order;
-      if (pos < (uint32_t)A->n_tiles) tile_idx = order ? (int)order[pos] : (int)pos;
-      else queue_open = false;
-    }
+    int tile_idx = queue_open ? take_queue_tile(lane, queue_open) : -1;
     if (tile_idx < 0) {
       if (steal_tries >= RT_STEAL_TRIES) break;
       steal_tries += 1;
       LG(LG_JOIN_X, 1);
-      LGT0();
-      // two-level scan with agent-scope loads: groups of 64 tiles that still have an open tile (open_groups[g] > 0),
-      // then the tiles of one such group.  Start positions differ per wave so that joiners spread over the open tiles.
-      RT_KArgs A = cold_args();
-      const int n_tiles = A->n_tiles;
-      const uint32_t *open_groups = A->open_groups, *tile_next = A->tile_next;
-      const int n_groups = (n_tiles + 63) >> 6;
-      const int g_rounds = (n_groups + 63) >> 6;
-      const uint32_t hsh = ((uint32_t)wave_id * 2654435761u + (uint32_t)steal_tries * 40503u) >> 8;
-      const int g_start = (int)(hsh % (uint32_t)g_rounds);
-      for (int i = 0; i < g_rounds && tile_idx < 0; i++) {
-        int r = g_start + i;
-        if (r >= g_rounds) r -= g_rounds;
-        int g = r * 64 + lane;
-        uint32_t n_open = 0;
-        if (g < n_groups) n_open = __hip_atomic_load(&open_groups[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned long long gm = __ballot(n_open != 0u);
-        while (gm && tile_idx < 0) {
-          int nth = (int)((hsh >> 6) % (uint32_t)__popcll(gm));
-          unsigned long long m = gm;
-          for (int k = 0; k < nth; k++) m &= m - 1ull;
-          int gl = (int)__builtin_ctzll(m);
-          gm &= ~(1ull << gl);
-          int cand = (r * 64 + gl) * 64 + lane;
-          uint32_t taken = 0xFFFFFFFFu;
-          if (cand < n_tiles) taken = __hip_atomic_load(&tile_next[cand], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          unsigned long long open = __ballot(taken < n_chunks_tile);
-          if (open) {
-            // two random open tiles of the group, the one with more units left: fewer, longer joins (every join ends with
-            // a drain of the paths in flight)
-            const int n_open_tiles = (int)__popcll(open);
-            int best = 0;
-            uint32_t best_taken = 0xFFFFFFFFu;
-#pragma unroll
-            for (int c = 0; c < RT_JOIN_CHOICES; c++) {
-              int nt = (int)(((hsh >> 12) * (uint32_t)(2 * c + 1) + (uint32_t)c * 7u) % (uint32_t)n_open_tiles);
-              unsigned long long mm = open;
-              for (int k = 0; k < nt; k++) mm &= mm - 1ull;
-              const int pk_lane = (int)__builtin_ctzll(mm);
-              const uint32_t tk = (uint32_t)__builtin_amdgcn_readlane((int)taken, pk_lane);
-              if (tk < best_taken) { best_taken = tk; best = pk_lane; }
-            }
-            tile_idx = cand - lane + best;
-          }
-        }
-      }
-      LGT1(LG_CYC_JOIN);
+      tile_idx = join_open_tile(lane, wave_id, steal_tries, n_chunks_tile LG_ARG);
       if (tile_idx < 0) break;                      // nothing left to join
     }
 
     int tile_x0, tile_y0;
     RT_KViewP vrec = nullptr;             // VIEWS: the record of this tile's view
-    {
-      RT_KArgs A = cold_args();
-      int vt = tile_idx;                  // the tile within its view
-      if constexpr (VIEWS) {
-        const int tu = __builtin_amdgcn_readfirstlane(tile_idx);
-        const uint32_t view = (uint32_t)tu / (uint32_t)A->tiles_per_view;
-        vt = tu - (int)view * A->tiles_per_view;
-        vrec = (RT_KViewP)A->views + view;
-      }
-      const int lchunk = vt >> 4, sub = vt & 15;
-      const int chunk = A->local_chunks[lchunk];
-      const int chunks_x = A->chunks_x;
-      tile_x0 = (chunk % chunks_x) * 32 + (sub & 3) * 8;
-      tile_y0 = (chunk / chunks_x) * 32 + (sub >> 2) * 8;
-      if (tile_x0 >= A->width || tile_y0 >= A->height) {
-        // tile entirely outside the image: mark it exhausted (once) so that no wave tries to join it
-        if (lane == 0) {
-          uint32_t old = atomicMax(&A->tile_next[tile_idx], n_chunks_tile);
-          if (old < n_chunks_tile) atomicSub(&A->open_groups[tile_idx >> 6], 1u);
-        }
-        continue;
-      }
-    }
-    // ---- can a camera ray of this tile touch the scene at all? ----
-    // The primary rays of the tile share the origin and lie inside the pyramid through the corners of the tile's pixel
-    // footprint.  If every populated child box of the ROOT lies outside one of the pyramid's four side planes -- by a
-    // relative margin of 1e-3, a thousand times the rounding error of the slab test -- then ray_aabbs_hit_8 returns
-    // "no candidate" for every one of them (raytracer.c:190-230, :459-472): the ray costs one node visit and goes to the
-    // environment.  Such rays skip the root block here and are counted as that one visit.  (Lanes 0..7 test one child
-    // box each; only rays with finite reciprocal direction take the shortcut, see ray_setup.)
+    if (!tile_origin<VIEWS>(lane, tile_idx, n_chunks_tile, tile_x0, tile_y0, vrec)) continue;      // a tile outside the image
+    // can a camera ray of the tile touch a child of the root at all?  (and the tile's pyramid, for the node and leaf blocks)
     bool tile_root_miss = false;
     if (leaf_level >= 0) {
-      RT_KArgs A = cold_args();
       typename CamSrc<VIEWS>::type S;
-      if constexpr (VIEWS) S = vrec; else S = A;
-      const float m = 0.05f;                                   // footprint margin in pixels
-      const float ux0 = ((float)tile_x0 - 0.5f - m) * 2.0f * A->inv_width - 1.0f;
-      const float ux1 = ((float)tile_x0 + 7.5f + m) * 2.0f * A->inv_width - 1.0f;
-      const float uy0 = ((float)tile_y0 - 0.5f - m) * 2.0f * A->inv_height - 1.0f;
-      const float uy1 = ((float)tile_y0 + 7.5f + m) * 2.0f * A->inv_height - 1.0f;
-      const float asp = A->aspect, fl = S->focal_length;
-      rt_v3 c[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        float cx = ((q == 1 || q == 2) ? ux1 : ux0) * asp, cy = -((q >= 2) ? uy1 : uy0), cz = -fl;
-        c[q] = rt_v3_make(S->cam[0][0] * cx + S->cam[0][1] * cy + S->cam[0][2] * cz,
-                          S->cam[1][0] * cx + S->cam[1][1] * cy + S->cam[1][2] * cz,
-                          S->cam[2][0] * cx + S->cam[2][1] * cy + S->cam[2][2] * cz);
-      }
-      const rt_v3 o = rt_v3_make(S->cam[0][3], S->cam[1][3], S->cam[2][3]);
-      rt_v3 pn[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        rt_v3 n = rt_v3_cross(c[q], c[(q + 1) & 3]);
-        if (rt_v3_dot(n, c[(q + 2) & 3]) > 0.0f) n = rt_v3_scale(n, -1.0f);      // outward: the opposite corner is inside
-        pn[q] = n;
-      }
-      float *pyr = lds_at(smem, pyr_off);
-      if (lane == 0) {                                         // the pyramid of this tile, for the node blocks
-#pragma unroll
-        for (int q = 0; q < 4; q++) { pyr[q * 4 + 0] = pn[q].x; pyr[q * 4 + 1] = pn[q].y; pyr[q * 4 + 2] = pn[q].z; }
-        pyr[16] = o.x; pyr[17] = o.y; pyr[18] = o.z;
-      }
-      if (lane < 40) reinterpret_cast<uint32_t *>(pyr)[24 + lane] = 0u;      // the cull masks found for this tile so far
-      bool may_hit = false;
-      if (lane < 8) {
-        const float *nb = P.nodes + lane;                      // child `lane` of node 0: rows are 8 floats apart
-        rt_v3 lo = rt_v3_make(nb[0] - o.x, nb[8] - o.y, nb[16] - o.z);
-        rt_v3 hi = rt_v3_make(nb[24] - o.x, nb[32] - o.y, nb[40] - o.z);
-        const bool empty = nb[0] == 0.0f && nb[8] == 0.0f && nb[16] == 0.0f && nb[24] == 0.0f && nb[32] == 0.0f && nb[40] == 0.0f;
-        bool outside = empty;                                  // the all-zero box of an unpopulated child never hits
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          rt_v3 n = pn[q];
-          float lox = n.x * lo.x, hix = n.x * hi.x, loy = n.y * lo.y, hiy = n.y * hi.y, loz = n.z * lo.z, hiz = n.z * hi.z;
-          float nearest = fminf(lox, hix) + fminf(loy, hiy) + fminf(loz, hiz);     // smallest n . (p - o) over the box
-          float extent = fmaxf(fabsf(lox), fabsf(hix)) + fmaxf(fabsf(loy), fabsf(hiy)) + fmaxf(fabsf(loz), fabsf(hiz));
-          // (+ the placement error of a fused slab distance, see pyramid_cull_mask)
-          float coarse = fabsf(n.x) * (fabsf(o.x) + fmaxf(fabsf(nb[0]), fabsf(nb[24]))) + fabsf(n.y) * (fabsf(o.y) + fmaxf(fabsf(nb[8]), fabsf(nb[32]))) +
-                         fabsf(n.z) * (fabsf(o.z) + fmaxf(fabsf(nb[16]), fabsf(nb[40])));
-          if (nearest > 1e-3f * extent + 1e-6f * coarse) outside = true;        // (NaN compares false: not outside)
-        }
-        may_hit = !outside;
-      }
-      tile_root_miss = __ballot(may_hit) == 0ull;
+      if constexpr (VIEWS) S = vrec; else S = cold_args();
+      tile_root_miss = tile_pyramid(S, P.nodes, smem, pyr_off, lane, tile_x0, tile_y0);
     }
-    // ---- does the pyramid, pruned through the tree, reach a leaf group at all? ----
-    // Breadth-first from the root with the node blocks' own plane test (pyramid_cull_mask on the LDS nodes): the surviving
-    // children of a listed node join the list; a surviving child that is a leaf group ends the walk.  A tile whose walk ends
-    // without one is LEAFLESS: every child box that a NaN-free camera ray of the tile can enter is a listed node, none of them
-    // leads to a triangle, so the ray's outcome is known -- no hit -- and only its node visits remain to be counted (the
-    // leafless form of the batch loop below).  Caps: RT_LEAFLESS_MAX listed nodes, 4 survivors per node (node_enter_few's
-    // limit), every listed node LDS resident; a tile over a cap is an ordinary tile.  The list lives in row 0 of the wave's perm
-    // stack, which is free while no lane of the wave traverses: entry i >= 1 at [i] = byte offset of (parent node, child slot) in
-    // the LDS node image | index of the parent in the list << 20 | 1 << 31 (marks an entry), the node itself at [RT_LEAFLESS_MAX + i].
-#define RT_LEAFLESS_MAX 8
-    int n_list = 0;                       // listed nodes of a leafless tile (the root counts); 0: not leafless
+    // does the pyramid, pruned through the tree, reach a leaf group at all?  n_list: listed nodes of a LEAFLESS tile, 0: not leafless
     // (the launch constants through empty asm: tests and offsets formed from them here are not hoisted out of the tile loop into
     //  scalar registers that live, and spill, for the whole kernel)
+    int n_list = 0;
     int ll_levels = leaf_level, ll_nodes = pyr_nodes, ll_leaf0 = P.last_row_offset;
     asm volatile("" : "+s"(ll_levels), "+s"(ll_nodes), "+s"(ll_leaf0));
-    if (ll_levels >= 1 && ll_nodes > 0 && !tile_root_miss) {
-      const float *pyr = lds_at(smem, pyr_off);
-      uint32_t *list = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off) - ll_levels * (RT_LDS_PERM_LEVEL_BYTES / 4));      // row 0 of `perm`
-      n_list = 1;
-      for (int head = 0; head < n_list; head++) {
-        const int nd = head ? __builtin_amdgcn_readfirstlane((int)list[RT_LEAFLESS_MAX + head]) : 0;
-        const uint32_t surv = 0xFFu & ~pyramid_cull_mask(lds_nodes, pyr, nd);
-        // into the (tile, node) mask cache of the node blocks: the root visit in front of the traversal finds the root's there
-        if (lane_now() == 0) reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off))[32 + (nd & 31)] = ((uint32_t)(nd + 1) << 8) | (0xFFu & ~surv);
-        if (surv) {
-          const int ns = (int)__popc(surv);
-          // children that are leaf groups, or nodes outside the LDS image (its last node's children at the most), or a cap
-          if (8 * nd + 1 >= ll_leaf0 || 8 * nd + 8 >= ll_nodes || ns > 4 || n_list + ns > RT_LEAFLESS_MAX) { n_list = 0; break; }
-          const int k = lane_now();             // lane k < 8: child k
-          if (k < 8 && ((surv >> k) & 1u)) {
-            const int at = n_list + (int)__popc(surv & ((1u << k) - 1u));
-            list[at] = (uint32_t)(nd * RT_LDS_NODE_BYTES + k * 4) | ((uint32_t)head << 20) | 0x80000000u;
-            list[RT_LEAFLESS_MAX + at] = (uint32_t)(8 * nd + 1 + k);
-          }
-          n_list += ns;
-        }
-      }
-    }
+    if (ll_levels >= 1 && ll_nodes > 0 && !tile_root_miss) n_list = leafless_walk(smem, lds_nodes, pyr_off, ll_levels, ll_nodes, ll_leaf0);
     const uint32_t rays_before = w_rays;
     LG(LG_TILE_X, 1);
     LGM("tile_end");
@@ -363,14 +179,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     HitRec hit;
     hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
 
-    // The tile hands out UNITS (2 pixels x one block of samples = 128 paths at 64 samples, lanes on one or two
-    // pixels).  A wave grabs `grab_max` consecutive units per atomic while the tile has plenty left, fewer towards its
-    // end: what a wave still holds when the launch runs dry is its tail.  Current unit (wave-uniform): paths
-    // [c_next, c_end) at pixels (c_x0 .. c_x0 + 1, c_y), samples from c_s0.
+    // the tile's units as this wave holds them (grab_units, unit_decode)
     bool tile_open = true;
-    int  c_next = 0, c_end = 0, c_x0 = 0, c_y = 0, c_pix0 = 0, c_s0 = 0;
-    uint32_t u_cur = 0, u_end = 0, grab = queue_open ? (uint32_t)cold_args()->grab_max : 1u;
-    bool took_any = false;
+    TileUnits U;
+    tile_units_init(U, queue_open);
     int  n_parked = 0;                   // hits of this tile waiting in the wave's slice of `park`
     uint32_t *park = cold_args()->park;
 
@@ -404,34 +216,28 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       uint32_t *tile_next = A->tile_next, *open_groups = A->open_groups;
       uint32_t n_sky = 0;                 // paths served here: their root visit is COUNTED (like the oracle's) but not executed
       // lane i: entry i of the tile's node list, 0 past its end (the pass below stops there: no count in a scalar register)
-      const uint32_t *list = reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off)) - ll_levels * (RT_LDS_PERM_LEVEL_BYTES / 4);
-      const uint32_t list_entry = (n_list > 1 && lane_now() < n_list) ? list[lane_now() & (RT_LEAFLESS_MAX - 1)] : 0u;
+      const uint32_t *list = leafless_list(smem, pyr_off, ll_levels);
+      const uint32_t list_entry = (n_list > 1 && lane_now() < n_list) ? list[RT_LL_ENTRY + (lane_now() & (RT_LL_MAX - 1))] : 0u;
       for (;;) {
-        if (c_next >= c_end) {
-          if (u_cur + 1u < u_end) {
-            u_cur += 1u;
+        if (U.c_next >= U.c_end) {
+          if (U.u_cur + 1u < U.u_end) {
+            U.u_cur += 1u;
           } else {
+            // (grab_units() written out: as a call, with the arguments this loop holds, it shifts the SGPR spills of the VIEWS instances)
             uint32_t u0 = 0;
-            if (lane == 0) u0 = atomicAdd(&tile_next[tile_idx], grab);
+            if (lane == 0) u0 = atomicAdd(&tile_next[tile_idx], U.grab);
             u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);
             if (u0 >= n_chunks_tile) { tile_open = false; break; }
-            u_cur = u0;
-            u_end = u0 + grab < n_chunks_tile ? u0 + grab : n_chunks_tile;
-            if (u_end == n_chunks_tile && lane == 0) atomicSub(&open_groups[tile_idx >> 6], 1u);
+            U.u_cur = u0;
+            U.u_end = u0 + U.grab < n_chunks_tile ? u0 + U.grab : n_chunks_tile;
+            if (U.u_end == n_chunks_tile && lane == 0) atomicSub(&open_groups[tile_idx >> 6], 1u);
             if (t_wave_start) t_last_grab = __builtin_amdgcn_s_memrealtime();
             LG(LG_GRAB_X, 1);
-            const uint32_t left = n_chunks_tile - u_end;
-            grab = left >= 8u * gmax ? gmax : (left >= 8u && gmax >= 2u ? 2u : 1u);
-            took_any = true;
+            const uint32_t left = n_chunks_tile - U.u_end;
+            U.grab = left >= 8u * gmax ? gmax : (left >= 8u && gmax >= 2u ? 2u : 1u);
+            U.took_any = true;
           }
-          const uint32_t grp = u_cur >> 2, pair = u_cur & 3u;
-          const uint32_t row = grp / n_sb, sb = grp - row * n_sb;
-          c_x0 = tile_x0 + (int)pair * 2;
-          c_y = tile_y0 + (int)row;
-          c_pix0 = (int)row * 8 + (int)pair * 2;
-          c_s0 = sample_first + (int)(sb << shift);
-          c_next = 0;
-          c_end = (c_y < height && c_x0 < width) ? unit_paths : 0;
+          unit_decode(U, tile_x0, tile_y0, shift, unit_paths, n_sb, sample_first, width, height);
           continue;
         }
         // RT_SKY_PATHS paths per lane and iteration.  Two or three -- independent chains of primary ray -> environment lookup for
@@ -444,7 +250,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 #endif
         LGM("sky_begin");
         LGT0();
-        const int avail = c_end - c_next;
+        const int avail = U.c_end - U.c_next;
         const int take = avail < 64 * RT_SKY_PATHS ? avail : 64 * RT_SKY_PATHS;
         const int l = lane_now();
         bool valid[RT_SKY_PATHS];
@@ -455,14 +261,14 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 #pragma unroll
         for (int q = 0; q < RT_SKY_PATHS; q++) {
           const int kq = l + 64 * q;
-          const int k = c_next + kq;
+          const int k = U.c_next + kq;
           pxs[q] = k >> shift;
-          const int sm = c_s0 + (k & ((1 << shift) - 1));
-          const int x = c_x0 + pxs[q];
+          const int sm = U.c_s0 + (k & ((1 << shift) - 1));
+          const int x = U.c_x0 + pxs[q];
           valid[q] = kq < take && x < width && sm < sample_end;
           rt_v3 o = rt_v3_make(0, 0, 0);
           dirs[q] = rt_v3_make(0, 0, 1);
-          if (valid[q]) primary_ray(PP, x, c_y, sm, o, dirs[q]);
+          if (valid[q]) primary_ray(PP, x, U.c_y, sm, o, dirs[q]);
           ray_setup<SHORT_DIV>(rs[q], o, dirs[q]);
           slow = slow || (valid[q] && !rs[q].fast);
         }
@@ -496,7 +302,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           if (valid[q]) {
             const rt_v3 bg = background_lookup(SP, dirs[q]);
             const rt_v3 radiance = rt_v3_mul_add(bg, rt_v3_make(1, 1, 1), rt_v3_make(0, 0, 0));      // tint 1, emission 0 (raytracer.c:554)
-            unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + (c_pix0 + pxs[q]) * 6);
+            unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + (U.c_pix0 + pxs[q]) * 6);
             atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
             atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
             atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
@@ -506,13 +312,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         w_paths += nv; w_rays += nv; w_nodes += nv; w_bgs += nv;      // (the skipped root visit counts, as in the general loop)
         n_sky += nv;
         LG(LG_SKY_X, 1); LG(LG_SKY_L, nv);
-        c_next += take;
+        U.c_next += take;
         LGT1(LG_CYC_SKY);
         LGM("sky_end");
       }
-      // counters[CNT_SKIPPED_ROOT]: node visits that are counted but not executed (bench.py's roofline footnote)
+      // counters[RT_CNT_SKIPPED_ROOT]: node visits that are counted but not executed (bench.py's roofline footnote)
       // counters[RT_CNT_LEAFLESS]: paths of leafless tiles served here; their root visits are executed, not skipped
-      if (n_sky != 0u && lane == 0) atomicAdd(cold_args()->counters + (tile_root_miss ? CNT_SKIPPED_ROOT : RT_CNT_LEAFLESS), (unsigned long long)n_sky);
+      if (n_sky != 0u && lane == 0) atomicAdd(cold_args()->counters + (tile_root_miss ? RT_CNT_SKIPPED_ROOT : RT_CNT_LEAFLESS), (unsigned long long)n_sky);
     }
 
     for (;;) {
@@ -647,65 +453,39 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           LGM("regen_begin");
           while (need) {
             LG(LG_REGEN_X, 1);
-            if (c_next >= c_end) {
-              if (u_cur + 1u < u_end) {
-                u_cur += 1u;
+            if (U.c_next >= U.c_end) {
+              if (U.u_cur + 1u < U.u_end) {
+                U.u_cur += 1u;
               } else {
-                uint32_t u0 = 0;
-                if (lane == 0) u0 = atomicAdd(&A->tile_next[tile_idx], grab);
-                u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);
-                if (u0 >= n_chunks_tile) {
+                if (!grab_units(lane, tile_idx, n_chunks_tile, A->tile_next, A->open_groups, (uint32_t)A->grab_max, U, t_wave_start, t_last_grab LG_ARG)) {
                   tile_open = false;
                   LGD0((int)__popcll(__ballot(phase != PH_NEED || got)) + n_parked);      // (ledger builds: the tile's drain starts here)
                   break;
                 }
-                u_cur = u0;
-                u_end = u0 + grab < n_chunks_tile ? u0 + grab : n_chunks_tile;
-                // exactly one wave receives the tile's last unit: it closes the tile in the group summary
-                if (u_end == n_chunks_tile && lane == 0) atomicSub(&A->open_groups[tile_idx >> 6], 1u);
-                LG(LG_GRAB_X, 1);
-                if (t_wave_start) t_last_grab = __builtin_amdgcn_s_memrealtime();
-                // next grab: `grab_max` units while the tile has plenty left, fewer towards its end.
-                // (A launch-wide count of the remaining units would be the better guide, but a counter that every grab
-                // updates -- one address or 64 shards of one line -- made the frame 2x slower: measured, removed.)
-                const uint32_t left = n_chunks_tile - u_end;
-                const uint32_t gmax = (uint32_t)A->grab_max;
-                grab = left >= 8u * gmax ? gmax : (left >= 8u && gmax >= 2u ? 2u : 1u);
-                took_any = true;
               }
-              // unit u -> (row, sample block, pixel pair): all sample blocks of a row before the next row, so a
-              // pixel's texture / geometry footprint is touched in one burst
-              const uint32_t grp = u_cur >> 2, pair = u_cur & 3u;
-              const uint32_t n_sb = (uint32_t)A->n_sample_blocks;
-              const uint32_t row = grp / n_sb, sb = grp - row * n_sb;
-              c_x0 = tile_x0 + (int)pair * 2;
-              c_y = tile_y0 + (int)row;
-              c_pix0 = (int)row * 8 + (int)pair * 2;
-              c_s0 = A->sample_first + (int)(sb << shift);
-              c_next = 0;
-              c_end = (c_y < A->height && c_x0 < width) ? unit_paths : 0;      // units outside the image have no paths
+              unit_decode(U, tile_x0, tile_y0, shift, unit_paths, (uint32_t)A->n_sample_blocks, A->sample_first, width, A->height);
               continue;
             }
             const int n_need = (int)__popcll(need);
-            const int avail = c_end - c_next;
+            const int avail = U.c_end - U.c_next;
             const int take = n_need < avail ? n_need : avail;
             // set bits of `need` below this lane (v_mbcnt: no lane mask kept in registers)
             const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
             bool valid = false;
             if (phase == PH_NEED && !got && rank < take) {
               // k -> (pixel of the row, sample of the chunk), pixel-major: the lanes of a wave stay on a few pixels
-              int k = c_next + rank;
+              int k = U.c_next + rank;
               int px = k >> shift;
-              int sm = c_s0 + (k & ((1 << shift) - 1));
-              int x = c_x0 + px;
+              int sm = U.c_s0 + (k & ((1 << shift) - 1));
+              int x = U.c_x0 + px;
               if (x < width && sm < sample_end) {
                 valid = true;
-                if (SP.max_bounces > 0) { got = true; gx = x; gy = c_y; gs = sm; gp = c_pix0 + px; }
+                if (SP.max_bounces > 0) { got = true; gx = x; gy = U.c_y; gs = sm; gp = U.c_pix0 + px; }
                 // max_bounces == 0: the path exists and is black (the loop of raytracer.c:512 runs zero times)
               }
             }
             w_paths += (uint32_t)__popcll(__ballot(valid));
-            c_next += take;
+            U.c_next += take;
             need = __ballot(phase == PH_NEED && !got);
           }
           LGM("regen_end");
@@ -744,9 +524,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           dirty = 0;
           live = 0;
           // (at level -1 the word holds no children yet: 1 tells the root visit below that it serves this ray -- the ray is NaN-free and
-          //  the root has one to four populated children (pyr[19]); the LDS read hides behind the ray set-up here, and a scene whose
+          //  the root has one to four populated children (RT_PYR_ROOT_POP); the LDS read hides behind the ray set-up here, and a scene whose
           //  root the visit does not serve pays one ballot per traversal call for it, no LDS round trip)
-          cur = (LDSN && ray.fast && reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off))[19] != 0u) ? 1u : 0u;
+          cur = (LDSN && ray.fast && reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off))[RT_PYR_ROOT_POP] != 0u) ? 1u : 0u;
           level = -1;
           node = 0;
           child = (leaf_level >= 0) ? 0 : P.last_row_offset;
@@ -760,7 +540,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         {
           const uint32_t n_skip = (uint32_t)__popcll(__ballot(skip_root));
           w_nodes += n_skip;
-          if (n_skip != 0u && lane == 0) atomicAdd(cold_args()->counters + CNT_SKIPPED_ROOT, (unsigned long long)n_skip);   // (rare: a sky tile outside the sky loop)
+          if (n_skip != 0u && lane == 0) atomicAdd(cold_args()->counters + RT_CNT_SKIPPED_ROOT, (unsigned long long)n_skip);   // (rare: a sky tile outside the sky loop)
         }
         LGM("s_end");
         LGT1(LG_CYC_S);
@@ -777,12 +557,12 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       // ================= the root visit of the rays that the S block started =================
       // Every such ray sits at the root (level -1, PH_NODE) and would take the first traversal round for it, camera rays in a culled
       // block of their own and bounce rays in a full one: 8 slab tests and the rank order of 8, where only the root's POPULATED
-      // children can be candidates.  With at most four of those (the word at pyr[19]) the visit runs here, for camera and bounce
+      // children can be candidates.  With at most four of those (the word RT_PYR_ROOT_POP of the pyramid area) the visit runs here, for camera and bounce
       // rays together, as node_enter_few() over a wave-uniform set: the populated children, less those the tile's pyramid cannot
       // touch when every ray at the root is a camera ray of the tile (the root's entry of the (tile, node) mask cache, written by
       // the tile set-up; a child the pyramid culls is a miss for a camera ray anyway).  Same word as the node block's, same state
       // after it: the first child and PH_NODE / PH_LEAF, or PH_MISS at level -1 where the pop would end -- a lane that traversed
-      // and has finished, for the exit rule below.  Rays that are not NaN-free, and roots left to the node blocks (pyr[19] == 0),
+      // and has finished, for the exit rule below.  Rays that are not NaN-free, and roots left to the node blocks (RT_PYR_ROOT_POP == 0),
       // keep child = 0, PH_NODE.
       if (LDSN) {
         const bool at_root = phase == PH_NODE && level < 0 && cur != 0u;      // (`cur`: set where the ray starts; ray.fast itself is in scratch here)
@@ -792,7 +572,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           LG(LG_ROOTF_X, 1); LG(LG_ROOTF_L, n_root);
           // (both words in one LDS round trip; this glue runs once per traversal call and waits for whatever it reads)
           uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
-          const uint32_t w_pop = pw[19], w_cull = pw[32];
+          const uint32_t w_pop = pw[RT_PYR_ROOT_POP], w_cull = pw[RT_PYR_NODE_CACHE];      // (node 0's cache entry)
           uint32_t rsurv = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_pop);      // (not 0: `cur`)
           w_nodes += (uint32_t)n_root;
           // The count: one LDS add that returns nothing, by lane 0.  Written as the instruction itself: the atomic built-in compiles
@@ -800,7 +580,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           // for -- measured 0.03 ms per step of config #3 (profiles/r07_root_visits.md); same registers either way.  The address is
           // the pointer cast to the LDS address space, i.e. its 32-bit offset.
           if (lane_now() == 0) {
-            const uint32_t at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(pw + 20);
+            const uint32_t at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(pw + RT_PYR_ROOT_FUSED);
             asm volatile("ds_add_u32 %0, %1" : : "v"(at), "v"((uint32_t)n_root) : "memory");
           }
           if (__ballot(at_root && bounce != 0) == 0ull) {
@@ -835,30 +615,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     // ---------------- flush the wave's share of the tile: lane p owns pixel p ----------------
     LGD1();
     LGM("flush_begin");
-    if (took_any) {
+    if (U.took_any) {
       LGT0();
       LG(LG_FLUSH_X, 1);
-      int x = tile_x0 + (lane & 7), y = tile_y0 + (lane >> 3);
-      unsigned long long r = acc[lane * 3 + 0], g = acc[lane * 3 + 1], b = acc[lane * 3 + 2];
-      acc[lane * 3 + 0] = 0ull;
-      acc[lane * 3 + 1] = 0ull;
-      acc[lane * 3 + 2] = 0ull;
       RT_KArgs A = cold_args();
-      const int width = A->width;
-      if (x < width && y < A->height && (r | g | b) != 0ull) {
-        unsigned long long *base = A->accum;
-        if constexpr (VIEWS) base += (size_t)(vrec - (RT_KViewP)A->views) * (size_t)A->pixels_per_view * 3;   // this tile's view
-        unsigned long long *dst = base + ((size_t)y * width + x) * 3;
-        atomicAdd(dst + 0, r);
-        atomicAdd(dst + 1, g);
-        atomicAdd(dst + 2, b);
-      }
-      uint32_t *tile_cost = A->tile_cost;
-      if (tile_cost && lane == 0) atomicAdd(&tile_cost[tile_idx], w_rays - rays_before);
+      unsigned long long *frame = A->accum;
+      if constexpr (VIEWS) frame += (size_t)(vrec - (RT_KViewP)A->views) * (size_t)A->pixels_per_view * 3;   // this tile's view
+      flush_tile(acc, lane, tile_x0, tile_y0, frame, tile_idx, w_rays - rays_before);
       if (LDSN && lane == 0) {            // counters[RT_CNT_FUSED_ROOT]: the root visits this wave ran in front of its traversal calls
         uint32_t *pw = reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off));
-        const uint32_t n_fused = pw[20];
-        pw[20] = 0u;
+        const uint32_t n_fused = pw[RT_PYR_ROOT_FUSED];
+        pw[RT_PYR_ROOT_FUSED] = 0u;
         if (n_fused != 0u) atomicAdd(A->counters + RT_CNT_FUSED_ROOT, (unsigned long long)n_fused);
       }
       steal_tries = 0;                    // joined (or owned) a tile that had work: keep looking for more
@@ -875,13 +642,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   }
 
   if (lane == 0) {
-    atomicAdd(counters + CNT_PATHS, (unsigned long long)w_paths);
-    atomicAdd(counters + CNT_RAYS, (unsigned long long)w_rays);
-    atomicAdd(counters + CNT_NODES, (unsigned long long)w_nodes);
-    atomicAdd(counters + CNT_LEAVES, (unsigned long long)w_leaves);
-    atomicAdd(counters + CNT_SHADES, (unsigned long long)w_shades);
-    atomicAdd(counters + CNT_BG, (unsigned long long)w_bgs);
-    atomicAdd(counters + CNT_TEXTURED, (unsigned long long)w_tex);
+    atomicAdd(counters + RT_CNT_PATHS, (unsigned long long)w_paths);
+    atomicAdd(counters + RT_CNT_RAYS, (unsigned long long)w_rays);
+    atomicAdd(counters + RT_CNT_NODES, (unsigned long long)w_nodes);
+    atomicAdd(counters + RT_CNT_LEAVES, (unsigned long long)w_leaves);
+    atomicAdd(counters + RT_CNT_SHADES, (unsigned long long)w_shades);
+    atomicAdd(counters + RT_CNT_BG, (unsigned long long)w_bgs);
+    atomicAdd(counters + RT_CNT_TEXTURED, (unsigned long long)w_tex);
 #ifdef RT_LEDGER
     LG(LG_CYC_WAVE, (uint32_t)((__builtin_amdgcn_s_memtime() - lg_wave_t0) >> 4));
 #endif
@@ -1299,14 +1066,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, R
   const float4 *lds_nodes = smem;
   const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
   uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * perm_f4);
-  {
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
-    __syncthreads();
-  }
+  lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
+  __syncthreads();
   const int leaf_level = P.depth - 1;
   int  next = 0, end = 0;                                         // the wave's current grab: rays [next, end) are not handed out yet
   bool drained = false;                                           // the launch's counter has run past the list (wave-uniform)
@@ -1358,10 +1119,10 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, R
                                               n_trav0, ray, false, phase, level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
   }
   if (lane == 0) {
-    atomicAdd(Q.counters + 0, (unsigned long long)w_rays);
-    atomicAdd(Q.counters + 1, (unsigned long long)w_hits);
-    atomicAdd(Q.counters + 2, (unsigned long long)w_nodes);
-    atomicAdd(Q.counters + 3, (unsigned long long)w_leaves);
+    atomicAdd(Q.counters + RT_QCNT_RAYS, (unsigned long long)w_rays);
+    atomicAdd(Q.counters + RT_QCNT_HITS, (unsigned long long)w_hits);
+    atomicAdd(Q.counters + RT_QCNT_NODES, (unsigned long long)w_nodes);
+    atomicAdd(Q.counters + RT_QCNT_LEAVES, (unsigned long long)w_leaves);
   }
 }
 

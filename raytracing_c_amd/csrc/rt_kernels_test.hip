@@ -227,21 +227,15 @@ __global__ __launch_bounds__(16 * 64, 1) void rt_test_trace_stream_kernel(RT_KPa
   const int wave = threadIdx.x >> 6;
   const int n_lds = P.n_lds_nodes;
   const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * (perm_f4 + 96));
-  const int pyr_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4 - 16) * 16;
-  {
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += 16 * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
-    __syncthreads();
-  }
+  const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the path kernel's slice
+  uint32_t *perm = L.perm;
+  const int pyr_off = L.pyr_off;
+  lds_load_nodes<16 * 64>(smem, P.nodes, n_lds);
+  __syncthreads();
   if (PYRAMID) {
     float *pyr = lds_at(smem, pyr_off);
-    if (lane < 19) pyr[lane] = pyr_in[lane];
-    if (lane < 40) reinterpret_cast<uint32_t *>(pyr)[24 + lane] = 0u;
+    if (lane < RT_PYR_ORIGIN + 3) pyr[lane] = pyr_in[lane];      // planes and origin, as the caller built them
+    if (lane < RT_PYR_CACHE_WORDS) reinterpret_cast<uint32_t *>(pyr)[RT_PYR_LEAF_CACHE + lane] = 0u;
   }
   const int leaf_level = P.depth - 1;
   const int n_waves = (int)gridDim.x * 16, wave_id = (int)blockIdx.x * 16 + wave;

@@ -440,45 +440,30 @@ int copy_image_out(Image const *image, const uint8_t *d_image, int width, int he
   return 0;
 }
 
-// Of the node visits of the last rt_render_accumulate launch: how many were COUNTED but not executed -- the one root visit of
-// every camera path whose tile's pixel pyramid misses every child of the root (the reference, and the oracle, spend and count
-// it; the kernel proves its outcome per tile and skips it).  bench.py's roofline carries it as a footnote.
-extern "C" int rt_get_skipped_root_visits(u64 *out) {
-  if (!out) return rt_fail("rt_get_skipped_root_visits: NULL");
+// One counter of the last rt_render_accumulate launch.
+static int get_counter(const char *who, int index, u64 *out) {
+  if (!out) return rt_fail("%s: NULL", who);
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
   if (ensure_device(D) != 0) return -1;
   unsigned long long c[RT_N_COUNTERS];
   if (read_counters(D, c) != 0) return -1;
-  *out = c[7];
+  *out = c[index];
   return 0;
 }
 
+// Of the node visits of the last rt_render_accumulate launch: how many were COUNTED but not executed -- the one root visit of
+// every camera path whose tile's pixel pyramid misses every child of the root (the reference, and the oracle, spend and count
+// it; the kernel proves its outcome per tile and skips it).  bench.py's roofline carries it as a footnote.
+extern "C" int rt_get_skipped_root_visits(u64 *out) { return get_counter("rt_get_skipped_root_visits", RT_CNT_SKIPPED_ROOT, out); }
+
 // Camera paths of the last rt_render_accumulate launch that the leafless loop of the path kernel served (rt_kernels.hip).
-extern "C" int rt_get_leafless_paths(u64 *out) {
-  if (!out) return rt_fail("rt_get_leafless_paths: NULL");
-  Device &D = dev0();
-  std::lock_guard<std::mutex> lock(D.mutex);
-  if (ensure_device(D) != 0) return -1;
-  unsigned long long c[RT_N_COUNTERS];
-  if (read_counters(D, c) != 0) return -1;
-  *out = c[RT_CNT_LEAFLESS];
-  return 0;
-}
+extern "C" int rt_get_leafless_paths(u64 *out) { return get_counter("rt_get_leafless_paths", RT_CNT_LEAFLESS, out); }
 
 // Rays of the last rt_render_accumulate launch whose root visit ran at the top of a traversal call, in front of the traversal
 // rounds (rt_kernels.hip): every NaN-free ray that the sky / leafless loop does not serve, when the root has at most four populated
 // children.
-extern "C" int rt_get_fused_root_visits(u64 *out) {
-  if (!out) return rt_fail("rt_get_fused_root_visits: NULL");
-  Device &D = dev0();
-  std::lock_guard<std::mutex> lock(D.mutex);
-  if (ensure_device(D) != 0) return -1;
-  unsigned long long c[RT_N_COUNTERS];
-  if (read_counters(D, c) != 0) return -1;
-  *out = c[RT_CNT_FUSED_ROOT];
-  return 0;
-}
+extern "C" int rt_get_fused_root_visits(u64 *out) { return get_counter("rt_get_fused_root_visits", RT_CNT_FUSED_ROOT, out); }
 
 int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]) {
   HIP_TRY(hipDeviceSynchronize());
@@ -498,13 +483,13 @@ extern "C" int rt_get_counters(RT_Counters *out) {
   if (ensure_device(D) != 0) return -1;
   unsigned long long c[RT_N_COUNTERS];
   if (read_counters(D, c) != 0) return -1;
-  out->paths = c[0];
-  out->rays = c[1];
-  out->node_visits = c[2];
-  out->leaf_visits = c[3];
-  out->shades = c[4];
-  out->backgrounds = c[5];
-  out->textured = c[6];
+  out->paths = c[RT_CNT_PATHS];
+  out->rays = c[RT_CNT_RAYS];
+  out->node_visits = c[RT_CNT_NODES];
+  out->leaf_visits = c[RT_CNT_LEAVES];
+  out->shades = c[RT_CNT_SHADES];
+  out->backgrounds = c[RT_CNT_BG];
+  out->textured = c[RT_CNT_TEXTURED];
   return 0;
 }
 

@@ -203,8 +203,8 @@ int render_frame_multi(Scene const *scene, Image const *image, RT_Render_Params 
     T.upload_ms = J.upload_ms[r] > T.upload_ms ? J.upload_ms[r] : T.upload_ms;
     T.enqueue_ms = J.enqueue_ms[r] > T.enqueue_ms ? J.enqueue_ms[r] : T.enqueue_ms;
     const unsigned long long *c = W.counters_host;
-    sum.paths += c[0]; sum.rays += c[1]; sum.node_visits += c[2]; sum.leaf_visits += c[3]; sum.shades += c[4]; sum.backgrounds += c[5];
-    sum.textured += c[6];
+    sum.paths += c[RT_CNT_PATHS]; sum.rays += c[RT_CNT_RAYS]; sum.node_visits += c[RT_CNT_NODES]; sum.leaf_visits += c[RT_CNT_LEAVES];
+    sum.shades += c[RT_CNT_SHADES]; sum.backgrounds += c[RT_CNT_BG]; sum.textured += c[RT_CNT_TEXTURED];
   }
   T.gather_ms = (float)(now_ms() - t_g);
   {

@@ -235,9 +235,9 @@ extern "C" int rt_get_query_counters(RT_Query_Counters *out) {
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long c[RT_QUERY_COUNTERS];
   HIP_TRY(hipMemcpy(c, D.query.slots + (size_t)D.query.last * 64, sizeof c, hipMemcpyDeviceToHost));
-  out->rays = c[0];
-  out->hits = c[1];
-  out->node_visits = c[2];
-  out->leaf_visits = c[3];
+  out->rays = c[RT_QCNT_RAYS];
+  out->hits = c[RT_QCNT_HITS];
+  out->node_visits = c[RT_QCNT_NODES];
+  out->leaf_visits = c[RT_QCNT_LEAVES];
   return 0;
 }

@@ -3,8 +3,9 @@
 //
 //   rt_wf_camera_kernel   render_thread_proc's pixel / sample loop (raytracer.c:596-720) + the first ray_scene_hit of
 //                         every path (raytracer.c:513-514) + the environment for camera rays that leave the scene
-//                         (raytracer.c:554).  Persistent waves own 8x8 tiles and pull units of them exactly like the
-//                         tile-stream kernel (same counters, same joining); ALL lanes are camera rays of one tile, so
+//                         (raytracer.c:554).  Persistent waves own 8x8 tiles and pull units of them through the
+//                         tile-stream kernel's own stages (rt_tile.hip.h: take_queue_tile, join_open_tile, tile_origin,
+//                         tile_pyramid, grab_units, unit_decode, flush_tile; the same LDS slice, wave_lds); ALL lanes are camera rays of one tile, so
 //                         every node block can be culled by the tile's pyramid.  A hit is not shaded here: 9 dwords
 //                         (direction, t, triangle, u, v, pixel, sample) go to the hit queue and the lane takes the
 //                         next camera path.  No path state (tint, emission, rng, bounce) lives in registers.
@@ -90,20 +91,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
   const int wave = threadIdx.x >> 6;
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  float4 *wave_base = smem + n_lds * RT_LDS_NODE_F4 + wave * (perm_f4 + 96);
-  uint32_t *perm = reinterpret_cast<uint32_t *>(wave_base);
-  unsigned long long *acc = reinterpret_cast<unsigned long long *>(wave_base + perm_f4);
-  // (the perm row of the deepest node level is never written: it holds the tile's camera-ray pyramid and the cull-mask cache)
-  const int acc_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4) * 16;
-  const int pyr_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4 - 16) * 16;
+  const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the wave's LDS slice, laid out as the path kernel's
+  uint32_t *perm = L.perm;
+  unsigned long long *acc = L.acc;
+  const int acc_off = L.acc_off, pyr_off = L.pyr_off;
 
   if (LDSN) {
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
+    lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
     __syncthreads();          // the only workgroup barrier of the kernel; waves are independent afterwards
   }
 
@@ -129,138 +123,22 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
   for (;;) {
     // ---------------- take a tile: own one from the queue, or join one that still has units ----------------
     if (stopped) break;
-    int tile_idx = -1;
-    if (queue_open) {
-      RT_KArgs A = cold_args();
-      uint32_t pos = 0;
-      if (lane == 0) pos = atomicAdd(A->work_head, 1u);
-      pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-      const uint32_t *order = A->order;
-      if (pos < (uint32_t)A->n_tiles) tile_idx = order ? (int)order[pos] : (int)pos;
-      else queue_open = false;
-    }
+    int tile_idx = queue_open ? take_queue_tile(lane, queue_open) : -1;
     if (tile_idx < 0) {
       if (steal_tries >= RT_STEAL_TRIES) break;
       steal_tries += 1;
-      RT_KArgs A = cold_args();
-      const int n_tiles = A->n_tiles;
-      const uint32_t *open_groups = A->open_groups, *tile_next = A->tile_next;
-      const int n_groups = (n_tiles + 63) >> 6;
-      const int g_rounds = (n_groups + 63) >> 6;
-      const uint32_t hsh = ((uint32_t)wave_id * 2654435761u + (uint32_t)steal_tries * 40503u) >> 8;
-      const int g_start = (int)(hsh % (uint32_t)g_rounds);
-      for (int i = 0; i < g_rounds && tile_idx < 0; i++) {
-        int r = g_start + i;
-        if (r >= g_rounds) r -= g_rounds;
-        int g = r * 64 + lane;
-        uint32_t n_open = 0;
-        if (g < n_groups) n_open = __hip_atomic_load(&open_groups[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned long long gm = __ballot(n_open != 0u);
-        while (gm && tile_idx < 0) {
-          int nth = (int)((hsh >> 6) % (uint32_t)__popcll(gm));
-          unsigned long long m = gm;
-          for (int k = 0; k < nth; k++) m &= m - 1ull;
-          int gl = (int)__builtin_ctzll(m);
-          gm &= ~(1ull << gl);
-          int cand = (r * 64 + gl) * 64 + lane;
-          uint32_t taken = 0xFFFFFFFFu;
-          if (cand < n_tiles) taken = __hip_atomic_load(&tile_next[cand], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          unsigned long long open = __ballot(taken < n_chunks_tile);
-          if (open) {
-            const int n_open_tiles = (int)__popcll(open);
-            int best = 0;
-            uint32_t best_taken = 0xFFFFFFFFu;
-#pragma unroll
-            for (int c = 0; c < RT_JOIN_CHOICES; c++) {
-              int nt = (int)(((hsh >> 12) * (uint32_t)(2 * c + 1) + (uint32_t)c * 7u) % (uint32_t)n_open_tiles);
-              unsigned long long mm = open;
-              for (int k = 0; k < nt; k++) mm &= mm - 1ull;
-              const int pk_lane = (int)__builtin_ctzll(mm);
-              const uint32_t tk = (uint32_t)__builtin_amdgcn_readlane((int)taken, pk_lane);
-              if (tk < best_taken) { best_taken = tk; best = pk_lane; }
-            }
-            tile_idx = cand - lane + best;
-          }
-        }
-      }
+      tile_idx = join_open_tile(lane, wave_id, steal_tries, n_chunks_tile);
       if (tile_idx < 0) break;                      // nothing left to join
     }
 
     int tile_x0, tile_y0;
-    {
-      RT_KArgs A = cold_args();
-      const int lchunk = tile_idx >> 4, sub = tile_idx & 15;
-      const int chunk = A->local_chunks[lchunk];
-      const int chunks_x = A->chunks_x;
-      tile_x0 = (chunk % chunks_x) * 32 + (sub & 3) * 8;
-      tile_y0 = (chunk / chunks_x) * 32 + (sub >> 2) * 8;
-      if (tile_x0 >= A->width || tile_y0 >= A->height) {
-        if (lane == 0) {
-          uint32_t old = atomicMax(&A->tile_next[tile_idx], n_chunks_tile);
-          if (old < n_chunks_tile) atomicSub(&A->open_groups[tile_idx >> 6], 1u);
-        }
-        continue;
-      }
-    }
-    // ---- the tile's camera-ray pyramid (tile-stream kernel: same construction, same margin) ----
+    if (!tile_origin(lane, tile_idx, n_chunks_tile, tile_x0, tile_y0)) continue;      // a tile outside the image
     bool tile_root_miss = false;
-    rt_v3 cam_o;
+    if (leaf_level >= 0) tile_root_miss = tile_pyramid(cold_args(), P.nodes, smem, pyr_off, lane, tile_x0, tile_y0);
+    rt_v3 cam_o;                          // the origin of every ray of this kernel
     {
       RT_KArgs A = cold_args();
       cam_o = rt_v3_make(A->cam[0][3], A->cam[1][3], A->cam[2][3]);
-    }
-    if (leaf_level >= 0) {
-      RT_KArgs A = cold_args();
-      const float m = 0.05f;                                   // footprint margin in pixels
-      const float ux0 = ((float)tile_x0 - 0.5f - m) * 2.0f * A->inv_width - 1.0f;
-      const float ux1 = ((float)tile_x0 + 7.5f + m) * 2.0f * A->inv_width - 1.0f;
-      const float uy0 = ((float)tile_y0 - 0.5f - m) * 2.0f * A->inv_height - 1.0f;
-      const float uy1 = ((float)tile_y0 + 7.5f + m) * 2.0f * A->inv_height - 1.0f;
-      const float asp = A->aspect, fl = A->focal_length;
-      rt_v3 c[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        float cx = ((q == 1 || q == 2) ? ux1 : ux0) * asp, cy = -((q >= 2) ? uy1 : uy0), cz = -fl;
-        c[q] = rt_v3_make(A->cam[0][0] * cx + A->cam[0][1] * cy + A->cam[0][2] * cz,
-                          A->cam[1][0] * cx + A->cam[1][1] * cy + A->cam[1][2] * cz,
-                          A->cam[2][0] * cx + A->cam[2][1] * cy + A->cam[2][2] * cz);
-      }
-      const rt_v3 o = cam_o;
-      rt_v3 pn[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        rt_v3 n = rt_v3_cross(c[q], c[(q + 1) & 3]);
-        if (rt_v3_dot(n, c[(q + 2) & 3]) > 0.0f) n = rt_v3_scale(n, -1.0f);      // outward: the opposite corner is inside
-        pn[q] = n;
-      }
-      float *pyr = lds_at(smem, pyr_off);
-      if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) { pyr[q * 4 + 0] = pn[q].x; pyr[q * 4 + 1] = pn[q].y; pyr[q * 4 + 2] = pn[q].z; }
-        pyr[16] = o.x; pyr[17] = o.y; pyr[18] = o.z;
-      }
-      if (lane < 40) reinterpret_cast<uint32_t *>(pyr)[24 + lane] = 0u;      // the cull masks found for this tile so far
-      bool may_hit = false;
-      if (lane < 8) {
-        const float *nb = P.nodes + lane;                      // child `lane` of node 0: rows are 8 floats apart
-        rt_v3 lo = rt_v3_make(nb[0] - o.x, nb[8] - o.y, nb[16] - o.z);
-        rt_v3 hi = rt_v3_make(nb[24] - o.x, nb[32] - o.y, nb[40] - o.z);
-        const bool empty = nb[0] == 0.0f && nb[8] == 0.0f && nb[16] == 0.0f && nb[24] == 0.0f && nb[32] == 0.0f && nb[40] == 0.0f;
-        bool outside = empty;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          rt_v3 n = pn[q];
-          float lox = n.x * lo.x, hix = n.x * hi.x, loy = n.y * lo.y, hiy = n.y * hi.y, loz = n.z * lo.z, hiz = n.z * hi.z;
-          float nearest = fminf(lox, hix) + fminf(loy, hiy) + fminf(loz, hiz);
-          float extent = fmaxf(fabsf(lox), fabsf(hix)) + fmaxf(fabsf(loy), fabsf(hiy)) + fmaxf(fabsf(loz), fabsf(hiz));
-          // (+ the placement error of a fused slab distance, see pyramid_cull_mask)
-          float coarse = fabsf(n.x) * (fabsf(o.x) + fmaxf(fabsf(nb[0]), fabsf(nb[24]))) + fabsf(n.y) * (fabsf(o.y) + fmaxf(fabsf(nb[8]), fabsf(nb[32]))) +
-                         fabsf(n.z) * (fabsf(o.z) + fmaxf(fabsf(nb[16]), fabsf(nb[40])));
-          if (nearest > 1e-3f * extent + 1e-6f * coarse) outside = true;        // (NaN compares false: not outside)
-        }
-        may_hit = !outside;
-      }
-      tile_root_miss = __ballot(may_hit) == 0ull;
     }
     const uint32_t rays_before = w_rays;
 
@@ -275,9 +153,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
     hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
 
     bool tile_open = true;
-    int  c_next = 0, c_end = 0, c_x0 = 0, c_y = 0, c_pix0 = 0, c_s0 = 0;
-    uint32_t u_cur = 0, u_end = 0, grab = queue_open ? (uint32_t)cold_args()->grab_max : 1u;
-    bool took_any = false;
+    TileUnits U;
+    tile_units_init(U, queue_open);
+    unsigned long long no_time = 0ull;    // (this kernel keeps no wave times)
 
     for (;;) {
       // ================= S: environment for the misses, hits to the queue, new camera paths =================
@@ -327,52 +205,36 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
           const int width = A->width, sample_end = A->sample_end;
           const int max_bounces = A->max_bounces;
           while (need) {
-            if (c_next >= c_end) {
-              if (u_cur + 1u < u_end) {
-                u_cur += 1u;
+            if (U.c_next >= U.c_end) {
+              if (U.u_cur + 1u < U.u_end) {
+                U.u_cur += 1u;
               } else {
-                if (stopped) { tile_open = false; break; }
-                uint32_t u0 = 0;
-                if (lane == 0) u0 = atomicAdd(&A->tile_next[tile_idx], grab);
-                u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);
-                if (u0 >= n_chunks_tile) { tile_open = false; break; }
-                u_cur = u0;
-                u_end = u0 + grab < n_chunks_tile ? u0 + grab : n_chunks_tile;
-                if (u_end == n_chunks_tile && lane == 0) atomicSub(&A->open_groups[tile_idx >> 6], 1u);
-                const uint32_t left = n_chunks_tile - u_end;
-                const uint32_t gmax = (uint32_t)A->grab_max;
-                grab = left >= 8u * gmax ? gmax : (left >= 8u && gmax >= 2u ? 2u : 1u);
-                took_any = true;
+                if (stopped || !grab_units(lane, tile_idx, n_chunks_tile, A->tile_next, A->open_groups, (uint32_t)A->grab_max, U, 0ull, no_time)) {
+                  tile_open = false;
+                  break;
+                }
               }
-              const uint32_t grp = u_cur >> 2, pair = u_cur & 3u;
-              const uint32_t n_sb = (uint32_t)A->n_sample_blocks;
-              const uint32_t row = grp / n_sb, sb = grp - row * n_sb;
-              c_x0 = tile_x0 + (int)pair * 2;
-              c_y = tile_y0 + (int)row;
-              c_pix0 = (int)row * 8 + (int)pair * 2;
-              c_s0 = A->sample_first + (int)(sb << shift);
-              c_next = 0;
-              c_end = (c_y < A->height && c_x0 < width) ? unit_paths : 0;
+              unit_decode(U, tile_x0, tile_y0, shift, unit_paths, (uint32_t)A->n_sample_blocks, A->sample_first, width, A->height);
               continue;
             }
             const int n_need = (int)__popcll(need);
-            const int avail = c_end - c_next;
+            const int avail = U.c_end - U.c_next;
             const int take = n_need < avail ? n_need : avail;
             const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
             bool valid = false;
             if (phase == PH_NEED && !got && rank < take) {
-              int k = c_next + rank;
+              int k = U.c_next + rank;
               int px = k >> shift;
-              int sm = c_s0 + (k & ((1 << shift) - 1));
-              int x = c_x0 + px;
+              int sm = U.c_s0 + (k & ((1 << shift) - 1));
+              int x = U.c_x0 + px;
               if (x < width && sm < sample_end) {
                 valid = true;
-                if (max_bounces > 0) { got = true; gx = x; gy = c_y; gs = sm; gp = c_pix0 + px; }
+                if (max_bounces > 0) { got = true; gx = x; gy = U.c_y; gs = sm; gp = U.c_pix0 + px; }
                 // max_bounces == 0: the path exists and is black (the loop of raytracer.c:512 runs zero times)
               }
             }
             w_paths += (uint32_t)__popcll(__ballot(valid));
-            c_next += take;
+            U.c_next += take;
             need = __ballot(phase == PH_NEED && !got);
           }
           if (got) {
@@ -420,22 +282,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
     }
 
     // ---------------- flush the wave's share of the tile: lane p owns pixel p ----------------
-    if (took_any) {
-      int x = tile_x0 + (lane & 7), y = tile_y0 + (lane >> 3);
-      unsigned long long r = acc[lane * 3 + 0], g = acc[lane * 3 + 1], b = acc[lane * 3 + 2];
-      acc[lane * 3 + 0] = 0ull;
-      acc[lane * 3 + 1] = 0ull;
-      acc[lane * 3 + 2] = 0ull;
-      RT_KArgs A = cold_args();
-      const int width = A->width;
-      if (x < width && y < A->height && (r | g | b) != 0ull) {
-        unsigned long long *dst = A->accum + ((size_t)y * width + x) * 3;
-        atomicAdd(dst + 0, r);
-        atomicAdd(dst + 1, g);
-        atomicAdd(dst + 2, b);
-      }
-      uint32_t *tile_cost = A->tile_cost;
-      if (tile_cost && lane == 0) atomicAdd(&tile_cost[tile_idx], w_rays - rays_before);
+    if (U.took_any) {
+      flush_tile(acc, lane, tile_x0, tile_y0, cold_args()->accum, tile_idx, w_rays - rays_before);
       steal_tries = 0;
     }
   }
@@ -443,11 +291,11 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
   wf_close(A->wf_cnt_hit0, out);
   unsigned long long *counters = A->counters;
   if (lane == 0) {
-    atomicAdd(counters + CNT_PATHS, (unsigned long long)w_paths);
-    atomicAdd(counters + CNT_RAYS, (unsigned long long)w_rays);
-    atomicAdd(counters + CNT_NODES, (unsigned long long)w_nodes);
-    atomicAdd(counters + CNT_LEAVES, (unsigned long long)w_leaves);
-    atomicAdd(counters + CNT_BG, (unsigned long long)w_bgs);
+    atomicAdd(counters + RT_CNT_PATHS, (unsigned long long)w_paths);
+    atomicAdd(counters + RT_CNT_RAYS, (unsigned long long)w_rays);
+    atomicAdd(counters + RT_CNT_NODES, (unsigned long long)w_nodes);
+    atomicAdd(counters + RT_CNT_LEAVES, (unsigned long long)w_leaves);
+    atomicAdd(counters + RT_CNT_BG, (unsigned long long)w_bgs);
   }
 }
 
@@ -461,18 +309,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
   const int wave = threadIdx.x >> 6;
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  float4 *wave_base = smem + n_lds * RT_LDS_NODE_F4 + wave * (perm_f4 + 96);
-  uint32_t *perm = reinterpret_cast<uint32_t *>(wave_base);
-  unsigned long long *acc = reinterpret_cast<unsigned long long *>(wave_base + perm_f4);
-  const int acc_off = (n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * (perm_f4 + 96) + perm_f4) * 16;
+  const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // (the same slice as the camera kernel's; no pyramid here)
+  uint32_t *perm = L.perm;
+  unsigned long long *acc = L.acc;
+  const int acc_off = L.acc_off;
 
   if (LDSN) {
-    const float4 *g = reinterpret_cast<const float4 *>(P.nodes);
-    for (int i = threadIdx.x; i < n_lds * 12; i += WAVES * 64) {
-      int nd = i / 12, q = i - nd * 12;
-      smem[nd * RT_LDS_NODE_F4 + q] = g[i];
-    }
+    lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
     __syncthreads();
   }
   // Finished paths add to an 8x8-pixel accumulator tile in LDS, flushed to the frame when the wave moves on to rays of
@@ -536,20 +379,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
           const uint32_t key = ((pixel >> 19) << 13) | ((pixel & 0xFFFFu) >> 3);
           const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)__builtin_ctzll(mMiss));
           if (k0 != acc_key) {                                      // (wave-uniform) the tile in LDS goes to the frame
-            if (acc_key != 0xFFFFFFFFu) {
-              const int l = lane_now();
-              const int x = (int)(acc_key & 8191u) * 8 + (l & 7), y = (int)(acc_key >> 13) * 8 + (l >> 3);
-              unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + l * 6);
-              const unsigned long long r = ap[0], g = ap[1], b = ap[2];
-              ap[0] = 0ull; ap[1] = 0ull; ap[2] = 0ull;
-              const int width = A->width;
-              if (x < width && y < A->height && (r | g | b) != 0ull) {
-                unsigned long long *dst = frame + ((size_t)y * width + x) * 3;
-                atomicAdd(dst + 0, r);
-                atomicAdd(dst + 1, g);
-                atomicAdd(dst + 2, b);
-              }
-            }
+            if (acc_key != 0xFFFFFFFFu)
+              flush_tile(reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off)), lane_now(), (int)(acc_key & 8191u) * 8,
+                         (int)(acc_key >> 13) * 8, frame, -1, 0u);
             acc_key = k0;
           }
           if (phase == PH_MISS) {
@@ -631,24 +463,14 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
   }
 
   RT_KArgs A = cold_args();
-  if (acc_key != 0xFFFFFFFFu && A->accum) {
-    const int x = (int)(acc_key & 8191u) * 8 + (lane & 7), y = (int)(acc_key >> 13) * 8 + (lane >> 3);
-    const unsigned long long r = acc[lane * 3 + 0], g = acc[lane * 3 + 1], b = acc[lane * 3 + 2];
-    const int width = A->width;
-    if (x < width && y < A->height && (r | g | b) != 0ull) {
-      unsigned long long *dst = A->accum + ((size_t)y * width + x) * 3;
-      atomicAdd(dst + 0, r);
-      atomicAdd(dst + 1, g);
-      atomicAdd(dst + 2, b);
-    }
-  }
+  if (acc_key != 0xFFFFFFFFu && A->accum) flush_tile(acc, lane, (int)(acc_key & 8191u) * 8, (int)(acc_key >> 13) * 8, A->accum, -1, 0u);
   wf_close(A->wf_cnt_hit, out);
   unsigned long long *counters = A->counters;
   if (lane == 0) {
-    atomicAdd(counters + CNT_RAYS, (unsigned long long)w_rays);
-    atomicAdd(counters + CNT_NODES, (unsigned long long)w_nodes);
-    atomicAdd(counters + CNT_LEAVES, (unsigned long long)w_leaves);
-    atomicAdd(counters + CNT_BG, (unsigned long long)w_bgs);
+    atomicAdd(counters + RT_CNT_RAYS, (unsigned long long)w_rays);
+    atomicAdd(counters + RT_CNT_NODES, (unsigned long long)w_nodes);
+    atomicAdd(counters + RT_CNT_LEAVES, (unsigned long long)w_leaves);
+    atomicAdd(counters + RT_CNT_BG, (unsigned long long)w_bgs);
   }
   wf_finish_consumer(A->wf_ctl, A->wf_n_waves, w_in_alloc, w_in_head);
 }
@@ -763,8 +585,8 @@ __global__ __launch_bounds__(256, 4) void rt_wf_shade_kernel(RT_KParams P) {
 
   wf_close(P.wf_cnt_ray[qi], out);
   if (lane == 0) {
-    atomicAdd(P.counters + CNT_SHADES, (unsigned long long)w_shades);
-    atomicAdd(P.counters + CNT_TEXTURED, (unsigned long long)w_tex);
+    atomicAdd(P.counters + RT_CNT_SHADES, (unsigned long long)w_shades);
+    atomicAdd(P.counters + RT_CNT_TEXTURED, (unsigned long long)w_tex);
   }
   wf_finish_consumer(ctl, P.wf_n_waves, w_in_alloc, w_in_head);
 }

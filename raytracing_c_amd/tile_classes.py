@@ -1,4 +1,4 @@
-"""Host model of the path kernel's per-tile pyramid test (rt_kernels.hip: tile_root_miss; rt_dev.hip.h: pyramid_cull_mask).
+"""Host model of the path kernel's per-tile pyramid test (rt_tile.hip.h: tile_pyramid, the path kernel's tile_root_miss; rt_dev.hip.h: pyramid_cull_mask).
 
 For every 8x8 tile of a frame: the four side planes of the pyramid through the tile's pixel footprint, and the implicit 8-ary
 tree pruned by them, breadth-first from the root.  A tile is ROOT-MISS when the pyramid misses every child box of the root

@@ -38,6 +38,25 @@ def test_wavefront_frames_are_bit_exact(rt, oracle, name, w, h, s, b):
     _check(rt, name, w, h, s, b)
 
 
+@pytest.mark.parametrize("w,h", [(40, 24), (36, 20)])
+def test_chunk_with_tiles_inside_and_outside_the_image_through_both_pipelines(rt, oracle, w, h):
+    """Two chunks of 16 tiles, the second with one column of tiles in the image and three outside it, both with a row of tiles
+    below it (36 x 20: the last column and row are partial tiles).  Far fewer tiles than waves, so most waves join: the tiles
+    outside the image must be marked exhausted while others are joined.  Sums and the seven counters, bit for bit, from the
+    wavefront pipeline and from the path kernel."""
+    from raytracing_c_amd.configs import load_config
+    from tests import _oracle
+    hs, _ = load_config("quad")
+    want = _oracle.render(hs, w, h, 8, 2)
+    for pipeline in (1, 0):
+        assert rt.diag.rt_set_pipeline(pipeline) == 0
+        got = rt.render_frame(hs, w, h, 8, 2, want_accum=True, lib=rt.diag)
+        assert np.array_equal(got["accum"], want["accum"]), pipeline
+        assert np.array_equal(got["image"], want["image"]), pipeline
+        for k in ("paths", "rays", "node_visits", "leaf_visits", "shades", "backgrounds", "textured"):
+            assert want["counters"][k] == getattr(got["counters"], k), (pipeline, k)
+
+
 def test_many_passes_through_a_tiny_queue(rt, oracle):
     rt.diag.rt_set_wavefront_capacity(1024)         # the camera kernel fills its hit queue again and again
     _check(rt, "helmet", 192, 108, 8, 8)
