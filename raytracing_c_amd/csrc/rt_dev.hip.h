@@ -1181,11 +1181,19 @@ __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *
 // The camera rays of a wave sit on one or two pixels: most leaf blocks that hold camera rays hold (almost) nothing else, all
 // of them on ONE leaf group (config #3: 6.4 M of 16.8 M leaf blocks, 53 lanes each).  Such a block tests only the triangles the
 // tile's pyramid can touch.  Lane l tests triangle (l & 7) of leaf group g against plane ((l >> 3) & 3); returns the 8-bit mask
-// of the triangles that lie entirely outside one plane -- all three vertices by the relative margin of pyramid_cull_mask() -- :
-// no point of a ray inside the pyramid lies in such a triangle, so the point where the ray meets the triangle's plane has a
-// barycentric coordinate outside [0, 1] by far more than the test's epsilon and ray_triangles_hit_8 reports a miss for it
-// (raytracer.c:84-188), whatever the ray's t_max.  (Vertices b, c are a + (b - a), a + (c - a) here, an ulp off the reference's:
-// the `coarse` term of the margin covers a thousand of those.)
+// of the triangles whose FATTENED form lies entirely outside one plane.  The reference's test accepts u >= -EPSILON, v >= -EPSILON,
+// u + v <= 1 + EPSILON (raytracer.c:137-149): a triangle grown by 1e-4 of its own SIZE, whatever its distance -- with a vertex ten
+// times farther from the camera than another, that band reaches where all three vertices are clear of a plane.  f(p) = n . (p - o)
+// is affine in (u, v), f = f(a) + u n . e1 + v n . e2, so over the fattened triangle it is smallest at one of the corners
+// (-eps, -eps), (1 + 2 eps, -eps), (-eps, 1 + 2 eps), nowhere below  min f(vertex) - 2 eps (|n . e1| + |n . e2|).  A triangle is
+// culled when that bound -- with 2.5 eps -- clears the plane by the relative margin of pyramid_cull_mask(): no ray inside the
+// pyramid then meets the triangle's plane at a point the EXACT test accepts, and ray_triangles_hit_8 reports a miss for it
+// (raytracer.c:84-188), whatever the ray's t_max.  That much is proved.  The reference computes u and v in fp32: the cancellation
+// in `det` leaves them a relative error of about 1e-7 / |cos| of the incidence, which for a triangle 1e4 times larger than its
+// distance seen near the horizon approaches the band's own width.  The quarter of eps added to the bound and the margin's 1e-3
+// of the distance are there for that; that they suffice is NOT proved, it rests on the frames of tests/test_gpu_pyramid.py
+// (ratios up to 1e4, bit for bit).  (Vertices b, c are a + (b - a), a + (c - a) here, an ulp off the reference's: the `coarse`
+// term of the margin covers a thousand of those.)
 __device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const float *pyr, int g) {
   const int lane = lane_now();
   const float *tb = leaves + (size_t)g * 72 + (lane & 7);
@@ -1193,6 +1201,7 @@ __device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const
   const float ox = pyr[RT_PYR_ORIGIN], oy = pyr[RT_PYR_ORIGIN + 1], oz = pyr[RT_PYR_ORIGIN + 2];
   const float nx = pl[0], ny = pl[1], nz = pl[2];
   const float ax = tb[0], e1x = tb[8], e2x = tb[16], ay = tb[24], e1y = tb[32], e2y = tb[40], az = tb[48], e1z = tb[56], e2z = tb[64];
+  const float band = 2.5f * RT_EPS * (fabsf(nx * e1x + ny * e1y + nz * e1z) + fabsf(nx * e2x + ny * e2y + nz * e2z));
   bool outside = true;
 #pragma unroll
   for (int v = 0; v < 3; v++) {
@@ -1203,7 +1212,7 @@ __device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const
     const float val = px + py + pz;                                                   // n . (vertex - o)
     const float extent = fabsf(px) + fabsf(py) + fabsf(pz);
     const float coarse = fabsf(nx) * (fabsf(ox) + fabsf(vx)) + fabsf(ny) * (fabsf(oy) + fabsf(vy)) + fabsf(nz) * (fabsf(oz) + fabsf(vz));
-    outside = outside && (val > 1e-3f * extent + 1e-6f * coarse);                     // (NaN compares false: not outside)
+    outside = outside && (val - band > 1e-3f * extent + 1e-6f * coarse);              // (NaN compares false: not outside)
   }
   const uint32_t m = (uint32_t)__ballot(outside);                                     // lanes 0..31: 4 planes x 8 triangles
   return (m | (m >> 8) | (m >> 16) | (m >> 24)) & 0xFFu;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Worker of tests/test_gpu_diag.py and tests/test_gpu_contract_v1.py: runs in its OWN process with RT_LIB_PATH = librt_hip_diag.so
 (or librt_hip_v1.so, the product under numeric contract v1) -- the diagnostic build reads the RT_* experiment knobs from
-the environment at every launch -- and renders a list of jobs.  stdin: JSON list of {config, w, h, s, b, env: {...}, slabs: [...]}; stdout: one JSON line per job with the
+the environment at every launch -- and renders a list of jobs.  stdin: JSON list of {config, w, h, s, b, env: {...}, slabs: [...]}
+(config: a name of raytracing_c_amd/configs.py, or "pyramid:<scene of tests/_pyramid.py>"; optional expect + save: the sums of a
+slab whose digest is not `expect` are written to the file `save`); stdout: one JSON line per job with the
 sha256 of the radiance sums per slab and the counters of the last launch."""
 import ctypes as C
 import hashlib
@@ -26,7 +28,11 @@ def main():
     for job in jobs:
         name = job["config"] + ":" + job.get("shader", "disney")
         if name not in scenes:
-            hs, _ = load_config(job["config"], shader=job.get("shader", "disney"))
+            if job["config"].startswith("pyramid:"):         # a scene of tests/_pyramid.py, by its name there
+                from tests import _pyramid
+                hs = _pyramid.scene_by_name(job["config"][len("pyramid:"):])
+            else:
+                hs, _ = load_config(job["config"], shader=job.get("shader", "disney"))
             d = rt.lib.rt_scene_upload(C.byref(hs.scene))
             assert d, rt.last_error()
             scenes[name] = (hs, d)
@@ -42,7 +48,10 @@ def main():
                 if rt.lib.rt_render_accumulate(d, C.byref(p), accum.data_ptr(), None) != 0:
                     raise RuntimeError(rt.last_error())
                 torch.cuda.synchronize()
-                out["digests"].append(hashlib.sha256(accum.cpu().numpy().tobytes()).hexdigest())
+                sums = accum.cpu().numpy()
+                out["digests"].append(hashlib.sha256(sums.tobytes()).hexdigest())
+                if job.get("save") and out["digests"][-1] != job.get("expect"):      # for the parent's failure message
+                    np.save(job["save"], sums)
             c = rt.render.get_counters()
             out["counters"] = [c.rays, c.node_visits, c.leaf_visits, c.shades]
             out["contract"] = int(rt.lib.rt_math_contract())
