@@ -937,6 +937,34 @@ __device__ __forceinline__ void ray_setup(Ray3 &r, rt_v3 o, rt_v3 d) {
   r.fast = rt_slab_fast(o.x, o.y, o.z, r.inv_x, r.inv_y, r.inv_z, rt_slab_bias(o.x, r.inv_x), rt_slab_bias(o.y, r.inv_y), rt_slab_bias(o.z, r.inv_z));
 }
 
+// (hit, ray) -> the surface there: the fill of raytracer.c:159-184 from the 28-float triangle record `tb`.  The ONE copy of this
+// arithmetic: shade_hit(), feature_hit() (rt_features.hip) and rt_hit_attributes_kernel (rt_kernels.hip) are bit-exact against the
+// same oracle because they all read it here.  (Accessors for single values only: a member that returns a filled ShadeIn costs the
+// 16-wave path kernels 4 B of scratch, profiles/r10_summary.md; the callers fill theirs.)
+struct Surface {
+  float4 q0, q1, q2, q3, q4, q5, q6;      // the record: n_geo | material, three (vertex normal | uv part), tangent, bitangent, uv part
+  float  t0, t1, t2;                      // barycentric weights of the three vertices
+  rt_v3  point, n_geo, n_int;             // n_int: the interpolated normal, not normalised (raytracer.c:172-174)
+  __device__ __forceinline__ rt_v3 tangent() const { return rt_v3_make(q4.x, q4.y, q4.z); }
+  __device__ __forceinline__ rt_v3 bitangent() const { return rt_v3_make(q5.x, q5.y, q5.z); }
+  __device__ __forceinline__ float uvx() const { return rt_dot3(q1.w, t0, q3.w, t1, q5.w, t2); }
+  __device__ __forceinline__ float uvy() const { return rt_dot3(q2.w, t0, q4.w, t1, q6.x, t2); }
+  __device__ __forceinline__ int   material() const { return as_i(q0.w); }
+};
+__device__ __forceinline__ Surface surface_at(const float *tb, const HitRec &hit, const rt_v3 org, const rt_v3 dir) {
+  Surface s;
+  s.q0 = ld4(tb, 0); s.q1 = ld4(tb, 1); s.q2 = ld4(tb, 2); s.q3 = ld4(tb, 3);
+  s.q4 = ld4(tb, 4); s.q5 = ld4(tb, 5); s.q6 = ld4(tb, 6);
+  s.t1 = hit.u; s.t2 = hit.v;
+  s.t0 = 1.0f - s.t1 - s.t2;
+  s.point = rt_v3_madd(dir, hit.t, org);
+  s.n_geo = rt_v3_make(s.q0.x, s.q0.y, s.q0.z);
+  s.n_int = rt_v3_make(rt_dot3(s.q1.x, s.t0, s.q2.x, s.t1, s.q3.x, s.t2),
+                       rt_dot3(s.q1.y, s.t0, s.q2.y, s.t1, s.q3.y, s.t2),
+                       rt_dot3(s.q1.z, s.t0, s.q2.z, s.t1, s.q3.z, s.t2));
+  return s;
+}
+
 // One accepted closest hit -> pass-through or material evaluation and the next ray of the path
 // (raytracer.c:515-552).  Returns true when the path ended (radiance holds its value).
 template <class PT>
@@ -944,31 +972,23 @@ __device__ __forceinline__ bool shade_hit(const PT &P, const HitRec &hit, rt_v3 
                                           rt_v3 &tint, rt_v3 &emis, uint32_t &rng, int &bounce,
                                           LaneCounters &cn, rt_v3 &radiance) {
   bool done = false;
-  const float *tb = P.tris + (size_t)hit.tri * 28;
-  float4 q0 = ld4(tb, 0), q1 = ld4(tb, 1), q2 = ld4(tb, 2), q3 = ld4(tb, 3);
-  float4 q4 = ld4(tb, 4), q5 = ld4(tb, 5), q6 = ld4(tb, 6);
-  float t1 = hit.u, t2 = hit.v;
-  float t0 = 1.0f - t1 - t2;
-  rt_v3 point = rt_v3_madd(dir, hit.t, org);
-  rt_v3 n_geo = rt_v3_make(q0.x, q0.y, q0.z);
-  rt_v3 n_int = rt_v3_make(rt_dot3(q1.x, t0, q2.x, t1, q3.x, t2),
-                           rt_dot3(q1.y, t0, q2.y, t1, q3.y, t2),
-                           rt_dot3(q1.z, t0, q2.z, t1, q3.z, t2));
-  if (rt_v3_dot(n_geo, dir) > 0.0f || rt_v3_dot(n_int, dir) > 0.0f) {
+  const Surface s = surface_at(P.tris + (size_t)hit.tri * 28, hit, org, dir);
+  const rt_v3 point = s.point, n_geo = s.n_geo;
+  if (rt_v3_dot(n_geo, dir) > 0.0f || rt_v3_dot(s.n_int, dir) > 0.0f) {
     // back face: pass through, costs a bounce (raytracer.c:516-522)
     org = rt_v3_madd(dir, RT_EPS, point);
   } else {
     ShadeIn in;
     in.direction = dir;
-    in.normal = normalize_dev(n_int);
-    in.tangent = rt_v3_make(q4.x, q4.y, q4.z);
-    in.bitangent = rt_v3_make(q5.x, q5.y, q5.z);
-    in.uvx = rt_dot3(q1.w, t0, q3.w, t1, q5.w, t2);
-    in.uvy = rt_dot3(q2.w, t0, q4.w, t1, q6.x, t2);
+    in.normal = normalize_dev(s.n_int);
+    in.tangent = s.tangent();
+    in.bitangent = s.bitangent();
+    in.uvx = s.uvx();
+    in.uvy = s.uvy();
     rt_v3 out_dir, s_tint, s_emis;
     bool terminate;
     cn.shades += 1;
-    shade(P, as_i(q0.w), in, rng, out_dir, s_tint, s_emis, terminate, cn);
+    shade(P, s.material(), in, rng, out_dir, s_tint, s_emis, terminate, cn);
     emis = rt_v3_mul_add(s_emis, tint, emis);
     if (terminate) {
       done = true;
@@ -1026,6 +1046,10 @@ __device__ __forceinline__ int lane_now() {
   asm volatile("" : "+s"(ones));
   return (int)__builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
 }
+// set bits of a ballot below this lane: the lane's rank among the lanes of `mask` (v_mbcnt: no lane mask kept in registers)
+__device__ __forceinline__ int lane_rank(unsigned long long mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 // ---- the workgroup's LDS: the leading BVH nodes, then one slice per wave (rt_device.h, lds_split in rt_launch.cpp) ----
 // The node image, by all THREADS threads of the workgroup; the caller's __syncthreads() follows.
@@ -1049,16 +1073,35 @@ struct WaveLds {
   unsigned long long *acc;       // the accumulator tile
   int acc_off, pyr_off;          // byte offsets of the accumulator tile and the pyramid area from `smem`, wave-uniform: for lds_at()
 };
+// The perm stack of wave `wave` behind the node image, for slices `slice_f4` float4 apart: perm_stack_f4(depth) where the slice is
+// the stack alone (query and feature kernels: lds_split without a per-wave extra), more where the launch allocates more (wave_lds).
+__device__ __forceinline__ int perm_stack_f4(int depth) { return (depth > 0 ? depth : 1) * RT_LDS_PERM_LEVEL_F4; }
+__device__ __forceinline__ uint32_t *wave_perm(float4 *smem, int n_lds, int slice_f4, int wave) {
+  return reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * slice_f4);
+}
 __device__ __forceinline__ WaveLds wave_lds(float4 *smem, int n_lds, int depth, int wave) {
-  const int perm_f4 = (depth > 0 ? depth : 1) * RT_LDS_PERM_LEVEL_F4, slice_f4 = perm_f4 + RT_LDS_ACC_TILE_F4;
-  float4 *wave_base = smem + n_lds * RT_LDS_NODE_F4 + wave * slice_f4;
+  const int perm_f4 = perm_stack_f4(depth), slice_f4 = perm_f4 + RT_LDS_ACC_TILE_F4;
   const int base_f4 = n_lds * RT_LDS_NODE_F4 + __builtin_amdgcn_readfirstlane(wave) * slice_f4;
   WaveLds L;
-  L.perm = reinterpret_cast<uint32_t *>(wave_base);
-  L.acc = reinterpret_cast<unsigned long long *>(wave_base + perm_f4);
+  L.perm = wave_perm(smem, n_lds, slice_f4, wave);
+  L.acc = reinterpret_cast<unsigned long long *>(reinterpret_cast<float4 *>(L.perm) + perm_f4);
   L.acc_off = (base_f4 + perm_f4) * 16;
   L.pyr_off = (base_f4 + perm_f4 - RT_LDS_PERM_LEVEL_F4) * 16;
   return L;
+}
+// The accumulator tile: cleared by the wave (flush_tile leaves it cleared again), and one sample into pixel `pixel` of it.
+// (32-bit address arithmetic from the wave's byte offset: `acc + pixel * 3` is a 64-bit multiply-add on a pointer that is kept
+// in scratch)
+__device__ __forceinline__ void acc_tile_clear(unsigned long long *acc, const int lane) {
+  acc[lane] = 0ull;
+  acc[lane + 64] = 0ull;
+  acc[lane + 128] = 0ull;
+}
+__device__ __forceinline__ void tile_add_sample(float4 *smem, const int acc_off, const int pixel, const rt_v3 radiance) {
+  unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + pixel * 6);
+  atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
+  atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
+  atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
 }
 // the pyramid area, as words (floats or uint32_t) from pyr_off
 #define RT_PYR_PLANE      0      // [4 q .. 4 q + 2]: outward normal of side plane q of the tile's camera-ray pyramid
@@ -1269,6 +1312,33 @@ __device__ __forceinline__ RT_KArgs cold_args() {
   return p;
 }
 
+// A lane's traversal: what it does next and where it stands in the tree, and the closest hit so far.
+struct TravState {
+  int      phase, level, node, child;      // PH_*; the level of `node` (-1: above the root); the child to enter / test next
+  uint32_t cur, dirty, live;               // the children of `node` still to visit (3 bits each, count << 24); per level: re-test bit, has-children bit
+  HitRec   hit;
+};
+// No ray: the state of a lane that waits for one, as the struct's initialiser -- `TravState T = RT_TRAV_IDLE;`.  (An initialiser, not a
+// function: initialised through a reference or a returned struct, the path kernel's node and pop blocks come out with register
+// copies in other places, profiles/r10_summary.md.)
+#define RT_TRAV_IDLE {PH_NEED, -1, 0, 0, 0u, 0u, 0u, {RT_INF, -1, 0.0f, 0.0f}}
+// a new ray: traversal starts at the root, or at leaf group 0 of a tree without nodes (leaf_level = depth - 1 < 0).  hit.t = infinity:
+// a caller with a finite bound (raytracer.c:452) overwrites it.
+__device__ __forceinline__ void trav_start(TravState &T, const int leaf_level, const int last_row_offset) {
+  T.hit.t = RT_INF; T.hit.tri = -1; T.hit.u = 0; T.hit.v = 0;
+  T.dirty = 0; T.live = 0; T.cur = 0; T.level = -1; T.node = 0;
+  T.child = (leaf_level >= 0) ? 0 : last_row_offset;
+  T.phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+}
+
+// What a wave's traversal calls have in common: its LDS (wave_lds() / wave_perm()) and the launch's tree constants.
+struct TravWave {
+  float4       *smem;
+  const float4 *lds_nodes;
+  uint32_t     *perm;
+  int           n_lds, pyr_nodes, pyr_off, leaf_level, lane;      // pyr_nodes, pyr_off: PYRAMID only
+};
+
 // ---- the traversal blocks of the path kernels -------------------------------------------------------------------------
 // ray_bvh_node_hit (raytracer.c:443-483) for the 64 rays of a wave, phase-scheduled: per round the wave runs ONE block --
 // LEAF (8-triangle test, raytracer.c:84-188) or NODE (8-box slab test + near-first order, raytracer.c:190-230, :459-468),
@@ -1277,26 +1347,25 @@ __device__ __forceinline__ RT_KArgs cold_args() {
 // traversed at entry have finished (phase PH_HIT / PH_MISS).  This ONE function is the traversal of the tile-stream path
 // kernel (rt_kernels.hip), of the camera and trace kernels of the wavefront pipeline (rt_wavefront.hip) and of
 // rt_test_trace_stream_kernel (unit-level parity against oracle_trace_rays).
+//   W, T:    the wave's constants and the lane's state (above); w_nodes, w_leaves += the visits (wave-uniform counts).
 //   PYRAMID: node blocks whose lanes are camera rays (`is_cam`) of the wave's tile about to enter ONE node test only the
-//            child boxes the tile's pyramid (LDS, pyr_off) can touch (pyramid_cull_mask, node_enter_few).
+//            child boxes the tile's pyramid (LDS, W.pyr_off) can touch (pyramid_cull_mask, node_enter_few).
 //   ANY:     any-hit (rt_query_kernel's occlusion form): a lane whose leaf block ACCEPTED a triangle (t in [epsilon, hit.t)) ends
 //            with PH_HIT there instead of popping.  Same answer to "is there a hit" as the closest-hit traversal: until a triangle
 //            is accepted hit.t is the entry bound, no re-test bit is set and every node block sees the same bound, so the visits up
 //            to the first acceptance ARE the closest-hit traversal's first visits, and that one ends with PH_HIT exactly when it
 //            accepted at least once.
-struct TravState {
-  int      phase, level, node, child;
-  uint32_t cur, dirty, live;
-  HitRec   hit;
-};
-
 template <bool LDSN, bool SHORT_DIV, bool PYRAMID, bool ANY = false>
-__device__ __forceinline__ void traversal_blocks(const RT_KParams &P, float4 *smem, const float4 *lds_nodes, uint32_t *perm,
-                                                 const int lane, const int n_lds, const int pyr_nodes, const int pyr_off,
-                                                 const int leaf_level, const int exit_lanes, const int n_trav0, const Ray3 &ray,
-                                                 const bool is_cam, int &phase, int &level, int &node, int &child, uint32_t &cur,
-                                                 uint32_t &dirty, uint32_t &live, HitRec &hit, uint32_t &w_nodes, uint32_t &w_leaves,
+__device__ __forceinline__ void traversal_blocks(const RT_KParams &P, const TravWave &W, const Ray3 &ray, const bool is_cam, TravState &T,
+                                                 const int exit_lanes, const int n_trav0, uint32_t &w_nodes, uint32_t &w_leaves,
                                                  uint32_t *lg = nullptr) {
+  float4 *const smem = W.smem;
+  const float4 *const lds_nodes = W.lds_nodes;
+  uint32_t *const perm = W.perm;
+  const int lane = W.lane, n_lds = W.n_lds, pyr_nodes = W.pyr_nodes, pyr_off = W.pyr_off, leaf_level = W.leaf_level;
+  int &phase = T.phase, &level = T.level, &node = T.node, &child = T.child;
+  uint32_t &cur = T.cur, &dirty = T.dirty, &live = T.live;
+  HitRec &hit = T.hit;
   static_assert(!(ANY && PYRAMID), "the pyramid-culled leaf block has no any-hit exit");
   LG(LG_TRAV_CALLS, 1);
 #ifdef RT_LEDGER
@@ -1569,6 +1638,14 @@ struct ShadeParams {            // what shade_hit / background_lookup read (same
   int32_t bg_texture, max_bounces;
 };
 
+// ... filled from A: the kernel arguments, by pointer (cold_args(), &P).  Without materials: for background_lookup alone.
+template <class SPT, class ARGS>
+__device__ __forceinline__ void shade_params(SPT &SP, const ARGS A, const bool with_materials) {
+  SP.tris = with_materials ? A->tris : nullptr; SP.mats = with_materials ? A->mats : nullptr;
+  SP.textures = A->textures; SP.texels = A->texels;
+  SP.bg_texture = A->bg_texture; SP.max_bounces = A->max_bounces;
+}
+
 struct ShadeParamsLds : ShadeParams {};      // ... of a kernel that keeps the sRGB scale table in LDS (pow24_lds_init)
 template <> struct Pow24InLds<ShadeParamsLds> { static constexpr bool value = RT_MATH_POW24 != 0; };
 
@@ -1576,7 +1653,15 @@ struct PrimaryParams {          // what primary_ray reads
   float cam[3][4];
   float focal_length, inv_width, inv_height, aspect;
 };
-
+// ... filled from S, the camera (kernel arguments or a view record), and A, the frame constants (kernel arguments), both by pointer
+template <class CAM, class ARGS>
+__device__ __forceinline__ void primary_params(PrimaryParams &PP, const CAM S, const ARGS A) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) PP.cam[i][j] = S->cam[i][j];
+  PP.focal_length = S->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+}
 
 #include "rt_tile.hip.h"      // the stages of a tile-owning kernel's outer loop
 

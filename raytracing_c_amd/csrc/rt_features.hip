@@ -34,34 +34,26 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 }
 
 // One accepted closest hit (raytracer.c:515-552): a back face -> `org` advanced, returns false; else the feature values of the
-// hit, with the attribute arithmetic of shade_hit() and the normal / albedo fetches of shade() (rt_dev.hip.h).
+// hit, from surface_at() as shade_hit() reads it and the normal / albedo fetches of shade() (rt_dev.hip.h).
 template <class PT>
 __device__ __forceinline__ bool feature_hit(const PT &P, const HitRec &hit, rt_v3 &org, const rt_v3 dir, rt_v3 &albedo, rt_v3 &normal,
                                             rt_v3 &position) {
-  const float *tb = P.tris + (size_t)hit.tri * 28;
-  float4 q0 = ld4(tb, 0), q1 = ld4(tb, 1), q2 = ld4(tb, 2), q3 = ld4(tb, 3);
-  float4 q4 = ld4(tb, 4), q5 = ld4(tb, 5), q6 = ld4(tb, 6);
-  float t1 = hit.u, t2 = hit.v;
-  float t0 = 1.0f - t1 - t2;
-  rt_v3 point = rt_v3_madd(dir, hit.t, org);
-  rt_v3 n_geo = rt_v3_make(q0.x, q0.y, q0.z);
-  rt_v3 n_int = rt_v3_make(rt_dot3(q1.x, t0, q2.x, t1, q3.x, t2),
-                           rt_dot3(q1.y, t0, q2.y, t1, q3.y, t2),
-                           rt_dot3(q1.z, t0, q2.z, t1, q3.z, t2));
-  if (rt_v3_dot(n_geo, dir) > 0.0f || rt_v3_dot(n_int, dir) > 0.0f) {
+  const Surface s = surface_at(P.tris + (size_t)hit.tri * 28, hit, org, dir);
+  const rt_v3 point = s.point;
+  if (rt_v3_dot(s.n_geo, dir) > 0.0f || rt_v3_dot(s.n_int, dir) > 0.0f) {
     org = rt_v3_madd(dir, RT_EPS, point);            // back face: pass through, costs an iteration (raytracer.c:516-522)
     return false;
   }
   ShadeIn in;
   in.direction = dir;
-  in.normal = normalize_dev(n_int);
-  in.tangent = rt_v3_make(q4.x, q4.y, q4.z);
-  in.bitangent = rt_v3_make(q5.x, q5.y, q5.z);
-  in.uvx = rt_dot3(q1.w, t0, q3.w, t1, q5.w, t2);
-  in.uvy = rt_dot3(q2.w, t0, q4.w, t1, q6.x, t2);
+  in.normal = normalize_dev(s.n_int);
+  in.tangent = s.tangent();
+  in.bitangent = s.bitangent();
+  in.uvx = s.uvx();
+  in.uvy = s.uvy();
   // the material record: base colour, normal-map strength, the albedo and normal textures with their descriptors -- through the
   // scalar cache when every lane has the same material (see shade())
-  const int mat = as_i(q0.w);
+  const int mat = s.material();
   float4 m0;
   float strength;
   int tex_albedo, tex_normal;
@@ -107,19 +99,17 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_features_kernel(RT_KParams P
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int n_lds = P.n_lds_nodes;
-  const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * perm_f4);
   pow24_lds_init((int)threadIdx.x);
   lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
   __syncthreads();
   const int leaf_level = P.depth - 1;
+  // (the wave's slice is the perm stack alone; no pyramid)
+  const TravWave W = {smem, smem, wave_perm(smem, n_lds, perm_stack_f4(P.depth), wave), n_lds, 0, 0, leaf_level, lane};
   const int shift = F.shift;
   uint32_t next = 0, end = 0;                                     // the wave's current grab: units [next, end)
   uint32_t w_nodes = 0, w_leaves = 0;                             // (traversal_blocks counts them; not reported)
   ShadeParamsLds SP;
-  SP.tris = P.tris; SP.mats = P.mats; SP.textures = P.textures; SP.texels = P.texels;
-  SP.bg_texture = P.bg_texture; SP.max_bounces = P.max_bounces;
+  shade_params(SP, &P, true);
 
   for (;;) {
     if (next >= end) {
@@ -140,37 +130,28 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_features_kernel(RT_KParams P
     const int sm = P.sample_first + (int)(sb << shift) + (lane & ((1 << shift) - 1));
     const bool valid = x < P.width && y < P.height && sm < P.sample_end && P.max_bounces > 0;
 
-    int   phase = PH_NEED, bounce = 0;
+    int   bounce = 0;
     Ray3  ray;
     rt_v3 org = rt_v3_make(0, 0, 0), dir = rt_v3_make(0, 0, 1);
     if (valid) primary_ray(P, x, y, sm, org, dir);
-    int   level = -1, node = 0, child = 0;
-    uint32_t cur = 0, dirty = 0, live = 0;
-    HitRec hit;
-    hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+    TravState T = RT_TRAV_IDLE;
     float cov = 0.0f;
     rt_v3 albedo = rt_v3_make(0, 0, 0), normal = rt_v3_make(0, 0, 0), position = rt_v3_make(0, 0, 0);
     bool start = valid;
     for (;;) {
       // a new segment: traversal starts at the root (or at leaf group 0)
       ray_setup<false>(ray, org, dir);
-      if (start) {
-        hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
-        dirty = 0; live = 0; cur = 0; level = -1; node = 0;
-        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
-      }
-      const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+      if (start) trav_start(T, leaf_level, P.last_row_offset);
+      const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
       if (n_trav0 == 0) break;
-      traversal_blocks<true, false, false>(P, smem, lds_nodes, perm, lane, n_lds, 0, 0, leaf_level, 64, n_trav0, ray, false, phase,
-                                           level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
+      traversal_blocks<true, false, false>(P, W, ray, false, T, 64, n_trav0, w_nodes, w_leaves);
       // every lane that traversed has ended its segment: a feature hit, a back face (again, while iterations are left), or nothing
       start = false;
-      if (phase == PH_HIT) {
-        if (feature_hit(SP, hit, org, dir, albedo, normal, position)) cov = 1.0f;
+      if (T.phase == PH_HIT) {
+        if (feature_hit(SP, T.hit, org, dir, albedo, normal, position)) cov = 1.0f;
         else start = ++bounce < P.max_bounces;
       }
-      phase = PH_NEED;
+      T.phase = PH_NEED;
     }
 
     // ---- the unit's sums: the samples of a pixel are (1 << shift) neighbouring lanes ----

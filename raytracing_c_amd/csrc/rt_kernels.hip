@@ -70,7 +70,6 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
   const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the wave's LDS slice: perm stack, pyramid area, accumulator tile
-  uint32_t *perm = L.perm;
   unsigned long long *acc = L.acc;
   const int acc_off = L.acc_off, pyr_off = L.pyr_off;
 
@@ -91,9 +90,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     __syncthreads();          // (the sRGB scale table)
   }
 
-  acc[lane] = 0ull;
-  acc[lane + 64] = 0ull;
-  acc[lane + 128] = 0ull;
+  acc_tile_clear(acc, lane);
 
   // ---- the root's populated children: the only ones a ray's root visit has to test (in front of the traversal call, below) ----
   // The reference builder fills a tree of fixed capacity, so the root of a small scene has children without a triangle below them:
@@ -168,16 +165,12 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
     LGT1(LG_CYC_TILE);
 
     // ---------------- per-lane state ----------------
-    int   phase = PH_NEED;
     int   pix = 0, bounce = 0;
     uint32_t rng = 0;
     Ray3  ray;
     ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
     rt_v3 tint = rt_v3_make(1, 1, 1), emis = rt_v3_make(0, 0, 0);
-    int   level = -1, node = 0, child = 0;
-    uint32_t cur = 0, dirty = 0, live = 0;
-    HitRec hit;
-    hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+    TravState T = RT_TRAV_IDLE;
 
     // the tile's units as this wave holds them (grab_units, unit_decode)
     bool tile_open = true;
@@ -205,14 +198,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       const int width = A->width, height = A->height, sample_first = A->sample_first, sample_end = A->sample_end;
       const uint32_t n_sb = (uint32_t)A->n_sample_blocks, gmax = (uint32_t)A->grab_max;
       PrimaryParams PP;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) PP.cam[i][j] = S->cam[i][j];
-      PP.focal_length = S->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+      primary_params(PP, S, A);
       ShadeParamsLds SP;
-      SP.tris = nullptr; SP.mats = nullptr; SP.textures = A->textures; SP.texels = A->texels;
-      SP.bg_texture = A->bg_texture; SP.max_bounces = A->max_bounces;
+      shade_params(SP, A, false);
       uint32_t *tile_next = A->tile_next, *open_groups = A->open_groups;
       uint32_t n_sky = 0;                 // paths served here: their root visit is COUNTED (like the oracle's) but not executed
       // lane i: entry i of the tile's node list, 0 past its end (the pass below stops there: no count in a scalar register)
@@ -302,10 +290,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           if (valid[q]) {
             const rt_v3 bg = background_lookup(SP, dirs[q]);
             const rt_v3 radiance = rt_v3_mul_add(bg, rt_v3_make(1, 1, 1), rt_v3_make(0, 0, 0));      // tint 1, emission 0 (raytracer.c:554)
-            unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + (U.c_pix0 + pxs[q]) * 6);
-            atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
-            atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
-            atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
+            tile_add_sample(smem, acc_off, U.c_pix0 + pxs[q], radiance);
           }
           nv += (uint32_t)__popcll(__ballot(valid[q]));
         }
@@ -334,14 +319,13 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         rt_v3 org = ray.o, dir = ray.d;
         RT_KArgs A = cold_args();
         ShadeParamsLds SP;
-        SP.tris = A->tris; SP.mats = A->mats; SP.textures = A->textures; SP.texels = A->texels;
-        SP.bg_texture = A->bg_texture; SP.max_bounces = A->max_bounces;
+        shade_params(SP, A, true);
         // ---- environment for the paths that left the scene ----
 #ifdef RT_LEDGER
-        { const int n_env = (int)__popcll(__ballot(phase == PH_MISS)); LG(LG_ENV_X, n_env != 0); LG(LG_ENV_L, n_env); }
+        { const int n_env = (int)__popcll(__ballot(T.phase == PH_MISS)); LG(LG_ENV_X, n_env != 0); LG(LG_ENV_L, n_env); }
 #endif
         LGM("env_begin");
-        if (phase == PH_MISS) {
+        if (T.phase == PH_MISS) {
           cn.bgs = 1;
           rt_v3 bg = background_lookup(SP, dir);
           radiance = rt_v3_mul_add(bg, tint, emis);
@@ -357,8 +341,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         // wave-iteration shades a path does not matter: its state (rng included) travels with it, sums are order-free.
         bool shade_now = true;
         if (park) {
-          const unsigned long long mHit = __ballot(phase == PH_HIT);
-          const unsigned long long mIdle = __ballot(phase == PH_NEED) | __ballot(phase == PH_MISS);
+          const unsigned long long mHit = __ballot(T.phase == PH_HIT);
+          const unsigned long long mIdle = __ballot(T.phase == PH_NEED) | __ballot(T.phase == PH_MISS);
           const int h = (int)__popcll(mHit), f = (int)__popcll(mIdle);
           const int back = n_parked < f ? n_parked : f;                 // parked hits that fit into idle lanes
           uint32_t *pk = park + (size_t)__builtin_amdgcn_readfirstlane(wave_id) * (RT_PARK_FIELDS * RT_PARK_CAP);    // (scalar base)
@@ -367,28 +351,25 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
               LG(LG_PLOAD_X, 1); LG(LG_PLOAD_L, back);
               LGM("pload_begin");
               if (done) {                                               // (an environment lane is idle once its sample is added)
-                unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + pix * 6);
-                atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
-                atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
-                atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
-                phase = PH_NEED;
+                tile_add_sample(smem, acc_off, pix, radiance);
+                T.phase = PH_NEED;
                 done = false;
               }
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mIdle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mIdle, 0u));
-              if (phase == PH_NEED && rank < back) {
+              const int rank = lane_rank(mIdle);
+              if (T.phase == PH_NEED && rank < back) {
                 const uint32_t *q = pk + (n_parked - 1 - rank);         // most recently parked first
                 uint32_t v[RT_PARK_FIELDS];
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
                 for (int i = 0; i < RT_PARK_FIELDS; i++)
                   v[i] = __hip_atomic_load(q + i * RT_PARK_CAP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                hit.t = as_f((int)v[0]); hit.tri = (int)v[1]; hit.u = as_f((int)v[2]); hit.v = as_f((int)v[3]);
+                T.hit.t = as_f((int)v[0]); T.hit.tri = (int)v[1]; T.hit.u = as_f((int)v[2]); T.hit.v = as_f((int)v[3]);
                 org = rt_v3_make(as_f((int)v[4]), as_f((int)v[5]), as_f((int)v[6]));
                 dir = rt_v3_make(as_f((int)v[7]), as_f((int)v[8]), as_f((int)v[9]));
                 tint = rt_v3_make(as_f((int)v[10]), as_f((int)v[11]), as_f((int)v[12]));
                 emis = rt_v3_make(as_f((int)v[13]), as_f((int)v[14]), as_f((int)v[15]));
                 rng = v[16]; pix = (int)(v[17] & 63u); bounce = (int)(v[17] >> 6);
-                phase = PH_HIT;
+                T.phase = PH_HIT;
               }
               n_parked -= back;
               LGM("pload_end");
@@ -397,10 +378,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
             LG(LG_PSTORE_X, 1); LG(LG_PSTORE_L, h);
             LGM("pstore_begin");
             shade_now = false;
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mHit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mHit, 0u));
-            if (phase == PH_HIT) {
+            const int rank = lane_rank(mHit);
+            if (T.phase == PH_HIT) {
               uint32_t *q = pk + (n_parked + rank);
-              const uint32_t v[RT_PARK_FIELDS] = {(uint32_t)as_i(hit.t), (uint32_t)hit.tri, (uint32_t)as_i(hit.u), (uint32_t)as_i(hit.v),
+              const uint32_t v[RT_PARK_FIELDS] = {(uint32_t)as_i(T.hit.t), (uint32_t)T.hit.tri, (uint32_t)as_i(T.hit.u), (uint32_t)as_i(T.hit.v),
                                                   (uint32_t)as_i(org.x), (uint32_t)as_i(org.y), (uint32_t)as_i(org.z),
                                                   (uint32_t)as_i(dir.x), (uint32_t)as_i(dir.y), (uint32_t)as_i(dir.z),
                                                   (uint32_t)as_i(tint.x), (uint32_t)as_i(tint.y), (uint32_t)as_i(tint.z),
@@ -411,18 +392,18 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
               // the record is read back by ANOTHER lane of this wave (agent-scope loads below): the release / acquire pair at
               // wavefront scope states that order to the compiler; the hardware returns one wave's vector memory operations in order
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-              phase = PH_NEED;
+              T.phase = PH_NEED;
             }
             n_parked += h;
             LGM("pstore_end");
           }
         }
 #ifdef RT_LEDGER
-        { const int n_sh = (int)__popcll(__ballot(phase == PH_HIT && shade_now)); LG(LG_SHADE_X, n_sh != 0); LG(LG_SHADE_L, n_sh); }
+        { const int n_sh = (int)__popcll(__ballot(T.phase == PH_HIT && shade_now)); LG(LG_SHADE_X, n_sh != 0); LG(LG_SHADE_L, n_sh); }
 #endif
         LGM("shade_begin");
-        if (phase == PH_HIT && shade_now) {
-          done = shade_hit(SP, hit, org, dir, tint, emis, rng, bounce, cn, radiance);
+        if (T.phase == PH_HIT && shade_now) {
+          done = shade_hit(SP, T.hit, org, dir, tint, emis, rng, bounce, cn, radiance);
           start = !done;
         }
         LGM("shade_end");
@@ -431,13 +412,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 #endif
         LGM("accum_begin");
         if (done) {
-          // (32-bit address arithmetic from the wave's byte offset: `acc + pix * 3` is a 64-bit multiply-add on a pointer
-          // that is kept in scratch)
-          unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + pix * 6);
-          atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
-          atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
-          atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
-          phase = PH_NEED;
+          tile_add_sample(smem, acc_off, pix, radiance);
+          T.phase = PH_NEED;
         }
         LGM("accum_end");
         w_shades += (uint32_t)__popcll(__ballot(cn.shades != 0));
@@ -446,49 +422,11 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
 
         // ---- regeneration: idle lanes take the next paths of the tile, across chunk boundaries ----
         if (tile_open) {
-          unsigned long long need = __ballot(phase == PH_NEED);
-          bool got = false;
-          int  gx = 0, gy = 0, gs = 0, gp = 0;
-          const int width = A->width, sample_end = A->sample_end;
-          LGM("regen_begin");
-          while (need) {
-            LG(LG_REGEN_X, 1);
-            if (U.c_next >= U.c_end) {
-              if (U.u_cur + 1u < U.u_end) {
-                U.u_cur += 1u;
-              } else {
-                if (!grab_units(lane, tile_idx, n_chunks_tile, A->tile_next, A->open_groups, (uint32_t)A->grab_max, U, t_wave_start, t_last_grab LG_ARG)) {
-                  tile_open = false;
-                  LGD0((int)__popcll(__ballot(phase != PH_NEED || got)) + n_parked);      // (ledger builds: the tile's drain starts here)
-                  break;
-                }
-              }
-              unit_decode(U, tile_x0, tile_y0, shift, unit_paths, (uint32_t)A->n_sample_blocks, A->sample_first, width, A->height);
-              continue;
-            }
-            const int n_need = (int)__popcll(need);
-            const int avail = U.c_end - U.c_next;
-            const int take = n_need < avail ? n_need : avail;
-            // set bits of `need` below this lane (v_mbcnt: no lane mask kept in registers)
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-            bool valid = false;
-            if (phase == PH_NEED && !got && rank < take) {
-              // k -> (pixel of the row, sample of the chunk), pixel-major: the lanes of a wave stay on a few pixels
-              int k = U.c_next + rank;
-              int px = k >> shift;
-              int sm = U.c_s0 + (k & ((1 << shift) - 1));
-              int x = U.c_x0 + px;
-              if (x < width && sm < sample_end) {
-                valid = true;
-                if (SP.max_bounces > 0) { got = true; gx = x; gy = U.c_y; gs = sm; gp = U.c_pix0 + px; }
-                // max_bounces == 0: the path exists and is black (the loop of raytracer.c:512 runs zero times)
-              }
-            }
-            w_paths += (uint32_t)__popcll(__ballot(valid));
-            U.c_next += take;
-            need = __ballot(phase == PH_NEED && !got);
-          }
-          LGM("regen_end");
+          NewPath np = {0, 0, 0, 0};
+          const bool got = regen_paths(T.phase, np, SP.max_bounces > 0, U, tile_open, false, lane, tile_idx, n_chunks_tile, tile_x0, tile_y0,
+                                       shift, unit_paths, t_wave_start, t_last_grab, w_paths LG_ARG);
+          if (!tile_open) LGD0((int)__popcll(__ballot(T.phase != PH_NEED || got)) + n_parked);      // (ledger builds: the tile's drain starts here)
+          const int gx = np.x, gy = np.y, gs = np.sample, width = A->width;
 #ifdef RT_LEDGER
           { const int n_pr = (int)__popcll(__ballot(got)); LG(LG_PRIM_X, n_pr != 0); LG(LG_PRIM_L, n_pr); LG(LG_REGEN_L, n_pr); }
 #endif
@@ -496,15 +434,11 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           if (got) {
             typename CamSrc<VIEWS>::type S;
             if constexpr (VIEWS) S = vrec; else S = A;
-            pix = gp;
+            pix = np.pix;
             bounce = 0;
             rng = rt_path_seed(S->seed, (uint32_t)(gx + gy * width), (uint32_t)gs);
             PrimaryParams PP;
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-              for (int j = 0; j < 4; j++) PP.cam[i][j] = S->cam[i][j];
-            PP.focal_length = S->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+            primary_params(PP, S, A);
             primary_ray(PP, gx, gy, gs, org, dir);
             tint = rt_v3_make(1, 1, 1);
             emis = rt_v3_make(0, 0, 0);
@@ -520,20 +454,14 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         LGM("start_begin");
         if (start) {                      // a new ray: traversal starts at the root (or at leaf group 0)
           ray_setup<SHORT_DIV>(ray, org, dir);
-          hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
-          dirty = 0;
-          live = 0;
+          trav_start(T, leaf_level, P.last_row_offset);
           // (at level -1 the word holds no children yet: 1 tells the root visit below that it serves this ray -- the ray is NaN-free and
           //  the root has one to four populated children (RT_PYR_ROOT_POP); the LDS read hides behind the ray set-up here, and a scene whose
           //  root the visit does not serve pays one ballot per traversal call for it, no LDS round trip)
-          cur = (LDSN && ray.fast && reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off))[RT_PYR_ROOT_POP] != 0u) ? 1u : 0u;
-          level = -1;
-          node = 0;
-          child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-          phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+          T.cur = (LDSN && ray.fast && reinterpret_cast<const uint32_t *>(lds_at(smem, pyr_off))[RT_PYR_ROOT_POP] != 0u) ? 1u : 0u;
           // camera ray of a tile that cannot touch the scene: its one node visit finds no candidate (see tile_root_miss)
           skip_root = fresh && tile_root_miss && ray.fast;
-          if (skip_root) phase = PH_MISS;
+          if (skip_root) T.phase = PH_MISS;
         }
         LGM("start_end");
         w_rays += (uint32_t)__popcll(__ballot(start));
@@ -546,10 +474,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         LGT1(LG_CYC_S);
       }
 
-      const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+      const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
       if (n_trav0 == 0) {
-        if (__any(phase == PH_MISS)) continue;   // camera rays that skipped the root: straight to the environment
-        if (n_parked > 0 || __any(phase == PH_HIT)) continue;      // parked hits come back in the next S block
+        if (__any(T.phase == PH_MISS)) continue;   // camera rays that skipped the root: straight to the environment
+        if (n_parked > 0 || __any(T.phase == PH_HIT)) continue;      // parked hits come back in the next S block
         if (!tile_open) break;            // every path of the tile that this wave took has ended
         continue;                         // (nothing started, e.g. pixels outside the image: pull more)
       }
@@ -565,7 +493,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       // and has finished, for the exit rule below.  Rays that are not NaN-free, and roots left to the node blocks (RT_PYR_ROOT_POP == 0),
       // keep child = 0, PH_NODE.
       if (LDSN) {
-        const bool at_root = phase == PH_NODE && level < 0 && cur != 0u;      // (`cur`: set where the ray starts; ray.fast itself is in scratch here)
+        const bool at_root = T.phase == PH_NODE && T.level < 0 && T.cur != 0u;      // (`cur`: set where the ray starts; ray.fast itself is in scratch here)
         const int n_root = (int)__popcll(__ballot(at_root));
         if (n_root != 0) {
           LGM("root_begin");
@@ -588,15 +516,15 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
             if ((ce >> 8) == 1u) rsurv &= ~ce;
           }
           if (at_root) {
-            level = 0;
-            cur = rsurv ? node_enter_few<true>(ray, lds_nodes, 0, rsurv, RT_INF) : 0u;
-            if (cur >> 24) {
-              child = 1 + (int)(cur & 7u);
-              cur = ((cur >> 3) & 0x1FFFFFu) | (((cur >> 24) - 1u) << 24);
-              phase = (leaf_level == 0) ? PH_LEAF : PH_NODE;
+            T.level = 0;
+            T.cur = rsurv ? node_enter_few<true>(ray, lds_nodes, 0, rsurv, RT_INF) : 0u;
+            if (T.cur >> 24) {
+              T.child = 1 + (int)(T.cur & 7u);
+              T.cur = ((T.cur >> 3) & 0x1FFFFFu) | (((T.cur >> 24) - 1u) << 24);
+              T.phase = (leaf_level == 0) ? PH_LEAF : PH_NODE;
             } else {
-              level = -1;
-              phase = PH_MISS;
+              T.level = -1;
+              T.phase = PH_MISS;
             }
           }
           LGM("root_end");
@@ -607,9 +535,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       // while the tile still hands out paths, wait until `thresh` lanes want the S block (dense shading); once it is
       // exhausted nothing refills the lanes, and what matters is the latency of the remaining paths' bounce chains:
       // shade as soon as `drain_thresh` lanes wait
-      traversal_blocks<LDSN, SHORT_DIV, true>(P, smem, lds_nodes, perm, lane, n_lds, pyr_nodes, pyr_off, leaf_level,
-                                              tile_open ? thresh : drain_thresh, n_trav0, ray, bounce == 0, phase, level, node,
-                                              child, cur, dirty, live, hit, w_nodes, w_leaves LG_ARG);
+      const TravWave W = {smem, lds_nodes, L.perm, n_lds, pyr_nodes, pyr_off, leaf_level, lane};
+      traversal_blocks<LDSN, SHORT_DIV, true>(P, W, ray, bounce == 0, T, tile_open ? thresh : drain_thresh, n_trav0, w_nodes, w_leaves LG_ARG);
     }
 
     // ---------------- flush the wave's share of the tile: lane p owns pixel p ----------------
@@ -936,7 +863,7 @@ __global__ __launch_bounds__(1024) void rt_prepare_kernel(int n_tiles, uint32_t 
         uint32_t pos = 0;
         if (lane == 0) pos = atomicAdd(&hist[wave][b0], (uint32_t)__popcll(m));
         pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const int rank = lane_rank(m);
         if (bkt == b0) order[pos + (uint32_t)rank] = (uint32_t)i;
         todo &= ~m;
       }
@@ -1063,34 +990,31 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, R
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int n_lds = P.n_lds_nodes;
-  const float4 *lds_nodes = smem;
-  const int perm_f4 = (P.depth > 0 ? P.depth : 1) * 16;
-  uint32_t *perm = reinterpret_cast<uint32_t *>(smem + n_lds * RT_LDS_NODE_F4 + wave * perm_f4);
   lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
   __syncthreads();
   const int leaf_level = P.depth - 1;
+  // (the wave's slice is the perm stack alone; no pyramid)
+  const TravWave W = {smem, smem, wave_perm(smem, n_lds, perm_stack_f4(P.depth), wave), n_lds, 0, 0, leaf_level, lane};
   int  next = 0, end = 0;                                         // the wave's current grab: rays [next, end) are not handed out yet
   bool drained = false;                                           // the launch's counter has run past the list (wave-uniform)
 
-  int   phase = PH_NEED, idx = 0;
+  int   idx = 0;
   Ray3  ray;
   ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
-  int   level = -1, node = 0, child = 0;
-  uint32_t cur = 0, dirty = 0, live = 0, w_nodes = 0, w_leaves = 0, w_rays = 0, w_hits = 0;
-  HitRec hit;
-  hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+  uint32_t w_nodes = 0, w_leaves = 0, w_rays = 0, w_hits = 0;
+  TravState T = RT_TRAV_IDLE;
   for (;;) {
-    w_rays += (uint32_t)__popcll(__ballot(phase == PH_HIT || phase == PH_MISS));
-    w_hits += (uint32_t)__popcll(__ballot(phase == PH_HIT));
-    if (phase == PH_HIT || phase == PH_MISS) {
+    w_rays += (uint32_t)__popcll(__ballot(T.phase == PH_HIT || T.phase == PH_MISS));
+    w_hits += (uint32_t)__popcll(__ballot(T.phase == PH_HIT));
+    if (T.phase == PH_HIT || T.phase == PH_MISS) {
       // (a miss: t is still the entry bound, triangle -1, u = v = 0 -- nothing was accepted since the refill)
-      if (ANY) Q.flags[idx] = phase == PH_HIT ? 1 : 0;
-      else reinterpret_cast<float4 *>(Q.hits)[idx] = make_float4(hit.t, as_f(hit.tri), hit.u, hit.v);
-      phase = PH_NEED;
+      if (ANY) Q.flags[idx] = T.phase == PH_HIT ? 1 : 0;
+      else reinterpret_cast<float4 *>(Q.hits)[idx] = make_float4(T.hit.t, as_f(T.hit.tri), T.hit.u, T.hit.v);
+      T.phase = PH_NEED;
     }
     // refill: every lane without a ray takes the next one of the wave's grab; a grab that runs out is followed by the next
     for (;;) {
-      const unsigned long long need = __ballot(phase == PH_NEED);
+      const unsigned long long need = __ballot(T.phase == PH_NEED);
       if (need == 0ull || drained) break;
       if (next >= end) {
         uint32_t s = 0;
@@ -1100,23 +1024,19 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, R
         next = (int)s;
         end = (Q.n - next < Q.grab) ? Q.n : next + Q.grab;
       }
-      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-      if (phase == PH_NEED && next + rank < end) {
+      const int rank = lane_rank(need);
+      if (T.phase == PH_NEED && next + rank < end) {
         idx = next + rank;
         const float *r = Q.rays + (size_t)idx * 6;
         ray_setup<false>(ray, rt_v3_make(r[0], r[1], r[2]), rt_v3_make(r[3], r[4], r[5]));
-        hit.t = Q.t_max ? Q.t_max[idx] : RT_INF;                  // raytracer.c:452: hit.distance on entry is the upper bound
-        hit.tri = -1; hit.u = 0; hit.v = 0;
-        dirty = 0; live = 0; cur = 0; level = -1; node = 0;
-        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+        trav_start(T, leaf_level, P.last_row_offset);
+        if (Q.t_max) T.hit.t = Q.t_max[idx];                        // raytracer.c:452: hit.distance on entry is the upper bound
       }
       next += (int)__popcll(need);
     }
-    const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+    const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
     if (n_trav0 == 0) break;                                      // (only a drained wave gets here without a ray in flight)
-    traversal_blocks<true, false, false, ANY>(P, smem, lds_nodes, perm, lane, n_lds, 0, 0, leaf_level, drained ? 64 : Q.exit_lanes,
-                                              n_trav0, ray, false, phase, level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
+    traversal_blocks<true, false, false, ANY>(P, W, ray, false, T, drained ? 64 : Q.exit_lanes, n_trav0, w_nodes, w_leaves);
   }
   if (lane == 0) {
     atomicAdd(Q.counters + RT_QCNT_RAYS, (unsigned long long)w_rays);
@@ -1127,7 +1047,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void rt_query_kernel(RT_KParams P, R
 }
 
 // (ray, t, triangle, u, v) -> the reference's Hit without the Shader pair (RT_Device_Hit, rt_hip.h): the fill of raytracer.c:159-184
-// from the 28-float triangle record, with the expressions shade_hit() uses.  One thread per ray; a miss gets distance = t (the
+// from the 28-float triangle record, by surface_at() as shade_hit() reads it.  One thread per ray; a miss gets distance = t (the
 // entry bound), triangle = material = -1 and zeros.  Records are 88 bytes, 8-byte aligned: eleven 8-byte stores.
 __global__ void rt_hit_attributes_kernel(const float *tris, int n, const float *rays, const float *hits, float *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1143,22 +1063,18 @@ __global__ void rt_hit_attributes_kernel(const float *tris, int n, const float *
   if (tri >= 0) {
     const float *r = rays + (size_t)i * 6;
     const rt_v3 org = rt_v3_make(r[0], r[1], r[2]), dir = rt_v3_make(r[3], r[4], r[5]);
-    const float *tb = tris + (size_t)tri * 28;
-    float4 q0 = ld4(tb, 0), q1 = ld4(tb, 1), q2 = ld4(tb, 2), q3 = ld4(tb, 3);
-    float4 q4 = ld4(tb, 4), q5 = ld4(tb, 5), q6 = ld4(tb, 6);
-    const float t1 = h.z, t2 = h.w;
-    const float t0 = 1.0f - t1 - t2;
-    const rt_v3 point = rt_v3_madd(dir, h.x, org);
-    o[1] = rt_dot3(q1.x, t0, q2.x, t1, q3.x, t2);                 // normal (interpolated, not normalised: raytracer.c:172-174)
-    o[2] = rt_dot3(q1.y, t0, q2.y, t1, q3.y, t2);
-    o[3] = rt_dot3(q1.z, t0, q2.z, t1, q3.z, t2);
-    o[4] = q0.x; o[5] = q0.y; o[6] = q0.z;                        // normal_geo
-    o[7] = point.x; o[8] = point.y; o[9] = point.z;
-    o[10] = q4.x; o[11] = q4.y; o[12] = q4.z;                     // tangent
-    o[13] = q5.x; o[14] = q5.y; o[15] = q5.z;                     // bitangent
-    o[16] = rt_dot3(q1.w, t0, q3.w, t1, q5.w, t2);                // tex_coords
-    o[17] = rt_dot3(q2.w, t0, q4.w, t1, q6.x, t2);
-    o[19] = q0.w;                                                 // material id (int bits)
+    HitRec hit;
+    hit.t = h.x; hit.tri = tri; hit.u = h.z; hit.v = h.w;
+    const Surface s = surface_at(tris + (size_t)tri * 28, hit, org, dir);
+    const rt_v3 tangent = s.tangent(), bitangent = s.bitangent();
+    o[1] = s.n_int.x; o[2] = s.n_int.y; o[3] = s.n_int.z;         // normal (interpolated, not normalised: raytracer.c:172-174)
+    o[4] = s.n_geo.x; o[5] = s.n_geo.y; o[6] = s.n_geo.z;
+    o[7] = s.point.x; o[8] = s.point.y; o[9] = s.point.z;
+    o[10] = tangent.x; o[11] = tangent.y; o[12] = tangent.z;
+    o[13] = bitangent.x; o[14] = bitangent.y; o[15] = bitangent.z;
+    o[16] = s.uvx();                                              // tex_coords
+    o[17] = s.uvy();
+    o[19] = s.q0.w;                                               // material id (int bits)
   }
   float2 *dst = reinterpret_cast<float2 *>(out + (size_t)i * RT_HIT_DWORDS);
 #pragma unroll

@@ -137,8 +137,7 @@ __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_shade_kernel(RT_KPar
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   SP S;
-  S.tris = P.tris; S.mats = P.mats; S.textures = P.textures; S.texels = P.texels;
-  S.bg_texture = P.bg_texture; S.max_bounces = 0;
+  shade_params(S, &P, true);
   const float4 q0 = ld4(S.tris + (size_t)tri[i] * 28, 0);
   const float *f = in + (size_t)i * 14;
   ShadeIn si;
@@ -190,8 +189,7 @@ __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_background_kernel(RT
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   SP S;
-  S.tris = nullptr; S.mats = nullptr; S.textures = P.textures; S.texels = P.texels;
-  S.bg_texture = P.bg_texture; S.max_bounces = 0;
+  shade_params(S, &P, false);
   const rt_v3 c = background_lookup(S, rt_v3_make(dir[i * 3 + 0], dir[i * 3 + 1], dir[i * 3 + 2]));
   rgb[i * 3 + 0] = c.x; rgb[i * 3 + 1] = c.y; rgb[i * 3 + 2] = c.z;
 }
@@ -201,11 +199,7 @@ __global__ void rt_test_primary_ray_kernel(RT_KParams P, int n, const int *xys, 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   PrimaryParams PP;
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 4; c++) PP.cam[r][c] = P.cam[r][c];
-  PP.focal_length = P.focal_length; PP.inv_width = P.inv_width; PP.inv_height = P.inv_height; PP.aspect = P.aspect;
+  primary_params(PP, &P, &P);
   rt_v3 o, d;
   primary_ray(PP, xys[i * 3 + 0], xys[i * 3 + 1], xys[i * 3 + 2], o, d);
   float *r = rays + (size_t)i * 6;
@@ -228,7 +222,6 @@ __global__ __launch_bounds__(16 * 64, 1) void rt_test_trace_stream_kernel(RT_KPa
   const int n_lds = P.n_lds_nodes;
   const float4 *lds_nodes = smem;
   const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the path kernel's slice
-  uint32_t *perm = L.perm;
   const int pyr_off = L.pyr_off;
   lds_load_nodes<16 * 64>(smem, P.nodes, n_lds);
   __syncthreads();
@@ -238,48 +231,42 @@ __global__ __launch_bounds__(16 * 64, 1) void rt_test_trace_stream_kernel(RT_KPa
     if (lane < RT_PYR_CACHE_WORDS) reinterpret_cast<uint32_t *>(pyr)[RT_PYR_LEAF_CACHE + lane] = 0u;
   }
   const int leaf_level = P.depth - 1;
+  const TravWave W = {smem, lds_nodes, L.perm, n_lds, PYRAMID ? P.pyr_nodes : 0, pyr_off, leaf_level, lane};
   const int n_waves = (int)gridDim.x * 16, wave_id = (int)blockIdx.x * 16 + wave;
   const int per_wave = (n + n_waves - 1) / n_waves;
   int next = wave_id * per_wave;                                   // this wave's slice of the ray list
   const int end = next + per_wave < n ? next + per_wave : n;
 
-  int   phase = PH_NEED, idx = 0;
+  int   idx = 0;
   Ray3  ray;
   ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
-  int   level = -1, node = 0, child = 0;
-  uint32_t cur = 0, dirty = 0, live = 0, w_nodes = 0, w_leaves = 0;
-  HitRec hit;
-  hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+  uint32_t w_nodes = 0, w_leaves = 0;
+  TravState T = RT_TRAV_IDLE;
   for (;;) {
-    if (phase == PH_HIT || phase == PH_MISS) {
-      out_t[idx] = hit.t;
-      out_tri[idx] = hit.tri;
-      out_uv[idx * 2 + 0] = hit.u;
-      out_uv[idx * 2 + 1] = hit.v;
-      phase = PH_NEED;
+    if (T.phase == PH_HIT || T.phase == PH_MISS) {
+      out_t[idx] = T.hit.t;
+      out_tri[idx] = T.hit.tri;
+      out_uv[idx * 2 + 0] = T.hit.u;
+      out_uv[idx * 2 + 1] = T.hit.v;
+      T.phase = PH_NEED;
     }
     if (next < end) {
-      const unsigned long long need = __ballot(phase == PH_NEED);
-      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-      if (phase == PH_NEED && next + rank < end) {
+      const unsigned long long need = __ballot(T.phase == PH_NEED);
+      const int rank = lane_rank(need);
+      if (T.phase == PH_NEED && next + rank < end) {
         idx = next + rank;
         const float *r = rays + (size_t)idx * 6;
         ray_setup<SHORT_DIV>(ray, rt_v3_make(r[0], r[1], r[2]), rt_v3_make(r[3], r[4], r[5]));
-        hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
-        dirty = 0; live = 0; cur = 0; level = -1; node = 0;
-        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+        trav_start(T, leaf_level, P.last_row_offset);
       }
       next += (int)__popcll(need);
     }
-    const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+    const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
     if (n_trav0 == 0) {
       if (next >= end) break;
       continue;
     }
-    traversal_blocks<true, SHORT_DIV, PYRAMID>(P, smem, lds_nodes, perm, lane, n_lds, PYRAMID ? P.pyr_nodes : 0, pyr_off, leaf_level,
-                                               next < end ? exit_lanes : 1, n_trav0, ray, true, phase, level, node, child, cur, dirty,
-                                               live, hit, w_nodes, w_leaves);
+    traversal_blocks<true, SHORT_DIV, PYRAMID>(P, W, ray, true, T, next < end ? exit_lanes : 1, n_trav0, w_nodes, w_leaves);
   }
   if (lane == 0) {
     atomicAdd(visits + 0, (unsigned long long)w_nodes);

@@ -7,6 +7,7 @@
 //   tile_pyramid                       the tile's camera-ray pyramid into the wave's LDS slice; can a camera ray touch the root's children?
 //   leafless_walk                      (path kernel) does the pyramid, pruned through the tree, reach a leaf group at all?
 //   grab_units / unit_decode           the tile's units, one or more per atomic, and the pixels and samples of a unit
+//   regen_paths                        the wave's idle lanes take the next paths of the tile's units
 //   flush_tile                         the wave's accumulator tile to the frame
 //
 // Every stage is wave-uniform in what it decides.  Kernel arguments are read through cold_args() where they are used (rt_dev.hip.h),
@@ -281,6 +282,58 @@ __device__ __forceinline__ void unit_decode(TileUnits &U, const int tile_x0, con
   U.c_s0 = sample_first + (int)(sb << shift);
   U.c_next = 0;
   U.c_end = (U.c_y < height && U.c_x0 < width) ? unit_paths : 0;
+}
+
+// ---- regeneration: the wave's idle lanes take the next paths of the tile, across unit boundaries ----
+// A lane that is idle (`phase` == PH_NEED: the lane's own, by reference -- an idle flag computed by the caller compiles to another loop,
+// profiles/r10_summary.md) gets at most one path: true for it, `np` = its pixel, sample and pixel of the tile.  k -> (pixel of the row,
+// sample of the unit), pixel-major: the lanes of a wave stay on a few pixels.  w_paths += the paths handed out; with !start_paths
+// (max_bounces == 0) a path exists and is black -- the loop of raytracer.c:512 runs zero times -- so it is counted and no lane gets it.
+// Units come from grab_units() as the wave's run out -- not with `no_grab` (a camera kernel told to stop) -- and tile_open goes false
+// when the tile has none left.
+struct NewPath { int x, y, sample, pix; };
+__device__ __forceinline__ bool regen_paths(const int &phase, NewPath &np, const bool start_paths, TileUnits &U, bool &tile_open, const bool no_grab,
+                                            const int lane, const int tile_idx, const uint32_t n_chunks_tile, const int tile_x0, const int tile_y0,
+                                            const int shift, const int unit_paths, const unsigned long long t_wave_start,
+                                            unsigned long long &t_last_grab, uint32_t &w_paths, uint32_t *lg = nullptr) {
+  RT_KArgs A = cold_args();
+  unsigned long long need = __ballot(phase == PH_NEED);
+  bool got = false;
+  const int width = A->width, sample_end = A->sample_end;
+  LGM("regen_begin");
+  while (need) {
+    LG(LG_REGEN_X, 1);
+    if (U.c_next >= U.c_end) {
+      if (U.u_cur + 1u < U.u_end) {
+        U.u_cur += 1u;
+      } else if (no_grab || !grab_units(lane, tile_idx, n_chunks_tile, A->tile_next, A->open_groups, (uint32_t)A->grab_max, U, t_wave_start, t_last_grab LG_ARG)) {
+        tile_open = false;
+        break;
+      }
+      unit_decode(U, tile_x0, tile_y0, shift, unit_paths, (uint32_t)A->n_sample_blocks, A->sample_first, width, A->height);
+      continue;
+    }
+    const int n_need = (int)__popcll(need);
+    const int avail = U.c_end - U.c_next;
+    const int take = n_need < avail ? n_need : avail;
+    const int rank = lane_rank(need);
+    bool valid = false;
+    if (phase == PH_NEED && !got && rank < take) {
+      const int k = U.c_next + rank;
+      const int px = k >> shift;
+      const int sm = U.c_s0 + (k & ((1 << shift) - 1));
+      const int x = U.c_x0 + px;
+      if (x < width && sm < sample_end) {
+        valid = true;
+        if (start_paths) { got = true; np.x = x; np.y = U.c_y; np.sample = sm; np.pix = U.c_pix0 + px; }
+      }
+    }
+    w_paths += (uint32_t)__popcll(__ballot(valid));
+    U.c_next += take;
+    need = __ballot(phase == PH_NEED && !got);
+  }
+  LGM("regen_end");
+  return got;
 }
 
 // ---- flush: lane p owns pixel p of the tile at (tile_x0, tile_y0) ----

@@ -53,7 +53,7 @@ __device__ __forceinline__ bool wf_append(uint32_t *data, uint32_t *cnt, uint32_
     o.pos = 0;
     over = o.chunk >= soft_chunks;
   }
-  const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  const int rank = lane_rank(m);
   if (has) {
     uint32_t *dst = data + (size_t)o.chunk * (FIELDS * WF_CHUNK) + (uint32_t)(o.pos + rank);
 #pragma unroll
@@ -92,7 +92,6 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
   const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // the wave's LDS slice, laid out as the path kernel's
-  uint32_t *perm = L.perm;
   unsigned long long *acc = L.acc;
   const int acc_off = L.acc_off, pyr_off = L.pyr_off;
 
@@ -101,9 +100,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
     __syncthreads();          // the only workgroup barrier of the kernel; waves are independent afterwards
   }
 
-  acc[lane] = 0ull;
-  acc[lane + 64] = 0ull;
-  acc[lane + 128] = 0ull;
+  acc_tile_clear(acc, lane);
 
   uint32_t w_paths = 0, w_rays = 0, w_nodes = 0, w_leaves = 0, w_bgs = 0;
   const int shift = P.chunk_shift;
@@ -113,6 +110,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
   const int thresh = P.sched_thresh;
   const int pyr_nodes = LDSN ? P.pyr_nodes : 0;
   const int wave_id = (int)blockIdx.x * WAVES + wave;
+  const TravWave W = {smem, lds_nodes, L.perm, n_lds, pyr_nodes, pyr_off, leaf_level, lane};
 
   bool queue_open = true, stopped = false;
   int  steal_tries = 0;
@@ -143,14 +141,10 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
     const uint32_t rays_before = w_rays;
 
     // ---------------- per-lane state: a camera ray and its traversal; no path state ----------------
-    int   phase = PH_NEED;
     int   pix = 0, smp = 0;
     Ray3  ray;
     ray_setup(ray, cam_o, rt_v3_make(0, 0, 1));
-    int   level = -1, node = 0, child = 0;
-    uint32_t cur = 0, dirty = 0, live = 0;
-    HitRec hit;
-    hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+    TravState T = RT_TRAV_IDLE;
 
     bool tile_open = true;
     TileUnits U;
@@ -163,10 +157,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
         RT_KArgs A = cold_args();
         bool  done = false, start = false;
         rt_v3 radiance = rt_v3_make(0, 0, 0);
-        if (phase == PH_MISS) {
+        if (T.phase == PH_MISS) {
           ShadeParams SP;
-          SP.tris = nullptr; SP.mats = nullptr; SP.textures = A->textures; SP.texels = A->texels;
-          SP.bg_texture = A->bg_texture; SP.max_bounces = 0;
+          shade_params(SP, A, false);
           // cast_ray's `background * tint + emission` (raytracer.c:554) with tint = 1, emission = 0: x * 1 + 0 is x for every
           // x the quantisation can tell from zero
           radiance = background_lookup(SP, ray.d);
@@ -175,9 +168,9 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
         w_bgs += (uint32_t)__popcll(__ballot(done));
         {
           const uint32_t rec[WF_HIT0_FIELDS] = {(uint32_t)as_i(ray.d.x), (uint32_t)as_i(ray.d.y), (uint32_t)as_i(ray.d.z),
-                                                (uint32_t)as_i(hit.t), (uint32_t)hit.tri, (uint32_t)as_i(hit.u), (uint32_t)as_i(hit.v),
+                                                (uint32_t)as_i(T.hit.t), (uint32_t)T.hit.tri, (uint32_t)as_i(T.hit.u), (uint32_t)as_i(T.hit.v),
                                                 (uint32_t)(tile_x0 + (pix & 7)) | ((uint32_t)(tile_y0 + (pix >> 3)) << 16), (uint32_t)smp};
-          const bool is_hit = phase == PH_HIT;
+          const bool is_hit = T.phase == PH_HIT;
           if (wf_append<WF_HIT0_FIELDS>(A->wf_hit0, A->wf_cnt_hit0, A->wf_ctl + WF_HIT0_ALLOC * WF_CTL_STRIDE, out, is_hit, rec,
                                         (uint32_t)A->wf_soft_chunks)) {
             // the hit queue is (nearly) full: finish the unit at hand, take no more; the host runs the bounces and
@@ -186,99 +179,49 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_camera_k
             stopped = true;
             queue_open = false;
           }
-          if (is_hit) phase = PH_NEED;
+          if (is_hit) T.phase = PH_NEED;
         }
         if (done) {
-          unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + pix * 6);
-          atomicAdd(ap + 0, accum_quantize_dev(radiance.x));
-          atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
-          atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
-          phase = PH_NEED;
+          tile_add_sample(smem, acc_off, pix, radiance);
+          T.phase = PH_NEED;
         }
 
         // ---- regeneration: idle lanes take the next paths of the tile, across unit boundaries ----
         rt_v3 dir = ray.d;
         if (tile_open) {
-          unsigned long long need = __ballot(phase == PH_NEED);
-          bool got = false;
-          int  gx = 0, gy = 0, gs = 0, gp = 0;
-          const int width = A->width, sample_end = A->sample_end;
-          const int max_bounces = A->max_bounces;
-          while (need) {
-            if (U.c_next >= U.c_end) {
-              if (U.u_cur + 1u < U.u_end) {
-                U.u_cur += 1u;
-              } else {
-                if (stopped || !grab_units(lane, tile_idx, n_chunks_tile, A->tile_next, A->open_groups, (uint32_t)A->grab_max, U, 0ull, no_time)) {
-                  tile_open = false;
-                  break;
-                }
-              }
-              unit_decode(U, tile_x0, tile_y0, shift, unit_paths, (uint32_t)A->n_sample_blocks, A->sample_first, width, A->height);
-              continue;
-            }
-            const int n_need = (int)__popcll(need);
-            const int avail = U.c_end - U.c_next;
-            const int take = n_need < avail ? n_need : avail;
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-            bool valid = false;
-            if (phase == PH_NEED && !got && rank < take) {
-              int k = U.c_next + rank;
-              int px = k >> shift;
-              int sm = U.c_s0 + (k & ((1 << shift) - 1));
-              int x = U.c_x0 + px;
-              if (x < width && sm < sample_end) {
-                valid = true;
-                if (max_bounces > 0) { got = true; gx = x; gy = U.c_y; gs = sm; gp = U.c_pix0 + px; }
-                // max_bounces == 0: the path exists and is black (the loop of raytracer.c:512 runs zero times)
-              }
-            }
-            w_paths += (uint32_t)__popcll(__ballot(valid));
-            U.c_next += take;
-            need = __ballot(phase == PH_NEED && !got);
-          }
+          NewPath np = {0, 0, 0, 0};
+          const bool got = regen_paths(T.phase, np, A->max_bounces > 0, U, tile_open, stopped, lane, tile_idx, n_chunks_tile, tile_x0, tile_y0,
+                                       shift, unit_paths, 0ull, no_time, w_paths);
           if (got) {
-            pix = gp;
-            smp = gs;
+            pix = np.pix;
+            smp = np.sample;
             PrimaryParams PP;
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-              for (int j = 0; j < 4; j++) PP.cam[i][j] = A->cam[i][j];
-            PP.focal_length = A->focal_length; PP.inv_width = A->inv_width; PP.inv_height = A->inv_height; PP.aspect = A->aspect;
+            primary_params(PP, A, A);
             rt_v3 org;
-            primary_ray(PP, gx, gy, gs, org, dir);
+            primary_ray(PP, np.x, np.y, np.sample, org, dir);
             start = true;
           }
         }
         bool skip_root = false;
         if (start) {
           ray_setup<SHORT_DIV>(ray, cam_o, dir);
-          hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
-          dirty = 0;
-          live = 0;
-          cur = 0;
-          level = -1;
-          node = 0;
-          child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-          phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+          trav_start(T, leaf_level, P.last_row_offset);
           skip_root = tile_root_miss && ray.fast;       // its one node visit finds no candidate
-          if (skip_root) phase = PH_MISS;
+          if (skip_root) T.phase = PH_MISS;
         }
         w_rays += (uint32_t)__popcll(__ballot(start));
         w_nodes += (uint32_t)__popcll(__ballot(skip_root));
       }
 
-      const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+      const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
       if (n_trav0 == 0) {
-        if (__any(phase == PH_MISS)) continue;
+        if (__any(T.phase == PH_MISS)) continue;
         if (!tile_open) break;
         continue;
       }
 
       // ================= traversal: NODE / LEAF blocks until `thresh` lanes wait for S =================
-      traversal_blocks<LDSN, SHORT_DIV, true>(P, smem, lds_nodes, perm, lane, n_lds, pyr_nodes, pyr_off, leaf_level, thresh,
-                                              n_trav0, ray, true, phase, level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
+      traversal_blocks<LDSN, SHORT_DIV, true>(P, W, ray, true, T, thresh, n_trav0, w_nodes, w_leaves);
     }
 
     // ---------------- flush the wave's share of the tile: lane p owns pixel p ----------------
@@ -310,7 +253,6 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
   const int n_lds = LDSN ? P.n_lds_nodes : 0;
   const float4 *lds_nodes = smem;
   const WaveLds L = wave_lds(smem, n_lds, P.depth, wave);      // (the same slice as the camera kernel's; no pyramid here)
-  uint32_t *perm = L.perm;
   unsigned long long *acc = L.acc;
   const int acc_off = L.acc_off;
 
@@ -322,13 +264,12 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
   // another tile: a chunk of the ray queue descends from the hits ONE camera wave wrote, i.e. from one or two tiles.
   // (64-bit atomics on the frame execute at the memory side -- per lane to scattered addresses they were measured at
   // half of this kernel's time -- and stay in the in-order vmcnt queue in front of every later load.)
-  acc[lane] = 0ull;
-  acc[lane + 64] = 0ull;
-  acc[lane + 128] = 0ull;
+  acc_tile_clear(acc, lane);
   uint32_t acc_key = 0xFFFFFFFFu;          // (tile_y << 13) | tile_x of the pixels the LDS tile stands for
 
   uint32_t w_rays = 0, w_nodes = 0, w_leaves = 0, w_bgs = 0;
   const int leaf_level = P.depth - 1;
+  const TravWave W = {smem, lds_nodes, L.perm, n_lds, 0, 0, leaf_level, lane};
   const int thresh = P.sched_thresh;
   const int qi = (P.wf_bounce - 1) & 1;                      // rays of bounce b were written by the shade kernel of bounce b - 1
   const int w_in_alloc = WF_RAY0_ALLOC + 2 * qi, w_in_head = WF_RAY0_HEAD + 2 * qi;
@@ -345,32 +286,27 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
   out.chunk = WF_NONE;
   out.pos = WF_CHUNK;
 
-  int   phase = PH_NEED;
   uint32_t ray_idx = 0;
   Ray3  ray;
   ray_setup(ray, rt_v3_make(0, 0, 0), rt_v3_make(0, 0, 1));
-  int   level = -1, node = 0, child = 0;
-  uint32_t cur = 0, dirty = 0, live = 0;
-  HitRec hit;
-  hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
+  TravState T = RT_TRAV_IDLE;
 
   for (;;) {
     // ================= S: environment for the misses, hits to the queue, next rays =================
     {
       RT_KArgs A = cold_args();
       const uint32_t *rq = A->wf_ray[qi];
-      const unsigned long long mMiss = __ballot(phase == PH_MISS);
+      const unsigned long long mMiss = __ballot(T.phase == PH_MISS);
       if (mMiss) {
         rt_v3 radiance = rt_v3_make(0, 0, 0);
         uint32_t pixel = 0;
-        if (phase == PH_MISS) {
+        if (T.phase == PH_MISS) {
           const uint32_t *rr = rq + (size_t)(ray_idx >> 8) * (WF_RAY_FIELDS * WF_CHUNK) + (ray_idx & 255u);
           const rt_v3 tint = rt_v3_make(as_f((int)rr[6 * WF_CHUNK]), as_f((int)rr[7 * WF_CHUNK]), as_f((int)rr[8 * WF_CHUNK]));
           const rt_v3 emis = rt_v3_make(as_f((int)rr[9 * WF_CHUNK]), as_f((int)rr[10 * WF_CHUNK]), as_f((int)rr[11 * WF_CHUNK]));
           pixel = rr[13 * WF_CHUNK];
           ShadeParams SP;
-          SP.tris = nullptr; SP.mats = nullptr; SP.textures = A->textures; SP.texels = A->texels;
-          SP.bg_texture = A->bg_texture; SP.max_bounces = 0;
+          shade_params(SP, A, false);
           const rt_v3 bg = background_lookup(SP, ray.d);
           radiance = rt_v3_mul_add(bg, tint, emis);         // raytracer.c:554
         }
@@ -384,15 +320,11 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
                          (int)(acc_key >> 13) * 8, frame, -1, 0u);
             acc_key = k0;
           }
-          if (phase == PH_MISS) {
-            const unsigned long long qr = accum_quantize_dev(radiance.x), qg = accum_quantize_dev(radiance.y), qb = accum_quantize_dev(radiance.z);
+          if (T.phase == PH_MISS) {
             if (key == acc_key) {
-              const int pin = (int)(((pixel >> 16) & 7u) * 8u + (pixel & 7u));
-              unsigned long long *ap = reinterpret_cast<unsigned long long *>(lds_at(smem, acc_off) + pin * 6);
-              atomicAdd(ap + 0, qr);
-              atomicAdd(ap + 1, qg);
-              atomicAdd(ap + 2, qb);
+              tile_add_sample(smem, acc_off, (int)(((pixel >> 16) & 7u) * 8u + (pixel & 7u)), radiance);
             } else {                                                // a ray of another tile in the same block: straight to the frame
+              const unsigned long long qr = accum_quantize_dev(radiance.x), qg = accum_quantize_dev(radiance.y), qb = accum_quantize_dev(radiance.z);
               unsigned long long *dst = frame + ((size_t)(pixel >> 16) * A->width + (pixel & 0xFFFFu)) * 3;
               if (qr) atomicAdd(dst + 0, qr);
               if (qg) atomicAdd(dst + 1, qg);
@@ -401,17 +333,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
           }
         }
       }
-      w_bgs += (uint32_t)__popcll(__ballot(phase == PH_MISS));
+      w_bgs += (uint32_t)__popcll(__ballot(T.phase == PH_MISS));
       {
-        const uint32_t rec[WF_HIT_FIELDS] = {ray_idx, (uint32_t)as_i(hit.t), (uint32_t)hit.tri, (uint32_t)as_i(hit.u), (uint32_t)as_i(hit.v)};
-        wf_append<WF_HIT_FIELDS>(A->wf_hit, A->wf_cnt_hit, A->wf_ctl + WF_HIT_ALLOC * WF_CTL_STRIDE, out, phase == PH_HIT, rec, 0xFFFFFFFFu);
+        const uint32_t rec[WF_HIT_FIELDS] = {ray_idx, (uint32_t)as_i(T.hit.t), (uint32_t)T.hit.tri, (uint32_t)as_i(T.hit.u), (uint32_t)as_i(T.hit.v)};
+        wf_append<WF_HIT_FIELDS>(A->wf_hit, A->wf_cnt_hit, A->wf_ctl + WF_HIT_ALLOC * WF_CTL_STRIDE, out, T.phase == PH_HIT, rec, 0xFFFFFFFFu);
       }
-      if (phase == PH_MISS || phase == PH_HIT) phase = PH_NEED;
+      if (T.phase == PH_MISS || T.phase == PH_HIT) T.phase = PH_NEED;
 
       bool start = false;
       rt_v3 org = ray.o, dir = ray.d;
       if (input_open) {
-        unsigned long long need = __ballot(phase == PH_NEED);
+        unsigned long long need = __ballot(T.phase == PH_NEED);
         while (need) {
           if (rpos >= rcnt) {
             uint32_t c = 0;
@@ -426,8 +358,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
           const int n_need = (int)__popcll(need);
           const int avail = rcnt - rpos;
           const int take = n_need < avail ? n_need : avail;
-          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-          if (phase == PH_NEED && !start && rank < take) {
+          const int rank = lane_rank(need);
+          if (T.phase == PH_NEED && !start && rank < take) {
             ray_idx = rc * WF_CHUNK + (uint32_t)(rpos + rank);
             const uint32_t *rr = rq + (size_t)rc * (WF_RAY_FIELDS * WF_CHUNK) + (uint32_t)(rpos + rank);
             org = rt_v3_make(as_f((int)rr[0]), as_f((int)rr[1 * WF_CHUNK]), as_f((int)rr[2 * WF_CHUNK]));
@@ -435,31 +367,23 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_wf_trace_ke
             start = true;
           }
           rpos += take;
-          need = __ballot(phase == PH_NEED && !start);
+          need = __ballot(T.phase == PH_NEED && !start);
         }
       }
       if (start) {
         ray_setup<SHORT_DIV>(ray, org, dir);
-        hit.t = RT_INF; hit.tri = -1; hit.u = 0; hit.v = 0;
-        dirty = 0;
-        live = 0;
-        cur = 0;
-        level = -1;
-        node = 0;
-        child = (leaf_level >= 0) ? 0 : P.last_row_offset;
-        phase = (leaf_level >= 0) ? PH_NODE : PH_LEAF;
+        trav_start(T, leaf_level, P.last_row_offset);
       }
       w_rays += (uint32_t)__popcll(__ballot(start));
     }
 
-    const int n_trav0 = (int)__popcll(__ballot(phase == PH_NODE || phase == PH_LEAF));
+    const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
     if (n_trav0 == 0) {
       if (!input_open) break;
       continue;
     }
 
-    traversal_blocks<LDSN, SHORT_DIV, false>(P, smem, lds_nodes, perm, lane, n_lds, 0, 0, leaf_level, thresh, n_trav0, ray, false,
-                                             phase, level, node, child, cur, dirty, live, hit, w_nodes, w_leaves);
+    traversal_blocks<LDSN, SHORT_DIV, false>(P, W, ray, false, T, thresh, n_trav0, w_nodes, w_leaves);
   }
 
   RT_KArgs A = cold_args();
@@ -499,8 +423,7 @@ __global__ __launch_bounds__(256, 4) void rt_wf_shade_kernel(RT_KParams P) {
   out.pos = WF_CHUNK;
 
   ShadeParams SP;
-  SP.tris = P.tris; SP.mats = P.mats; SP.textures = P.textures; SP.texels = P.texels;
-  SP.bg_texture = P.bg_texture; SP.max_bounces = P.max_bounces;
+  shade_params(SP, &P, true);
 
   for (;;) {
     // ---- 64 records, across chunk boundaries ----
