@@ -8,6 +8,7 @@ import numpy as np
 
 F = np.float32
 H = (F(0.375), F(0.25), F(0.0625))
+TILE = (32, 8)                    # of a phase sub-lattice, x and y: what ONE workgroup of rt_guided.hip filters (used by lost_halo only)
 
 
 def _shifted(a, ox, oy):
@@ -25,9 +26,21 @@ def luminance(c):
     return c[..., 0] * F(0.2126) + c[..., 1] * F(0.7152) + c[..., 2] * F(0.0722)
 
 
+def _other_tile(h, w, s, d, axis):
+    """(h, w) bool: the tap s * d away along `axis` (0: x, 1: y) lies in another TILE of the pixel's sub-lattice than the pixel."""
+    u = np.arange(w if axis == 0 else h) // s
+    other = u // TILE[axis] != (u + d) // TILE[axis]
+    return np.broadcast_to(other[None, :] if axis == 0 else other[:, None], (h, w))
+
+
 def guided(color, coverage, albedo, normal, position, iterations=4, sigma_color=1.0, sigma_normal=0.2, sigma_position=1.0,
-           demodulate=True):
-    """out f32 (h, w, 3)."""
+           demodulate=True, lost_halo=None):
+    """out f32 (h, w, 3).
+
+    lost_halo, for tests of the TESTS only (it is not the contract): a dict with "step" and "axis" (0: x, 1: y).  At that step every
+    tap whose pixel lies in another 32 x 8 sub-lattice tile than the centre along that axis is skipped, as if a workgroup's halo had
+    never arrived; "pairs" receives the number of skipped (pixel, tap) pairs whose centre has coverage != 0 and whose weight is
+    > 0.  Inputs are worth running on the GPU at a size and step only if this changes their output (tests/test_guided_cpu.py)."""
     color, cov, normal, P = [np.ascontiguousarray(a, F) for a in (color, coverage, normal, position)]
     h, w = cov.shape
     with np.errstate(all="ignore"):
@@ -56,6 +69,10 @@ def guided(color, coverage, albedo, normal, position, iterations=4, sigma_color=
                 D = dn2 * k_n + dcov * dcov * k_n + pl * pl * k_p + dl * dl * kc
                 r = F(1.0) / (F(1.0) + D)
                 wgt = ((H[abs(dy)] * H[abs(dx)]) * r) * r
+                if lost_halo is not None and lost_halo["step"] == s:
+                    lost = valid & _other_tile(h, w, s, (dx, dy)[lost_halo["axis"]], lost_halo["axis"])
+                    lost_halo["pairs"] = lost_halo.get("pairs", 0) + int((lost & (cov != 0) & (wgt > 0)).sum())
+                    valid = valid & ~lost
                 sum_c = np.where(valid[..., None], sum_c + wgt[..., None] * cq, sum_c)
                 sum_w = np.where(valid, sum_w + wgt, sum_w)
             c = np.where((cov == 0)[..., None], c, sum_c / sum_w[..., None])

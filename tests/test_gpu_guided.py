@@ -3,7 +3,15 @@ numpy float32 restatement of its contract (tests/_guided.py): equal BIT FOR BIT 
 image sides, both ping-pong parities, both demodulate settings, partial coverage and sky, weights that underflow through denormals
 to 0, image sizes ragged against the 32 x 8 tile and degenerate ones, through the host call and through the device call on a
 non-default stream; output aliasing the input; u8 / f32 / both; behind a frame; no effect on frames, queries and feature passes;
-the staging given back."""
+the staging given back.
+
+ACROSS TILE BORDERS.  A workgroup filters a 32 x 8 tile of one phase sub-lattice; 37 x 21 has a second tile along x at step 1 only
+and along y up to step 2.  With two or more tiles per phase in the direction named -- so that halo slots are filled from pixels
+another workgroup filters, tile % tiles_x != 0, and blocks of the shorter phases own no pixel -- the filter is compared at
+steps 1, 2, 4 (131 x 70, tiles_x != tiles_y), 8 (259 x 67) and 16 (513 x 129) in x and y, at steps 32 and 64 (2079 x 12) and 128
+(4200 x 5) in x, and at steps 32, 64, 128 in y (19 x 1055, where phases_x = width < step), every iteration count from 1 up to each
+size's last (BORDER_SIZES); behind a frame at 136 x 72 (steps 1, 2, 4 in x and y, 8 in y).  That a halo lost at such a step would
+change at least 100 pixels of these very inputs is shown on the CPU (tests/test_guided_cpu.py).  Also: +inf sigmas, all and each."""
 import ctypes as C
 
 import numpy as np
@@ -54,6 +62,68 @@ def _want(P, iterations, demodulate):
     return G.guided(P["color"], P["coverage"], P["albedo"], P["normal"], P["position"], iterations, *SIGMAS, demodulate)
 
 
+# Sizes at which a phase sub-lattice spans SEVERAL 32 x 8 tiles at the steps named: (w, h) -> (the largest iteration count run,
+# {axis (0: x, 1: y): the steps at which the launch has >= 2 tiles along it AND a lost halo would change >= 100 pixels}).  The
+# claims are proved of these very inputs on the CPU (tests/test_guided_cpu.py: test_the_border_sizes_would_catch_a_lost_halo);
+# the smaller steps of each size have more tiles still.  Strips reach steps 32 .. 128 without the pixel count; in the tall one
+# phases_x = width < step, so phases_x != phases_y.  A strip's long side is just past 2048 / 4096 / 1024 and not a multiple of its
+# steps: the phases differ in length by one, so the last tile of the shorter ones is a block that owns no pixel; its short side
+# is what gives the single sub-lattice column or row past the border its 100 pixels.
+BORDER_SIZES = {
+    (131, 70): (3, {0: (1, 2, 4), 1: (1, 2, 4)}),               # 5 x 9, 3 x 5, 2 x 3 tiles: tiles_x != tiles_y
+    (259, 67): (4, {0: (8,), 1: (8,)}),                         # 2 x 2 at step 8; 3 x 3 at step 4
+    (513, 129): (5, {0: (2, 16), 1: (2, 16)}),                  # 2 x 2 at step 16; 9 x 9 at step 2, the 9th empty in every phase but 0
+    (2079, 12): (7, {0: (32, 64)}),                             # 65 or 64 sub-lattice columns at step 32, 33 or 32 at step 64
+    (4200, 5): (8, {0: (128,)}),                                # 33 or 32 at step 128
+    (19, 1055): (8, {1: (32, 64, 128)}),                        # 9 or 8 sub-lattice rows at step 128, 19 x 128 phases
+}
+_RECTANGLES = [(131, 70), (259, 67), (513, 129)]
+_STRIPS = [(2079, 12), (4200, 5), (19, 1055)]
+_COMBINATIONS = [("host", True), ("device", False), ("host", False), ("device", True)]
+_wants = {}
+
+
+def _shared_want(w, h, iterations, demodulate):
+    """The restatement's output for _shared(w, h): computed once, shared by the paths, read-only."""
+    key = (w, h, iterations, demodulate)
+    if key not in _wants:
+        _wants[key] = _want(_shared(w, h), iterations, demodulate)
+        _wants[key].setflags(write=False)
+    return _wants[key]
+
+
+def _differing(got, want, step):
+    """"" when equal in bits, else how many pixels differ and where the first ones sit on the last step's decomposition."""
+    ys, xs = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=2))
+    if len(ys) == 0:
+        return ""
+    first = ["(x, y) (%d, %d) phase (%d, %d) tile (%d, %d)" % (x, y, x % step, y % step, (x // step) // 32, (y // step) // 8)
+             for x, y in zip(xs[:6].tolist(), ys[:6].tolist())]
+    return "%d pixels differ; last step %d: %s" % (len(ys), step, "; ".join(first))
+
+
+def _compare_planes(rt, w, h, iterations, demodulate, path, sigmas=SIGMAS):
+    from tests import _guided as G
+    P = _shared(w, h)
+    if sigmas is SIGMAS:
+        want = _shared_want(w, h, iterations, demodulate)
+    else:
+        want = G.guided(P["color"], P["coverage"], P["albedo"], P["normal"], P["position"], iterations, *sigmas, demodulate)
+    kw = dict(iterations=iterations, sigma_color=sigmas[0], sigma_normal=sigmas[1], sigma_position=sigmas[2], demodulate=demodulate)
+    if path == "host":
+        got = rt.guided_denoise(P["color"], P["coverage"], P["albedo"], P["normal"], P["position"], **kw)
+    else:
+        got = _side_stream_call(rt, P, **kw)
+    assert got.dtype == F32 and got.shape == want.shape
+    message = _differing(got, want, 1 << (iterations - 1))
+    assert not message, message
+    assert got.tobytes() == want.tobytes()
+    sky = P["coverage"] == 0
+    assert sky.sum() >= 50 and got[sky].tobytes() == P["color"][sky].tobytes()
+    assert np.isfinite(got).all()
+    return got
+
+
 def _side_stream_call(rt, P, **kw):
     """rt.guided_denoise on torch tensors, on a stream that is not the default one."""
     import torch
@@ -99,6 +169,44 @@ def test_random_planes_37x21(rt, iterations, demodulate, path):
     sky = P["coverage"] == 0
     assert sky.sum() >= 50 and got[sky].tobytes() == P["color"][sky].tobytes()
     assert np.isfinite(got).all()
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+@pytest.mark.parametrize("demodulate", [True, False])
+@pytest.mark.parametrize("w,h,iterations", [(w, h, k) for w, h in _RECTANGLES for k in range(1, BORDER_SIZES[(w, h)][0] + 1)])
+def test_random_planes_across_tile_borders(rt, w, h, iterations, demodulate, path):
+    """Where 37 x 21 has ONE tile per phase in x from step 2 and in y from step 4 on, these sizes have at least two in both
+    directions at every step they run (BORDER_SIZES): the block -> (phase, tile) -> origin decode with tile % tiles_x != 0, halo
+    columns and rows filled from the pixels another workgroup filters, tiles_x != tiles_y, blocks of the smaller phases that own no
+    pixel.  Every iteration count from 1, so that the first one that fails names the step."""
+    _compare_planes(rt, w, h, iterations, demodulate, path)
+
+
+@pytest.mark.parametrize("w,h,iterations,path,demodulate", [(w, h, k) + _COMBINATIONS[(k + i) % 4] for i, (w, h) in enumerate(_STRIPS)
+                                                            for k in range(1, BORDER_SIZES[(w, h)][0] + 1)])
+def test_random_planes_on_strips(rt, w, h, iterations, path, demodulate):
+    """Steps 32, 64 and 128 with two tiles: along x on strips of 12 and 5 rows, along y on one of 19 columns, where phases_x =
+    min(step, width) = 19 while phases_y = step.  The four (path, demodulate) combinations take turns over the iteration counts:
+    each occurs at least once per strip."""
+    _compare_planes(rt, w, h, iterations, demodulate, path)
+
+
+INF = float("inf")
+
+
+@pytest.mark.parametrize("sigmas", [(INF, INF, INF), (INF, SIGMAS[1], SIGMAS[2]), (SIGMAS[0], INF, SIGMAS[2]), (SIGMAS[0], SIGMAS[1], INF)],
+                         ids=["all", "color", "normal", "position"])
+def test_infinite_sigmas(rt, sigmas):
+    """rt_hip.h: a sigma of +inf switches its term off, k = 1 / (inf * inf) = 0 -- on the GPU as in the restatement, bit for bit,
+    all three and each alone, at 131 x 70 with 3 iterations.  The term must be finite to be switched off (0 * inf is NaN on both
+    sides, and the contract asks for finite inputs): the largest pl * pl these planes can give stays far below the f32 maximum."""
+    w, h = 131, 70
+    P = _shared(w, h)
+    pl_max = 3.0 * (2.0 * float(P["normal"].max()) + 1.0) * 2.0 * float(np.abs(P["position"]).max())
+    assert pl_max * pl_max < 1e36
+    got = _compare_planes(rt, w, h, 3, True, "host", sigmas)
+    _compare_planes(rt, w, h, 3, False, "device", sigmas)
+    assert got.tobytes() != _shared_want(w, h, 3, True).tobytes()             # (the sigma reached the kernel)
 
 
 @pytest.mark.parametrize("w,h", [(1, 1), (1, 40), (40, 1), (33, 9)])
@@ -181,10 +289,10 @@ def _chain(rt, hs, w, h, s, b):
         want = G.guided(frame["linear"], cov, feats["albedo"], feats["normal"], feats["position"], 4, 1.0, 0.2, sp, demodulate)
         enc = G.encode_u8(want)
         got = rt.guided_denoise(frame["linear"], cov, feats["albedo"], feats["normal"], feats["position"], demodulate=demodulate)
-        assert got.tobytes() == want.tobytes(), demodulate                    # (sigma_position: the wrapper's default)
+        assert got.tobytes() == want.tobytes(), (demodulate, _differing(got, want, 8))      # (sigma_position: the wrapper's default)
         r = rt.render_denoised(hs, w, h, s, b, demodulate=demodulate)
         assert r["linear_noisy"].tobytes() == frame["linear"].tobytes()
-        assert r["linear_denoised"].tobytes() == want.tobytes(), demodulate
+        assert r["linear_denoised"].tobytes() == want.tobytes(), (demodulate, _differing(r["linear_denoised"], want, 8))
         assert r["image"].tobytes() == enc.tobytes()
     # the Image's layout: stride > width, 4 components; what is not a pixel's r, g, b stays
     stride, comp = w + 3, 4
@@ -203,6 +311,13 @@ def _chain(rt, hs, w, h, s, b):
 def test_behind_a_frame_random_scene(rt, oracle):
     from tests.test_gpu_random_scenes import make_scene
     _chain(rt, make_scene(6, 400), 40, 24, 4, 8)
+
+
+def test_behind_a_frame_across_tile_borders(rt, oracle):
+    """136 x 72, few samples: the chain's 4 iterations have 5 x 9, 3 x 5, 2 x 3 and 1 x 2 tiles per phase (steps 1, 2, 4, 8), where
+    40 x 24 has one from step 2 on -- the filter behind a real frame's buffers, and the padded Image, with tile borders in them."""
+    from tests.test_gpu_random_scenes import make_scene
+    _chain(rt, make_scene(6, 400), 136, 72, 2, 4)
 
 
 def test_behind_a_frame_passthrough_scene(rt, oracle):

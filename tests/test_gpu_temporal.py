@@ -3,7 +3,7 @@ rt_temporal.hip) against the numpy float32 restatement of its contract (tests/_t
 output, every plane of the new history, the length and the u8 image; every class of pixel the contract distinguishes; both
 demodulate settings, each tolerance finite and +inf; sizes ragged against the 32 x 8 tile and degenerate ones; through the host call
 and through the device call on a non-default stream; no history; output aliasing the input; every output alone; behind a frame with
-equal and with moving cameras, with and without the guided filter; a first frame against rt_render_denoised; reset; no effect on frames, queries, feature passes and the
+equal and with moving cameras, with and without the guided filter (also at 136 x 72, where the filter has tile borders); a first frame against rt_render_denoised; reset; no effect on frames, queries, feature passes and the
 guided filter; the staging given back and a history used after that."""
 import ctypes as C
 
@@ -258,10 +258,10 @@ def _move(hs, origin, right, offset):
         hs.scene.camera.view_matrix.rows[i][3] = float(F32(origin[i] + F32(offset) * right[i]))
 
 
-def _chain_inputs(rt, hs, offsets, lib=None):
+def _chain_inputs(rt, hs, offsets, lib=None, shape=None):
     """Per frame: (rt_render_frame's linear output, rt_render_features' planes, the camera) -- the restatement's inputs."""
     from tests import _temporal as T
-    w, h, s, b = SHAPE
+    w, h, s, b = shape or SHAPE
     M0, _ = T.camera_of(hs.scene.camera)
     origin, right = M0[:3, 3].copy(), M0[:3, 0].copy()
     frames = []
@@ -304,17 +304,13 @@ def test_equal_cameras_on_a_real_scene_give_the_recursion(rt, oracle, demodulate
             assert r["linear_out"][~hit].tobytes() == lin[~hit].tobytes()
 
 
-@pytest.mark.parametrize("guided", [False, True])
-def test_chain_with_a_moving_camera(rt, oracle, guided):
-    """Three frames while the camera moves sideways: rt_render_temporal equals the restatement chained over each frame's
-    rt_render_frame linear output and rt_render_features planes (then tests/_guided.py where the filter is on) -- linear_out,
-    length and the Image's bytes; the history keeps the UNFILTERED accumulation (or frame 2 would differ)."""
+def _moving_camera_chain(rt, hs, shape, guided, iterations):
+    """Three frames while the camera moves sideways; the history lengths the restatement gives per frame."""
     from tests import _guided as G, _temporal as T
-    hs = _spheres()
-    w, h, s, b = SHAPE
-    frames, origin, right = _chain_inputs(rt, hs, OFFSETS)
+    w, h, s, b = shape
+    frames, origin, right = _chain_inputs(rt, hs, OFFSETS, shape=shape)
     sp = G.sigma_position(frames[0][1]["position"], frames[0][1]["coverage"])
-    gkw = dict(iterations=3, sigma_color=1.0, sigma_normal=0.2, sigma_position=sp, demodulate=True)
+    gkw = dict(iterations=iterations, sigma_color=1.0, sigma_normal=0.2, sigma_position=sp, demodulate=True)
     hist, prev, lengths = None, None, []
     try:
         with rt.History(w, h) as history:
@@ -330,13 +326,33 @@ def test_chain_with_a_moving_camera(rt, oracle, guided):
                 r = rt.render_temporal(hs, w, h, s, b, history, seed=seed, guided=gkw if guided else None)
                 assert r["linear_noisy"].tobytes() == lin.tobytes(), k
                 assert r["length"].tobytes() == want["length"].tobytes(), k
-                assert r["linear_out"].tobytes() == last.tobytes(), k
+                differ = np.argwhere((r["linear_out"].view(np.uint32) != last.view(np.uint32)).any(axis=2))
+                assert r["linear_out"].tobytes() == last.tobytes(), (k, len(differ), differ[:6, ::-1].tolist())       # (x, y)
                 assert r["image"].tobytes() == T.encode_u8(last).tobytes(), k
                 lengths.append(want["length"])
     finally:
         _move(hs, origin, right, 0.0)
+    return lengths
+
+
+@pytest.mark.parametrize("guided", [False, True])
+def test_chain_with_a_moving_camera(rt, oracle, guided):
+    """Three frames while the camera moves sideways: rt_render_temporal equals the restatement chained over each frame's
+    rt_render_frame linear output and rt_render_features planes (then tests/_guided.py where the filter is on) -- linear_out,
+    length and the Image's bytes; the history keeps the UNFILTERED accumulation (or frame 2 would differ)."""
+    lengths = _moving_camera_chain(rt, _spheres(), SHAPE, guided, 3)
     # (of the 179 pixels that see a sphere) reuse over three frames, restarts, and bilinear mixes of history lengths
     assert (lengths[2] == 3).sum() >= 50 and (lengths[2] == 1).sum() >= 5 and ((lengths[2] > 1) & (lengths[2] < 3)).sum() >= 10
+
+
+def test_chain_with_the_filter_across_tile_borders(rt, oracle):
+    """The same chain at 136 x 72 with 4 iterations: 5 x 9, 3 x 5, 2 x 3 and 1 x 2 tiles per phase at steps 1, 2, 4, 8, where 40 x 24
+    has a single one from step 2 on.  Here the filter's colour input is the accumulation's output buffer, not the frame's.  A
+    random scene that covers most of the image: of the 5 605 hit pixels of the third frame 3 732 have three frames of history,
+    1 384 restart and 489 mix lengths (the restatement over the CPU oracle's planes)."""
+    from tests.test_gpu_random_scenes import make_scene
+    lengths = _moving_camera_chain(rt, make_scene(6, 400), (136, 72, 2, 4), True, 4)
+    assert (lengths[2] == 3).sum() >= 3000 and (lengths[2] == 1).sum() >= 1000 and ((lengths[2] > 1) & (lengths[2] < 3)).sum() >= 300
 
 
 def test_reset_gives_first_frame_output_again(rt, oracle):

@@ -2,7 +2,9 @@
 without a GPU: the exported names, every argument error reported before the device is touched, and the CONTRACT itself -- its
 numpy restatement (tests/_guided.py), which the GPU tests compare the kernel with bit for bit, must be a denoiser: a constant
 stays constant, edges between surfaces stay, noise drops on real frames, sky is returned as it came, and with every
-edge-stopping term switched off it is the plain 5 x 5 B-spline a-trous transform."""
+edge-stopping term switched off it is the plain 5 x 5 B-spline a-trous transform.  And of the GPU tests' own inputs: at every
+size, step and direction where they claim to compare the filter across the borders of its 32 x 8 workgroup tiles, a halo that never
+arrived would change at least 100 pixels."""
 import ctypes as C
 
 import numpy as np
@@ -304,3 +306,73 @@ def test_infinite_sigmas_give_the_plain_atrous_transform():
                             den[y, x] += wt
         c = num / den[..., None]
     assert np.abs(got - c).max() <= 1e-5
+
+
+# ---- the sizes the GPU tests run: would they catch a fault in the filter's tiling? ---------------------------------------------------
+
+def _tiling(w, h, s):
+    """The launch of one step as the header of rt_guided.hip states it: (phases_x, phases_y, tiles_x, tiles_y, the number of
+    blocks of a phase other than (0, 0) whose tile holds no pixel).  Block = phase + n_phases * tile, phase = px + phases_x * py,
+    tile = tx + tiles_x * ty; its pixels are x = px + s * (32 tx + i), y = py + s * (8 ty + j)."""
+    phases_x, phases_y = min(s, w), min(s, h)
+    sub_x, sub_y = (w + s - 1) // s, (h + s - 1) // s                          # the largest sub-lattice, that of phase (0, 0)
+    tiles_x, tiles_y = (sub_x + 31) // 32, (sub_y + 7) // 8
+    empty = sum(1 for py in range(phases_y) for px in range(phases_x) for ty in range(tiles_y) for tx in range(tiles_x)
+                if (px, py) != (0, 0) and (px + s * 32 * tx >= w or py + s * 8 * ty >= h))
+    return phases_x, phases_y, tiles_x, tiles_y, empty
+
+
+def _border_claims():
+    from tests.test_gpu_guided import BORDER_SIZES
+    return [(w, h, s, axis) for (w, h), (_, axes) in BORDER_SIZES.items() for axis, steps in axes.items() for s in steps]
+
+
+def test_the_lost_halo_variant_leaves_the_restatement_alone():
+    """lost_halo=None is the contract, byte for byte (every expectation above is unchanged); a step that is not run loses nothing."""
+    from tests import _guided as G
+    from tests.test_gpu_guided import SIGMAS, _planes
+    P = _planes(37, 21)
+    a = (P["color"], P["coverage"], P["albedo"], P["normal"], P["position"], 3, *SIGMAS, True)
+    want = G.guided(*a)
+    assert G.guided(*a, lost_halo=None).tobytes() == want.tobytes()
+    never = dict(step=8, axis=0)
+    assert G.guided(*a, lost_halo=never).tobytes() == want.tobytes() and "pairs" not in never
+    lost = dict(step=1, axis=0)                                               # 37 wide: two tiles at step 1
+    assert G.guided(*a, lost_halo=lost).tobytes() != want.tobytes() and lost["pairs"] > 0
+
+
+@pytest.mark.parametrize("w,h,step,axis", _border_claims())
+def test_the_border_sizes_would_catch_a_lost_halo(w, h, step, axis):
+    """A table of sizes proves nothing by itself.  For every (size, step, axis) that tests/test_gpu_guided.py claims to compare
+    across tile borders: the launch has at least two tiles along the axis and blocks that own no pixel; at least 100 (pixel, tap)
+    pairs cross a tile border with a weight that counts; and a filter whose halo never arrived at that step (_guided.guided's
+    lost_halo) would differ from the contract in the bits of at least 100 pixels OF THESE INPUTS."""
+    from tests import _guided as G
+    from tests.test_gpu_guided import BORDER_SIZES, SIGMAS, _planes
+    phases_x, phases_y, tiles_x, tiles_y, empty = _tiling(w, h, step)
+    assert (tiles_x, tiles_y)[axis] >= 2, (tiles_x, tiles_y)
+    if step == 1:
+        assert (phases_x, phases_y) == (1, 1)                                 # the image itself: there is no phase but (0, 0)
+    elif (w, h, step) == (131, 70, 2):
+        assert empty == 0                                                     # 66 or 65 columns, 35 rows: 3 x 5 tiles in every phase
+    else:                                                                     # (513 x 129 has step 2 with such blocks)
+        assert empty >= 1, empty
+    iterations = step.bit_length()                                            # the count whose last step this is
+    assert iterations <= BORDER_SIZES[(w, h)][0]
+    if (w, h) == (19, 1055):
+        assert (phases_x, phases_y) == (19, step)                             # phases_x = width < step
+    P = _planes(w, h)
+    a = (P["color"], P["coverage"], P["albedo"], P["normal"], P["position"], iterations, *SIGMAS, True)
+    lost = dict(step=step, axis=axis)
+    want, without = G.guided(*a), G.guided(*a, lost_halo=lost)
+    differing = int((want.view(np.uint32) != without.view(np.uint32)).any(axis=2).sum())
+    print(w, h, "step", step, "axis", axis, "tiles", tiles_x, tiles_y, "empty blocks", empty, "pairs", lost["pairs"], "pixels", differing)
+    assert lost["pairs"] >= 100, lost["pairs"]
+    assert differing >= 100, differing
+
+
+def test_37x21_has_one_tile_in_x_from_step_2_on():
+    """Why the sizes above exist: the workhorse of the GPU tests never has a second tile along x beyond step 1 (y: beyond 2)."""
+    for i in range(1, 8):
+        assert _tiling(37, 21, 1 << i)[2] == 1                                # ceil(ceil(37 / s) / 32) = 1 for s >= 2
+    assert [_tiling(37, 21, s)[3] for s in (1, 2, 4)] == [3, 2, 1]
