@@ -367,7 +367,8 @@ extern int rt_render_features(Scene const *scene, i32 width, i32 height, isize s
  *     a pixel with coverage_p == 0 keeps c_p: sky is not noisy, and the features say nothing about it
  *   Output: out_p = c_p * m_p; where coverage_p == 0, out_p = color_p bit for bit.  The u8 image is rt_encode_u8(out) per channel
  *     (rt_math.h), under the library's numeric contract like rt_resolve's.
- * Not done: variance-guided weights (SVGF), several devices, view batches.  (Reuse over time: temporal accumulation below.) */
+ * Not done: several devices, view batches.  (Reuse over time: temporal accumulation below; a luminance term measured in the pixel's
+ * own variance: "variance-guided denoising" further below.) */
 typedef struct {
   i32 iterations;
   f32 sigma_color, sigma_normal, sigma_position;
@@ -466,8 +467,8 @@ extern int rt_render_denoised(Scene const *scene, Image const *image, isize samp
  *   h + (c - h) * a bit for bit.  No history (first frame, after a reset): out = c_p * m_p and len = 1.
  * Out of scope: MOVING GEOMETRY -- after scene_refit_gpu a surface that moved off its old plane fails the plane test and restarts
  * there, one that slid within its own plane is reused wrongly; a host that deforms the mesh resets the history or accepts that
- * (per-triangle motion vectors need a triangle-id feature channel).  Variance / moment estimation and SVGF weights, several devices,
- * view batches, weighting frames by their sample counts. */
+ * (per-triangle motion vectors need a triangle-id feature channel).  Several devices, view batches, weighting frames by their
+ * sample counts.  (Moments and variance: "variance-guided denoising" below.) */
 typedef struct {
   f32 alpha;
   i32 max_history;
@@ -523,6 +524,107 @@ extern void        rt_history_destroy(RT_History *history);
 extern int rt_render_temporal(Scene const *scene, Image const *image, isize samples, isize max_bounces, RT_History *history,
                               RT_Temporal_Params const *temporal_params, RT_Guided_Params const *guided_params, f32 *linear_noisy,
                               f32 *linear_out, f32 *length);
+
+/* ---- variance-guided denoising ---------------------------------------------------------- */
+
+/* What SVGF (Schied et al. 2017) adds to the two passes above: the filter learns how noisy a pixel still is.  The accumulation
+ * carries the first and second moment of the luminance next to the colour; a second launch turns them into a variance per pixel
+ * (from the 7 x 7 neighbourhood where the history is shorter than 4 frames); and the filter's luminance term is measured in that
+ * variance instead of one fixed sigma_color.  Kernels of their own (csrc/rt_variance.hip), which share the accumulation's pixel and
+ * the filter's tile with the kernels above; rt_guided_denoise*, rt_temporal_accumulate*, rt_render_denoised and rt_render_temporal
+ * return what they returned, and the 48-byte history record is unchanged.
+ *
+ * All three contracts: only f32 + - * / , comparisons and selects (floorf only where THE ACCUMULATION has it); every operation
+ * rounded on its own (no fused multiply-add, exp, sqrt or reciprocal); sums left to right as written; every comparison with NaN
+ * is false; lum(c) = c.r * 0.2126f + c.g * 0.7152f + c.b * 0.0722f left to right.  A float32 restatement on the CPU is equal bit for
+ * bit (tests/_variance.py).
+ *
+ * THE MOMENTS.  A moments buffer is 16 B per pixel: one plane of float4 (m1, m2, 0, 0), the accumulated first and second moment of
+ * the luminance of the demodulated colour; rt_temporal_moments_bytes() is its size.  Everything of THE ACCUMULATION holds and
+ * gives the same bits for out, the history, length and the image.  In addition, for every pixel with cov != 0:
+ *     L_p = lum(c_p);  S_p = L_p * L_p        (c_p the accumulation's own, demodulated when demodulate is set)
+ *     over the valid taps in tap order, next to sum_c and sum_n:  sum_1 = sum_1 + b * m1_q;  sum_2 = sum_2 + b * m2_q
+ *     if usable && sum_w > 0, with the accumulation's a:
+ *         h_1 = sum_1 / sum_w;  h_2 = sum_2 / sum_w;  m1' = h_1 + (L_p - h_1) * a;  m2' = h_2 + (S_p - h_2) * a
+ *     otherwise m1' = L_p, m2' = S_p
+ *     v = m2' - m1' * m1';  var_t = v > 0.0f ? v : 0.0f;  the moments record is (m1', m2', 0, 0)
+ *   A pixel with cov == 0 has the moments record (0, 0, 0, 0) and variance 0.  On the input side a history and its moments are given
+ *   both or neither (refused otherwise); the moments output must not overlap the moments input (refused).
+ *
+ * THE VARIANCE.  A second launch, which reads only what the first wrote -- the new history's planes (c', len'), (N, cov), (W, 0)
+ * and the new moments -- and writes the variance plane f32[h][w].
+ *   Parameters: sigma_normal, sigma_position > 0 and not NaN, +inf switches the term off; the host computes k_n and k_p as the
+ *     guided filter does.
+ *   Per pixel p with cov_p != 0:
+ *     if len'_p >= 4.0f: var_p = var_t, computed from the moments record by the expression above.
+ *     otherwise the 49 taps dy = -3 .. 3 (outer), dx = -3 .. 3 (inner), q = (x + dx, y + dy); a tap outside the image or with
+ *     cov_q == 0 is skipped; for each tap that counts
+ *         dn = N_p - N_q;  dn2 = dn.x * dn.x + dn.y * dn.y + dn.z * dn.z
+ *         dcov = cov_p - cov_q
+ *         e = W_q - W_p;  pl = N_p.x * e.x + N_p.y * e.y + N_p.z * e.z
+ *         D = dn2 * k_n + dcov * dcov * k_n + pl * pl * k_p, left to right
+ *         r = 1.0f / (1.0f + D);  wgt = r * r                     (the centre has wgt = 1, so s_w >= 1)
+ *         s_w = s_w + wgt;  s_1 = s_1 + wgt * m1'_q;  s_2 = s_2 + wgt * m2'_q
+ *       e1 = s_1 / s_w;  e2 = s_2 / s_w;  v = e2 - e1 * e1;  v = v > 0.0f ? v : 0.0f;  var_p = v * (4.0f / len'_p)
+ *   A pixel with cov_p == 0 has var_p = 0.  The threshold 4 and the boost 4 / len are SVGF's: part of the contract, no parameters.
+ *
+ * THE VARIANCE-GUIDED FILTER.  THE FILTER, with these differences and no others.
+ *   One more input: variance f32[h][w], finite and >= 0, the variance of the demodulated luminance (what THE VARIANCE writes);
+ *     v(0) = variance.
+ *   In iteration i, for every pixel p:
+ *     g_p = a 3 x 3 Gaussian of the current v at UNIT spacing, whatever the step: taps dy = -1 .. 1 (outer), dx = -1 .. 1 (inner),
+ *       taps outside the image skipped;  gs = gs + (G[|dy|] * G[|dx|]) * v_q;  gw = gw + G[|dy|] * G[|dx|],  G = {0.5f, 0.25f};
+ *       g_p = gs / gw
+ *     kv_p = k_c / (g_p + 1e-8f): sigma_color is now a multiple of the pixel's standard deviation (SVGF's value is 4); with
+ *       sigma_color = +inf, k_c = 0 and kv_p = 0
+ *     the last term of D is (dl * dl) * kv_p in place of dl * dl * kc_i; nothing is halved per iteration; L_q = lum(c_q) as before
+ *     next to sum_c and sum_w:  sum_v = sum_v + (wgt * wgt) * v_q
+ *     c'_p = sum_c / sum_w;  v'_p = sum_v / (sum_w * sum_w);  a pixel with cov_p == 0 keeps c_p and v_p
+ *   Outputs: THE FILTER's, and optionally variance_out f32[h][w], the last v.
+ *   Consequence: with sigma_color = +inf the colour output equals rt_guided_denoise's with sigma_color = +inf bit for bit. */
+typedef struct { f32 sigma_normal, sigma_position; } RT_Variance_Params;                         /* 8 bytes */
+
+/* rt_temporal_accumulate() / rt_temporal_accumulate_host() with the moments, in the same launch, and the variance launch behind it
+ * when a variance is wanted.  Argument checks, aliasing rules, staging and locking are those calls'; in addition:
+ *   d_moments_in  : rt_temporal_moments_bytes(width, height) bytes, 16-byte aligned; given exactly when d_history_in is (refused
+ *                   otherwise)
+ *   d_moments_out : as many bytes, 16-byte aligned, required; must not overlap d_moments_in
+ *   d_variance    : f32[h][w], optional; vp is read (and required) only when it is wanted, and checked whenever it is given
+ * Host level: moments_in f32[h][w][2] (m1, m2) or NULL, given exactly when history_in is; moments_out f32[h][w][2] and variance
+ * f32[h][w] are optional outputs and count as such.  A refused call leaves its outputs untouched. */
+extern i64 rt_temporal_moments_bytes(i32 width, i32 height);
+extern int rt_temporal_accumulate_moments(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                          Camera const *previous_camera, void const *d_color, void const *d_coverage,
+                                          void const *d_albedo, void const *d_normal, void const *d_position, void const *d_history_in,
+                                          void *d_history_out, void *d_out, void *d_length, void *d_image, RT_Variance_Params const *vp,
+                                          void const *d_moments_in, void *d_moments_out, void *d_variance, void *stream);
+extern int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                               Camera const *previous_camera, f32 const *color, RT_Features const *planes,
+                                               RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
+                                               f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
+                                               f32 *moments_out, f32 *variance);
+
+/* rt_guided_denoise() / rt_guided_denoise_host() as THE VARIANCE-GUIDED FILTER.  d_variance / variance f32[h][w] is required;
+ * d_variance_out / variance_out f32[h][w] is optional and counts as an output.  d_work: rt_guided_variance_work_bytes(width,
+ * height) bytes, 16-byte aligned: 64 B per pixel -- two ping-pong buffers of float4 (r, g, b, v) and the two guide planes.
+ * Everything else as the calls they extend. */
+extern i64 rt_guided_variance_work_bytes(i32 width, i32 height);
+extern int rt_guided_denoise_variance(i32 width, i32 height, RT_Guided_Params const *params, void const *d_color, void const *d_coverage,
+                                      void const *d_albedo, void const *d_normal, void const *d_position, void *d_out, void *d_image,
+                                      void *d_work, void *stream, void const *d_variance, void *d_variance_out);
+extern int rt_guided_denoise_variance_host(i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
+                                           RT_Features const *planes, f32 *out, u8 *image, f32 const *variance, f32 *variance_out);
+
+/* A variance-guided frame in one call: rt_render_temporal()'s pipeline with the moments pass in place of the plain accumulation,
+ * the variance launch behind it and the variance-guided filter -- mandatory here -- over the accumulated output.  The history
+ * gains two moments buffers, allocated by the first such frame, ping-ponged with the histories, owned and given back like them
+ * and emptied by rt_history_reset().  A non-empty history whose last frame was written by rt_render_temporal() has no valid
+ * moments: the call is refused until rt_history_reset().  rt_render_temporal() after rt_render_svgf() is allowed and invalidates
+ * the moments.  `variance` (optional, f32[h][w]) returns the INPUT of the filter, THE VARIANCE's estimate; everything else as
+ * rt_render_temporal().  One device only. */
+extern int rt_render_svgf(Scene const *scene, Image const *image, isize samples, isize max_bounces, RT_History *history,
+                          RT_Temporal_Params const *temporal_params, RT_Variance_Params const *variance_params,
+                          RT_Guided_Params const *guided_params, f32 *linear_noisy, f32 *linear_out, f32 *length, f32 *variance);
 
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */

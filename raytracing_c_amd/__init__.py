@@ -13,3 +13,4 @@ from .query import closest_hits, occluded, closest_hits_device, occluded_device,
 from .features import render_features   # noqa: F401
 from .guided import guided_denoise, render_denoised   # noqa: F401
 from .temporal import temporal_accumulate, render_temporal, History   # noqa: F401
+from .variance import temporal_accumulate_moments, guided_denoise_variance, render_svgf   # noqa: F401

@@ -10,8 +10,8 @@
 //   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
-//   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter) and temporal accumulation (the
-//                     reprojected history), each on the device level, on the host level and behind a frame (one pipeline)
+//   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter), temporal accumulation (the
+//                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -94,6 +94,20 @@ int rt_launch_temporal(const RT_TParams *P, const float *color, const float *cov
 int rt_launch_temporal_pack(int n_pixels, const float *c, const float *len, const float *cov, const float *n, const float *w, void *hist,
                             hipStream_t stream);
 int rt_launch_temporal_unpack(int n_pixels, const void *hist, float *c, float *len, float *cov, float *n, float *w, hipStream_t stream);
+// ... in rt_variance.hip
+int rt_launch_temporal_moments(const RT_TParams *P, const float *color, const float *coverage, const float *albedo, const float *normal,
+                               const float *position, const void *hist_in, void *hist_out, float *out, float *length, uint8_t *image,
+                               const void *mom_in, void *mom_out, hipStream_t stream);
+int rt_launch_variance(int width, int height, float k_n, float k_p, const void *hist, const void *mom, float *variance,
+                       hipStream_t stream);
+int rt_launch_variance_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
+                            const float *normal, const float *position, const float *variance, void *c0, void *g0, void *g1,
+                            hipStream_t stream);
+int rt_launch_variance_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate,
+                              const void *src, void *dst, const void *g0, const void *g1, const float *color, const float *albedo,
+                              float *out, uint8_t *image, float *var_out, hipStream_t stream);
+int rt_launch_moments_pack(int n_pixels, const float *planar, void *mom, hipStream_t stream);
+int rt_launch_moments_unpack(int n_pixels, const void *mom, float *planar, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -257,6 +271,8 @@ struct GuidedState {
   DevMem<float>   out;                        // [pixels][3]
   DevMem<uint8_t> image;                      // [pixels][3]
   DevMem<uint8_t> work;                       // rt_guided_work_bytes()
+  DevMem<float>   variance;                   // rt_guided_denoise_variance_host: the variance plane [pixels] in ...
+  DevMem<float>   variance_out;               // ... and out (grown by that call alone)
 };
 
 // Temporal accumulation (rt_post.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame, a history
@@ -270,6 +286,10 @@ struct TemporalState {
   DevMem<float>   out;                        // [pixels][3]
   DevMem<float>   length;                     // [pixels]
   DevMem<uint8_t> image;                      // [pixels][3]
+  // rt_temporal_accumulate_moments_host and rt_render_svgf alone grow these:
+  DevMem<uint8_t> mom[2];                     // rt_temporal_moments_bytes() each: read, written
+  DevMem<float>   mom_planar;                 // moments as the host has them, [pixels][2]
+  DevMem<float>   variance;                   // [pixels]: the variance launch's output, the variance-guided filter's input
   std::vector<RT_History *> histories;        // every live RT_History (slot 0 only)
 };
 
@@ -313,6 +333,8 @@ struct RT_History {
   DevMem<uint8_t> buf[2];                     // the two histories; [cur] is the one the last frame wrote
   int             cur = 0;
   bool            valid = false;              // buf[cur] holds a history and `camera` its camera
+  DevMem<uint8_t> mom[2];                     // the moments of the two histories (rt_render_svgf allocates them), ping-ponged with buf
+  bool            moments_valid = false;      // mom[cur] holds the moments of buf[cur]: the last frame was rt_render_svgf's
   Camera          camera;
 };
 #pragma GCC visibility pop

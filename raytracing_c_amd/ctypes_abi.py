@@ -178,6 +178,14 @@ assert C.sizeof(RT_Temporal_Params) == 20
 RT_TEMPORAL_HISTORY_PER_PIXEL = 48    # three float4 records
 
 
+class RT_Variance_Params(C.Structure):  # rt_hip.h: the variance estimate's parameters
+    _fields_ = [("sigma_normal", f32), ("sigma_position", f32)]
+
+
+assert C.sizeof(RT_Variance_Params) == 8
+RT_TEMPORAL_MOMENTS_PER_PIXEL = 16    # one float4 record (m1, m2, 0, 0)
+
+
 # numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
 _HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
@@ -223,6 +231,8 @@ EXPORTED_SYMBOLS = [
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
     "rt_history_destroy", "rt_render_temporal",
+    "rt_temporal_moments_bytes", "rt_temporal_accumulate_moments", "rt_temporal_accumulate_moments_host",
+    "rt_guided_variance_work_bytes", "rt_guided_denoise_variance", "rt_guided_denoise_variance_host", "rt_render_svgf",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_fused_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 

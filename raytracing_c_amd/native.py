@@ -164,6 +164,21 @@ def _declare(d):
         d.rt_history_destroy.restype = None
         d.rt_render_temporal.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, vp, P(abi.RT_Temporal_Params),
                                          P(abi.RT_Guided_Params), vp, vp, vp]
+    if hasattr(d, "rt_render_svgf"):
+        d.rt_temporal_moments_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_temporal_moments_bytes.restype = C.c_int64
+        d.rt_temporal_accumulate_moments.argtypes = ([C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera)]
+                                                     + [vp] * 10 + [P(abi.RT_Variance_Params)] + [vp] * 4)
+        d.rt_temporal_accumulate_moments_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera),
+                                                          vp, P(abi.RT_Features), P(abi.RT_History_Planes), P(abi.RT_History_Planes),
+                                                          vp, vp, vp, P(abi.RT_Variance_Params), vp, vp, vp]
+        d.rt_guided_variance_work_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_guided_variance_work_bytes.restype = C.c_int64
+        d.rt_guided_denoise_variance.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params)] + [vp] * 11
+        d.rt_guided_denoise_variance_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Guided_Params), vp, P(abi.RT_Features), vp, vp, vp,
+                                                      vp]
+        d.rt_render_svgf.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, vp, P(abi.RT_Temporal_Params),
+                                     P(abi.RT_Variance_Params), P(abi.RT_Guided_Params), vp, vp, vp, vp]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
