@@ -99,14 +99,81 @@ def accumulate_moments(color, coverage, albedo, normal, position, cam, prev_cam=
     return dict(out=out, length=length, history=hist, moments=mom, var_t=var_t, classes=classes)
 
 
-def variance(history, moments, sigma_normal=0.2, sigma_position=1.0, lost_halo=None):
+TILE_W, TILE_H = 32, 8                        # the variance launch's workgroup: one thread per pixel, four waves of two rows
+HALO_W, HALO_H = TILE_W + 6, TILE_H + 6       # with the 7 x 7 window's halo
+ALL_SKY, EARLY, HALO_WITH_LONG, HALO_ALL_SHORT = range(4)
+TILE_KINDS = ("all sky", "early return with surface", "halo tile with long pixels", "halo tile all short")
+
+
+def tiles(h, w):
+    """(ty, tx, rows, columns) of every 32 x 8 tile of an h x w image, in the launch's block order; the slices are clipped."""
+    for ty in range((h + TILE_H - 1) // TILE_H):
+        for tx in range((w + TILE_W - 1) // TILE_W):
+            yield ty, tx, slice(ty * TILE_H, min(h, (ty + 1) * TILE_H)), slice(tx * TILE_W, min(w, (tx + 1) * TILE_W))
+
+
+def tile_classes(length, coverage):
+    """What the variance launch does with every 32 x 8 tile of a NEW history: dict of (tiles_y, tiles_x) arrays -- kind (an index
+    into TILE_KINDS: no surface pixel; surface pixels and none of them short, so the workgroup stores var_t and leaves; a short
+    pixel and a long one; surface pixels that are all short), sky (the tile holds a sky pixel as well as whatever else), ragged (the
+    image ends inside the tile) -- and count(kind, sky=None, ragged=None), the number of tiles of a kind with those marks."""
+    length, cov = np.ascontiguousarray(length, F), np.ascontiguousarray(coverage, F)
+    h, w = cov.shape
+    shape = ((h + TILE_H - 1) // TILE_H, (w + TILE_W - 1) // TILE_W)
+    kind, sky, ragged = np.zeros(shape, np.int32), np.zeros(shape, bool), np.zeros(shape, bool)
+    for ty, tx, ys, xs in tiles(h, w):
+        surface = cov[ys, xs] != 0
+        short = surface & ~(length[ys, xs] >= F(4.0))
+        kind[ty, tx] = (ALL_SKY if not surface.any() else EARLY if not short.any() else
+                        HALO_ALL_SHORT if (short == surface).all() else HALO_WITH_LONG)
+        sky[ty, tx] = not surface.all()
+        ragged[ty, tx] = surface.shape != (TILE_H, TILE_W)
+
+    def count(k, sky_=None, ragged_=None):
+        m = kind == k
+        m = m if sky_ is None else m & (sky == sky_)
+        m = m if ragged_ is None else m & (ragged == ragged_)
+        return int(m.sum())
+    return dict(kind=kind, sky=sky, ragged=ragged, count=count)
+
+
+def tile_counts(length, coverage):
+    """tile_classes as one printable dict: the number of tiles per kind; of the early returns, how many are ragged and how many
+    hold sky pixels."""
+    c = tile_classes(length, coverage)
+    n = {TILE_KINDS[k]: c["count"](k) for k in range(4)}
+    n["early and ragged"], n["early with sky pixels"] = c["count"](EARLY, ragged_=True), c["count"](EARLY, sky_=True)
+    return n
+
+
+def _tile_of(h, w):
+    """Per pixel: the tile's (ty, tx) and the pixel's (ly, lx) within it, as (h, w) int arrays."""
+    ys, xs = np.mgrid[0:h, 0:w]
+    return ys // TILE_H, xs // TILE_W, ys % TILE_H, xs % TILE_W
+
+
+def variance(history, moments, sigma_normal=0.2, sigma_position=1.0, lost_halo=None, tile_decision=None, tile_threshold=None):
     """THE VARIANCE of a NEW history and its NEW moments: float32 (h, w).
 
     lost_halo, for tests of the TESTS only (it is not the contract): a dict with "axis" (0: x, 1: y).  Every tap that lies in another
-    32 x 8 tile than its centre along that axis is skipped, as if the workgroup's halo had never arrived."""
+    32 x 8 tile than its centre along that axis is skipped, as if the workgroup's halo had never arrived.
+
+    tile_decision="wave", for tests of the TESTS only (it is not the contract): whether to stage the halo is decided per wave -- 64
+    threads, two rows of the tile -- instead of per workgroup.  In a tile with a short pixel a wave without one neither stages nor
+    counts: slot i of the 38 x 14 halo tile, filled by thread i % 256, arrives only if wave (i % 256) // 64 has a short pixel, and a
+    slot that has not arrived counts as coverage 0.
+
+    tile_threshold=3.0, for tests of the TESTS only (it is not the contract): the workgroup asks for a length below that threshold
+    where the pixel asks for one below 4 -- a tile whose shortest surface length is >= the threshold writes var_t everywhere."""
+    assert tile_decision in (None, "wave")
     length, cov, N, W = [np.ascontiguousarray(history[k], F) for k in ("length", "coverage", "normal", "position")]
     moments = np.ascontiguousarray(moments, F)
     h, w = cov.shape
+    tyi, txi, ly, lx = _tile_of(h, w)
+    short = (cov != 0) & ~(length >= F(4.0))
+    if tile_decision == "wave":
+        stages = np.zeros((tyi.max() + 1, txi.max() + 1, TILE_H // 2), bool)
+        np.logical_or.at(stages, (tyi, txi, ly // 2), short)
     with np.errstate(all="ignore"):
         k_n, k_p = [F(1.0) / (F(s) * F(s)) for s in (sigma_normal, sigma_position)]
         var_t, _ = temporal_variance(moments)
@@ -121,6 +188,9 @@ def variance(history, moments, sigma_normal=0.2, sigma_position=1.0, lost_halo=N
             counts = valid & (covq != 0)
             if lost_halo is not None:
                 counts = counts & ~_other_tile(h, w, 1, (dx, dy)[lost_halo["axis"]], lost_halo["axis"])
+            if tile_decision == "wave":
+                slot = (ly + 3 + dy) * HALO_W + (lx + 3 + dx)
+                counts = counts & stages[tyi, txi, (slot % (TILE_W * TILE_H)) // 64]
             dn = N - Nq
             dn2 = dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1] + dn[..., 2] * dn[..., 2]
             dcov = cov - covq
@@ -137,6 +207,10 @@ def variance(history, moments, sigma_normal=0.2, sigma_position=1.0, lost_halo=N
         v = np.where(v > F(0.0), v, F(0.0))
         spatial = v * (F(4.0) / length)
         var = np.where(cov == 0, F(0.0), np.where(length >= F(4.0), var_t, spatial))
+        if tile_threshold is not None:
+            below = np.zeros((tyi.max() + 1, txi.max() + 1), bool)
+            np.logical_or.at(below, (tyi, txi), (cov != 0) & ~(length >= F(tile_threshold)))
+            var = np.where(below[tyi, txi] | (cov == 0), var, var_t)
     assert var.dtype == F
     return var
 

@@ -92,9 +92,9 @@ def _case(w, h):
     return _cases[(w, h)]
 
 
-def _want(P, hist, demodulate, tol, prev=CAM_OLD):
+def _want(P, hist, demodulate, tol, prev=CAM_OLD, kw=KW):
     from tests import _temporal as T
-    r = T.accumulate(*_args(P), CAM_NEW, prev, hist, normal_tolerance=tol[0], plane_tolerance=tol[1], demodulate=demodulate, **KW)
+    r = T.accumulate(*_args(P), CAM_NEW, prev, hist, normal_tolerance=tol[0], plane_tolerance=tol[1], demodulate=demodulate, **kw)
     r["image"] = T.encode_u8(r["out"])
     return r
 
@@ -108,12 +108,12 @@ def _same(got, want, what=""):
         assert got["history"][k].tobytes() == want["history"][k].tobytes(), (what, "history", k)
 
 
-def _host(rt, P, hist, demodulate, tol, prev=CAM_OLD, lib=None):
+def _host(rt, P, hist, demodulate, tol, prev=CAM_OLD, lib=None, kw=KW):
     return rt.temporal_accumulate(*_args(P), CAM_NEW, prev, hist, normal_tolerance=tol[0], plane_tolerance=tol[1], demodulate=demodulate,
-                                  image=True, lib=lib, **KW)
+                                  image=True, lib=lib, **kw)
 
 
-def _device(rt, P, hist, demodulate, tol, prev=CAM_OLD):
+def _device(rt, P, hist, demodulate, tol, prev=CAM_OLD, kw=KW):
     """rt.temporal_accumulate on torch tensors, on a stream that is not the default one."""
     import torch
     from tests import _temporal as T
@@ -123,7 +123,7 @@ def _device(rt, P, hist, demodulate, tol, prev=CAM_OLD):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         got = rt.temporal_accumulate(*t, CAM_NEW, prev, th, normal_tolerance=tol[0], plane_tolerance=tol[1], demodulate=demodulate,
-                                     image=True, **KW)
+                                     image=True, **kw)
     side.synchronize()
     rec = got["history"].cpu().numpy()
     assert not rec[2, ..., 3].any()                                                   # the fourth component of (W, 0)
@@ -166,6 +166,33 @@ def test_degenerate_sizes(rt, w, h):
         want = _want(P, hist, demodulate, tol)
         _same(_host(rt, P, hist, demodulate, tol), want, ("host", demodulate, tol))
         _same(_device(rt, P, hist, demodulate, tol), want, ("device", demodulate, tol))
+
+
+# (alpha, max_history, the factor on the input history's lengths): alpha = 1 and a history of one frame; max_history = 2, under which
+# no new length reaches 4; the smallest alpha and the largest max_history the call admits, with lengths far below the cap, around it
+# (4 x 2^18 = 2^20) and all above it -- there len = n + 1 = 1048577 needs 21 of float32's 24 bits, and a = 1 / len
+PARAMETER_EDGES = [(1.0, 1, 1), (0.2, 2, 1), (2.0 ** -24, 2 ** 20, 1), (2.0 ** -24, 2 ** 20, 2 ** 18), (2.0 ** -24, 2 ** 20, 2 ** 22)]
+
+
+def scaled_history(hist, scale):
+    """The history with its length plane multiplied (exactly: a power of two) by scale."""
+    hist = dict(hist)
+    hist["length"] = (hist["length"] * F32(scale)).astype(F32)
+    return hist
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+@pytest.mark.parametrize("alpha,max_history,scale", PARAMETER_EDGES)
+def test_parameter_edges_37x21(rt, alpha, max_history, scale, path):
+    """The new frame of the synthetic case over tests/test_gpu_variance.py's history with lengths 1 .. 6 (times the scale), at the
+    ends of alpha and max_history.  What these settings reach is shown on the CPU (tests/test_variance_cpu.py)."""
+    from tests.test_gpu_variance import moments_case
+    P, hist, _ = moments_case(37, 21)
+    hist, kw = scaled_history(hist, scale), dict(alpha=alpha, max_history=max_history)
+    want = _want(P, hist, True, TOLERANCES[0], kw=kw)
+    got = (_host if path == "host" else _device)(rt, P, hist, True, TOLERANCES[0], kw=kw)
+    _same(got, want, (alpha, max_history, scale))
+    assert np.isfinite(got["out"]).all() and np.isfinite(got["length"]).all()
 
 
 def test_no_history(rt):

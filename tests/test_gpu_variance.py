@@ -5,7 +5,8 @@ BIT (tobytes), through the host path and through the device path on a non-defaul
 The moments pass and the variance launch run on tests/test_gpu_temporal.py's synthetic planes (imported, not edited) with a random
 moments plane -- some m2 < m1 * m1 -- and random history lengths 1 .. 6, at 37 x 21 (2 x 3 tiles of the variance kernel) and 131 x 70,
 with every tolerance pair, both demodulate settings, +inf sigmas together and each alone, degenerate sizes, no history, every output
-alone, d_out == d_color; out, history, length and image are rt_temporal_accumulate's.  The variance-guided filter runs at
+alone, d_out == d_color; out, history, length and image are rt_temporal_accumulate's.  Every tile of those inputs stages the halo:
+designed_case builds the ones that do not, for tests/test_gpu_variance_tiles.py.  The variance-guided filter runs at
 tests/test_gpu_guided.py's sizes, for the reason it has them, over variance planes that span 0 and eight decades.  That every class of
 pixel occurs and that a lost halo or a prefilter on the lattice would change at least 100 pixels OF THESE VERY INPUTS is shown on the
 CPU (tests/test_variance_cpu.py)."""
@@ -63,10 +64,71 @@ def moments_case(w, h):
     return _mcases[(w, h)]
 
 
-def moments_want(P, hist, mom, demodulate, tol, vs, prev=CAM_OLD):
+_dcases = {}
+DESIGNED_SIZES = [(131, 70), (97, 27), (65, 17)]
+
+
+def designed_case(w, h, variant=0):
+    """(the new frame's planes, a history, its moments) under a STATIC camera -- previous and current camera are CAM_OLD --, made tile
+    by tile of the variance launch so that whole 32 x 8 tiles leave before the halo, which moments_case never does.  The new frame is
+    the history's own view with another colour: hx == x exactly, tap 0 has weight 1 and is valid, and the new length is
+    min(L0, max_history) + 1.  Tile t = ty * tiles_x + tx has class t % 6:
+      0  L0 = 5: long.                   1  L0 = 3: exactly 4.0, long at the boundary.        2  L0 = nextafter(3, 0): short by one ulp.
+      3  L0 = 5 but for short pixels with L0 = 1, alternately one single pixel (a row from {0, 3, 4, 7}, the first or the last
+         column) and the two rows of ONE wave (rows 2v, 2v + 1, v cycling 0 .. 3), both clipped to a ragged tile.
+      4  the NEW frame is sky over the whole tile.       5  L0 = 5, the left half of the (clipped) tile is sky in the new frame.
+    variant: other seeds."""
+    from tests import _temporal as T
+    from tests.test_gpu_temporal import _view
+    if (w, h, variant) not in _dcases:
+        old = _view(CAM_OLD, w, h, 5 + 10 * w + 1000 * variant, False)
+        hist = dict(T.accumulate(*_args(old), CAM_OLD, CAM_OLD, None)["history"])
+        rng = np.random.default_rng(w + h + 1000 * variant)
+        P = {k: np.array(v) for k, v in old.items()}
+        P["color"] = rng.gamma(2.0, 0.4, (h, w, 3)).astype(F32)
+        surface = hist["coverage"] > 0
+        m1 = rng.gamma(2.0, 0.4, (h, w)).astype(F32)
+        ys, xs = np.mgrid[0:h, 0:w]
+        below = (xs // 4 + ys // 3) % 3 == 0
+        m2 = (m1 * m1 * np.where(below, rng.uniform(0.3, 0.9, (h, w)), rng.uniform(1.0, 2.0, (h, w))).astype(F32)).astype(F32)
+        mom = (np.stack([m1, m2], -1) * surface[..., None]).astype(F32)
+        L0 = np.zeros((h, w), F32)
+        tiles_x, n3 = (w + 31) // 32, 0
+        for ty in range((h + 7) // 8):
+            for tx in range(tiles_x):
+                rows, cols = slice(ty * 8, min(h, ty * 8 + 8)), slice(tx * 32, min(w, tx * 32 + 32))
+                th, tw = rows.stop - rows.start, cols.stop - cols.start
+                cls = (ty * tiles_x + tx) % 6
+                L0[rows, cols] = {1: 3.0, 2: np.nextafter(F32(3.0), F32(0.0))}.get(cls, 5.0)
+                if cls == 3:
+                    if n3 % 2 == 0:
+                        row, col = min((0, 3, 4, 7)[(n3 // 2) % 4], th - 1), (0, tw - 1)[(n3 // 2) % 2]
+                        L0[rows.start + row, cols.start + col] = 1.0
+                    else:
+                        v = min((n3 // 2) % 4, (th - 1) // 2)
+                        L0[rows.start + 2 * v:min(rows.stop, rows.start + 2 * v + 2), cols] = 1.0
+                    n3 += 1
+                elif cls in (4, 5):
+                    cols = cols if cls == 4 else slice(cols.start, cols.start + (tw + 1) // 2)
+                    for k in ("coverage", "albedo", "normal", "position"):
+                        P[k][rows, cols] = 0.0
+        hist["length"] = np.where(surface, L0, 0).astype(F32)
+        for a in (*P.values(), *hist.values(), mom):
+            a.setflags(write=False)
+        _dcases[(w, h, variant)] = (P, hist, mom)
+    return _dcases[(w, h, variant)]
+
+
+def designed_want(w, h, max_history=5, variant=0):
+    """The restatement over designed_case under the static camera: moments_want's dict."""
+    P, hist, mom = designed_case(w, h, variant)
+    return moments_want(P, hist, mom, True, TOLERANCES[0], VSIGMAS, cam=CAM_OLD, kw=dict(alpha=0.2, max_history=max_history))
+
+
+def moments_want(P, hist, mom, demodulate, tol, vs, prev=CAM_OLD, cam=CAM_NEW, kw=KW):
     from tests import _temporal as T, _variance as V
-    r = V.accumulate_moments(*_args(P), CAM_NEW, prev, hist, mom, normal_tolerance=tol[0], plane_tolerance=tol[1],
-                             demodulate=demodulate, **KW)
+    r = V.accumulate_moments(*_args(P), cam, prev, hist, mom, normal_tolerance=tol[0], plane_tolerance=tol[1],
+                             demodulate=demodulate, **kw)
     r["variance"] = V.variance(r["history"], r["moments"], *vs)
     r["image"] = T.encode_u8(r["out"])
     return r
@@ -107,12 +169,12 @@ def _pack_moments(mom):
     return rec
 
 
-def _mhost(rt, P, hist, mom, demodulate, tol, vs, prev=CAM_OLD):
-    return rt.temporal_accumulate_moments(*_args(P), CAM_NEW, prev, hist, mom, normal_tolerance=tol[0], plane_tolerance=tol[1],
-                                          demodulate=demodulate, sigma_normal=vs[0], sigma_position=vs[1], image=True, **KW)
+def _mhost(rt, P, hist, mom, demodulate, tol, vs, prev=CAM_OLD, cam=CAM_NEW, kw=KW):
+    return rt.temporal_accumulate_moments(*_args(P), cam, prev, hist, mom, normal_tolerance=tol[0], plane_tolerance=tol[1],
+                                          demodulate=demodulate, sigma_normal=vs[0], sigma_position=vs[1], image=True, **kw)
 
 
-def _mdevice(rt, P, hist, mom, demodulate, tol, vs, prev=CAM_OLD):
+def _mdevice(rt, P, hist, mom, demodulate, tol, vs, prev=CAM_OLD, cam=CAM_NEW, kw=KW):
     """rt.temporal_accumulate_moments on torch tensors, on a stream that is not the default one."""
     import torch
     from tests import _temporal as T
@@ -122,8 +184,8 @@ def _mdevice(rt, P, hist, mom, demodulate, tol, vs, prev=CAM_OLD):
     tm = None if mom is None else torch.from_numpy(_pack_moments(mom)).cuda()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        got = rt.temporal_accumulate_moments(*t, CAM_NEW, prev, th, tm, normal_tolerance=tol[0], plane_tolerance=tol[1],
-                                             demodulate=demodulate, sigma_normal=vs[0], sigma_position=vs[1], image=True, **KW)
+        got = rt.temporal_accumulate_moments(*t, cam, prev, th, tm, normal_tolerance=tol[0], plane_tolerance=tol[1],
+                                             demodulate=demodulate, sigma_normal=vs[0], sigma_position=vs[1], image=True, **kw)
     side.synchronize()
     rec = got["moments"].cpu().numpy()
     assert not rec[..., 2:].any()                                                     # (m1, m2, 0, 0)
@@ -444,7 +506,8 @@ def svgf_parameters(frames, iterations=3):
 @pytest.mark.parametrize("shape", SVGF_SHAPES)
 def test_svgf_chain_with_a_moving_camera(rt, oracle, shape):
     """Five frames while the camera moves: every frame's linear_out, length, variance and Image equal the restatement chained over
-    the GPU's own noisy frames and feature planes; the variance returned is the filter's INPUT."""
+    the GPU's own noisy frames and feature planes; the variance returned is the filter's INPUT.  At 136 x 72 some frame has a
+    tile of the variance launch that holds a surface and no short pixel, so that its workgroup leaves before the halo."""
     from tests import _temporal as T, _variance as V
     hs = _spheres()
     w, h, s, b = shape
@@ -452,7 +515,7 @@ def test_svgf_chain_with_a_moving_camera(rt, oracle, shape):
     par = svgf_parameters(frames)
     g = par["guided_params"]
     hist = mom = prev = None
-    short_and_long = []
+    short_and_long, tile_counts = [], []
     try:
         with rt.History(w, h) as history:
             for k, (seed, off) in enumerate(zip(SEEDS5, OFFSETS5)):
@@ -471,9 +534,14 @@ def test_svgf_chain_with_a_moving_camera(rt, oracle, shape):
                 assert r["image"].tobytes() == T.encode_u8(want["linear_out"]).tobytes(), k
                 assert want["variance_out"].tobytes() != want["variance"].tobytes()
                 short_and_long.append((int(want["classes"]["short"].sum()), int(want["classes"]["long"].sum())))
+                tile_counts.append(V.tile_counts(want["history"]["length"], want["history"]["coverage"]))
     finally:
         _move(hs, origin, right, 0.0)
     print(short_and_long)
+    for k, counts in enumerate(tile_counts):
+        print("frame", k, "tiles of the variance launch:", counts)
+    if (w, h) == (136, 72):                    # (40 x 24 has six tiles, each with a silhouette: none is long throughout)
+        assert any(counts["early return with surface"] >= 1 for counts in tile_counts), tile_counts     # the launch's common path
     assert short_and_long[0][1] == 0 and short_and_long[4][1] >= 20 and short_and_long[4][0] >= 5     # both branches of the variance
 
 

@@ -1,6 +1,7 @@
 """Variance-guided denoising without a GPU: the CONTRACTS themselves -- their numpy restatement (tests/_variance.py), which the GPU
 tests compare the kernels with bit for bit -- must extend the accumulation and the filter without changing them, must estimate a
-variance, and must denoise; and the inputs of tests/test_gpu_variance.py must be able to tell a wrong kernel from a right one."""
+variance, and must denoise; and the inputs of tests/test_gpu_variance.py and tests/test_gpu_variance_tiles.py must be able to tell a
+wrong kernel from a right one -- the latter's must hold every class of tile of the variance launch."""
 import numpy as np
 import pytest
 
@@ -234,3 +235,120 @@ def test_the_wrong_readings_leave_the_restatement_alone():
     got = V.guided(*_args(P), v, 2, *FSIGMAS, True, lost_halo=dict(step=8, axis=0), prefilter_on_lattice=False)
     assert got[0].tobytes() == want.tobytes() and got[1].tobytes() == want_v.tobytes()
     assert (want_v >= 0).all() and np.isfinite(want_v).all() and len(np.unique(np.floor(np.log10(v[v > 0])))) >= 7
+
+
+# ---- 6. the variance launch's tiles: the GPU tests' inputs reach every class of tile, and would expose a wrong tile decision ---------
+
+NEARLY_4 = np.nextafter(F32(4.0), F32(0.0))                    # 3.9999998
+
+
+def _tiles_of_one_length(r, value):
+    """The number of tiles with a surface whose every surface pixel has exactly that new length."""
+    from tests import _variance as V
+    length, cov = r["history"]["length"], r["history"]["coverage"]
+    h, w = cov.shape
+    return sum(1 for _, _, ys, xs in V.tiles(h, w) if (cov[ys, xs] != 0).any() and (length[ys, xs][cov[ys, xs] != 0] == value).all())
+
+
+@pytest.mark.parametrize("w,h", [(131, 70), (97, 27), (65, 17)])
+def test_the_designed_input_has_every_class_of_tile(w, h):
+    """tests/test_gpu_variance.py's designed_case at alpha = 0.2, max_history = 5: tiles that return early (ragged ones and ones
+    with sky pixels among them), sky tiles, halo tiles, tiles at exactly 4.0 and tiles one ulp below.  Measured at 131 x 70: 23 early
+    returns with surface (6 ragged, 8 with sky pixels), 15 halo tiles (8 all short), 7 all sky; 97 x 27: 7, 6 (3), 3; 65 x 17: 4, 3
+    (2), 2.  With max_history = 2 no tile returns early with surface."""
+    from tests import _variance as V
+    from tests.test_gpu_variance import DESIGNED_SIZES, designed_case, designed_want
+    assert (w, h) in DESIGNED_SIZES
+    P, hist, _ = designed_case(w, h)
+    r = designed_want(w, h, 5)
+    assert not r["classes"]["fresh"].any() and r["classes"]["clamped"].sum() >= 100
+    assert set(np.unique(r["length"]).tolist()) == {0.0, 2.0, float(NEARLY_4), 4.0, 6.0}
+    assert (r["length"][P["coverage"] != 0] == np.minimum(hist["length"], F32(5.0))[P["coverage"] != 0] + F32(1.0)).all()
+    n = V.tile_counts(r["history"]["length"], r["history"]["coverage"])
+    n["exactly 4.0"], n["3.9999998"] = _tiles_of_one_length(r, F32(4.0)), _tiles_of_one_length(r, NEARLY_4)
+    halo = n["halo tile with long pixels"] + n["halo tile all short"]
+    print(w, h, n)
+    c = V.tile_classes(r["history"]["length"], r["history"]["coverage"])
+    assert c["count"](V.EARLY, ragged_=False) >= 1 and c["count"](V.HALO_ALL_SHORT, ragged_=True) >= 1     # full and ragged, told apart
+    least = (10, 3, 3, 3, 5, 2, 2) if (w, h) == (131, 70) else (1, 1, 1, 1, 1, 1, 1)
+    got = (n["early return with surface"], n["early and ragged"], n["early with sky pixels"], n["all sky"], halo, n["exactly 4.0"],
+           n["3.9999998"])
+    assert all(g >= l for g, l in zip(got, least)), (got, least)
+    assert n["halo tile with long pixels"] >= 1 and n["halo tile all short"] >= 1
+    capped = designed_want(w, h, 2)
+    n2 = V.tile_counts(capped["history"]["length"], capped["history"]["coverage"])
+    print(w, h, "max_history 2:", n2)
+    assert n2["early return with surface"] == 0 and n2["halo tile all short"] >= 5 and n2["all sky"] == n["all sky"]
+    assert set(np.unique(capped["length"]).tolist()) == {0.0, 2.0, 3.0} and not capped["classes"]["long"].any()
+
+
+def test_the_random_lengths_have_no_early_return():
+    """Why designed_case exists: moments_case(131, 70) draws a length per pixel, so every one of its 45 tiles stages the halo."""
+    from tests import _variance as V
+    from tests.test_gpu_temporal import TOLERANCES
+    from tests.test_gpu_variance import VSIGMAS, moments_case, moments_want
+    P, hist, mom = moments_case(131, 70)
+    for tol in TOLERANCES:
+        r = moments_want(P, hist, mom, True, tol, VSIGMAS)
+        n = V.tile_counts(r["history"]["length"], r["history"]["coverage"])
+        assert n["early return with surface"] == 0 and n["all sky"] == 0 and n["halo tile with long pixels"] == 45, n
+
+
+@pytest.mark.parametrize("w,h", [(131, 70), (97, 27)])
+def test_the_designed_input_would_catch_a_wrong_tile_decision(w, h):
+    """A decision taken per wave instead of per workgroup, and a workgroup threshold of 3 against the pixel's 4, each change the bits
+    of >= 100 pixels of the designed input (measured: 156 and 162 for the wave, 1577 and 608 for the threshold)."""
+    from tests import _variance as V
+    from tests.test_gpu_variance import VSIGMAS, designed_want
+    r = designed_want(w, h, 5)
+    same = V.variance(r["history"], r["moments"], *VSIGMAS, tile_decision=None, tile_threshold=None)
+    assert same.tobytes() == r["variance"].tobytes()
+    assert V.variance(r["history"], r["moments"], *VSIGMAS, tile_threshold=4.0).tobytes() == r["variance"].tobytes()
+    for kw in (dict(tile_decision="wave"), dict(tile_threshold=3.0)):
+        wrong = V.variance(r["history"], r["moments"], *VSIGMAS, **kw)
+        differing = int((wrong.view(np.uint32) != r["variance"].view(np.uint32)).sum())
+        print(w, h, kw, "pixels", differing)
+        assert differing >= 100, (kw, differing)
+
+
+def test_a_second_designed_input_differs_where_tiles_return_early():
+    """The two inputs of the GPU test that stores twice into the same buffers: a result left behind by the first call is wrong for
+    the second on >= 1000 pixels of tiles that return early."""
+    from tests import _variance as V
+    from tests.test_gpu_variance import designed_want
+    a, b = designed_want(131, 70, 5, 0), designed_want(131, 70, 5, 1)
+    c = V.tile_classes(b["history"]["length"], b["history"]["coverage"])
+    ys, xs = np.mgrid[0:70, 0:131]
+    early = c["kind"][ys // V.TILE_H, xs // V.TILE_W] == V.EARLY
+    assert ((a["variance"].view(np.uint32) != b["variance"].view(np.uint32)) & early).sum() >= 1000
+    assert V.tile_counts(a["history"]["length"], a["history"]["coverage"]) == V.tile_counts(b["history"]["length"], b["history"]["coverage"])
+
+
+def test_the_parameter_edges_reach_what_they_are_for():
+    """tests/test_gpu_temporal.py's PARAMETER_EDGES over the 37 x 21 history with lengths 1 .. 6: both restatements stay finite at all
+    five; the new lengths reach 1048577.0 = 2^20 + 1 where the scaled lengths reach the cap; with max_history <= 2 every surface
+    pixel is short; and the moments leave the accumulation alone there too."""
+    from tests import _temporal as T
+    from tests.test_gpu_temporal import CAM_NEW, CAM_OLD, PARAMETER_EDGES, TOLERANCES, _args, scaled_history
+    from tests.test_gpu_variance import VSIGMAS, moments_case, moments_want
+    assert PARAMETER_EDGES == [(1.0, 1, 1), (0.2, 2, 1), (2.0 ** -24, 2 ** 20, 1), (2.0 ** -24, 2 ** 20, 2 ** 18),
+                               (2.0 ** -24, 2 ** 20, 2 ** 22)]
+    P, hist, mom = moments_case(37, 21)
+    for alpha, max_history, scale in PARAMETER_EDGES:
+        scaled, kw = scaled_history(hist, scale), dict(alpha=alpha, max_history=max_history)
+        assert set(np.unique(scaled["length"]).tolist()) == {k * float(scale) for k in range(7)}
+        plain = T.accumulate(*_args(P), CAM_NEW, CAM_OLD, scaled, **kw)
+        r = moments_want(P, scaled, mom, True, TOLERANCES[0], VSIGMAS, kw=kw)
+        assert plain["out"].tobytes() == r["out"].tobytes() and plain["length"].tobytes() == r["length"].tobytes()
+        for a in (r["out"], r["length"], r["moments"], r["variance"], r["history"]["color"]):
+            assert np.isfinite(a).all(), (alpha, max_history, scale)
+        blended = r["classes"]["blended"]
+        print(alpha, max_history, scale, "largest length", float(r["length"].max()), "short", int(r["classes"]["short"].sum()),
+              "long", int(r["classes"]["long"].sum()), "blended", int(blended.sum()))
+        assert blended.sum() >= 100
+        if scale >= 2 ** 18:
+            assert r["length"].max() == F32(1048577.0) and (r["length"] == F32(1048577.0)).sum() >= 20
+        if max_history <= 2:
+            assert not r["classes"]["long"].any() and r["classes"]["short"].sum() >= 100
+        else:
+            assert r["classes"]["long"].sum() >= 20 and r["classes"]["short"].sum() >= 20
