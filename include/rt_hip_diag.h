@@ -62,6 +62,12 @@ extern int rt_test_srgb_sweep(u64 out[3]);
 /* the tile-stream kernel's fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit patterns:
  * out[0] differing patterns (0 expected), out[1] first differing pattern + 1 */
 extern int rt_test_quantize_sweep(u64 out[2]);
+/* the sky loop's sample reduction (group_sum3_u64, rt_dev.hip.h) on lanes a test chooses: three channels of n = n_waves x 64
+ * values, channel c of lane i & 63 of wave i >> 6 at in[c * n + i]; a lane with valid[i] == 0 contributes 0.  out[c * n + i] = the
+ * sum mod 2^64 of channel c over lane i's aligned group of `group` lanes (4, 16 or 64), which every lane of the group must hold. */
+extern int rt_test_group_sum(i32 group, i32 n_waves, u64 const *in, u8 const *valid, u64 *out);
+/* the group size the path kernel's sky loop is built with (RT_SKY_ADD_GROUP) */
+extern int rt_test_sky_add_group(void);
 
 /* Closest hit of n rays (host arrays, 6 f32 per ray: origin, direction) against
  * an uploaded scene: out_t[n], out_tri[n] (-1 = miss), out_uv[2n]. */

@@ -1103,6 +1103,87 @@ __device__ __forceinline__ void tile_add_sample(float4 *smem, const int acc_off,
   atomicAdd(ap + 1, accum_quantize_dev(radiance.y));
   atomicAdd(ap + 2, accum_quantize_dev(radiance.z));
 }
+// ---- the sky loop's sample adds: summed over groups of lanes in registers, one LDS add per group ----
+// 64 lanes that add to ONE pixel are 64 read-modify-writes of one LDS address, three times per batch, and the LDS array serialises
+// them: 86 cycles of the CU's one array per ds_add_u64 against 10.6 without conflicts (tools/exp/lds_add_bench.hip).  The
+// quantised samples are integers mod 2^64, so their sum over a group of lanes is order-free: an xor butterfly of DPP moves (no LDS
+// traffic) leaves every lane of an aligned group of G lanes with the group's sum, and the group's first lane adds it.
+// Bit-identical accumulators.
+// RT_SKY_ADD_GROUP (G): 4, 16 or 64 lanes.  4 is the measured choice (profiles/r11_sample_adds.md): +26 VALU per batch of 746
+// and 48/63 of the loop's conflict cycles gone -- config #3 -1.25 %, tower -1.06 %; 16 (+44 VALU, 60/63) measured +0.1 % / +1.1 %
+// and 64 slower still: past the quads the loop pays more for the instructions than the LDS array gives back.
+#ifndef RT_SKY_ADD_GROUP
+#define RT_SKY_ADD_GROUP 4
+#endif
+static_assert(RT_SKY_ADD_GROUP == 4 || RT_SKY_ADD_GROUP == 16 || RT_SKY_ADD_GROUP == 64, "RT_SKY_ADD_GROUP: 4, 16 or 64");
+// v of the lane a DPP control names (all lanes of the wave active: every source lane exists)
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(const unsigned long long v) {
+  // (mov_dpp: no previous value of the destination to set up; the halves through a vector, not shifts and an or)
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  u32x2 p = __builtin_bit_cast(u32x2, v);
+  p.x = (uint32_t)__builtin_amdgcn_mov_dpp((int)p.x, CTRL, 0xF, 0xF, true);
+  p.y = (uint32_t)__builtin_amdgcn_mov_dpp((int)p.y, CTRL, 0xF, 0xF, true);
+  return __builtin_bit_cast(unsigned long long, p);
+}
+// One step of the butterfly for the three channels of a sample: v += v of the lane the control names.  (The channels side by side:
+// a DPP read of a register needs two idle states after the VALU write, which one channel after the other pays as s_nop.)
+template <int CTRL>
+__device__ __forceinline__ void dpp_add3_u64(unsigned long long &r, unsigned long long &g, unsigned long long &b) {
+  const unsigned long long pr = dpp_u64<CTRL>(r), pg = dpp_u64<CTRL>(g), pb = dpp_u64<CTRL>(b);
+  r += pr; g += pg; b += pb;
+}
+// rows of 16 lanes that each hold their sum -> the sum of the wave in every lane: v_permlane16_swap and v_permlane32_swap
+// (gfx950) of the value with a copy of itself
+__device__ __forceinline__ unsigned long long rows_sum_u64(unsigned long long v) {
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  // rows (r0 r1 r2 r3) -> (r0 r0 r2 r2) and (r1 r1 r3 r3): the odd rows of the first operand change places with the even rows of the second
+  u32x2 p = __builtin_bit_cast(u32x2, v);
+  const auto l16 = __builtin_amdgcn_permlane16_swap(p.x, p.x, false, false), h16 = __builtin_amdgcn_permlane16_swap(p.y, p.y, false, false);
+  u32x2 a = {l16[0], h16[0]}, b = {l16[1], h16[1]};
+  v = __builtin_bit_cast(unsigned long long, a) + __builtin_bit_cast(unsigned long long, b);
+  // halves (a a b b) -> (a a a a) and (b b b b)
+  p = __builtin_bit_cast(u32x2, v);
+  const auto l32 = __builtin_amdgcn_permlane32_swap(p.x, p.x, false, false), h32 = __builtin_amdgcn_permlane32_swap(p.y, p.y, false, false);
+  a = u32x2{l32[0], h32[0]}; b = u32x2{l32[1], h32[1]};
+  return __builtin_bit_cast(unsigned long long, a) + __builtin_bit_cast(unsigned long long, b);
+}
+// The sums of r, g and b over the lane's aligned group of G lanes, mod 2^64, in every lane of the group.  Steps: lane ^ 1 and
+// lane ^ 2 (quad_perm [1,0,3,2], [2,3,0,1]), then -- the quads being uniform -- 7 - lane of the half row and 15 - lane of the row
+// (row_half_mirror, row_mirror), then across the rows.
+template <int G>
+__device__ __forceinline__ void group_sum3_u64(unsigned long long &r, unsigned long long &g, unsigned long long &b) {
+  static_assert(G == 4 || G == 16 || G == 64, "group_sum3_u64: groups of 4, 16 or 64 lanes");
+  dpp_add3_u64<0xB1>(r, g, b);
+  dpp_add3_u64<0x4E>(r, g, b);
+  if (G >= 16) {
+    dpp_add3_u64<0x141>(r, g, b);
+    dpp_add3_u64<0x140>(r, g, b);
+  }
+  if (G >= 64) { r = rows_sum_u64(r); g = rows_sum_u64(g); b = rows_sum_u64(b); }
+}
+// One LDS add without return, as the instruction itself: where the compiler can prove the address wave-uniform it expands the
+// atomic built-in into a scalar loop over the active lanes (v_readlane, nine scalar instructions per lane).  `at`: the LDS byte address.
+__device__ __forceinline__ void lds_add_u64_noret(const uint32_t at, const unsigned long long r, const unsigned long long g,
+                                                  const unsigned long long b) {
+  asm volatile("ds_add_u64 %0, %1\n\tds_add_u64 %0, %2 offset:8\n\tds_add_u64 %0, %3 offset:16" : : "v"(at), "v"(r), "v"(g), "v"(b) : "memory");
+}
+// The quantised sample (r, g, b) of every lane -- 0 from a lane without one (`has`) -- into pixel `pixel` of the tile.  `grouped`
+// (wave-uniform): the lanes of every aligned group of RT_SKY_ADD_GROUP share their pixel; then the first lane of a group adds the
+// group's sum.  Else every lane adds its own.
+__device__ __forceinline__ void tile_add_samples_grouped(float4 *smem, const int acc_off, const int pixel, const bool grouped, const bool has,
+                                                         unsigned long long r, unsigned long long g, unsigned long long b) {
+  bool adds = true;
+  if (grouped) {
+    group_sum3_u64<RT_SKY_ADD_GROUP>(r, g, b);
+    adds = (lane_now() & (RT_SKY_ADD_GROUP - 1)) == 0;
+  }
+  if (adds && has) {
+    // (32-bit arithmetic on the tile's LDS address: `+ pixel * 6` on the pointer is a 64-bit multiply-add)
+    const uint32_t at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)lds_at(smem, acc_off) + (uint32_t)pixel * 24u;
+    lds_add_u64_noret(at, r, g, b);
+  }
+}
 // the pyramid area, as words (floats or uint32_t) from pyr_off
 #define RT_PYR_PLANE      0      // [4 q .. 4 q + 2]: outward normal of side plane q of the tile's camera-ray pyramid
 #define RT_PYR_ORIGIN     16     // [16 .. 18]: the common ray origin

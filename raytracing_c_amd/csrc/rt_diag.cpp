@@ -14,6 +14,9 @@ int rt_launch_test_math(int op, int n, const float *x, const float *y, float *ou
 int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_srgb_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_sky_add_group(void);
+int rt_launch_test_group_sum(int group, int n_waves, const unsigned long long *in, const unsigned char *valid, unsigned long long *out,
+                              hipStream_t stream);
 int rt_launch_test_trace(const RT_KParams *P, int n, const float *rays, float *out_t, int *out_tri, float *out_uv,
                          hipStream_t stream);
 int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, const float *pyr, int exit_lanes, int n_blocks,
@@ -244,6 +247,30 @@ extern "C" int rt_test_srgb_sweep(u64 out[3]) { return run_sweep(rt_launch_test_
 // The tile-stream kernel's shift-based fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit
 // patterns: out[0] differing patterns (0 expected), out[1] first differing pattern + 1.
 extern "C" int rt_test_quantize_sweep(u64 out[2]) { return run_sweep(rt_launch_test_quantize_sweep, "rt_test_quantize_sweep", out, 2); }
+
+// The sky loop's sample reduction on crafted lanes (rt_hip_diag.h): three channels of n_waves x 64 values, out[c * n + i] = the sum of
+// channel c over lane i's aligned group of `group` lanes.
+extern "C" int rt_test_group_sum(i32 group, i32 n_waves, u64 const *in, u8 const *valid, u64 *out) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if ((group != 4 && group != 16 && group != 64) || n_waves <= 0 || n_waves > 65535 || !in || !valid || !out)
+    return rt_fail("rt_test_group_sum: bad arguments");
+  const size_t n = (size_t)n_waves * 64;
+  DevMem<unsigned long long> din, dout;
+  DevMem<unsigned char> dvalid;
+  HIP_TRY(din.grow(3 * n));
+  HIP_TRY(dout.grow(3 * n));
+  HIP_TRY(dvalid.grow(n));
+  HIP_TRY(hipMemcpy(din, in, 3 * n * sizeof(u64), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dvalid, valid, n, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_group_sum(group, n_waves, din, dvalid, dout, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, 3 * n * sizeof(u64), hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_group_sum failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_sky_add_group(void) { return rt_launch_test_sky_add_group(); }
 
 // The tile order the preparation kernel derives from per-tile costs (rays of the previous launch): order[] must be a
 // permutation of 0 .. n_tiles - 1 with non-increasing cost buckets (rt_kernels.hip: cost_bucket, 4 per power of two).

@@ -287,11 +287,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         }
 #pragma unroll
         for (int q = 0; q < RT_SKY_PATHS; q++) {
+          // The samples of a batch start at sample 0 or a multiple of 64 of their unit (c_next), `shift` bits of k per pixel: the
+          // lanes of an aligned group of G share a pixel exactly when G <= 2^shift.  Then the group's samples are summed in
+          // registers and one lane adds (tile_add_samples_grouped); with fewer samples per pixel every lane adds its own, as before.
+          unsigned long long qr = 0ull, qg = 0ull, qb = 0ull;
           if (valid[q]) {
             const rt_v3 bg = background_lookup(SP, dirs[q]);
             const rt_v3 radiance = rt_v3_mul_add(bg, rt_v3_make(1, 1, 1), rt_v3_make(0, 0, 0));      // tint 1, emission 0 (raytracer.c:554)
-            tile_add_sample(smem, acc_off, U.c_pix0 + pxs[q], radiance);
+            qr = accum_quantize_dev(radiance.x); qg = accum_quantize_dev(radiance.y); qb = accum_quantize_dev(radiance.z);
           }
+          // (2^shift as half the unit's paths, which the loop holds anyway: the same test on `shift` costs every instance two more spilled SGPRs)
+          tile_add_samples_grouped(smem, acc_off, U.c_pix0 + pxs[q], U.c_end >= 2 * RT_SKY_ADD_GROUP, valid[q], qr, qg, qb);
           nv += (uint32_t)__popcll(__ballot(valid[q]));
         }
         w_paths += nv; w_rays += nv; w_nodes += nv; w_bgs += nv;      // (the skipped root visit counts, as in the general loop)

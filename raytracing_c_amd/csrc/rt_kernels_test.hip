@@ -73,6 +73,18 @@ __global__ void rt_test_quantize_sweep_kernel(unsigned long long *counts) {
   if (first) atomicMax(&counts[1], (unsigned long long)first);
 }
 
+// group_sum3_u64<G> (the sky loop's sample reduction, three values at once) on values a test chooses: one wave per block, lane
+// i & 63 of wave i >> 6, channel c at [c * n + i]; a lane that is not valid contributes 0, as in the loop.  Every lane writes
+// what it holds afterwards.
+template <int G>
+__global__ __launch_bounds__(64) void rt_test_group_sum_kernel(const unsigned long long *in, const unsigned char *valid, unsigned long long *out) {
+  const size_t n = (size_t)gridDim.x * 64, i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  unsigned long long r = 0ull, g = 0ull, b = 0ull;
+  if (valid[i]) { r = in[i]; g = in[n + i]; b = in[2 * n + i]; }
+  group_sum3_u64<G>(r, g, b);
+  out[i] = r; out[n + i] = g; out[2 * n + i] = b;
+}
+
 // srgb_to_linear_tex1(x) against rt_srgb_to_linear1(x) for every float in [0, 2] and in [-0.046875, -0.03125]: counts[0] =
 // patterns compared (2^30 + 2^22), counts[1] = patterns that differ, counts[2] = first differing pattern + 1.
 __global__ void rt_test_srgb_sweep_kernel(unsigned long long *counts) {
@@ -301,6 +313,16 @@ extern "C" int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t 
   hipLaunchKernelGGL(rt_test_rcp_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);
   return (int)hipGetLastError();
 }
+
+extern "C" int rt_launch_test_group_sum(int group, int n_waves, const unsigned long long *in, const unsigned char *valid,
+                                        unsigned long long *out, hipStream_t stream) {
+  if (group == 4) hipLaunchKernelGGL(rt_test_group_sum_kernel<4>, dim3(n_waves), dim3(64), 0, stream, in, valid, out);
+  else if (group == 16) hipLaunchKernelGGL(rt_test_group_sum_kernel<16>, dim3(n_waves), dim3(64), 0, stream, in, valid, out);
+  else hipLaunchKernelGGL(rt_test_group_sum_kernel<64>, dim3(n_waves), dim3(64), 0, stream, in, valid, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_sky_add_group(void) { return RT_SKY_ADD_GROUP; }
 
 extern "C" int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream) {
   hipLaunchKernelGGL(rt_test_quantize_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);

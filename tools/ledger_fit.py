@@ -37,7 +37,7 @@ def _node_any(c):
 
 
 BLOCKS = [
-    ("SKY_X", "sky loop: a batch of up to 64 camera paths of a tile whose pyramid misses the root (primary ray, fast flag, environment, accumulate)", "SKY_X", "SKY_L", 624, 0.85, 1.15),
+    ("SKY_X", "sky loop: a batch of up to 64 camera paths of a tile whose pyramid misses the root (primary ray, fast flag, environment, group sum of 4 lanes, accumulate)", "SKY_X", "SKY_L", 650, 0.85, 1.15),
     ("S_ITER", "S block: entry, park decision, counters, exit into the traversal loop", "S_ITER", None, None, 20, 400),
     ("ENV_X", "S: environment lookup of the misses (atan2, asin, bilinear fetch, 3 x pow)", "ENV_X", "ENV_L", 369, 0.9, 1.1),
     ("SHADE_T", "S: shade_hit, Disney material with 4 textures (helmet)", _disney_tex, "SHADE_L", 1747, 0.75, 1.05),

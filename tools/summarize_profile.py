@@ -100,6 +100,19 @@ def main(tag):
                            "waves_per_simd": 4}
         lines += [f"VALU issue = 2 cycles x SQ_INSTS_VALU / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) = "
                   f"**{traffic['valu']['issue_frac']:.2f}** of the SIMD cycles of the launch", ""]
+    if "SQ_LDS_BANK_CONFLICT" in counters and "GRBM_GUI_ACTIVE" in counters:
+        # the CU's one LDS array: conflict cycles per CU against the cycles of the launch; a sample add of n lanes on one address
+        # costs n - 1 of them per channel, so a kernel whose waves sit on one pixel reads 3 x paths x 63/64
+        per_cu, launch = counters["SQ_LDS_BANK_CONFLICT"] / 256.0, counters["GRBM_GUI_ACTIVE"] / 8.0
+        line = (f"LDS bank conflicts per CU = SQ_LDS_BANK_CONFLICT / 256 CUs = {per_cu/1e6:.2f} M cycles = **{per_cu/launch:.3f}** of the "
+                f"launch's {launch/1e6:.1f} M cycles (GRBM_GUI_ACTIVE / 8 XCDs)")
+        import re
+        m = re.search(r"(\d+)x(\d+), (\d+) spp", bench["config"]["workload"]) if bench else None
+        if m:
+            paths = int(m.group(1)) * int(m.group(2)) * int(m.group(3))
+            line += (f"; SQ_LDS_BANK_CONFLICT {counters['SQ_LDS_BANK_CONFLICT']/1e9:.3f} G beside 3 x {paths} paths x 63/64 = "
+                     f"{3.0 * paths * 63 / 64 / 1e9:.3f} G (every sample add serialised on its pixel)")
+        lines += [line, ""]
     open(os.path.join(dst, f"{tag}_summary.md"), "w").write("\n".join(lines))
     if traffic:
         json.dump(traffic, open(os.path.join(dst, f"{tag}_traffic.json"), "w"), indent=1)
