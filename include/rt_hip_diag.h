@@ -68,6 +68,11 @@ extern int rt_test_quantize_sweep(u64 out[2]);
 extern int rt_test_group_sum(i32 group, i32 n_waves, u64 const *in, u8 const *valid, u64 *out);
 /* the group size the path kernel's sky loop is built with (RT_SKY_ADD_GROUP) */
 extern int rt_test_sky_add_group(void);
+/* the two orderings of a node block's eight children (node_order_keys, node_order_rank, rt_dev.hip.h) on distances a test chooses,
+ * one lane per case: t_min[8 i + k] = the bit pattern of child k's entry distance, at least that of RT_EPSILON; cand[8 i + k] != 0 =
+ * the child is a candidate.  out[3 i] = the order word from the 32-bit keys, out[3 i + 1] = the word from the rank sort, out[3 i + 2] =
+ * 1 when the keys of the case are not exact, so that a node block takes the rank sort (its first word then means nothing) */
+extern int rt_test_node_order(i32 n, u32 const *t_min, u8 const *cand, u32 *out);
 
 /* Closest hit of n rays (host arrays, 6 f32 per ray: origin, direction) against
  * an uploaded scene: out_t[n], out_tri[n] (-1 = miss), out_uv[2n]. */

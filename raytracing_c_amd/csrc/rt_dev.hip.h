@@ -144,19 +144,29 @@ __device__ __forceinline__ int   as_i(float f) { return __float_as_int(f); }
 __device__ __forceinline__ float fmin_hw(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ float fmax_hw(float a, float b) { return __builtin_fmaxf(a, b); }
 
+// The FAST form in two parts: the entry distance itself -- fmax(RT_EPS, ...) of NaN-free operands: never NaN, never below
+// RT_EPS, whether the child is a candidate or not -- and the candidate test.
+__device__ __forceinline__ float slab_entry_fast(const Ray3 &r, const rt_v3 &bs, float mnx, float mny, float mnz,
+                                                 float mxx, float mxy, float mxz, float t_max, bool &cand) {
+  float t0x = rt_slab_t_fast(mnx, r.o.x, r.inv_x, bs.x), t1x = rt_slab_t_fast(mxx, r.o.x, r.inv_x, bs.x);
+  float t0y = rt_slab_t_fast(mny, r.o.y, r.inv_y, bs.y), t1y = rt_slab_t_fast(mxy, r.o.y, r.inv_y, bs.y);
+  float t0z = rt_slab_t_fast(mnz, r.o.z, r.inv_z, bs.z), t1z = rt_slab_t_fast(mxz, r.o.z, r.inv_z, bs.z);
+  float sx = fmin_hw(t0x, t1x), sy = fmin_hw(t0y, t1y), sz = fmin_hw(t0z, t1z);
+  float bx = fmax_hw(t0x, t1x), by = fmax_hw(t0y, t1y), bz = fmax_hw(t0z, t1z);
+  float t_minv = fmax_hw(RT_EPS, fmax_hw(sx, fmax_hw(sy, sz)));
+  float t_maxv = fmin_hw(t_max, fmin_hw(bx, fmin_hw(by, bz)));
+  // t_maxv <= t_max, so "entry < exit" already implies the candidate test entry < t_max
+  cand = t_minv < t_maxv;
+  return t_minv;
+}
+
 template <bool FAST>
 __device__ __forceinline__ float slab_entry(const Ray3 &r, const rt_v3 &bs, float mnx, float mny, float mnz,
                                             float mxx, float mxy, float mxz, float t_max) {
   if (FAST) {
-    float t0x = rt_slab_t_fast(mnx, r.o.x, r.inv_x, bs.x), t1x = rt_slab_t_fast(mxx, r.o.x, r.inv_x, bs.x);
-    float t0y = rt_slab_t_fast(mny, r.o.y, r.inv_y, bs.y), t1y = rt_slab_t_fast(mxy, r.o.y, r.inv_y, bs.y);
-    float t0z = rt_slab_t_fast(mnz, r.o.z, r.inv_z, bs.z), t1z = rt_slab_t_fast(mxz, r.o.z, r.inv_z, bs.z);
-    float sx = fmin_hw(t0x, t1x), sy = fmin_hw(t0y, t1y), sz = fmin_hw(t0z, t1z);
-    float bx = fmax_hw(t0x, t1x), by = fmax_hw(t0y, t1y), bz = fmax_hw(t0z, t1z);
-    float t_minv = fmax_hw(RT_EPS, fmax_hw(sx, fmax_hw(sy, sz)));
-    float t_maxv = fmin_hw(t_max, fmin_hw(bx, fmin_hw(by, bz)));
-    // t_maxv <= t_max, so "entry < exit" already implies the candidate test entry < t_max
-    return (t_minv < t_maxv) ? t_minv : RT_INF;
+    bool cand;
+    const float t_minv = slab_entry_fast(r, bs, mnx, mny, mnz, mxx, mxy, mxz, t_max, cand);
+    return cand ? t_minv : RT_INF;
   } else {
     // ONLY for rays that are not NaN-free (Ray3::fast false): under contract v2 the two forms round differently, so a
     // NaN-free ray must never come through here (callers branch per lane: traversal_blocks, trace_ray)
@@ -203,11 +213,13 @@ __device__ __forceinline__ float slab_entry_child_any(const float *n, const Ray3
 // the near-first visiting order of the children that can still matter:
 //   bits 0..23  child indices, nearest first (ties: lowest index first)
 //   bits 24..27 how many of them are candidates (entry < hit_t)
-// This is the selection loop of raytracer.c:459-468 done once, as a rank sort.
-// Candidate distances are positive floats or +inf, so they order like their bit
-// patterns: rank arithmetic runs on integers (sign bit of a difference), without
-// compare/select pairs.  Non-candidates (+inf) rank behind every candidate, so
-// the 8 ranks are a permutation and the word needs no per-child condition.
+// This is the selection loop of raytracer.c:459-468 done once: as a sorting network
+// on exact keys for the FAST slab forms (node_order_keys), as a rank sort otherwise
+// (node_order_rank).  For the rank sort: candidate distances are positive floats or
+// +inf, so they order like their bit patterns: rank arithmetic runs on integers (sign
+// bit of a difference), without compare/select pairs.  Non-candidates (+inf) rank
+// behind every candidate, so the 8 ranks are a permutation and the word needs no
+// per-child condition.
 #define NODE_GLOBAL 0     // per-lane vector loads from HBM/L2/L1
 #define NODE_SCALAR 1     // wave-uniform node: s_load through the scalar cache
 #define NODE_LDS_ORDERED 3   // per-lane reads from the workgroup's LDS copy of the top of the tree, the slab planes picked by address (FAST rays, boxes with min <= max)
@@ -232,16 +244,109 @@ static inline int raise_lds_limit(const void *kernel, uint32_t *devices, int sme
   return 0;
 }
 
-template <bool FAST, int MODE>
-__device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &r, int node, float hit_t,
-                                               const float4 *lds_nodes) {
+// The same order from exact 32-bit KEYS, for the FAST slab forms: their entry distance is fmax(RT_EPS, ...) of NaN-free
+// operands, so its bit pattern is at least that of RT_EPS, for candidates and non-candidates alike.  With
+// raw = bits(t_minv) - bits(RT_EPS) the key of child k is (raw << 3) | k for a candidate and RT_KEY_MISS | k otherwise: nothing
+// is truncated while raw < RT_KEY_RAW_END = 2^29 - 1 (distances below about 1.8e15; at 2^29 - 1 the key would be a miss key),
+// and sorted as unsigned integers the keys stand in ascending distance, ties by index, non-candidates last by index -- the
+// ranks of the rank sort, the whole word.  Eight keys sort in the 19 comparators of node_order_keys(), a v_min_u32 and a
+// v_max_u32 each, and the three low bits of the sorted keys ARE the word.  A block in which the largest of its eight raw values
+// (a non-candidate's counts too: three v_max3_u32, where leaving those out would take eight selects) reaches RT_KEY_RAW_END
+// is redone by the rank sort, for the whole wave: node_enter().
+#define RT_KEY_BASE    0x38D1B717u      // bits(RT_EPS)
+#define RT_KEY_MISS    0xFFFFFFF8u
+#define RT_KEY_RAW_END 0x1FFFFFFFu
+static_assert(__builtin_bit_cast(uint32_t, RT_EPS) == RT_KEY_BASE, "the keys count from the bit pattern of RT_EPS");
+static_assert(((RT_KEY_RAW_END - 1u) << 3 | 7u) < RT_KEY_MISS && (RT_KEY_RAW_END << 3) == RT_KEY_MISS, "the largest exact key is below the miss keys");
+
+struct NodeKeys {
+  uint32_t key[8];
+  uint32_t max_raw;       // the largest raw value so far
+  uint32_t n_cand;
+};
+__device__ __forceinline__ void node_key_put(NodeKeys &K, int k, float t_minv, bool cand) {
+  const uint32_t raw = __float_as_uint(t_minv) - RT_KEY_BASE;
+  K.max_raw = raw > K.max_raw ? raw : K.max_raw;
+  K.key[k] = cand ? ((raw << 3) | (uint32_t)k) : (RT_KEY_MISS | (uint32_t)k);
+  // hipcc counts two children per v_cndmask_b32 + v_addc_co_u32 on the compare masks; spelling the add-with-carry as asm, one per
+  // child, is the same 8 instructions but holds the masks differently and costs the 16-wave path kernel a spilled VGPR
+  K.n_cand += cand ? 1u : 0u;
+}
+__device__ __forceinline__ bool node_keys_exact(const NodeKeys &K) { return K.max_raw < RT_KEY_RAW_END; }
+
+#define RT_KEY_CMPX(a, b) do { const uint32_t lo_ = K.key[a] < K.key[b] ? K.key[a] : K.key[b], hi_ = K.key[a] < K.key[b] ? K.key[b] : K.key[a]; \
+                               K.key[a] = lo_; K.key[b] = hi_; } while (0)
+__device__ __forceinline__ uint32_t node_order_keys(NodeKeys &K) {
+  RT_KEY_CMPX(0, 2); RT_KEY_CMPX(1, 3); RT_KEY_CMPX(4, 6); RT_KEY_CMPX(5, 7);
+  RT_KEY_CMPX(0, 4); RT_KEY_CMPX(1, 5); RT_KEY_CMPX(2, 6); RT_KEY_CMPX(3, 7);
+  RT_KEY_CMPX(0, 1); RT_KEY_CMPX(2, 3); RT_KEY_CMPX(4, 5); RT_KEY_CMPX(6, 7);
+  RT_KEY_CMPX(2, 4); RT_KEY_CMPX(3, 5);
+  RT_KEY_CMPX(1, 4); RT_KEY_CMPX(3, 6);
+  RT_KEY_CMPX(1, 2); RT_KEY_CMPX(3, 4); RT_KEY_CMPX(5, 6);
+  uint32_t w = 0;
+#pragma unroll
+  for (int m = 0; m < 8; m++) w = __builtin_amdgcn_alignbit(K.key[m], w, 3);     // the index of place m comes in at the top
+  return (w >> 8) | (K.n_cand << 24);
+}
+#undef RT_KEY_CMPX
+
+// The rank sort: d[k] = the bit pattern of child k's entry distance, +inf for a non-candidate
+__device__ __forceinline__ uint32_t node_order_rank(const int (&d)[8]) {
+  // rank[k] starts at k (the pairs (j,k), j<k, it loses by default) and moves by the sign bits
+  int rank[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) rank[k] = k;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+#pragma unroll
+    for (int k = j + 1; k < 8; k++) {
+      int kb = (int)((uint32_t)(d[k] - d[j]) >> 31);      // 1 iff d[k] < d[j]
+      rank[j] += kb;
+      rank[k] -= kb;
+    }
+  }
+  uint32_t w = 0, n_inf = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    int sh;       // 3 * rank as one full-rate v_lshl_add_u32 (hipcc turns r + 2r into a quarter-rate v_mul_lo_u32)
+    asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(sh) : "v"(rank[j]));
+    w |= (uint32_t)j << sh;
+    n_inf += ((uint32_t)d[j] + 0x00800000u) >> 31;          // 1 iff d[j] == +inf
+  }
+  return w | ((8u - n_inf) << 24);
+}
+
+// One child's slab result into the form the block sorts: a key (KEYED, FAST only) or the rank sort's d[]
+template <bool KEYED>
+__device__ __forceinline__ void node_child_put(NodeKeys &K, int (&d)[8], int k, float t_minv, bool cand) {
+  if (KEYED) node_key_put(K, k, t_minv, cand);
+  else d[k] = as_i(cand ? t_minv : RT_INF);
+}
+
+// KEYED = false: the rank sort, the only form of the FAST = false instantiations (their t_minv can be NaN and rt_max_ps is not
+// fmax) and the one that redoes a FAST block whose keys would not be exact.  KEYED = true: FAST only; precondition as for the
+// rank sort -- candidate distances are positive floats -- and t_minv >= RT_EPS for every child, which every FAST slab form
+// guarantees (slab_entry_fast); the caller checks `exact`.
+template <bool FAST, int MODE, bool KEYED>
+__device__ __forceinline__ uint32_t node_enter_form(const RT_KParams &P, const Ray3 &r, int node, float hit_t,
+                                                    const float4 *lds_nodes, bool &exact) {
+  static_assert(FAST || !KEYED, "keys are for the FAST slab forms only");
   int d[8];
+  NodeKeys K;
+  K.max_raw = 0u;
+  K.n_cand = 0u;
   const rt_v3 bs = FAST ? slab_bias3(r) : rt_v3_make(0.0f, 0.0f, 0.0f);
   if (MODE == NODE_SCALAR) {               // `node` is wave-uniform: node data lives in SGPRs
     cfloat *nb = as_scalar_ptr(P.nodes) + (size_t)node * 48;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-      d[k] = as_i(slab_entry<FAST>(r, bs, nb[k], nb[8 + k], nb[16 + k], nb[24 + k], nb[32 + k], nb[40 + k], hit_t));
+      if (FAST) {
+        bool cand;
+        const float t_minv = slab_entry_fast(r, bs, nb[k], nb[8 + k], nb[16 + k], nb[24 + k], nb[32 + k], nb[40 + k], hit_t, cand);
+        node_child_put<KEYED>(K, d, k, t_minv, cand);
+      } else {
+        d[k] = as_i(slab_entry<false>(r, bs, nb[k], nb[8 + k], nb[16 + k], nb[24 + k], nb[32 + k], nb[40 + k], hit_t));
+      }
     }
   } else if (MODE == NODE_LDS_ORDERED) {
     static_assert(FAST || MODE != NODE_LDS_ORDERED, "the ordered LDS form is for FAST rays only");
@@ -266,7 +371,7 @@ __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &
         const float sz = rt_slab_t_fast(nzs[k], r.o.z, r.inv_z, bs.z), bzz = rt_slab_t_fast(fzs[k], r.o.z, r.inv_z, bs.z);
         const float t_minv = fmax_hw(RT_EPS, fmax_hw(sx, fmax_hw(sy, sz)));
         const float t_maxv = fmin_hw(hit_t, fmin_hw(bxx, fmin_hw(byy, bzz)));
-        d[h * 4 + k] = as_i((t_minv < t_maxv) ? t_minv : RT_INF);
+        node_child_put<KEYED>(K, d, h * 4 + k, t_minv, t_minv < t_maxv);
       }
     }
   } else {
@@ -275,35 +380,40 @@ __device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &
     for (int h = 0; h < 2; h++) {          // children 0-3, then 4-7: half the node in registers at a time
       float4 mnx = nb[0 + h], mny = nb[2 + h], mnz = nb[4 + h];
       float4 mxx = nb[6 + h], mxy = nb[8 + h], mxz = nb[10 + h];
-      d[h * 4 + 0] = as_i(slab_entry<FAST>(r, bs, mnx.x, mny.x, mnz.x, mxx.x, mxy.x, mxz.x, hit_t));
-      d[h * 4 + 1] = as_i(slab_entry<FAST>(r, bs, mnx.y, mny.y, mnz.y, mxx.y, mxy.y, mxz.y, hit_t));
-      d[h * 4 + 2] = as_i(slab_entry<FAST>(r, bs, mnx.z, mny.z, mnz.z, mxx.z, mxy.z, mxz.z, hit_t));
-      d[h * 4 + 3] = as_i(slab_entry<FAST>(r, bs, mnx.w, mny.w, mnz.w, mxx.w, mxy.w, mxz.w, hit_t));
+      const float c_mnx[4] = {mnx.x, mnx.y, mnx.z, mnx.w}, c_mny[4] = {mny.x, mny.y, mny.z, mny.w}, c_mnz[4] = {mnz.x, mnz.y, mnz.z, mnz.w};
+      const float c_mxx[4] = {mxx.x, mxx.y, mxx.z, mxx.w}, c_mxy[4] = {mxy.x, mxy.y, mxy.z, mxy.w}, c_mxz[4] = {mxz.x, mxz.y, mxz.z, mxz.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        if (FAST) {
+          bool cand;
+          const float t_minv = slab_entry_fast(r, bs, c_mnx[k], c_mny[k], c_mnz[k], c_mxx[k], c_mxy[k], c_mxz[k], hit_t, cand);
+          node_child_put<KEYED>(K, d, h * 4 + k, t_minv, cand);
+        } else {
+          d[h * 4 + k] = as_i(slab_entry<false>(r, bs, c_mnx[k], c_mny[k], c_mnz[k], c_mxx[k], c_mxy[k], c_mxz[k], hit_t));
+        }
+      }
     }
   }
+  if (KEYED) {
+    exact = node_keys_exact(K);
+    return node_order_keys(K);
+  }
+  exact = true;
+  return node_order_rank(d);
+}
 
-  // rank[k] starts at k (the pairs (j,k), j<k, it loses by default) and moves by the sign bits
-  int rank[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) rank[k] = k;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-#pragma unroll
-    for (int k = j + 1; k < 8; k++) {
-      int kb = (int)((uint32_t)(d[k] - d[j]) >> 31);      // 1 iff d[k] < d[j]
-      rank[j] += kb;
-      rank[k] -= kb;
-    }
-  }
-  uint32_t w = 0, n_inf = 0;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    int sh;       // 3 * rank as one full-rate v_lshl_add_u32 (hipcc turns r + 2r into a quarter-rate v_mul_lo_u32)
-    asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(sh) : "v"(rank[j]));
-    w |= (uint32_t)j << sh;
-    n_inf += ((uint32_t)d[j] + 0x00800000u) >> 31;          // 1 iff d[j] == +inf
-  }
-  return w | ((8u - n_inf) << 24);
+template <bool FAST, int MODE>
+__device__ __forceinline__ uint32_t node_enter(const RT_KParams &P, const Ray3 &r, int node, float hit_t,
+                                               const float4 *lds_nodes) {
+  bool exact;
+  const uint32_t w = node_enter_form<FAST, MODE, FAST>(P, r, node, hit_t, lds_nodes, exact);
+  if (!FAST || __builtin_expect(__ballot(!exact) == 0ull, 1)) return w;
+  // Once in a blue moon: the whole block again, from the node's address on.  The empty asm makes `node` a new value to the
+  // compiler: otherwise it shares the loads and the slab arithmetic of the two forms and keeps the node's 48 planes alive up
+  // to this branch, which costs the path kernel 11 spilled VGPRs.
+  if (MODE == NODE_SCALAR) asm volatile("" : "+s"(node));
+  else asm volatile("" : "+v"(node));
+  return node_enter_form<FAST, MODE, false>(P, r, node, hit_t, lds_nodes, exact);
 }
 
 // 1 / x in six instructions where hipcc's IEEE division takes eleven (one of them the double-length v_rcp_f32 in both):

@@ -17,6 +17,7 @@ int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream
 int rt_launch_test_sky_add_group(void);
 int rt_launch_test_group_sum(int group, int n_waves, const unsigned long long *in, const unsigned char *valid, unsigned long long *out,
                               hipStream_t stream);
+int rt_launch_test_node_order(int n, const uint32_t *t_min, const unsigned char *cand, uint32_t *out, hipStream_t stream);
 int rt_launch_test_trace(const RT_KParams *P, int n, const float *rays, float *out_t, int *out_tri, float *out_uv,
                          hipStream_t stream);
 int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, const float *pyr, int exit_lanes, int n_blocks,
@@ -271,6 +272,26 @@ extern "C" int rt_test_group_sum(i32 group, i32 n_waves, u64 const *in, u8 const
 }
 
 extern "C" int rt_test_sky_add_group(void) { return rt_launch_test_sky_add_group(); }
+
+// The two orderings of a node block's children on crafted distances (rt_hip_diag.h): n cases of eight entry distances (bit patterns)
+// and eight candidate flags; out[3 i ..] = the word from the keys, the word from the rank sort, 1 when the keys are not exact.
+extern "C" int rt_test_node_order(i32 n, u32 const *t_min, u8 const *cand, u32 *out) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (n <= 0 || n > (1 << 24) || !t_min || !cand || !out) return rt_fail("rt_test_node_order: bad arguments");
+  DevMem<uint32_t> dt, dout;
+  DevMem<unsigned char> dcand;
+  HIP_TRY(dt.grow((size_t)n * 8));
+  HIP_TRY(dcand.grow((size_t)n * 8));
+  HIP_TRY(dout.grow((size_t)n * 3));
+  HIP_TRY(hipMemcpy(dt, t_min, (size_t)n * 8 * sizeof(u32), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dcand, cand, (size_t)n * 8, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_node_order(n, dt, dcand, dout, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, (size_t)n * 3 * sizeof(u32), hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_node_order failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
 
 // The tile order the preparation kernel derives from per-tile costs (rays of the previous launch): order[] must be a
 // permutation of 0 .. n_tiles - 1 with non-increasing cost buckets (rt_kernels.hip: cost_bucket, 4 per power of two).

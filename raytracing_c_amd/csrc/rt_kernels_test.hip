@@ -85,6 +85,35 @@ __global__ __launch_bounds__(64) void rt_test_group_sum_kernel(const unsigned lo
   out[i] = r; out[n + i] = g; out[2 * n + i] = b;
 }
 
+// The two orderings of a node block's children (rt_dev.hip.h) on distances a test chooses, one lane per case: t_min[8 i + k] = the
+// bit pattern of child k's entry distance (at least that of RT_EPS, as every FAST slab form gives it), cand[8 i + k] != 0 = the
+// child is a candidate.  out[3 i] = the word of node_order_keys(), [3 i + 1] = the word of node_order_rank(), [3 i + 2] = 1 when
+// the keys of the case are not exact (node_keys_exact) and a node block takes the rank sort.
+__global__ void rt_test_node_order_kernel(int n, const uint32_t *t_min, const unsigned char *cand, uint32_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  NodeKeys K;
+  K.max_raw = 0u;
+  K.n_cand = 0u;
+  int d[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const float t = __uint_as_float(t_min[(size_t)i * 8 + k]);
+    const bool c = cand[(size_t)i * 8 + k] != 0;
+    node_child_put<true>(K, d, k, t, c);
+    node_child_put<false>(K, d, k, t, c);
+  }
+  const bool exact = node_keys_exact(K);
+  out[(size_t)i * 3 + 0] = node_order_keys(K);
+  out[(size_t)i * 3 + 1] = node_order_rank(d);
+  out[(size_t)i * 3 + 2] = exact ? 0u : 1u;
+}
+
+extern "C" int rt_launch_test_node_order(int n, const uint32_t *t_min, const unsigned char *cand, uint32_t *out, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_node_order_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, t_min, cand, out);
+  return (int)hipGetLastError();
+}
+
 // srgb_to_linear_tex1(x) against rt_srgb_to_linear1(x) for every float in [0, 2] and in [-0.046875, -0.03125]: counts[0] =
 // patterns compared (2^30 + 2^22), counts[1] = patterns that differ, counts[2] = first differing pattern + 1.
 __global__ void rt_test_srgb_sweep_kernel(unsigned long long *counts) {
