@@ -204,6 +204,13 @@ typedef struct {
   int32_t tiles_x;             /* ceil(width / 32): block b is tile (b % tiles_x, b / tiles_x) of 32 x 8 pixels            */
 } RT_TParams;
 
+/* A frame on the device, as the post passes read it (rt_guided.hip, rt_temporal.hip, rt_variance.hip and the host side of them,
+ * rt_post.cpp): the linear colour f32[h][w][3] and the four first-hit planes of rt_features.hip, coverage f32[h][w], the others
+ * f32[h][w][3].  albedo may be NULL where `demodulate` is 0: nothing reads it then. */
+typedef struct {
+  const float *color, *coverage, *albedo, *normal, *position;
+} RT_Frame;
+
 #define WF_CHUNK        256
 #define WF_HIT0_FIELDS  9      /* direction (3), t, triangle, u, v, pixel (y << 16 | x), sample                         */
 #define WF_HIT_FIELDS   5      /* index of the ray record (chunk * WF_CHUNK + slot), t, triangle, u, v                  */

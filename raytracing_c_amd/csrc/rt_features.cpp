@@ -127,7 +127,7 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   const size_t pixels = (size_t)width * height;
   HIP_TRY(S.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(S.planes.grow(pixels * RT_FEATURE_CHANNELS));
-  const FeaturePlanes f = split_feature_planes(S.planes, pixels);
+  const RT_Features f = split_feature_planes(S.planes, pixels);
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
   auto pass = [&](RT_Device_Scene *d) -> int {
     HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));

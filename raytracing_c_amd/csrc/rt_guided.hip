@@ -34,19 +34,18 @@ __global__ __launch_bounds__(GD_TX * GD_TY) void rt_guided_filter_kernel(int wid
                              albedo, out, image, nullptr);
 }
 
-extern "C" int rt_launch_guided_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
-                                     const float *normal, const float *position, void *c0, void *g0, void *g1, hipStream_t stream) {
-  hipLaunchKernelGGL(rt_guided_pack_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, demodulate, color, coverage,
-                     albedo, normal, position, (float4 *)c0, (float4 *)g0, (float4 *)g1);
+extern "C" int rt_launch_guided_pack(int n_pixels, int demodulate, RT_Frame frame, void *c0, void *g0, void *g1, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_guided_pack_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, demodulate, frame.color,
+                     frame.coverage, frame.albedo, frame.normal, frame.position, (float4 *)c0, (float4 *)g0, (float4 *)g1);
   return (int)hipGetLastError();
 }
 
 extern "C" int rt_launch_guided_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate,
-                                       const void *src, void *dst, const void *g0, const void *g1, const float *color,
-                                       const float *albedo, float *out, uint8_t *image, hipStream_t stream) {
+                                       const void *src, void *dst, const void *g0, const void *g1, RT_Frame frame, float *out,
+                                       uint8_t *image, hipStream_t stream) {
   const GuidedGrid G = guided_grid(width, height, step);
   hipLaunchKernelGGL(rt_guided_filter_kernel, dim3(G.blocks), dim3(GD_TX, GD_TY), 0, stream, width, height, step, G.phases_x,
                      G.phases_y, G.tiles_x, k_n, k_p, k_c, last, demodulate, (const float4 *)src, (float4 *)dst, (const float4 *)g0,
-                     (const float4 *)g1, color, albedo, out, image);
+                     (const float4 *)g1, frame.color, frame.albedo, out, image);
   return (int)hipGetLastError();
 }

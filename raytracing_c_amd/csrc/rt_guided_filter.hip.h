@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_math.h"
+#include "rt_device.h"
 
 #define GD_TX 32                  // pixels of a sub-lattice per workgroup tile: 32 x 8, one thread each
 #define GD_TY 8

@@ -11,7 +11,8 @@
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
 //   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter), temporal accumulation (the
-//                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline)
+//                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline);
+//                     a stage reads one RT_Frame (rt_device.h) and is launched in one place, which chooses its plain or variance / moments kernel
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -81,31 +82,26 @@ int rt_launch_refit(int len, int depth, int n_internal, const void *d_src, const
                     float *d_leaves, float *d_tris, unsigned char *d_populated, unsigned int *d_max_edge_bits, hipStream_t stream);
 // ... in rt_scene_refit.c: scene_refit's validation alone; source_of_slot (optional, triangles.len entries) receives the inverse map
 int rt_refit_check(Scene const *scene, Triangle_Slice src, i32 const *slot_of_source, i32 *source_of_slot);
-// ... in rt_guided.hip
-int rt_launch_guided_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
-                          const float *normal, const float *position, void *c0, void *g0, void *g1, hipStream_t stream);
+// ... in rt_guided.hip (RT_Frame, rt_device.h: the frame a post pass reads)
+int rt_launch_guided_pack(int n_pixels, int demodulate, RT_Frame frame, void *c0, void *g0, void *g1, hipStream_t stream);
 int rt_launch_guided_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate, const void *src,
-                            void *dst, const void *g0, const void *g1, const float *color, const float *albedo, float *out,
-                            uint8_t *image, hipStream_t stream);
+                            void *dst, const void *g0, const void *g1, RT_Frame frame, float *out, uint8_t *image, hipStream_t stream);
 // ... in rt_temporal.hip
-int rt_launch_temporal(const RT_TParams *P, const float *color, const float *coverage, const float *albedo, const float *normal,
-                       const float *position, const void *hist_in, void *hist_out, float *out, float *length, uint8_t *image,
-                       hipStream_t stream);
+int rt_launch_temporal(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out, float *length,
+                       uint8_t *image, hipStream_t stream);
 int rt_launch_temporal_pack(int n_pixels, const float *c, const float *len, const float *cov, const float *n, const float *w, void *hist,
                             hipStream_t stream);
 int rt_launch_temporal_unpack(int n_pixels, const void *hist, float *c, float *len, float *cov, float *n, float *w, hipStream_t stream);
 // ... in rt_variance.hip
-int rt_launch_temporal_moments(const RT_TParams *P, const float *color, const float *coverage, const float *albedo, const float *normal,
-                               const float *position, const void *hist_in, void *hist_out, float *out, float *length, uint8_t *image,
-                               const void *mom_in, void *mom_out, hipStream_t stream);
+int rt_launch_temporal_moments(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out, float *length,
+                               uint8_t *image, const void *mom_in, void *mom_out, hipStream_t stream);
 int rt_launch_variance(int width, int height, float k_n, float k_p, const void *hist, const void *mom, float *variance,
                        hipStream_t stream);
-int rt_launch_variance_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
-                            const float *normal, const float *position, const float *variance, void *c0, void *g0, void *g1,
+int rt_launch_variance_pack(int n_pixels, int demodulate, RT_Frame frame, const float *variance, void *c0, void *g0, void *g1,
                             hipStream_t stream);
 int rt_launch_variance_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate,
-                              const void *src, void *dst, const void *g0, const void *g1, const float *color, const float *albedo,
-                              float *out, uint8_t *image, float *var_out, hipStream_t stream);
+                              const void *src, void *dst, const void *g0, const void *g1, RT_Frame frame, float *out, uint8_t *image,
+                              float *var_out, hipStream_t stream);
 int rt_launch_moments_pack(int n_pixels, const float *planar, void *mom, hipStream_t stream);
 int rt_launch_moments_unpack(int n_pixels, const void *mom, float *planar, hipStream_t stream);
 }
@@ -256,18 +252,20 @@ struct FeatureState {
   DevMem<float>              planes;          // coverage [pixels], then albedo, normal, position [pixels][3] each
 };
 
-// The four planes of such a buffer.
-struct FeaturePlanes {
-  float *coverage, *albedo, *normal, *position;
-};
-static inline FeaturePlanes split_feature_planes(float *planes, size_t pixels) {
+// The four planes of such a buffer, to write (the resolve) ...
+static inline RT_Features split_feature_planes(float *planes, size_t pixels) {
   return {planes, planes + pixels, planes + pixels * 4, planes + pixels * 7};
+}
+// ... and, with a colour, as the frame the post passes read (RT_Frame, rt_device.h)
+static inline RT_Frame device_frame(const float *color, RT_Features const &planes) {
+  return {color, planes.coverage, planes.albedo, planes.normal, planes.position};
 }
 
 // Guided denoiser (rt_post.cpp): the device staging of the host-level calls, kept between calls, given back with the device slot
-// (release_staging).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes: it uses work and out.
+// (release_staging).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes (one RT_Frame): it uses
+// work and out.
 struct GuidedState {
-  DevMem<float>   in;                         // rt_guided_denoise_host: color [pixels][3], then planes as FeatureState's
+  DevMem<float>   in;                         // the host-level calls' RT_Frame: color [pixels][3], then planes as FeatureState's
   DevMem<float>   out;                        // [pixels][3]
   DevMem<uint8_t> image;                      // [pixels][3]
   DevMem<uint8_t> work;                       // rt_guided_work_bytes()
@@ -275,13 +273,14 @@ struct GuidedState {
   DevMem<float>   variance_out;               // ... and out (grown by that call alone)
 };
 
-// Temporal accumulation (rt_post.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame, a history
-// as 11 planar f32 (staged in, later staged out), the two histories as records -- and the f32 output of rt_render_temporal, kept
-// between calls; and the histories hosts keep (rt_history_create), whose device memory is part of this slot's staging: giving the
-// staging back (release_temporal_state) empties every one of them, so that none points at memory of a slot that was torn down.
+// Temporal accumulation (rt_post.cpp): the device staging of rt_temporal_accumulate_host -- the 13 planar f32 of the frame (one
+// RT_Frame), a history as 11 planar f32 (staged in, later staged out: rt_post.cpp's HISTORY_PLANES is their one description), the
+// two histories as records -- and the f32 output of rt_render_temporal, kept between calls; and the histories hosts keep
+// (rt_history_create), whose device memory is part of this slot's staging: giving the staging back (release_temporal_state) empties
+// every one of them (RT_History::release), so that none points at memory of a slot that was torn down.
 struct TemporalState {
-  DevMem<float>   in;                         // color [pixels][3], then planes as FeatureState's
-  DevMem<float>   planar;                     // a history as planes: colour [pixels][3], length, coverage [pixels], N, W [pixels][3]
+  DevMem<float>   in;                         // the host-level calls' RT_Frame: color [pixels][3], then planes as FeatureState's
+  DevMem<float>   planar;                     // a history as planes, HISTORY_PLANES: colour [pixels][3], length, coverage [pixels], N, W [pixels][3]
   DevMem<uint8_t> hist[2];                    // rt_temporal_history_bytes() each: read, written
   DevMem<float>   out;                        // [pixels][3]
   DevMem<float>   length;                     // [pixels]
@@ -336,6 +335,14 @@ struct RT_History {
   DevMem<uint8_t> mom[2];                     // the moments of the two histories (rt_render_svgf allocates them), ping-ponged with buf
   bool            moments_valid = false;      // mom[cur] holds the moments of buf[cur]: the last frame was rt_render_svgf's
   Camera          camera;
+  // Gives the device memory back: the history is empty, as after rt_history_reset().  Slot 0's GPU current.
+  void release() {
+    buf[0].reset();
+    buf[1].reset();
+    mom[0].reset();
+    mom[1].reset();
+    valid = moments_valid = false;
+  }
 };
 #pragma GCC visibility pop
 

@@ -4,6 +4,11 @@
 // estimated from them, and the filter steered by that variance.  Each on the device level (device pointers, launches on the caller's stream), on the host level (host arrays
 // through library-owned staging) and behind a frame (rt_render_denoised, rt_render_temporal, rt_render_svgf: one pipeline -- frame,
 // feature pass, optionally the accumulation, optionally the filter -- in ONE scene-checked call).  Nothing here computes a pixel on the CPU.
+//
+// The frame a stage reads is ONE value (RT_Frame, rt_device.h), built by whoever has the pointers: the extern "C" entry points
+// (frame_of), upload_host_frame and render_post from the staging.  What a stage may write, and what its variance / moments form adds,
+// is one struct per stage (FilterIO, AccumulateIO; absent = NULL).  Every stage is launched in ONE place (launch_pack, launch_filter,
+// launch_accumulate), which chooses the plain kernel or its variance / moments form by whether the optional pointer is given.
 
 #include "rt_host.h"
 
@@ -16,6 +21,28 @@ static_assert(sizeof(RT_Variance_Params) == 8, "two sigmas");
 #define RT_TEMPORAL_MOMENTS_PER_PIXEL 16   // (m1, m2, 0, 0): one float4
 #define RT_TEMPORAL_MAX_HISTORY (1 << 20)
 #define RT_HOST_FRAME_F32 (3 + RT_FEATURE_CHANNELS)   // a staged host frame, f32 per pixel: the colour, then the planes as FeatureState keeps them
+
+// What the filter may write, and what its variance-guided form adds (device pointers; the host's in the host-level calls).
+// variance_in given: THE VARIANCE-GUIDED FILTER -- the colour records carry the variance, k_c is not scaled per iteration, and
+// variance_out (optional) receives the last v.
+struct FilterIO { float *out; uint8_t *image; const float *variance_in; float *variance_out; };   // [h][w][3], [h][w][3], [h][w], [h][w]
+
+// What the accumulation may write besides the new history, and what its moments form adds.  moments_out given: THE MOMENTS in the
+// same launch (moments_in exactly when there is a history to read; records on the device, f32[h][w][2] in the host-level calls), and
+// when `variance` is wanted THE VARIANCE behind it, with vp.
+struct AccumulateIO {
+  float *out, *length; uint8_t *image;                                             // [h][w][3], [h][w], [h][w][3]
+  const void *moments_in; void *moments_out; float *variance; RT_Variance_Params const *vp;
+};
+
+// A history as a host has it (RT_History_Planes) and as TemporalState::planar stages it: the planes in the order
+// rt_temporal_pack_history / rt_temporal_unpack_history take them -- name, f32 per pixel, where it begins in `planar` (in pixels).
+struct HistoryPlane { const char *name; int floats, offset; f32 *RT_History_Planes::*member; };
+static constexpr HistoryPlane HISTORY_PLANES[5] = {
+    {"color", 3, 0, &RT_History_Planes::color},       {"length", 1, 3, &RT_History_Planes::length},
+    {"coverage", 1, 4, &RT_History_Planes::coverage}, {"normal", 3, 5, &RT_History_Planes::normal},
+    {"position", 3, 8, &RT_History_Planes::position}};
+#define RT_HISTORY_PLANAR_F32 (HISTORY_PLANES[4].offset + HISTORY_PLANES[4].floats)   // 11: TemporalState::planar, f32 per pixel
 
 // ---------------------------------------------------------------------------------
 // what can be checked without the device.  `who` prefixes the messages.
@@ -53,14 +80,13 @@ static int check_variance(const char *who, RT_Variance_Params const *v) {
   return 0;
 }
 
-// A frame on the device: the colour and the four planes (the albedo only where `demodulate` reads it).
-static int check_device_frame(const char *who, void const *d_color, void const *d_coverage, void const *d_albedo, void const *d_normal,
-                              void const *d_position, int demodulate) {
-  if (!d_color) return rt_fail("%s: d_color is NULL", who);
-  if (!d_coverage) return rt_fail("%s: d_coverage is NULL", who);
-  if (!d_albedo && demodulate) return rt_fail("%s: d_albedo is NULL and demodulate is set", who);
-  if (!d_normal) return rt_fail("%s: d_normal is NULL", who);
-  if (!d_position) return rt_fail("%s: d_position is NULL", who);
+// A frame on the device (the albedo only where `demodulate` reads it).
+static int check_device_frame(const char *who, RT_Frame const &f, int demodulate) {
+  if (!f.color) return rt_fail("%s: d_color is NULL", who);
+  if (!f.coverage) return rt_fail("%s: d_coverage is NULL", who);
+  if (!f.albedo && demodulate) return rt_fail("%s: d_albedo is NULL and demodulate is set", who);
+  if (!f.normal) return rt_fail("%s: d_normal is NULL", who);
+  if (!f.position) return rt_fail("%s: d_position is NULL", who);
   return 0;
 }
 
@@ -75,66 +101,99 @@ static int check_host_frame(const char *who, f32 const *color, RT_Features const
   return 0;
 }
 
-// The calls that answer with a size or an object have ONE message for a size check_image_size() refuses.
+// An output an entry point offers, by the name its message has for it; name NULL: this form of the entry point does not offer it.
+struct Output { const char *name; const void *p; };
+// Refuses a call that wants none of them: "a, b and c are NULL".
+template <int N> static int check_wanted(const char *who, const Output (&outs)[N]) {
+  int offered = 0, k = 0;
+  for (const Output &o : outs) {
+    if (o.name && o.p) return 0;
+    offered += o.name != nullptr;
+  }
+  char names[128] = "";
+  for (const Output &o : outs)
+    if (o.name) snprintf(names + strlen(names), sizeof names - strlen(names), "%s%s", ++k == 1 ? "" : k == offered ? " and " : ", ", o.name);
+  return rt_fail("%s: no output is wanted (%s are NULL)", who, names);
+}
+
+// d_<what>_in (optional) and d_<what>_out, `bytes` each, must lie apart: a pixel reads records that other pixels write.
+static int check_apart(const char *who, const char *what, const void *in, const void *out, uintptr_t bytes) {
+  if (!in) return 0;
+  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+  if ((a <= b ? b - a : a - b) < bytes) return rt_fail("%s: d_%s_in and d_%s_out overlap (the reads are gathers)", who, what, what);
+  return 0;
+}
+
+// The calls that answer with a size or an object have ONE message for a size check_image_size() refuses.  (check_image_size has
+// two, "is invalid" and "is too large", which every other call here reports: the one text cannot come out of it.)
 static bool size_refused(const char *who, i32 width, i32 height) {
   if (width > 0 && height > 0 && (int64_t)width * height <= RT_MAX_PIXELS) return false;
   rt_fail("%s: image size %dx%d is invalid", who, width, height);
   return true;
 }
-
-extern "C" i64 rt_guided_work_bytes(i32 width, i32 height) {
-  return size_refused("rt_guided_work_bytes", width, height) ? -1 : (i64)width * height * RT_GUIDED_WORK_PER_PIXEL;
+static i64 bytes_of(const char *who, i32 width, i32 height, int per_pixel) {
+  return size_refused(who, width, height) ? -1 : (i64)width * height * per_pixel;
 }
 
-extern "C" i64 rt_temporal_history_bytes(i32 width, i32 height) {
-  return size_refused("rt_temporal_history_bytes", width, height) ? -1 : (i64)width * height * RT_TEMPORAL_HISTORY_PER_PIXEL;
-}
-
-extern "C" i64 rt_guided_variance_work_bytes(i32 width, i32 height) {
-  return size_refused("rt_guided_variance_work_bytes", width, height) ? -1 : (i64)width * height * RT_GUIDED_WORK_PER_PIXEL;
-}
-
-extern "C" i64 rt_temporal_moments_bytes(i32 width, i32 height) {
-  return size_refused("rt_temporal_moments_bytes", width, height) ? -1 : (i64)width * height * RT_TEMPORAL_MOMENTS_PER_PIXEL;
-}
+extern "C" i64 rt_guided_work_bytes(i32 w, i32 h) { return bytes_of("rt_guided_work_bytes", w, h, RT_GUIDED_WORK_PER_PIXEL); }
+extern "C" i64 rt_temporal_history_bytes(i32 w, i32 h) { return bytes_of("rt_temporal_history_bytes", w, h, RT_TEMPORAL_HISTORY_PER_PIXEL); }
+extern "C" i64 rt_guided_variance_work_bytes(i32 w, i32 h) { return bytes_of("rt_guided_variance_work_bytes", w, h, RT_GUIDED_WORK_PER_PIXEL); }
+extern "C" i64 rt_temporal_moments_bytes(i32 w, i32 h) { return bytes_of("rt_temporal_moments_bytes", w, h, RT_TEMPORAL_MOMENTS_PER_PIXEL); }
 
 // ---------------------------------------------------------------------------------
-// the stages
+// the stages.  Every pointer is on the current device; the launches go on `stream`.
 
-// Enqueues the pack launch and g->iterations filter launches on `stream`.  Every pointer is on the current device; every input
-// is in d_work before d_out / d_image are written (the last launch reads a pixel's colour and albedo only to write that pixel).
-// d_variance given: THE VARIANCE-GUIDED FILTER -- the colour records carry the variance, k_c is not scaled per iteration, and
-// d_variance_out (optional) receives the last v.
-static int enqueue_guided(i32 width, i32 height, RT_Guided_Params const *g, void const *d_color, void const *d_coverage,
-                          void const *d_albedo, void const *d_normal, void const *d_position, void *d_out, void *d_image, void *d_work,
-                          hipStream_t stream, void const *d_variance = nullptr, void *d_variance_out = nullptr) {
-  const size_t pixels = (size_t)width * height;
-  uint8_t *w = (uint8_t *)d_work;
-  void *buf[2] = {w, w + pixels * 16}, *g0 = w + pixels * 32, *g1 = w + pixels * 48;
-  int rc = d_variance ? rt_launch_variance_pack((int)pixels, g->demodulate, (const float *)d_color, (const float *)d_coverage,
-                                                (const float *)d_albedo, (const float *)d_normal, (const float *)d_position,
-                                                (const float *)d_variance, buf[0], g0, g1, stream)
-                      : rt_launch_guided_pack((int)pixels, g->demodulate, (const float *)d_color, (const float *)d_coverage,
-                                              (const float *)d_albedo, (const float *)d_normal, (const float *)d_position, buf[0], g0, g1,
-                                              stream);
-  if (rc != 0) return rt_fail("guided pack kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+// The filter's work area (rt_guided_work_bytes): the two colour buffers the iterations ping-pong between, then the two guide planes.
+struct GuidedWork { void *buf[2], *g0, *g1; };
+
+// 0, or the refusal of a launch whose launcher returned the HIP error rc: `message` is "... kernel launch failed: %s".
+static int launched(int rc, const char *message) { return rc == 0 ? 0 : rt_fail(message, hipGetErrorString((hipError_t)rc)); }
+
+// THE VARIANT OF A STAGE IS CHOSEN HERE, in its one launch: the plain kernel (rt_guided.hip, rt_temporal.hip) or its variance /
+// moments form (rt_variance.hip), by whether the optional input or output is given.
+static int launch_pack(size_t pixels, int demodulate, RT_Frame const &f, const float *variance, GuidedWork const &w, hipStream_t stream) {
+  return launched(variance ? rt_launch_variance_pack((int)pixels, demodulate, f, variance, w.buf[0], w.g0, w.g1, stream)
+                           : rt_launch_guided_pack((int)pixels, demodulate, f, w.buf[0], w.g0, w.g1, stream),
+                  "guided pack kernel launch failed: %s");
+}
+
+// Iteration i of g->iterations, step 1 << i, from w.buf[i & 1] into the other; the last one writes what `o` wants.
+static int launch_filter(i32 width, i32 height, RT_Guided_Params const *g, int i, GuidedWork const &w, RT_Frame const &f,
+                         FilterIO const &o, hipStream_t stream) {
   const float k_c = 1.0f / (g->sigma_color * g->sigma_color), k_n = 1.0f / (g->sigma_normal * g->sigma_normal),
               k_p = 1.0f / (g->sigma_position * g->sigma_position);
-  for (int i = 0; i < g->iterations; i++) {
-    const int last = i == g->iterations - 1;
-    if (d_variance) {
-      rc = rt_launch_variance_filter(width, height, 1 << i, k_n, k_p, k_c, last, g->demodulate, buf[i & 1], buf[(i & 1) ^ 1], g0, g1,
-                                     (const float *)d_color, (const float *)d_albedo, last ? (float *)d_out : nullptr,
-                                     last ? (uint8_t *)d_image : nullptr, last ? (float *)d_variance_out : nullptr, stream);
-      if (rc != 0) return rt_fail("variance-guided filter kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-      continue;
-    }
-    const float kc_i = k_c * (float)(1u << (2 * i));            // the colour sigma halves every iteration
-    rc = rt_launch_guided_filter(width, height, 1 << i, k_n, k_p, kc_i, last, g->demodulate, buf[i & 1], buf[(i & 1) ^ 1], g0, g1,
-                                 (const float *)d_color, (const float *)d_albedo, last ? (float *)d_out : nullptr,
-                                 last ? (uint8_t *)d_image : nullptr, stream);
-    if (rc != 0) return rt_fail("guided filter kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
+  const bool variance_guided = o.variance_in != nullptr;
+  const float kc_i = variance_guided ? k_c : k_c * (float)(1u << (2 * i));     // the plain filter's colour sigma halves every iteration
+  const int last = i == g->iterations - 1;
+  void *const src = w.buf[i & 1], *const dst = w.buf[(i & 1) ^ 1];
+  const FilterIO lo = last ? o : FilterIO{};
+  if (variance_guided)
+    return launched(rt_launch_variance_filter(width, height, 1 << i, k_n, k_p, kc_i, last, g->demodulate, src, dst, w.g0, w.g1, f, lo.out,
+                                              lo.image, lo.variance_out, stream),
+                    "variance-guided filter kernel launch failed: %s");
+  return launched(rt_launch_guided_filter(width, height, 1 << i, k_n, k_p, kc_i, last, g->demodulate, src, dst, w.g0, w.g1, f, lo.out,
+                                          lo.image, stream),
+                  "guided filter kernel launch failed: %s");
+}
+
+static int launch_accumulate(RT_TParams const &P, RT_Frame const &f, const void *history_in, void *history_out, AccumulateIO const &a,
+                             hipStream_t stream) {
+  if (a.moments_out)
+    return launched(rt_launch_temporal_moments(&P, f, history_in, history_out, a.out, a.length, a.image, a.moments_in, a.moments_out, stream),
+                    "temporal moments kernel launch failed: %s");
+  return launched(rt_launch_temporal(&P, f, history_in, history_out, a.out, a.length, a.image, stream), "temporal kernel launch failed: %s");
+}
+
+// Enqueues the pack launch and g->iterations filter launches.  Every input is in d_work before o.out / o.image are written (the last
+// launch reads a pixel's colour and albedo only to write that pixel).
+static int enqueue_guided(i32 width, i32 height, RT_Guided_Params const *g, RT_Frame const &f, FilterIO const &o, void *d_work,
+                          hipStream_t stream) {
+  const size_t pixels = (size_t)width * height;
+  uint8_t *b = (uint8_t *)d_work;
+  const GuidedWork w = {{b, b + pixels * 16}, b + pixels * 32, b + pixels * 48};
+  if (launch_pack(pixels, g->demodulate, f, o.variance_in, w, stream) != 0) return -1;
+  for (int i = 0; i < g->iterations; i++)
+    if (launch_filter(width, height, g, i, w, f, o, stream) != 0) return -1;
   return 0;
 }
 
@@ -146,14 +205,10 @@ static void temporal_camera(RT_TCamera *c, Camera const *cam) {
   c->focal_length = cam->focal_length;
 }
 
-// Enqueues the launch on `stream`.  Every pointer is on the current device; prev is read only when d_history_in is given.
-// d_moments_out given: THE MOMENTS in the same launch (d_moments_in exactly when d_history_in), and when d_variance is wanted THE
-// VARIANCE behind it, which reads d_history_out and d_moments_out.
-static int enqueue_temporal(i32 width, i32 height, RT_Temporal_Params const *t, Camera const *cam, Camera const *prev,
-                            void const *d_color, void const *d_coverage, void const *d_albedo, void const *d_normal,
-                            void const *d_position, void const *d_history_in, void *d_history_out, void *d_out, void *d_length,
-                            void *d_image, hipStream_t stream, RT_Variance_Params const *vp = nullptr,
-                            void const *d_moments_in = nullptr, void *d_moments_out = nullptr, void *d_variance = nullptr) {
+// Enqueues the accumulation, and behind its moments form, when a.variance is wanted, the variance launch, which reads d_history_out
+// and a.moments_out.  prev is read only when d_history_in is given.
+static int enqueue_temporal(i32 width, i32 height, RT_Temporal_Params const *t, Camera const *cam, Camera const *prev, RT_Frame const &f,
+                            const void *d_history_in, void *d_history_out, AccumulateIO const &a, hipStream_t stream) {
   RT_TParams P;
   memset(&P, 0, sizeof P);
   temporal_camera(&P.cur, cam);
@@ -169,111 +224,89 @@ static int enqueue_temporal(i32 width, i32 height, RT_Temporal_Params const *t, 
   P.max_history = (float)t->max_history;
   P.demodulate = t->demodulate;
   P.tiles_x = (width + 31) / 32;
-  if (!d_moments_out) {
-    int rc = rt_launch_temporal(&P, (const float *)d_color, (const float *)d_coverage, (const float *)d_albedo, (const float *)d_normal,
-                                (const float *)d_position, d_history_in, d_history_out, (float *)d_out, (float *)d_length,
-                                (uint8_t *)d_image, stream);
-    if (rc != 0) return rt_fail("temporal kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-  }
-  int rc = rt_launch_temporal_moments(&P, (const float *)d_color, (const float *)d_coverage, (const float *)d_albedo,
-                                      (const float *)d_normal, (const float *)d_position, d_history_in, d_history_out, (float *)d_out,
-                                      (float *)d_length, (uint8_t *)d_image, d_moments_in, d_moments_out, stream);
-  if (rc != 0) return rt_fail("temporal moments kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-  if (!d_variance) return 0;
-  const float k_n = 1.0f / (vp->sigma_normal * vp->sigma_normal), k_p = 1.0f / (vp->sigma_position * vp->sigma_position);
-  rc = rt_launch_variance(width, height, k_n, k_p, d_history_out, d_moments_out, (float *)d_variance, stream);
-  if (rc != 0) return rt_fail("variance kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return 0;
+  if (launch_accumulate(P, f, d_history_in, d_history_out, a, stream) != 0) return -1;
+  if (!a.moments_out || !a.variance) return 0;
+  const float k_n = 1.0f / (a.vp->sigma_normal * a.vp->sigma_normal), k_p = 1.0f / (a.vp->sigma_position * a.vp->sigma_position);
+  return launched(rt_launch_variance(width, height, k_n, k_p, d_history_out, a.moments_out, a.variance, stream),
+                  "variance kernel launch failed: %s");
 }
 
 // ---- device level -------------------------------------------------------------------------------------------------------------
 // (everything that can be checked without the device is checked before it is touched)
 
-// rt_guided_denoise and rt_guided_denoise_variance (with_variance: d_variance is required, d_variance_out optional)
-static int guided_device(const char *who, bool with_variance, i32 width, i32 height, RT_Guided_Params const *params, void const *d_color,
-                         void const *d_coverage, void const *d_albedo, void const *d_normal, void const *d_position, void *d_out,
-                         void *d_image, void *d_work, void *stream, void const *d_variance, void *d_variance_out) {
+// The frame of an entry point's five device pointers: the only casts.
+static RT_Frame frame_of(void const *d_color, void const *d_coverage, void const *d_albedo, void const *d_normal,
+                                void const *d_position) {
+  return {(const float *)d_color, (const float *)d_coverage, (const float *)d_albedo, (const float *)d_normal, (const float *)d_position};
+}
+
+static int device_ready() {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  return ensure_device(D);
+}
+
+// rt_guided_denoise and rt_guided_denoise_variance (with_variance: o.variance_in is required, o.variance_out optional)
+static int guided_device(const char *who, bool with_variance, i32 width, i32 height, RT_Guided_Params const *params, RT_Frame const &f,
+                         FilterIO const &o, void *d_work, hipStream_t stream) {
   if (check_guided(who, width, height, params) != 0) return -1;
-  if (check_device_frame(who, d_color, d_coverage, d_albedo, d_normal, d_position, params->demodulate) != 0) return -1;
-  if (with_variance) {
-    if (!d_variance) return rt_fail("%s: d_variance is NULL", who);
-    if (!d_out && !d_image && !d_variance_out)
-      return rt_fail("%s: no output is wanted (d_out, d_image and d_variance_out are NULL)", who);
-  } else if (!d_out && !d_image) return rt_fail("%s: no output is wanted (d_out and d_image are NULL)", who);
+  if (check_device_frame(who, f, params->demodulate) != 0) return -1;
+  if (with_variance && !o.variance_in) return rt_fail("%s: d_variance is NULL", who);
+  const Output outs[] = {{"d_out", o.out}, {"d_image", o.image}, {with_variance ? "d_variance_out" : nullptr, o.variance_out}};
+  if (check_wanted(who, outs) != 0) return -1;
   if (!d_work) return rt_fail("%s: d_work is NULL", who);
   if ((uintptr_t)d_work & 15) return rt_fail("%s: d_work must be 16-byte aligned", who);
-  Device &D = dev0();
-  {
-    std::lock_guard<std::mutex> lock(D.mutex);
-    if (ensure_device(D) != 0) return -1;
-  }
-  return enqueue_guided(width, height, params, d_color, d_coverage, d_albedo, d_normal, d_position, d_out, d_image, d_work,
-                        (hipStream_t)stream, d_variance, d_variance_out);
+  if (device_ready() != 0) return -1;
+  return enqueue_guided(width, height, params, f, o, d_work, stream);
 }
 
 extern "C" int rt_guided_denoise(i32 width, i32 height, RT_Guided_Params const *params, void const *d_color, void const *d_coverage,
                                  void const *d_albedo, void const *d_normal, void const *d_position, void *d_out, void *d_image,
                                  void *d_work, void *stream) {
-  return guided_device("rt_guided_denoise", false, width, height, params, d_color, d_coverage, d_albedo, d_normal, d_position, d_out,
-                       d_image, d_work, stream, nullptr, nullptr);
+  return guided_device("rt_guided_denoise", false, width, height, params, frame_of(d_color, d_coverage, d_albedo, d_normal, d_position),
+                       {(float *)d_out, (uint8_t *)d_image}, d_work, (hipStream_t)stream);
 }
 
 extern "C" int rt_guided_denoise_variance(i32 width, i32 height, RT_Guided_Params const *params, void const *d_color,
                                           void const *d_coverage, void const *d_albedo, void const *d_normal, void const *d_position,
                                           void *d_out, void *d_image, void *d_work, void *stream, void const *d_variance,
                                           void *d_variance_out) {
-  return guided_device("rt_guided_denoise_variance", true, width, height, params, d_color, d_coverage, d_albedo, d_normal, d_position,
-                       d_out, d_image, d_work, stream, d_variance, d_variance_out);
+  return guided_device("rt_guided_denoise_variance", true, width, height, params, frame_of(d_color, d_coverage, d_albedo, d_normal, d_position),
+                       {(float *)d_out, (uint8_t *)d_image, (const float *)d_variance, (float *)d_variance_out}, d_work, (hipStream_t)stream);
 }
 
-// rt_temporal_accumulate and rt_temporal_accumulate_moments (with_moments: d_moments_out is required, d_moments_in goes with
-// d_history_in, vp is required when d_variance is wanted)
+// rt_temporal_accumulate and rt_temporal_accumulate_moments (with_moments: a.moments_out is required, a.moments_in goes with
+// d_history_in, a.vp is required when a.variance is wanted)
 static int temporal_device(const char *who, bool with_moments, i32 width, i32 height, RT_Temporal_Params const *params,
-                           Camera const *camera, Camera const *previous_camera, void const *d_color, void const *d_coverage,
-                           void const *d_albedo, void const *d_normal, void const *d_position, void const *d_history_in,
-                           void *d_history_out, void *d_out, void *d_length, void *d_image, RT_Variance_Params const *vp,
-                           void const *d_moments_in, void *d_moments_out, void *d_variance, void *stream) {
+                           Camera const *camera, Camera const *previous_camera, RT_Frame const &f, void const *d_history_in,
+                           void *d_history_out, AccumulateIO const &a, hipStream_t stream) {
   if (check_temporal(who, width, height, params) != 0) return -1;
-  if (with_moments && (vp || d_variance) && check_variance(who, vp) != 0) return -1;
+  if (with_moments && (a.vp || a.variance) && check_variance(who, a.vp) != 0) return -1;
   if (!camera) return rt_fail("%s: camera is NULL", who);
   if (d_history_in && !previous_camera) return rt_fail("%s: previous_camera is NULL and a history is given", who);
-  if (check_device_frame(who, d_color, d_coverage, d_albedo, d_normal, d_position, params->demodulate) != 0) return -1;
+  if (check_device_frame(who, f, params->demodulate) != 0) return -1;
   if (!d_history_out) return rt_fail("%s: d_history_out is NULL", who);
   if (((uintptr_t)d_history_out | (uintptr_t)d_history_in) & 15) return rt_fail("%s: the histories must be 16-byte aligned", who);
-  if (d_history_in) {
-    const uintptr_t a = (uintptr_t)d_history_in, b = (uintptr_t)d_history_out;
-    const uintptr_t bytes = (uintptr_t)width * height * RT_TEMPORAL_HISTORY_PER_PIXEL;
-    if ((a <= b ? b - a : a - b) < bytes) return rt_fail("%s: d_history_in and d_history_out overlap (the reads are gathers)", who);
-  }
+  const uintptr_t pixels = (uintptr_t)width * height;
+  if (check_apart(who, "history", d_history_in, d_history_out, pixels * RT_TEMPORAL_HISTORY_PER_PIXEL) != 0) return -1;
   if (with_moments) {
-    if (!d_moments_out) return rt_fail("%s: d_moments_out is NULL", who);
-    if (d_history_in && !d_moments_in) return rt_fail("%s: a history is given without its moments (d_moments_in is NULL)", who);
-    if (!d_history_in && d_moments_in) return rt_fail("%s: moments are given without their history (d_history_in is NULL)", who);
-    if (((uintptr_t)d_moments_out | (uintptr_t)d_moments_in) & 15) return rt_fail("%s: the moments must be 16-byte aligned", who);
-    if (d_moments_in) {
-      const uintptr_t a = (uintptr_t)d_moments_in, b = (uintptr_t)d_moments_out;
-      const uintptr_t bytes = (uintptr_t)width * height * RT_TEMPORAL_MOMENTS_PER_PIXEL;
-      if ((a <= b ? b - a : a - b) < bytes) return rt_fail("%s: d_moments_in and d_moments_out overlap (the reads are gathers)", who);
-    }
+    if (!a.moments_out) return rt_fail("%s: d_moments_out is NULL", who);
+    if (d_history_in && !a.moments_in) return rt_fail("%s: a history is given without its moments (d_moments_in is NULL)", who);
+    if (!d_history_in && a.moments_in) return rt_fail("%s: moments are given without their history (d_history_in is NULL)", who);
+    if (((uintptr_t)a.moments_out | (uintptr_t)a.moments_in) & 15) return rt_fail("%s: the moments must be 16-byte aligned", who);
+    if (check_apart(who, "moments", a.moments_in, a.moments_out, pixels * RT_TEMPORAL_MOMENTS_PER_PIXEL) != 0) return -1;
   }
-  Device &D = dev0();
-  {
-    std::lock_guard<std::mutex> lock(D.mutex);
-    if (ensure_device(D) != 0) return -1;
-  }
-  return enqueue_temporal(width, height, params, camera, previous_camera, d_color, d_coverage, d_albedo, d_normal, d_position,
-                          d_history_in, d_history_out, d_out, d_length, d_image, (hipStream_t)stream, vp, d_moments_in, d_moments_out,
-                          d_variance);
+  if (device_ready() != 0) return -1;
+  return enqueue_temporal(width, height, params, camera, previous_camera, f, d_history_in, d_history_out, a, stream);
 }
 
 extern "C" int rt_temporal_accumulate(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
                                       Camera const *previous_camera, void const *d_color, void const *d_coverage, void const *d_albedo,
                                       void const *d_normal, void const *d_position, void const *d_history_in, void *d_history_out,
                                       void *d_out, void *d_length, void *d_image, void *stream) {
-  return temporal_device("rt_temporal_accumulate", false, width, height, params, camera, previous_camera, d_color, d_coverage, d_albedo,
-                         d_normal, d_position, d_history_in, d_history_out, d_out, d_length, d_image, nullptr, nullptr, nullptr, nullptr,
-                         stream);
+  return temporal_device("rt_temporal_accumulate", false, width, height, params, camera, previous_camera,
+                         frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out,
+                         {(float *)d_out, (float *)d_length, (uint8_t *)d_image}, (hipStream_t)stream);
 }
 
 extern "C" int rt_temporal_accumulate_moments(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
@@ -282,37 +315,38 @@ extern "C" int rt_temporal_accumulate_moments(i32 width, i32 height, RT_Temporal
                                               void const *d_history_in, void *d_history_out, void *d_out, void *d_length, void *d_image,
                                               RT_Variance_Params const *vp, void const *d_moments_in, void *d_moments_out,
                                               void *d_variance, void *stream) {
-  return temporal_device("rt_temporal_accumulate_moments", true, width, height, params, camera, previous_camera, d_color, d_coverage,
-                         d_albedo, d_normal, d_position, d_history_in, d_history_out, d_out, d_length, d_image, vp, d_moments_in,
-                         d_moments_out, d_variance, stream);
+  const AccumulateIO a = {(float *)d_out, (float *)d_length, (uint8_t *)d_image, d_moments_in, d_moments_out, (float *)d_variance, vp};
+  return temporal_device("rt_temporal_accumulate_moments", true, width, height, params, camera, previous_camera,
+                         frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out, a, (hipStream_t)stream);
 }
 
 // ---- host level ---------------------------------------------------------------------------------------------------------------
 // The host-level calls run on the NULL stream: it does not wait for the lane streams of frames in flight.
 
-// Copies a host frame into `in` (RT_HOST_FRAME_F32 f32 per pixel): the colour at `in` itself, behind it the planes, *d; d->albedo
-// is NULL when the host gave none.
-static int upload_host_frame(float *in, size_t pixels, f32 const *color, RT_Features const *planes, FeaturePlanes *d) {
+// Copies a host frame into `in` (RT_HOST_FRAME_F32 f32 per pixel): the colour at `in` itself, behind it the planes.  *f is the frame
+// on the device; f->albedo is NULL when the host gave none.
+static int upload_host_frame(float *in, size_t pixels, f32 const *color, RT_Features const *planes, RT_Frame *f) {
   const size_t f3 = pixels * 3 * sizeof(float), f1 = pixels * sizeof(float);
-  *d = split_feature_planes(in + pixels * 3, pixels);
+  RT_Features d = split_feature_planes(in + pixels * 3, pixels);
   HIP_TRY(hipMemcpy(in, color, f3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d->coverage, planes->coverage, f1, hipMemcpyHostToDevice));
-  if (planes->albedo) HIP_TRY(hipMemcpy(d->albedo, planes->albedo, f3, hipMemcpyHostToDevice));
-  else d->albedo = nullptr;
-  HIP_TRY(hipMemcpy(d->normal, planes->normal, f3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d->position, planes->position, f3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.coverage, planes->coverage, f1, hipMemcpyHostToDevice));
+  if (planes->albedo) HIP_TRY(hipMemcpy(d.albedo, planes->albedo, f3, hipMemcpyHostToDevice));
+  else d.albedo = nullptr;
+  HIP_TRY(hipMemcpy(d.normal, planes->normal, f3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.position, planes->position, f3, hipMemcpyHostToDevice));
+  *f = device_frame(in, d);
   return 0;
 }
 
-// rt_guided_denoise_host and rt_guided_denoise_variance_host (with_variance: variance is required, variance_out optional)
+// rt_guided_denoise_host and rt_guided_denoise_variance_host (with_variance: h.variance_in is required, h.variance_out optional);
+// h holds the host's pointers
 static int guided_host(const char *who, bool with_variance, i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
-                       RT_Features const *planes, f32 *out, u8 *image, f32 const *variance, f32 *variance_out) {
+                       RT_Features const *planes, FilterIO const &h) {
   if (check_guided(who, width, height, params) != 0) return -1;
   if (check_host_frame(who, color, planes, params->demodulate) != 0) return -1;
-  if (with_variance) {
-    if (!variance) return rt_fail("%s: variance is NULL", who);
-    if (!out && !image && !variance_out) return rt_fail("%s: no output is wanted (out, image and variance_out are NULL)", who);
-  } else if (!out && !image) return rt_fail("%s: no output is wanted (out and image are NULL)", who);
+  if (with_variance && !h.variance_in) return rt_fail("%s: variance is NULL", who);
+  const Output outs[] = {{"out", h.out}, {"image", h.image}, {with_variance ? "variance_out" : nullptr, h.variance_out}};
+  if (check_wanted(who, outs) != 0) return -1;
 
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
@@ -321,60 +355,58 @@ static int guided_host(const char *who, bool with_variance, i32 width, i32 heigh
   const size_t pixels = (size_t)width * height;
   HIP_TRY(S.in.grow(pixels * RT_HOST_FRAME_F32));
   HIP_TRY(S.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
-  if (out) HIP_TRY(S.out.grow(pixels * 3));
-  if (image) HIP_TRY(S.image.grow(pixels * 3));
-  if (variance) HIP_TRY(S.variance.grow(pixels));
-  if (variance_out) HIP_TRY(S.variance_out.grow(pixels));
+  if (h.out) HIP_TRY(S.out.grow(pixels * 3));
+  if (h.image) HIP_TRY(S.image.grow(pixels * 3));
+  if (h.variance_in) HIP_TRY(S.variance.grow(pixels));
+  if (h.variance_out) HIP_TRY(S.variance_out.grow(pixels));
   hipStream_t stream = nullptr;
-  FeaturePlanes d;
-  if (upload_host_frame(S.in, pixels, color, planes, &d) != 0) return -1;
-  if (variance) HIP_TRY(hipMemcpy(S.variance, variance, pixels * sizeof(float), hipMemcpyHostToDevice));
-  if (enqueue_guided(width, height, params, S.in, d.coverage, d.albedo, d.normal, d.position, out ? S.out.get() : nullptr,
-                     image ? S.image.get() : nullptr, S.work, stream, variance ? S.variance.get() : nullptr,
-                     variance_out ? S.variance_out.get() : nullptr) != 0)
-    return -1;
+  RT_Frame f;
+  if (upload_host_frame(S.in, pixels, color, planes, &f) != 0) return -1;
+  if (h.variance_in) HIP_TRY(hipMemcpy(S.variance, h.variance_in, pixels * sizeof(float), hipMemcpyHostToDevice));
+  const FilterIO d = {h.out ? S.out.get() : nullptr, h.image ? S.image.get() : nullptr, h.variance_in ? S.variance.get() : nullptr,
+                      h.variance_out ? S.variance_out.get() : nullptr};
+  if (enqueue_guided(width, height, params, f, d, S.work, stream) != 0) return -1;
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
-  if (out) HIP_TRY(hipMemcpy(out, S.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (image) HIP_TRY(hipMemcpy(image, S.image, pixels * 3, hipMemcpyDeviceToHost));
-  if (variance_out) HIP_TRY(hipMemcpy(variance_out, S.variance_out, pixels * sizeof(float), hipMemcpyDeviceToHost));
+  if (h.out) HIP_TRY(hipMemcpy(h.out, S.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (h.image) HIP_TRY(hipMemcpy(h.image, S.image, pixels * 3, hipMemcpyDeviceToHost));
+  if (h.variance_out) HIP_TRY(hipMemcpy(h.variance_out, S.variance_out, pixels * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int rt_guided_denoise_host(i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
                                       RT_Features const *planes, f32 *out, u8 *image) {
-  return guided_host("rt_guided_denoise_host", false, width, height, params, color, planes, out, image, nullptr, nullptr);
+  return guided_host("rt_guided_denoise_host", false, width, height, params, color, planes, {out, image});
 }
 
 extern "C" int rt_guided_denoise_variance_host(i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
                                                RT_Features const *planes, f32 *out, u8 *image, f32 const *variance, f32 *variance_out) {
-  return guided_host("rt_guided_denoise_variance_host", true, width, height, params, color, planes, out, image, variance, variance_out);
+  return guided_host("rt_guided_denoise_variance_host", true, width, height, params, color, planes, {out, image, variance, variance_out});
 }
 
 static const char *missing_history_plane(RT_History_Planes const *h) {
-  return !h->color ? "color" : !h->length ? "length" : !h->coverage ? "coverage" : !h->normal ? "normal" : !h->position ? "position" : nullptr;
+  for (const HistoryPlane &pl : HISTORY_PLANES)
+    if (!(h->*pl.member)) return pl.name;
+  return nullptr;
 }
 
-// rt_temporal_accumulate_host and rt_temporal_accumulate_moments_host (with_moments: moments_in goes with history_in, moments_out
-// and variance are optional outputs, vp is required when variance is wanted)
+// rt_temporal_accumulate_host and rt_temporal_accumulate_moments_host (with_moments: h.moments_in goes with history_in,
+// h.moments_out and h.variance are optional outputs, h.vp is required when h.variance is wanted); h holds the host's pointers
 static int temporal_host(const char *who, bool with_moments, i32 width, i32 height, RT_Temporal_Params const *params,
                          Camera const *camera, Camera const *previous_camera, f32 const *color, RT_Features const *planes,
-                         RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out, f32 *length, u8 *image,
-                         RT_Variance_Params const *vp, f32 const *moments_in, f32 *moments_out, f32 *variance) {
+                         RT_History_Planes const *history_in, RT_History_Planes const *history_out, AccumulateIO const &h) {
   if (check_temporal(who, width, height, params) != 0) return -1;
-  if (with_moments && (vp || variance) && check_variance(who, vp) != 0) return -1;
+  if (with_moments && (h.vp || h.variance) && check_variance(who, h.vp) != 0) return -1;
   if (!camera) return rt_fail("%s: camera is NULL", who);
   if (history_in && !previous_camera) return rt_fail("%s: previous_camera is NULL and a history is given", who);
   if (check_host_frame(who, color, planes, params->demodulate) != 0) return -1;
   if (history_in && missing_history_plane(history_in)) return rt_fail("%s: history_in->%s is NULL", who, missing_history_plane(history_in));
   if (history_out && missing_history_plane(history_out)) return rt_fail("%s: history_out->%s is NULL", who, missing_history_plane(history_out));
-  if (with_moments) {
-    if (history_in && !moments_in) return rt_fail("%s: a history is given without its moments (moments_in is NULL)", who);
-    if (!history_in && moments_in) return rt_fail("%s: moments are given without their history (history_in is NULL)", who);
-    if (!history_out && !out && !length && !image && !moments_out && !variance)
-      return rt_fail("%s: no output is wanted (history_out, out, length, image, moments_out and variance are NULL)", who);
-  } else if (!history_out && !out && !length && !image)
-    return rt_fail("%s: no output is wanted (history_out, out, length and image are NULL)", who);
+  if (with_moments && history_in && !h.moments_in) return rt_fail("%s: a history is given without its moments (moments_in is NULL)", who);
+  if (with_moments && !history_in && h.moments_in) return rt_fail("%s: moments are given without their history (history_in is NULL)", who);
+  const Output outs[] = {{"history_out", history_out}, {"out", h.out}, {"length", h.length}, {"image", h.image},
+                         {with_moments ? "moments_out" : nullptr, h.moments_out}, {with_moments ? "variance" : nullptr, h.variance}};
+  if (check_wanted(who, outs) != 0) return -1;
 
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
@@ -382,65 +414,54 @@ static int temporal_host(const char *who, bool with_moments, i32 width, i32 heig
   TemporalState &S = D.temporal;
   const size_t pixels = (size_t)width * height, f3 = pixels * 3 * sizeof(float), f1 = pixels * sizeof(float);
   HIP_TRY(S.in.grow(pixels * RT_HOST_FRAME_F32));
-  HIP_TRY(S.planar.grow(pixels * 11));
+  HIP_TRY(S.planar.grow(pixels * RT_HISTORY_PLANAR_F32));
   HIP_TRY(S.hist[0].grow(pixels * RT_TEMPORAL_HISTORY_PER_PIXEL));
   HIP_TRY(S.hist[1].grow(pixels * RT_TEMPORAL_HISTORY_PER_PIXEL));
-  if (out) HIP_TRY(S.out.grow(pixels * 3));
-  if (length) HIP_TRY(S.length.grow(pixels));
-  if (image) HIP_TRY(S.image.grow(pixels * 3));
+  if (h.out) HIP_TRY(S.out.grow(pixels * 3));
+  if (h.length) HIP_TRY(S.length.grow(pixels));
+  if (h.image) HIP_TRY(S.image.grow(pixels * 3));
   if (with_moments) {
     HIP_TRY(S.mom[0].grow(pixels * RT_TEMPORAL_MOMENTS_PER_PIXEL));
     HIP_TRY(S.mom[1].grow(pixels * RT_TEMPORAL_MOMENTS_PER_PIXEL));
     HIP_TRY(S.mom_planar.grow(pixels * 2));
-    if (variance) HIP_TRY(S.variance.grow(pixels));
+    if (h.variance) HIP_TRY(S.variance.grow(pixels));
   }
-  float *h_col = S.planar, *h_len = S.planar + pixels * 3, *h_cov = S.planar + pixels * 4, *h_nrm = S.planar + pixels * 5,
-        *h_pos = S.planar + pixels * 8;
+  float *pl[5];                                                 // the staged planes, in HISTORY_PLANES' order
+  for (int k = 0; k < 5; k++) pl[k] = S.planar + pixels * HISTORY_PLANES[k].offset;
   hipStream_t stream = nullptr;
-  FeaturePlanes d;
-  if (upload_host_frame(S.in, pixels, color, planes, &d) != 0) return -1;
+  RT_Frame f;
+  if (upload_host_frame(S.in, pixels, color, planes, &f) != 0) return -1;
   if (history_in) {
-    HIP_TRY(hipMemcpy(h_col, history_in->color, f3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h_len, history_in->length, f1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h_cov, history_in->coverage, f1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h_nrm, history_in->normal, f3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h_pos, history_in->position, f3, hipMemcpyHostToDevice));
-    int rc = rt_launch_temporal_pack((int)pixels, h_col, h_len, h_cov, h_nrm, h_pos, S.hist[0], stream);
-    if (rc != 0) return rt_fail("temporal pack kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    for (int k = 0; k < 5; k++)
+      HIP_TRY(hipMemcpy(pl[k], history_in->*HISTORY_PLANES[k].member, f1 * HISTORY_PLANES[k].floats, hipMemcpyHostToDevice));
+    int rc = rt_launch_temporal_pack((int)pixels, pl[0], pl[1], pl[2], pl[3], pl[4], S.hist[0], stream);
+    if (launched(rc, "temporal pack kernel launch failed: %s") != 0) return -1;
     if (with_moments) {
-      HIP_TRY(hipMemcpy(S.mom_planar, moments_in, 2 * f1, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(S.mom_planar, h.moments_in, 2 * f1, hipMemcpyHostToDevice));
       rc = rt_launch_moments_pack((int)pixels, S.mom_planar, S.mom[0], stream);
-      if (rc != 0) return rt_fail("moments pack kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (launched(rc, "moments pack kernel launch failed: %s") != 0) return -1;
     }
   }
-  if (enqueue_temporal(width, height, params, camera, previous_camera, S.in, d.coverage, d.albedo, d.normal, d.position,
-                       history_in ? S.hist[0].get() : nullptr, S.hist[1], out ? S.out.get() : nullptr,
-                       length ? S.length.get() : nullptr, image ? S.image.get() : nullptr, stream, vp,
-                       with_moments && history_in ? S.mom[0].get() : nullptr, with_moments ? S.mom[1].get() : nullptr,
-                       variance ? S.variance.get() : nullptr) != 0)
+  const AccumulateIO d = {h.out ? S.out.get() : nullptr, h.length ? S.length.get() : nullptr, h.image ? S.image.get() : nullptr,
+                          with_moments && history_in ? S.mom[0].get() : nullptr, with_moments ? S.mom[1].get() : nullptr,
+                          h.variance ? S.variance.get() : nullptr, h.vp};
+  if (enqueue_temporal(width, height, params, camera, previous_camera, f, history_in ? S.hist[0].get() : nullptr, S.hist[1], d,
+                       stream) != 0)
     return -1;
-  if (moments_out) {
-    int rc = rt_launch_moments_unpack((int)pixels, S.mom[1], S.mom_planar, stream);
-    if (rc != 0) return rt_fail("moments unpack kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
-  if (history_out) {
-    int rc = rt_launch_temporal_unpack((int)pixels, S.hist[1], h_col, h_len, h_cov, h_nrm, h_pos, stream);
-    if (rc != 0) return rt_fail("temporal unpack kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-  }
+  const int rc_m = h.moments_out ? rt_launch_moments_unpack((int)pixels, S.mom[1], S.mom_planar, stream) : 0;
+  if (launched(rc_m, "moments unpack kernel launch failed: %s") != 0) return -1;
+  const int rc_h = history_out ? rt_launch_temporal_unpack((int)pixels, S.hist[1], pl[0], pl[1], pl[2], pl[3], pl[4], stream) : 0;
+  if (launched(rc_h, "temporal unpack kernel launch failed: %s") != 0) return -1;
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
-  if (history_out) {
-    HIP_TRY(hipMemcpy(history_out->color, h_col, f3, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(history_out->length, h_len, f1, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(history_out->coverage, h_cov, f1, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(history_out->normal, h_nrm, f3, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(history_out->position, h_pos, f3, hipMemcpyDeviceToHost));
-  }
-  if (out) HIP_TRY(hipMemcpy(out, S.out, f3, hipMemcpyDeviceToHost));
-  if (length) HIP_TRY(hipMemcpy(length, S.length, f1, hipMemcpyDeviceToHost));
-  if (image) HIP_TRY(hipMemcpy(image, S.image, pixels * 3, hipMemcpyDeviceToHost));
-  if (moments_out) HIP_TRY(hipMemcpy(moments_out, S.mom_planar, 2 * f1, hipMemcpyDeviceToHost));
-  if (variance) HIP_TRY(hipMemcpy(variance, S.variance, f1, hipMemcpyDeviceToHost));
+  if (history_out)
+    for (int k = 0; k < 5; k++)
+      HIP_TRY(hipMemcpy(history_out->*HISTORY_PLANES[k].member, pl[k], f1 * HISTORY_PLANES[k].floats, hipMemcpyDeviceToHost));
+  if (h.out) HIP_TRY(hipMemcpy(h.out, S.out, f3, hipMemcpyDeviceToHost));
+  if (h.length) HIP_TRY(hipMemcpy(h.length, S.length, f1, hipMemcpyDeviceToHost));
+  if (h.image) HIP_TRY(hipMemcpy(h.image, S.image, pixels * 3, hipMemcpyDeviceToHost));
+  if (h.moments_out) HIP_TRY(hipMemcpy(h.moments_out, S.mom_planar, 2 * f1, hipMemcpyDeviceToHost));
+  if (h.variance) HIP_TRY(hipMemcpy(h.variance, S.variance, f1, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -449,7 +470,7 @@ extern "C" int rt_temporal_accumulate_host(i32 width, i32 height, RT_Temporal_Pa
                                            RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
                                            f32 *length, u8 *image) {
   return temporal_host("rt_temporal_accumulate_host", false, width, height, params, camera, previous_camera, color, planes, history_in,
-                       history_out, out, length, image, nullptr, nullptr, nullptr, nullptr);
+                       history_out, {out, length, image});
 }
 
 extern "C" int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
@@ -458,7 +479,7 @@ extern "C" int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Tem
                                                    f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
                                                    f32 *moments_out, f32 *variance) {
   return temporal_host("rt_temporal_accumulate_moments_host", true, width, height, params, camera, previous_camera, color, planes,
-                       history_in, history_out, out, length, image, vp, moments_in, moments_out, variance);
+                       history_in, history_out, {out, length, image, moments_in, moments_out, variance, vp});
 }
 
 // ---- the history a host keeps ---------------------------------------------------------------------------------------------------
@@ -467,14 +488,7 @@ extern "C" int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Tem
 // device idle.
 void release_temporal_state(Device &D) {
   std::vector<RT_History *> keep = std::move(D.temporal.histories);
-  for (RT_History *h : keep) {
-    h->buf[0].reset();
-    h->buf[1].reset();
-    h->mom[0].reset();
-    h->mom[1].reset();
-    h->valid = false;
-    h->moments_valid = false;
-  }
+  for (RT_History *h : keep) h->release();
   D.temporal = TemporalState();
   D.temporal.histories = std::move(keep);
 }
@@ -495,8 +509,7 @@ extern "C" int rt_history_reset(RT_History *history) {
   if (!history) return rt_fail("rt_history_reset: history is NULL");
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
-  history->valid = false;                                       // (the memory stays for the next frame)
-  history->moments_valid = false;
+  history->valid = history->moments_valid = false;              // (the memory stays for the next frame)
   return 0;
 }
 
@@ -509,49 +522,61 @@ extern "C" void rt_history_destroy(RT_History *history) {
   if (history->buf[0] || history->buf[1]) {                     // (memory exists only after a frame: the device is there)
     DeviceGuard guard(D);
     (void)hipDeviceSynchronize();                               // whatever still reads the histories finishes first
-    history->buf[0].reset();
-    history->buf[1].reset();
-    history->mom[0].reset();
-    history->mom[1].reset();
+    history->release();
   }
   delete history;
 }
 
 // ---- behind a frame -----------------------------------------------------------------------------------------------------------
 
-// What both entry points check of `image` before its size goes into 32 bits, and after their stages' parameters.
-static int check_frame_image(const char *who, Image const *image) {
+// The three entry points: their word for the frame in the one-device refusal; their stages -- `history`: the accumulation,
+// `variance`: it carries the moments and the filter is the variance-guided one, `must_filter`: the filter's params are required --;
+// their list of the outputs in the refusal of a call that wants none.
+struct PostFrame { const char *what; bool history, variance, must_filter; const char *outputs; };
+static const PostFrame DENOISED = {"a denoised frame", false, false, true, "no pixels and no linear_denoised"};
+static const PostFrame ACCUMULATED = {"an accumulated frame", true, false, false, "no pixels, no linear_out, no length"};
+static const PostFrame SVGF = {"a variance-guided frame", true, true, true, "no pixels, no linear_out, no length, no variance"};
+
+// The stages' arguments (NULL: the entry point has no such stage, or g: the caller wants no filter), and what the caller wants back
+// besides the Image (f32, each optional): the frame as rendered, the last stage's output, the history lengths, the filter's variance.
+struct PostStages { RT_Guided_Params const *g; RT_History *history; RT_Temporal_Params const *t; RT_Variance_Params const *vp; };
+struct PostOutputs { f32 *linear_noisy, *linear_out, *length, *variance; };
+
+// The frame, the four planes of its feature pass, then the stages that are given -- the accumulation against s.history (s.t), the
+// filter (s.g) -- in one scene-checked call.  W.linear is the noisy frame, D.temporal.out / length serve the accumulation,
+// D.guided.work / out the filter, and W.image receives the encoding of the LAST stage.  s.vp (with history and g): rt_render_svgf
+// -- the accumulation carries the history's moments, the variance launch follows it into D.temporal.variance, and the filter is
+// the variance-guided one.
+static int render_post(const char *who, PostFrame const &kind, Scene const *scene, Image const *image, isize samples, isize max_bounces,
+                       PostStages const &s, PostOutputs const &o) {
+  // before the device lock: the image's size before it goes into 32 bits, the stages' parameters, the rest of the frame's
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  if (!image) return rt_fail("%s: image is NULL", who);
+  if (kind.history && !s.history) return rt_fail("%s: history is NULL", who);
   if (image->width <= 0 || image->height <= 0 || image->width > 0x7fffffff || image->height > 0x7fffffff)
     return rt_fail("%s: image size %ldx%ld is invalid", who, (long)image->width, (long)image->height);
-  return 0;
-}
-
-static int check_frame_rest(const char *who, Image const *image, isize samples, isize max_bounces) {
+  const i32 width = (i32)image->width, height = (i32)image->height;
+  if (kind.history && check_temporal(who, width, height, s.t) != 0) return -1;
+  if (kind.variance && check_variance(who, s.vp) != 0) return -1;
+  if ((kind.must_filter || s.g) && check_guided(who, width, height, s.g) != 0) return -1;
   if (check_image_layout(image, who) != 0) return -1;
   if (samples <= 0 || samples > 0x7fffffff) return rt_fail("%s: samples must be positive and fit 32 bits (got %ld)", who, (long)samples);
   if (max_bounces < 0 || max_bounces > 0x7fffffff) return rt_fail("%s: max_bounces must be >= 0 and fit 32 bits (got %ld)", who, (long)max_bounces);
-  return 0;
-}
+  if (!image->pixels.data && !o.linear_out && !o.length && !o.variance) return rt_fail("%s: no output is wanted (%s)", who, kind.outputs);
 
-// The frame, the four planes of its feature pass, then the stages that are given -- the accumulation against `history` (t), the
-// filter (g) -- in one scene-checked call.  W.linear is the noisy frame, D.temporal.out / length serve the accumulation,
-// D.guided.work / out the filter, and W.image receives the encoding of the LAST stage.  The arguments are checked by the callers;
-// `what` is their word for the frame in the one-device refusal.  vp (with history and g): rt_render_svgf -- the accumulation carries
-// the history's moments, the variance launch follows it into D.temporal.variance, and the filter is the variance-guided one.
-static int render_post(const char *who, const char *what, Scene const *scene, Image const *image, isize samples, isize max_bounces,
-                       RT_History *history, RT_Temporal_Params const *t, RT_Guided_Params const *g, f32 *linear_noisy, f32 *linear_out,
-                       f32 *length, RT_Variance_Params const *vp = nullptr, f32 *variance = nullptr) {
+  RT_History *const history = s.history;
+  RT_Guided_Params const *const g = s.g;
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
   if (history && (image->width != history->width || image->height != history->height))
     return rt_fail("%s: the image is %ldx%ld and the history %dx%d", who, (long)image->width, (long)image->height, history->width,
                    history->height);
-  if (vp && history->valid && history->buf[0] && history->buf[1] && !(history->moments_valid && history->mom[0] && history->mom[1]))
+  if (s.vp && history->valid && history->buf[0] && history->buf[1] && !(history->moments_valid && history->mom[0] && history->mom[1]))
     return rt_fail("%s: the history's last frame was written by rt_render_temporal and has no moments: call rt_history_reset first", who);
   const double t_start = now_ms();
   if (ensure_device(D) != 0) return -1;
   if (rt_device_count() > 1)
-    return rt_fail("%s: %s renders on one device, and %d are set (rt_set_devices)", who, what, rt_device_count());
+    return rt_fail("%s: %s renders on one device, and %d are set (rt_set_devices)", who, kind.what, rt_device_count());
   RT_Render_Params p;
   if (fill_frame_params(&p, image, samples, max_bounces, g_seed.load()) != 0) return -1;
   forget_multi_counters();
@@ -565,46 +590,47 @@ static int render_post(const char *who, const char *what, Scene const *scene, Im
   if (ensure_ws_buffers(W, p.width, p.height, 0, 0) != 0) return -1;
   HIP_TRY(F.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(F.planes.grow(pixels * RT_FEATURE_CHANNELS));
-  const bool want_accumulated = history && (g || linear_out);   // the accumulation's f32 output: the filter's input, or the caller's
+  const bool want_accumulated = history && (g || o.linear_out);   // the accumulation's f32 output: the filter's input, or the caller's
   const uint8_t *h_in = nullptr;
-  uint8_t *h_out = nullptr, *m_out = nullptr;
-  const uint8_t *m_in = nullptr;
+  uint8_t *h_out = nullptr;
+  AccumulateIO a = {};                                            // (a.variance: the variance launch's output, the filter's input)
   if (history) {
     if (!history->buf[0] || !history->buf[1]) history->valid = false;          // (given back with the staging: from nothing)
     HIP_TRY(history->buf[0].grow(pixels * RT_TEMPORAL_HISTORY_PER_PIXEL));
     HIP_TRY(history->buf[1].grow(pixels * RT_TEMPORAL_HISTORY_PER_PIXEL));
     if (want_accumulated) HIP_TRY(S.out.grow(pixels * 3));
-    if (length) HIP_TRY(S.length.grow(pixels));
+    if (o.length) HIP_TRY(S.length.grow(pixels));
     h_in = history->valid ? history->buf[history->cur].get() : nullptr;
     h_out = history->buf[history->cur ^ 1];
-    if (vp) {
+    a = {want_accumulated ? S.out.get() : nullptr, o.length ? S.length.get() : nullptr, g ? nullptr : W.image.get()};
+    if (s.vp) {
       HIP_TRY(history->mom[0].grow(pixels * RT_TEMPORAL_MOMENTS_PER_PIXEL));
       HIP_TRY(history->mom[1].grow(pixels * RT_TEMPORAL_MOMENTS_PER_PIXEL));
       HIP_TRY(S.variance.grow(pixels));
-      m_in = h_in ? history->mom[history->cur].get() : nullptr;
-      m_out = history->mom[history->cur ^ 1];
+      a.moments_in = h_in ? history->mom[history->cur].get() : nullptr;
+      a.moments_out = history->mom[history->cur ^ 1];
+      a.variance = S.variance;
+      a.vp = s.vp;
     }
   }
   if (g) {
     HIP_TRY(G.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
-    if (linear_out) HIP_TRY(G.out.grow(pixels * 3));
+    if (o.linear_out) HIP_TRY(G.out.grow(pixels * 3));
   }
-  const FeaturePlanes f = split_feature_planes(F.planes, pixels);
+  const RT_Features planes = split_feature_planes(F.planes, pixels);
   hipStream_t stream = nullptr;
   // (a pass that is run again after a scene edit reads the same old history and writes the same new one)
   auto pass = [&](RT_Device_Scene *d) -> int {
     if (enqueue_frame(D, d, &scene->camera, &p, W, stream, 0, nullptr, nullptr, W.linear) != 0) return -1;
     HIP_TRY(hipMemsetAsync(F.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
     if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream) != 0) return -1;
-    if (enqueue_resolve(&p, F.sums, f.coverage, f.albedo, f.normal, f.position, stream) != 0) return -1;
-    if (history && enqueue_temporal(p.width, p.height, t, &scene->camera, &history->camera, W.linear, f.coverage, f.albedo, f.normal,
-                                    f.position, h_in, h_out, want_accumulated ? S.out.get() : nullptr,
-                                    length ? S.length.get() : nullptr, g ? nullptr : W.image.get(), stream, vp, m_in, m_out,
-                                    vp ? S.variance.get() : nullptr) != 0)
+    if (enqueue_resolve(&p, F.sums, planes.coverage, planes.albedo, planes.normal, planes.position, stream) != 0) return -1;
+    if (history && enqueue_temporal(p.width, p.height, s.t, &scene->camera, &history->camera, device_frame(W.linear, planes), h_in, h_out,
+                                    a, stream) != 0)
       return -1;
     if (!g) return 0;
-    return enqueue_guided(p.width, p.height, g, history ? S.out.get() : W.linear.get(), f.coverage, f.albedo, f.normal, f.position,
-                          linear_out ? G.out.get() : nullptr, W.image, G.work, stream, vp ? S.variance.get() : nullptr);
+    const FilterIO f = {o.linear_out ? G.out.get() : nullptr, W.image, a.variance};
+    return enqueue_guided(p.width, p.height, g, device_frame(history ? S.out.get() : W.linear.get(), planes), f, G.work, stream);
   };
   if (!scene_checked(D, scene, stream, &T, pass)) {                // (a scene edited since the copy: uploaded and rendered again)
     if (history) history->valid = history->moments_valid = false;   // (the new history may be half written, the old one is not current)
@@ -613,62 +639,34 @@ static int render_post(const char *who, const char *what, Scene const *scene, Im
   if (history) {
     history->cur ^= 1;
     history->valid = true;
-    history->moments_valid = vp != nullptr;                       // (rt_render_temporal leaves the moments behind)
+    history->moments_valid = s.vp != nullptr;                     // (rt_render_temporal leaves the moments behind)
     history->camera = scene->camera;
   }
 
   if (copy_image_out(image, W.image, p.width, p.height, stream) != 0) return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
-  if (linear_noisy) HIP_TRY(hipMemcpy(linear_noisy, W.linear, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (linear_out) HIP_TRY(hipMemcpy(linear_out, g ? G.out.get() : S.out.get(), pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (length) HIP_TRY(hipMemcpy(length, S.length, pixels * sizeof(float), hipMemcpyDeviceToHost));
-  if (variance) HIP_TRY(hipMemcpy(variance, S.variance, pixels * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.linear_noisy) HIP_TRY(hipMemcpy(o.linear_noisy, W.linear, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.linear_out) HIP_TRY(hipMemcpy(o.linear_out, g ? G.out.get() : S.out.get(), pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.length) HIP_TRY(hipMemcpy(o.length, S.length, pixels * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.variance) HIP_TRY(hipMemcpy(o.variance, S.variance, pixels * sizeof(float), hipMemcpyDeviceToHost));
   return finish_frame(D, W, stream, T, t_start);
 }
 
 extern "C" int rt_render_denoised(Scene const *scene, Image const *image, isize samples, isize max_bounces,
                                   RT_Guided_Params const *params, f32 *linear_noisy, f32 *linear_denoised) {
-  const char *who = "rt_render_denoised";
-  if (!scene) return rt_fail("%s: scene is NULL", who);
-  if (!image) return rt_fail("%s: image is NULL", who);
-  if (check_frame_image(who, image) != 0) return -1;
-  if (check_guided(who, (i32)image->width, (i32)image->height, params) != 0) return -1;
-  if (check_frame_rest(who, image, samples, max_bounces) != 0) return -1;
-  if (!image->pixels.data && !linear_denoised) return rt_fail("%s: no output is wanted (no pixels and no linear_denoised)", who);
-  return render_post(who, "a denoised frame", scene, image, samples, max_bounces, nullptr, nullptr, params, linear_noisy,
-                     linear_denoised, nullptr);
+  return render_post("rt_render_denoised", DENOISED, scene, image, samples, max_bounces, {params}, {linear_noisy, linear_denoised});
 }
 
 extern "C" int rt_render_temporal(Scene const *scene, Image const *image, isize samples, isize max_bounces, RT_History *history,
                                   RT_Temporal_Params const *temporal_params, RT_Guided_Params const *guided_params, f32 *linear_noisy,
                                   f32 *linear_out, f32 *length) {
-  const char *who = "rt_render_temporal";
-  if (!scene) return rt_fail("%s: scene is NULL", who);
-  if (!image) return rt_fail("%s: image is NULL", who);
-  if (!history) return rt_fail("%s: history is NULL", who);
-  if (check_frame_image(who, image) != 0) return -1;
-  if (check_temporal(who, (i32)image->width, (i32)image->height, temporal_params) != 0) return -1;
-  if (guided_params && check_guided(who, (i32)image->width, (i32)image->height, guided_params) != 0) return -1;
-  if (check_frame_rest(who, image, samples, max_bounces) != 0) return -1;
-  if (!image->pixels.data && !linear_out && !length) return rt_fail("%s: no output is wanted (no pixels, no linear_out, no length)", who);
-  return render_post(who, "an accumulated frame", scene, image, samples, max_bounces, history, temporal_params, guided_params,
-                     linear_noisy, linear_out, length);
+  return render_post("rt_render_temporal", ACCUMULATED, scene, image, samples, max_bounces, {guided_params, history, temporal_params},
+                     {linear_noisy, linear_out, length});
 }
 
 extern "C" int rt_render_svgf(Scene const *scene, Image const *image, isize samples, isize max_bounces, RT_History *history,
                               RT_Temporal_Params const *temporal_params, RT_Variance_Params const *variance_params,
                               RT_Guided_Params const *guided_params, f32 *linear_noisy, f32 *linear_out, f32 *length, f32 *variance) {
-  const char *who = "rt_render_svgf";
-  if (!scene) return rt_fail("%s: scene is NULL", who);
-  if (!image) return rt_fail("%s: image is NULL", who);
-  if (!history) return rt_fail("%s: history is NULL", who);
-  if (check_frame_image(who, image) != 0) return -1;
-  if (check_temporal(who, (i32)image->width, (i32)image->height, temporal_params) != 0) return -1;
-  if (check_variance(who, variance_params) != 0) return -1;
-  if (check_guided(who, (i32)image->width, (i32)image->height, guided_params) != 0) return -1;
-  if (check_frame_rest(who, image, samples, max_bounces) != 0) return -1;
-  if (!image->pixels.data && !linear_out && !length && !variance)
-    return rt_fail("%s: no output is wanted (no pixels, no linear_out, no length, no variance)", who);
-  return render_post(who, "a variance-guided frame", scene, image, samples, max_bounces, history, temporal_params, guided_params,
-                     linear_noisy, linear_out, length, variance_params, variance);
+  return render_post("rt_render_svgf", SVGF, scene, image, samples, max_bounces,
+                     {guided_params, history, temporal_params, variance_params}, {linear_noisy, linear_out, length, variance});
 }

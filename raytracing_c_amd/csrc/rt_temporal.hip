@@ -49,13 +49,12 @@ __global__ __launch_bounds__(256) void rt_temporal_unpack_history(int n_pixels, 
   w[p3] = h2.x; w[p3 + 1] = h2.y; w[p3 + 2] = h2.z;
 }
 
-extern "C" int rt_launch_temporal(const RT_TParams *P, const float *color, const float *coverage, const float *albedo,
-                                  const float *normal, const float *position, const void *hist_in, void *hist_out, float *out,
-                                  float *length, uint8_t *image, hipStream_t stream) {
+extern "C" int rt_launch_temporal(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out, float *length,
+                                  uint8_t *image, hipStream_t stream) {
   // tiles_x * tiles_y <= pixels / 256 + width / 32 + height / 8 + 1 < 2^26 for the 2^28 pixels the host admits
   const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
-  hipLaunchKernelGGL(rt_temporal_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, color, coverage, albedo, normal, position,
-                     (const float4 *)hist_in, (float4 *)hist_out, out, length, image);
+  hipLaunchKernelGGL(rt_temporal_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage, frame.albedo, frame.normal,
+                     frame.position, (const float4 *)hist_in, (float4 *)hist_out, out, length, image);
   return (int)hipGetLastError();
 }
 

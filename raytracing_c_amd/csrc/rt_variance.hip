@@ -140,14 +140,13 @@ __global__ __launch_bounds__(256) void rt_moments_unpack(int n_pixels, const flo
   planar[(size_t)p * 2 + 1] = m.y;
 }
 
-extern "C" int rt_launch_temporal_moments(const RT_TParams *P, const float *color, const float *coverage, const float *albedo,
-                                          const float *normal, const float *position, const void *hist_in, void *hist_out, float *out,
+extern "C" int rt_launch_temporal_moments(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out,
                                           float *length, uint8_t *image, const void *mom_in, void *mom_out, hipStream_t stream) {
   // (as rt_launch_temporal: fewer than 2^26 blocks for the 2^28 pixels the host admits)
   const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
-  hipLaunchKernelGGL(rt_temporal_moments_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, color, coverage, albedo, normal,
-                     position, (const float4 *)hist_in, (float4 *)hist_out, out, length, image, (const float4 *)mom_in,
-                     (float4 *)mom_out);
+  hipLaunchKernelGGL(rt_temporal_moments_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage, frame.albedo,
+                     frame.normal, frame.position, (const float4 *)hist_in, (float4 *)hist_out, out, length, image,
+                     (const float4 *)mom_in, (float4 *)mom_out);
   return (int)hipGetLastError();
 }
 
@@ -160,21 +159,20 @@ extern "C" int rt_launch_variance(int width, int height, float k_n, float k_p, c
   return (int)hipGetLastError();
 }
 
-extern "C" int rt_launch_variance_pack(int n_pixels, int demodulate, const float *color, const float *coverage, const float *albedo,
-                                       const float *normal, const float *position, const float *variance, void *c0, void *g0, void *g1,
+extern "C" int rt_launch_variance_pack(int n_pixels, int demodulate, RT_Frame frame, const float *variance, void *c0, void *g0, void *g1,
                                        hipStream_t stream) {
-  hipLaunchKernelGGL(rt_variance_pack_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, demodulate, color, coverage,
-                     albedo, normal, position, variance, (float4 *)c0, (float4 *)g0, (float4 *)g1);
+  hipLaunchKernelGGL(rt_variance_pack_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, demodulate, frame.color,
+                     frame.coverage, frame.albedo, frame.normal, frame.position, variance, (float4 *)c0, (float4 *)g0, (float4 *)g1);
   return (int)hipGetLastError();
 }
 
 extern "C" int rt_launch_variance_filter(int width, int height, int step, float k_n, float k_p, float k_c, int last, int demodulate,
-                                         const void *src, void *dst, const void *g0, const void *g1, const float *color,
-                                         const float *albedo, float *out, uint8_t *image, float *var_out, hipStream_t stream) {
+                                         const void *src, void *dst, const void *g0, const void *g1, RT_Frame frame, float *out,
+                                         uint8_t *image, float *var_out, hipStream_t stream) {
   const GuidedGrid G = guided_grid(width, height, step);
   hipLaunchKernelGGL(rt_variance_filter_kernel, dim3(G.blocks), dim3(GD_TX, GD_TY), 0, stream, width, height, step, G.phases_x,
                      G.phases_y, G.tiles_x, k_n, k_p, k_c, last, demodulate, (const float4 *)src, (float4 *)dst, (const float4 *)g0,
-                     (const float4 *)g1, color, albedo, out, image, var_out);
+                     (const float4 *)g1, frame.color, frame.albedo, out, image, var_out);
   return (int)hipGetLastError();
 }
 

@@ -220,6 +220,7 @@ def _declare_diag(d):
     d.rt_test_srgb_sweep.argtypes = [vp]
     d.rt_test_quantize_sweep.argtypes = [vp]
     d.rt_test_group_sum.argtypes = [C.c_int32, C.c_int32, vp, vp, vp]
+    d.rt_test_sky_add_group.argtypes = []
     d.rt_test_node_order.argtypes = [C.c_int32, vp, vp, vp]
     d.rt_test_trace.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     d.rt_test_texture.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
