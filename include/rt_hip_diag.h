@@ -59,6 +59,16 @@ extern int rt_test_rcp_sweep(u64 out[6]);
 /* the kernels' sRGB decode of a texture sample against rt_srgb_to_linear1() for every float in [0, 2] (and 4 M negative ones):
  * out[0] patterns compared, out[1] differing (0 expected), out[2] first differing pattern + 1 */
 extern int rt_test_srgb_sweep(u64 out[3]);
+/* the short forms the environment lookup and the normalisations use on the device (csrc/rt_dev.hip.h) against the rt_math.h
+ * functions they stand for, both computed on the device.  which = 0 .. 5 compare all 2^32 bit patterns x:
+ *   0 atan_pos_dev(x) / rt_atanf_pos(x)     1 asin_dev(x) / rt_asinf(x)     2 inv_sqrt_exact(x) / the reciprocal of rt_sqrtf(x)
+ *   3, 4 the background's u, v of the angle x without tex_taps' negative-coordinate wrap / with it, over the angles the
+ *        arctangent (|x| <= RT_PI or NaN) and the arcsine (|x| <= pi/2 or NaN) can return     5 sqrt_dev(x) / rt_sqrtf(x)
+ * which = 6 compares atan2_dev(y, x) / rt_atan2f(y, x) on 2^26 pairs drawn from `seed`.
+ * out[0] patterns or pairs compared, out[1] differing, a NaN equal to any NaN (0 expected), out[2] first differing pattern or
+ * pair index + 1, out[3] differing when a NaN must have the same bits as well.
+ * rt_test_math() takes the forms as ops 14 .. 18: atan2_dev(x, y), atan_pos_dev, asin_dev, inv_sqrt_exact, sqrt_dev. */
+extern int rt_test_env_sweep(i32 which, u32 seed, u64 out[4]);
 /* the tile-stream kernel's fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit patterns:
  * out[0] differing patterns (0 expected), out[1] first differing pattern + 1 */
 extern int rt_test_quantize_sweep(u64 out[2]);

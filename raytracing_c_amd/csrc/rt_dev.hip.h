@@ -447,9 +447,103 @@ __device__ __forceinline__ bool rcp_exact_outside(float x) {
   return __builtin_fabsf(x) >= RT_SHORT_DIV_MAX_X && __builtin_fabsf(x) < RT_INF;
 }
 
-// rt_v3_normalize() (rt_math.h: v * (1 / sqrt(v.v))) with the reciprocal from rcp_exact(): a square root lies in [0, 2^64] or
-// is infinite / NaN, inside the domain on which rcp_exact() equals the division -- same bits, 5 instructions fewer.
-__device__ __forceinline__ rt_v3 normalize_dev(rt_v3 v) { return rt_v3_scale(v, rcp_exact(rt_sqrtf(rt_v3_dot(v, v)))); }
+// ---- short forms of the libm stand-ins' divisions and square roots (rt_math.h stays the definition) -----------------------
+// Each is a function of ONE float and is compared with the unmodified rt_math.h function over all 2^32 bit patterns on the
+// device (rt_test_env_sweep, tests/test_gpu_env_forms.py): the sweep, not an argument about rounding, is what ships a form.
+// What the sweeps threw out is in profiles/r13_env_forms.md.
+
+// The correctly rounded square root of a NORMAL x (or 0 / infinity / NaN / negative): v_sqrt_f32 (1 ulp) moved to its lower or
+// upper neighbour where the exact residual asks for it -- the two corrections of hipcc's own sequence, and both are needed (with
+// either one left out the sweeps of asin_dev and inv_sqrt_exact find differing patterns).  hipcc's 17 instructions also scale
+// denormals up in front, scale the root down behind, and pass 0 / infinity through by a class test; zero and infinity come
+// through the corrections unchanged without it (their residuals are 0 or NaN: neither compare fires).  raw = the v_sqrt_f32.
+__device__ __forceinline__ float sqrt_normal(float x, float &raw) {
+  const float r = __builtin_amdgcn_sqrtf(x);
+  raw = r;
+  const float dn = __int_as_float(__float_as_int(r) - 1), up = __int_as_float(__float_as_int(r) + 1);
+  const float vp = __builtin_fmaf(-dn, r, x), vs = __builtin_fmaf(-up, r, x);
+  float s = (vp <= 0.0f) ? dn : r;
+  s = (vs > 0.0f) ? up : s;
+  return s;
+}
+
+// rt_sqrtf(s) for EVERY float s in 15 instructions instead of 17: the compiler's sequence without its class test.
+__device__ __forceinline__ float sqrt_dev(float s) {
+  const bool tiny = s < 0x1p-96f;                       // denormals (v_sqrt_f32 flushes them); zero and negatives ride along
+  float raw;
+  const float r = sqrt_normal(s * (tiny ? 0x1p32f : 1.0f), raw);
+  return r * (tiny ? 0x1p-16f : 1.0f);
+}
+
+// rcp_exact(rt_sqrtf(s)) = RN(1 / RN(sqrt(s))) for EVERY float s -- negative (NaN), +-0 (+-infinity), denormal, infinite (0), NaN --
+// in 19 instructions instead of 23.  A square root is 0, infinite, NaN or in [2^-75, 2^64]: its reciprocal needs neither of
+// rcp_exact()'s 2^24 scalings; the root's class test folds into the reciprocal's v_div_fixup_f32, which reads the class off the
+// raw v_sqrt_f32; and the root's scale-down by 2^-16 becomes the reciprocal's scale-up by 2^16 (exact either way).
+__device__ __forceinline__ float inv_sqrt_exact(float s) {
+  const bool tiny = s < 0x1p-96f;
+  float raw;
+  const float r = sqrt_normal(s * (tiny ? 0x1p32f : 1.0f), raw);
+  const float y = __builtin_amdgcn_rcpf(r);
+  const float e = __builtin_fmaf(-r, y, 1.0f);
+  const float z = __builtin_fmaf(e, y, y);
+  return __builtin_amdgcn_div_fixupf(z, raw, 1.0f) * (tiny ? 0x1p16f : 1.0f);
+}
+
+// rt_asinf(x) for EVERY float x.  Its square root takes 0.5 (1 - a) with a in (0.5, 1]: 0 or in [2^-25, 0.25), never a
+// denormal, never infinite -- sqrt_normal() alone, 9 instructions instead of 17.
+__device__ __forceinline__ float asin_dev(float x) {
+  float a = rt_absf(x);
+  if (a > 1.0f) a = 1.0f;
+  int   big = a > 0.5f;
+  float z, w, raw;
+  if (big) { z = 0.5f * (1.0f - a); w = sqrt_normal(z, raw); } else { w = a; z = a * a; }
+  float p = rt_fmaf(rt_fmaf(rt_fmaf(rt_fmaf(4.2163199048E-2f, z, 2.4181311049E-2f), z, 4.5470025998E-2f), z, 7.4953002686E-2f),
+                    z, 1.6666752422E-1f);
+  p = rt_fmaf(p * z, w, w);
+  if (big) p = 1.5707963267948966192f - (p + p);
+  return x < 0.0f ? -p : p;
+}
+
+// rt_atanf_pos(a) for EVERY float a (negative and NaN included: they take the small range, as there).  rt_math.h divides in
+// two of its three ranges, -1 / a above 2.414 and (a - 1) / (a + 1) above 0.414, and if-converted that is two IEEE sequences of
+// 11 instructions for every lane.  Here numerator and denominator are picked per lane and ONE quotient is formed in 4
+// instructions: v_rcp_f32, the product, its exact residual, one correction.  (The Newton step on the reciprocal that rcp_exact()
+// takes first changes no pattern here and is left out.)  The middle range's denominator lies in (1.41, 3.42].  The upper range's
+// reaches infinity, where the residual would be NaN: it is clamped to 2^100 -- from there on the quotient is below 2^-100 in
+// magnitude, flushed or not, and pi/2 + (q + q^3 P) is pi/2 whatever it is, as it is for -1 / a.
+__device__ __forceinline__ float atan_pos_dev(float a) {
+  const bool big = a > 2.414213562373095f, mid = a > 0.4142135623730950f;
+  const float num = big ? -1.0f : a - 1.0f;
+  const float den = __builtin_fminf(big ? a : a + 1.0f, 0x1p100f);
+  const float yb = big ? 1.5707963267948966192f : (mid ? 0.7853981633974483096f : 0.0f);
+  const float y = __builtin_amdgcn_rcpf(den);
+  const float q0 = num * y;
+  const float q = __builtin_fmaf(__builtin_fmaf(-den, q0, num), y, q0);
+  const float t = mid ? q : a;
+  const float z = t * t;
+  const float p = rt_fmaf(rt_fmaf(rt_fmaf(8.05374449538e-2f, z, -1.38776856032E-1f), z, 1.99777106478E-1f), z, -3.33329491539E-1f);
+  return yb + rt_fmaf(p * z, t, t);
+}
+
+// rt_atan2f(y, x) with atan_pos_dev() inside; y / x is a division of two operands and stays the IEEE sequence, the zero and sign
+// cases are rt_math.h's line by line.
+__device__ __forceinline__ float atan2_dev(float y, float x) {
+  if (x == 0.0f) {
+    if (y > 0.0f) return 1.5707963267948966192f;
+    if (y < 0.0f) return -1.5707963267948966192f;
+    return 0.0f;
+  }
+  if (y == 0.0f) return x < 0.0f ? RT_PI : 0.0f;
+  float q = y / x;
+  float a = atan_pos_dev(rt_absf(q));
+  if (q < 0.0f) a = -a;
+  float w = 0.0f;
+  if (x < 0.0f) w = (y < 0.0f) ? -RT_PI : RT_PI;
+  return w + a;
+}
+
+// rt_v3_normalize() (rt_math.h: v * (1 / sqrt(v.v))) with the inverse length from inv_sqrt_exact(): same bits.
+__device__ __forceinline__ rt_v3 normalize_dev(rt_v3 v) { return rt_v3_scale(v, inv_sqrt_exact(rt_v3_dot(v, v))); }
 
 // rt_accum_quantize() (rt_math.h: clamp to [0, 2^20], times 2^32 in double, truncate to u64) by shifts of the mantissa:
 // mantissa << 29 is the value at exponent field 147 (2^20), one right shift brings it to its own exponent.  Same integer
@@ -656,11 +750,18 @@ __device__ __forceinline__ rt_v3 texel_rgb(uint32_t t) {
 struct TexTaps { int i00, i10, i01, i11; float a, b; };
 struct TexQuad { uint32_t q00, q10, q01, q11; };
 
+// one coordinate's wrap rules: WRAP = false leaves out the negative-coordinate wrap, for a caller whose coordinates are never
+// negative (background_lookup(): bg_coord_u / bg_coord_v); NaN passes the wrap untouched either way
+template <bool WRAP>
+__device__ __forceinline__ float tex_wrap_fract(float t) {
+  if (WRAP && t < 0) t += (float)(-(int)t + 1);
+  return rt_fractf(t);
+}
+
+template <bool WRAP = true>
 __device__ __forceinline__ TexTaps tex_taps(const RT_DTexture &T, float tx, float ty) {
-  if (tx < 0) tx += (float)(-(int)tx + 1);
-  if (ty < 0) ty += (float)(-(int)ty + 1);
-  tx = rt_fractf(tx);
-  ty = rt_fractf(ty);
+  tx = tex_wrap_fract<WRAP>(tx);
+  ty = tex_wrap_fract<WRAP>(ty);
   float px = tx * (float)T.width;
   float py = ty * (float)T.height;
   int u = (int)px, v = (int)py;
@@ -690,7 +791,7 @@ __device__ __forceinline__ rt_v3 tex_combine(const TexQuad &q, const TexTaps &t)
   return rt_v3_lerp(c0, c1, t.b);
 }
 
-template <class PT>
+template <bool WRAP = true, class PT>
 __device__ __forceinline__ rt_v3 tex_bilinear(const PT &P, int tex, float tx, float ty) {
   RT_DTexture T;
   // the descriptor of a texture every lane of the block samples comes through the scalar cache (see shade())
@@ -702,7 +803,7 @@ __device__ __forceinline__ rt_v3 tex_bilinear(const PT &P, int tex, float tx, fl
   } else {
     T = P.textures[tex];
   }
-  const TexTaps t = tex_taps(T, tx, ty);
+  const TexTaps t = tex_taps<WRAP>(T, tx, ty);
   const TexQuad q = tex_fetch(P.texels + T.offset, t);
   return tex_combine(q, t);
 }
@@ -760,14 +861,17 @@ __device__ __forceinline__ rt_v3 srgb_to_linear_tex(rt_v3 v) {
   return rt_v3_make(srgb_to_linear_tex1<POW24_LDS>(v.x), srgb_to_linear_tex1<POW24_LDS>(v.y), srgb_to_linear_tex1<POW24_LDS>(v.z));
 }
 
-// driver.c:95-104
+// driver.c:95-104.  The two coordinates as functions of the angle: for every float atan2_dev() can return (|t| <= RT_PI, or NaN)
+// u is never negative, and neither is v for every float asin_dev() can return (|t| <= pi/2 as a float, or NaN) -- RT_PI as a
+// float exceeds pi by 2.8e-8 of it, but RN(1 / 2 pi) and RN(1 / pi) fall short by 4.0e-8 -- so tex_taps' negative-coordinate wrap
+// never fires (rt_test_env_sweep compares wrap + fract with fract alone over all those angles) and the lookup leaves it out.
+__device__ __forceinline__ float bg_coord_u(float t) { return rt_madd(t, 1.0f / (2.0f * RT_PI), 0.5f); }
+__device__ __forceinline__ float bg_coord_v(float t) { return rt_madd(-t, 1.0f / RT_PI, 0.5f); }
 template <class PT>
 __device__ __forceinline__ rt_v3 background_lookup(const PT &P, rt_v3 dir) {
-  float inv_pi = 1.0f / RT_PI;
-  float inv_two_pi = 1.0f / (2.0f * RT_PI);
-  float u = rt_madd(rt_atan2f(dir.z, dir.x), inv_two_pi, 0.5f);
-  float v = rt_madd(-rt_asinf(dir.y), inv_pi, 0.5f);
-  return srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_bilinear(P, P.bg_texture, u, v));
+  float u = bg_coord_u(atan2_dev(dir.z, dir.x));
+  float v = bg_coord_v(asin_dev(dir.y));
+  return srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_bilinear<false>(P, P.bg_texture, u, v));
 }
 
 // ---------------------------------------------------------------------------------
@@ -785,31 +889,31 @@ __device__ __forceinline__ float ggx_D(float roughness, float NoH) {          //
 __device__ __forceinline__ float smith_G(float NDotV, float alpha2) {         // driver.c:217-221
   float a = alpha2 * alpha2;
   float b = NDotV * NDotV;
-  return (2.0f * NDotV) / (NDotV + rt_sqrtf(rt_madd(-a, b, a + b)));
+  return (2.0f * NDotV) / (NDotV + sqrt_dev(rt_madd(-a, b, a + b)));
 }
 
 __device__ __forceinline__ rt_v3 cosine_hemisphere(uint32_t &rng) {           // driver.c:118-127
   float angle = rt_rand_f32(&rng) * 2.0f * RT_PI;
-  float distance = rt_sqrtf(rt_rand_f32(&rng));
+  float distance = sqrt_dev(rt_rand_f32(&rng));
   float s, c;
   rt_sincosf(angle, &s, &c);
-  return rt_v3_make(s * distance, c * distance, rt_sqrtf(rt_madd(-distance, distance, 1.0f)));
+  return rt_v3_make(s * distance, c * distance, sqrt_dev(rt_madd(-distance, distance, 1.0f)));
 }
 
 __device__ __forceinline__ rt_v3 ggx_vndf(rt_v3 V, float ax, float ay, uint32_t &rng) {  // driver.c:230-250
   rt_v3 Vh = normalize_dev(rt_v3_make(ax * V.x, ay * V.y, V.z));
   float lensq = rt_dot2(Vh.x, Vh.x, Vh.y, Vh.y);
-  rt_v3 T1 = lensq > 0.0f ? rt_v3_scale(rt_v3_make(-Vh.y, Vh.x, 0.0f), rcp_exact(rt_sqrtf(lensq))) : rt_v3_make(1, 0, 0);
+  rt_v3 T1 = lensq > 0.0f ? rt_v3_scale(rt_v3_make(-Vh.y, Vh.x, 0.0f), inv_sqrt_exact(lensq)) : rt_v3_make(1, 0, 0);
   rt_v3 T2 = rt_v3_cross(Vh, T1);
-  float r = rt_sqrtf(rt_rand_f32(&rng));
+  float r = sqrt_dev(rt_rand_f32(&rng));
   float phi = 2.0f * RT_PI * rt_rand_f32(&rng);
   float sn, cs;
   rt_sincosf(phi, &sn, &cs);
   float t1 = r * cs;
   float t2 = r * sn;
   float s = rt_madd(0.5f, Vh.z, 0.5f);
-  t2 = rt_madd(1.0f - s, rt_sqrtf(rt_madd(-t1, t1, 1.0f)), s * t2);
-  rt_v3 Nh = rt_v3_comb3(T1, t1, T2, t2, Vh, rt_sqrtf(rt_max_ps(0.0f, rt_madd(-t2, t2, rt_madd(-t1, t1, 1.0f)))));
+  t2 = rt_madd(1.0f - s, sqrt_dev(rt_madd(-t1, t1, 1.0f)), s * t2);
+  rt_v3 Nh = rt_v3_comb3(T1, t1, T2, t2, Vh, sqrt_dev(rt_max_ps(0.0f, rt_madd(-t2, t2, rt_madd(-t1, t1, 1.0f)))));
   return normalize_dev(rt_v3_make(ax * Nh.x, ay * Nh.y, rt_max_ps(0.0f, Nh.z)));
 }
 
@@ -1018,8 +1122,7 @@ __device__ __forceinline__ void primary_ray(const PT &P, int x, int y, int sampl
   float uvx = rt_madd(((float)x + jitter - 0.5f) * 2.0f, inv_width, -1.0f);
   float uvy = rt_madd(((float)y + jitter - 0.5f) * 2.0f, inv_height, -1.0f);
   float dx = uvx * aspect, dy = -uvy, dz = -P.focal_length;
-  // (rcp_exact: a square root lies in [0, 2^64] or is infinite / NaN -- inside the domain on which it equals the division)
-  float inv_length = rcp_exact(rt_sqrtf(rt_dot3(dx, dx, dy, dy, dz, dz)));
+  float inv_length = inv_sqrt_exact(rt_dot3(dx, dx, dy, dy, dz, dz));
   float rx = rt_dot3(P.cam[0][0], dx, P.cam[0][1], dy, P.cam[0][2], dz);
   float ry = rt_dot3(P.cam[1][0], dx, P.cam[1][1], dy, P.cam[1][2], dz);
   float rz = rt_dot3(P.cam[2][0], dx, P.cam[2][1], dy, P.cam[2][2], dz);

@@ -13,6 +13,7 @@ extern "C" {
 int rt_launch_test_math(int op, int n, const float *x, const float *y, float *out, hipStream_t stream);
 int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_srgb_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_env_sweep(int which, uint32_t seed, unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_sky_add_group(void);
 int rt_launch_test_group_sum(int group, int n_waves, const unsigned long long *in, const unsigned char *valid, unsigned long long *out,
@@ -244,6 +245,25 @@ extern "C" int rt_test_rcp_sweep(u64 out[6]) { return run_sweep(rt_launch_test_r
 // rt_srgb_to_linear1() for every float in [0, 2] (and 4 M negative ones): out[0] patterns compared, out[1] differing (0 expected),
 // out[2] first differing pattern + 1.
 extern "C" int rt_test_srgb_sweep(u64 out[3]) { return run_sweep(rt_launch_test_srgb_sweep, "rt_test_srgb_sweep", out, 3); }
+
+// The short forms of the environment lookup and the normalisations (atan_pos_dev, asin_dev, inv_sqrt_exact, the background's
+// coordinates without the negative wrap, sqrt_dev: which = 0 .. 5) against the rt_math.h functions over all 2^32 bit patterns, and
+// atan2_dev against rt_atan2f on 2^26 pairs drawn from `seed` (which = 6): out[0] patterns or pairs compared, out[1] differing
+// (0 expected), out[2] first differing pattern or pair index + 1, out[3] differing when a NaN must keep its bits (rt_hip_diag.h).
+extern "C" int rt_test_env_sweep(i32 which, u32 seed, u64 out[4]) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  if (which < 0 || which > 6 || !out) return rt_fail("rt_test_env_sweep: bad arguments");
+  DevMem<unsigned long long> b;
+  HIP_TRY(b.grow(4));
+  HIP_TRY(hipMemset(b, 0, 4 * sizeof(unsigned long long)));
+  int rc = rt_launch_test_env_sweep(which, seed, b, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, b, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_env_sweep failed: %s", hipGetErrorString((hipError_t)rc));
+  if (out[2]) out[2] = 0x100000000ull - out[2] + 1;          // the kernel keeps 2^32 - the lowest differing pattern
+  return 0;
+}
 
 // The tile-stream kernel's shift-based fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit
 // patterns: out[0] differing patterns (0 expected), out[1] first differing pattern + 1.

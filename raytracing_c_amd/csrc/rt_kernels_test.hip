@@ -25,6 +25,11 @@ __global__ void rt_test_math_kernel(int op, int n, const float *x, const float *
   case 11: r = rcp_exact(a); break;
   case 12: r = rcp_exact_outside(a) ? 1.0f : 0.0f; break;
   case 13: r = srgb_to_linear_tex1(a); break;
+  case 14: r = atan2_dev(a, b); break;
+  case 15: r = atan_pos_dev(a); break;
+  case 16: r = asin_dev(a); break;
+  case 17: r = inv_sqrt_exact(a); break;
+  case 18: r = sqrt_dev(a); break;
   default: break;
   }
   out[i] = r;
@@ -130,6 +135,84 @@ __global__ void rt_test_srgb_sweep_kernel(unsigned long long *counts) {
   atomicAdd(&counts[0], (unsigned long long)n);
   if (bad) atomicAdd(&counts[1], (unsigned long long)bad);
   if (first) atomicMax(&counts[2], (unsigned long long)first);
+}
+
+// The short forms of the environment lookup and of the normalisations (rt_dev.hip.h) against the UNMODIFIED rt_math.h functions,
+// compiled here for the device.  WHICH 0 .. 5 walk all 2^32 bit patterns x:
+//   0  atan_pos_dev(x)    against rt_atanf_pos(x)
+//   1  asin_dev(x)        against rt_asinf(x)
+//   2  inv_sqrt_exact(x)  against rcp_exact(rt_sqrtf(x)), and against the division 1.0f / rt_sqrtf(x) that rcp_exact() stands for
+//   3  the background's u for the angle x, tex_wrap_fract<false>(bg_coord_u(x)) against tex_taps' wrap and fract
+//      tex_wrap_fract<true>(...), over every x atan2_dev() can return: |x| <= RT_PI, or NaN
+//   4  the same for v = bg_coord_v(x) over every x asin_dev() can return: |x| <= pi/2 (as a float), or NaN
+//   5  sqrt_dev(x)        against rt_sqrtf(x)
+// WHICH 6: atan2_dev(y, x) against rt_atan2f(y, x) on 2^26 pairs drawn from `seed`: even pairs two random bit patterns (every
+// exponent, so quotients that overflow, underflow and are NaN), odd pairs two random values of either sign between 2^-7 and 1
+// (quotients in all three ranges of the arctangent).
+// counts[0] = patterns (pairs) compared, [1] = differing ones, NaN equal to NaN, [2] = 2^32 - the LOWEST differing pattern (pair
+// index), 0 when there is none (a maximum over the threads; rt_test_env_sweep turns it into the pattern + 1), [3] = differing ones
+// when a NaN must have the same bits too.
+template <int WHICH>
+__device__ __forceinline__ bool env_form_pair(uint32_t b, uint32_t seed, float &want, float &got) {
+  const float x = __uint_as_float(b);
+  switch (WHICH) {
+  case 0: want = rt_atanf_pos(x); got = atan_pos_dev(x); return true;
+  case 1: want = rt_asinf(x); got = asin_dev(x); return true;
+  case 2: want = rcp_exact(rt_sqrtf(x)); got = inv_sqrt_exact(x); return true;
+  case 3: want = tex_wrap_fract<true>(bg_coord_u(x)); got = tex_wrap_fract<false>(bg_coord_u(x)); return !(__builtin_fabsf(x) > RT_PI);
+  case 4: want = tex_wrap_fract<true>(bg_coord_v(x)); got = tex_wrap_fract<false>(bg_coord_v(x)); return !(__builtin_fabsf(x) > 1.5707963267948966192f);
+  case 5: want = rt_sqrtf(x); got = sqrt_dev(x); return true;
+  default: {
+    uint32_t by = rt_pcg(seed ^ (2u * b)), bx = rt_pcg(seed ^ (2u * b + 1u));
+    if (b & 1u) {
+      by = (by & 0x807FFFFFu) | ((120u + ((by >> 23) & 7u)) << 23);
+      bx = (bx & 0x807FFFFFu) | ((120u + ((bx >> 23) & 7u)) << 23);
+    }
+    want = rt_atan2f(__uint_as_float(by), __uint_as_float(bx));
+    got = atan2_dev(__uint_as_float(by), __uint_as_float(bx));
+    return true;
+  }
+  }
+}
+
+template <int WHICH>
+__global__ void rt_test_env_sweep_kernel(uint32_t per_thread, uint32_t seed, unsigned long long *counts) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t n = 0, bad = 0, strict = 0;
+  unsigned long long first = 0;
+  for (uint32_t k = 0; k < per_thread; k++) {
+    const uint32_t b = tid * per_thread + k;
+    float want, got;
+    if (!env_form_pair<WHICH>(b, seed, want, got)) continue;
+    if (WHICH == 2) {                                   // ... and the division itself
+      const float q = 1.0f / rt_sqrtf(__uint_as_float(b));
+      const bool q_nan = q != q;
+      if (q_nan ? got == got : __float_as_uint(q) != __float_as_uint(got)) { bad += 1; if (!first) first = (unsigned long long)b + 1ull; }
+    }
+    const uint32_t w = __float_as_uint(want), g = __float_as_uint(got);
+    const bool w_nan = (w & 0x7FFFFFFFu) > 0x7F800000u, g_nan = (g & 0x7FFFFFFFu) > 0x7F800000u;
+    n += 1;
+    if (w_nan ? !g_nan : g != w) { bad += 1; if (!first) first = (unsigned long long)b + 1ull; }
+    strict += (g != w) ? 1u : 0u;
+  }
+  atomicAdd(&counts[0], (unsigned long long)n);
+  if (bad) atomicAdd(&counts[1], (unsigned long long)bad);
+  if (first) atomicMax(&counts[2], 0x100000000ull - (first - 1ull));
+  if (strict) atomicAdd(&counts[3], (unsigned long long)strict);
+}
+
+extern "C" int rt_launch_test_env_sweep(int which, uint32_t seed, unsigned long long *counts, hipStream_t stream) {
+  const dim3 grid(65536), block(256);                  // 2^24 threads: 256 patterns each, or 4 pairs each
+  switch (which) {
+  case 0: hipLaunchKernelGGL(rt_test_env_sweep_kernel<0>, grid, block, 0, stream, 256u, seed, counts); break;
+  case 1: hipLaunchKernelGGL(rt_test_env_sweep_kernel<1>, grid, block, 0, stream, 256u, seed, counts); break;
+  case 2: hipLaunchKernelGGL(rt_test_env_sweep_kernel<2>, grid, block, 0, stream, 256u, seed, counts); break;
+  case 3: hipLaunchKernelGGL(rt_test_env_sweep_kernel<3>, grid, block, 0, stream, 256u, seed, counts); break;
+  case 4: hipLaunchKernelGGL(rt_test_env_sweep_kernel<4>, grid, block, 0, stream, 256u, seed, counts); break;
+  case 5: hipLaunchKernelGGL(rt_test_env_sweep_kernel<5>, grid, block, 0, stream, 256u, seed, counts); break;
+  default: hipLaunchKernelGGL(rt_test_env_sweep_kernel<6>, grid, block, 0, stream, 4u, seed, counts); break;
+  }
+  return (int)hipGetLastError();
 }
 
 __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_trace_kernel(RT_KParams P, int n, const float *rays,
