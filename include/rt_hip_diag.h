@@ -126,6 +126,27 @@ extern int rt_test_texture(RT_Device_Scene *dscene, i32 tex, i32 n, f32 const *u
  * vector loads: the caller decides which by the order of its items. */
 extern int rt_test_shade(RT_Device_Scene *dscene, i32 mode, i32 n, i32 const *tri, f32 const *in, u32 const *state_in,
                          f32 *out, u32 *state_out, i32 *terminate, i32 *textured);
+/* ONE PATH STEP on hits a test chooses: shade_hit() -- raytracer.c:515-552 and the `for` of :510: face test, the surface at the
+ * hit (surface_at), shade(), carried tint and emission, the next origin, the bounce count.  CPU counterpart: oracle_fill_hit +
+ * oracle_path_step (tests/test_gpu_shade_hit.py).
+ *   mode        0 = shade_hit<ShadeParams> (the wavefront shade kernel's), 1 = <ShadeParamsLds> (the path kernel's), 2 =
+ *               <RT_KParams> (cast_ray_lane's, the lightmap)
+ *   max_bounces what the step's exhaustion rule compares with
+ *   tri[n]      triangle slot of the hit; hit = 3 floats per item: t, u, v; ray = 6: origin, direction; carry = 6: tint, emission;
+ *               state_in[n] the RNG state, bounce_in[n] the bounce count before the step
+ *   out         15 floats per item: origin, direction, tint, emission as they stand afterwards, radiance (-1, -2, -3 where the
+ *               step did not write it)
+ *   out_words   5 words per item: RNG state, bounce, done (0 / 1), the increments of the `shades` and `textured` counters
+ * Refused with a message: a slot outside the scene or without a triangle, vertex texture coordinates that are not finite, and
+ * barycentrics that make the interpolated texture coordinates non-finite.  Everything else -- NaN directions, zero normals,
+ * infinite distances -- is the function's business.  LANE LAYOUT as rt_test_shade: item i is lane i & 63 of wave i >> 6, so the
+ * order of the items decides which lanes are inside shade_hit()'s `else` when shade() takes its ballot. */
+extern int rt_test_shade_hit(RT_Device_Scene *dscene, i32 mode, i32 max_bounces, i32 n, i32 const *tri, f32 const *hit, f32 const *ray,
+                             f32 const *carry, u32 const *state_in, i32 const *bounce_in, f32 *out, u32 *out_words);
+/* feature_hit<ShadeParamsLds>() (rt_features.hip: the feature kernel's copy of the face test and the pass-through) on the same
+ * kind of item.  out = 12 floats per item: origin afterwards, albedo, normal, position (zero on a back face); flag[n] = what it
+ * returned (1 = a feature hit, 0 = passed through).  Refuses what rt_test_shade_hit refuses. */
+extern int rt_test_feature_hit(RT_Device_Scene *dscene, i32 n, i32 const *tri, f32 const *hit, f32 const *ray, f32 *out, i32 *flag);
 /* sample_disney() (driver.c:287-348) on raw parameters: params = 8 floats per item (roughness, metalness, sheen, sheen_tint,
  * aniso2, base colour), in_dir = 3; out_dir = 3, brdf = 4 per item (rgb and the weight-pdf; <= 0 ends the path) */
 extern int rt_test_brdf(i32 n, f32 const *params, f32 const *in_dir, u32 const *state_in, f32 *out_dir, f32 *brdf, u32 *state_out);

@@ -90,10 +90,31 @@ static void ray_triangles_8_scalar(Ray const *ray, Triangles const *triangles, i
   }
 }
 
+/* raytracer.c:160-186: the fill of `Hit` for triangle `t` accepted at `distance` with barycentrics (t1, t2) */
+static void fill_hit(Ray const *ray, Triangles const *triangles, f32 distance, isize t, f32 t1, f32 t2, Hit *hit) {
+  rt_v3 dir = V(ray->direction), org = V(ray->position);
+  Triangle_AOS const *aos = &triangles->aos[t];
+
+  hit->distance = distance;
+  f32 t0 = 1.0f - t1 - t2;
+  tl_bary_u = t1;
+  tl_bary_v = t2;
+
+  hit->point = U(rt_v3_madd(dir, distance, org));
+  hit->normal.x = rt_dot3(aos->normal_a.x, t0, aos->normal_b.x, t1, aos->normal_c.x, t2);
+  hit->normal.y = rt_dot3(aos->normal_a.y, t0, aos->normal_b.y, t1, aos->normal_c.y, t2);
+  hit->normal.z = rt_dot3(aos->normal_a.z, t0, aos->normal_b.z, t1, aos->normal_c.z, t2);
+  hit->tex_coords.x = rt_dot3(aos->tex_coords_a.x, t0, aos->tex_coords_b.x, t1, aos->tex_coords_c.x, t2);
+  hit->tex_coords.y = rt_dot3(aos->tex_coords_a.y, t0, aos->tex_coords_b.y, t1, aos->tex_coords_c.y, t2);
+  hit->shader     = aos->shader;
+  hit->normal_geo = aos->normal;
+  hit->tangent    = aos->tangent;
+  hit->bitangent  = aos->bitangent;
+}
+
 /* raytracer.c:157-187: horizontal minimum, closer-hit test and the fill of `Hit` (scalar in the reference as well) */
 static bool ray_triangles_hit_8_fill(Ray const *ray, Triangles const *triangles, isize offset, Hit *hit, i32 *lane_out,
                                      f32 const us[8], f32 const vs[8], f32 const distances[8]) {
-  rt_v3 dir = V(ray->direction), org = V(ray->position);
   i32 triangle_index;
   f32 min;
 #if ORACLE_HAVE_AVX2
@@ -103,26 +124,8 @@ static bool ray_triangles_hit_8_fill(Ray const *ray, Triangles const *triangles,
     min = min_f32x8(distances, 0.0f, &triangle_index);
 
   if (min < hit->distance) {
-    hit->distance = min;
     isize t = triangle_index + offset;
-    Triangle_AOS const *aos = &triangles->aos[t];
-
-    f32 t1 = us[triangle_index];
-    f32 t2 = vs[triangle_index];
-    f32 t0 = 1.0f - t1 - t2;
-    tl_bary_u = t1;
-    tl_bary_v = t2;
-
-    hit->point = U(rt_v3_madd(dir, min, org));
-    hit->normal.x = rt_dot3(aos->normal_a.x, t0, aos->normal_b.x, t1, aos->normal_c.x, t2);
-    hit->normal.y = rt_dot3(aos->normal_a.y, t0, aos->normal_b.y, t1, aos->normal_c.y, t2);
-    hit->normal.z = rt_dot3(aos->normal_a.z, t0, aos->normal_b.z, t1, aos->normal_c.z, t2);
-    hit->tex_coords.x = rt_dot3(aos->tex_coords_a.x, t0, aos->tex_coords_b.x, t1, aos->tex_coords_c.x, t2);
-    hit->tex_coords.y = rt_dot3(aos->tex_coords_a.y, t0, aos->tex_coords_b.y, t1, aos->tex_coords_c.y, t2);
-    hit->shader     = aos->shader;
-    hit->normal_geo = aos->normal;
-    hit->tangent    = aos->tangent;
-    hit->bitangent  = aos->bitangent;
+    fill_hit(ray, triangles, min, t, us[triangle_index], vs[triangle_index], hit);
     if (lane_out) *lane_out = (i32)t;
     return true;
   }
@@ -666,6 +669,48 @@ static void oracle_debug_shader_proc(rawptr _data, Shader_Input const *input, Sh
 }
 
 /* ------------------------------------------------------------------------- */
+/* raytracer.c:515-551  the hit arm of one path's loop body: face test, shader input, shader call, carried tint and
+ * emission, next origin.  Returns true where the reference `break`s (the shader terminated the path); false where it
+ * `continue`s or falls through to the next iteration. */
+static bool path_hit(Oracle_Config const *cfg, Ray *ray, Hit const *hit, rt_v3 *accumulated_tint, rt_v3 *emission) {
+  rt_v3 rd = V(ray->direction);
+  if (rt_v3_dot(V(hit->normal_geo), rd) > 0.0f || rt_v3_dot(V(hit->normal), rd) > 0.0f) {
+    ray->position = U(rt_v3_madd(rd, RT_EPS, V(hit->point)));
+    return false;
+  }
+
+  Shader_Input shader_input;
+  shader_input.direction  = ray->direction;
+  shader_input.normal     = U(rt_v3_normalize(V(hit->normal)));
+  shader_input.normal_geo = hit->normal_geo;
+  shader_input.tangent    = hit->tangent;
+  shader_input.bitangent  = hit->bitangent;
+  shader_input.position   = hit->point;
+  shader_input.tex_coords = hit->tex_coords;
+  Shader_Output shader_output;
+  memset(&shader_output, 0, sizeof shader_output);
+
+  tl_counters.shades += 1;
+  if (hit->shader.proc == cfg->disney_proc && cfg->disney_proc) {
+    oracle_disney_shader_proc(hit->shader.data, &shader_input, &shader_output);
+  } else if (hit->shader.proc == cfg->debug_proc && cfg->debug_proc) {
+    oracle_debug_shader_proc(hit->shader.data, &shader_input, &shader_output);
+  } else {
+    hit->shader.proc(hit->shader.data, &shader_input, &shader_output);
+  }
+
+  *emission = rt_v3_mul_add(V(shader_output.emission), *accumulated_tint, *emission);
+  if (shader_output.terminate) return true;
+
+  ray->direction    = shader_output.direction;
+  *accumulated_tint = rt_v3_mul(*accumulated_tint, V(shader_output.tint));
+
+  f32 below = (rt_v3_dot(V(hit->normal_geo), V(shader_output.direction)) < 0.0f) ? 1.0f : 0.0f;
+  f32 position_bias = (0.5f - below) * 2.0f * RT_EPS;
+  ray->position = U(rt_v3_madd(V(hit->normal_geo), position_bias, V(hit->point)));
+  return false;
+}
+
 /* raytracer.c:505-558  one path                                              */
 static rt_v3 cast_ray(Scene const *scene, Oracle_Config const *cfg, Ray ray, isize max_bounces) {
   rt_v3 accumulated_tint = rt_v3_make(1, 1, 1);
@@ -677,41 +722,7 @@ static rt_v3 cast_ray(Scene const *scene, Oracle_Config const *cfg, Ray ray, isi
     hit.distance = RT_INF;
     ray_scene_hit(&ray, scene, &hit, NULL);
     if (hit.distance != RT_INF) {
-      rt_v3 rd = V(ray.direction);
-      if (rt_v3_dot(V(hit.normal_geo), rd) > 0.0f || rt_v3_dot(V(hit.normal), rd) > 0.0f) {
-        ray.position = U(rt_v3_madd(rd, RT_EPS, V(hit.point)));
-        continue;
-      }
-
-      Shader_Input shader_input;
-      shader_input.direction  = ray.direction;
-      shader_input.normal     = U(rt_v3_normalize(V(hit.normal)));
-      shader_input.normal_geo = hit.normal_geo;
-      shader_input.tangent    = hit.tangent;
-      shader_input.bitangent  = hit.bitangent;
-      shader_input.position   = hit.point;
-      shader_input.tex_coords = hit.tex_coords;
-      Shader_Output shader_output;
-      memset(&shader_output, 0, sizeof shader_output);
-
-      tl_counters.shades += 1;
-      if (hit.shader.proc == cfg->disney_proc && cfg->disney_proc) {
-        oracle_disney_shader_proc(hit.shader.data, &shader_input, &shader_output);
-      } else if (hit.shader.proc == cfg->debug_proc && cfg->debug_proc) {
-        oracle_debug_shader_proc(hit.shader.data, &shader_input, &shader_output);
-      } else {
-        hit.shader.proc(hit.shader.data, &shader_input, &shader_output);
-      }
-
-      emission = rt_v3_mul_add(V(shader_output.emission), accumulated_tint, emission);
-      if (shader_output.terminate) break;
-
-      ray.direction    = shader_output.direction;
-      accumulated_tint = rt_v3_mul(accumulated_tint, V(shader_output.tint));
-
-      f32 below = (rt_v3_dot(V(hit.normal_geo), V(shader_output.direction)) < 0.0f) ? 1.0f : 0.0f;
-      f32 position_bias = (0.5f - below) * 2.0f * RT_EPS;
-      ray.position = U(rt_v3_madd(V(hit.normal_geo), position_bias, V(hit.point)));
+      if (path_hit(cfg, &ray, &hit, &accumulated_tint, &emission)) break;
     } else {
       tl_counters.backgrounds += 1;
       rt_v3 bg;
@@ -1020,6 +1031,36 @@ void oracle_cast_ray(Scene const *scene, Oracle_Config const *config, Ray const 
   rt_v3 c = cast_ray(scene, config, *ray, max_bounces);
   *state = random_state;
   rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+}
+
+/* raytracer.c:160-186 on its own: the `Hit` of a hit the caller names (triangle, distance, barycentrics) */
+void oracle_fill_hit(Scene const *scene, Ray const *ray, f32 t, i32 triangle, f32 u, f32 v, Hit *out) {
+  memset(out, 0, sizeof *out);
+  fill_hit(ray, &scene->triangles, t, triangle, u, v, out);
+}
+
+/* One iteration of cast_ray()'s loop for a ray that hit: path_hit(), then -- unless the shader ended the path -- the `for`'s
+ * increment and its exhaustion rule (the path's value is `emission` when the loop breaks or runs out).  *done is set to 1 with `radiance` written when the
+ * path ended here, else to 0 with `radiance` left alone.  counters = { shades, textured } this step added. */
+void oracle_path_step(Scene const *scene, Oracle_Config const *config, Ray *ray, Hit const *hit, f32 tint[3], f32 emission[3],
+                      u32 *state, i32 *bounce, isize max_bounces, i32 *done, f32 radiance[3], u64 counters[2]) {
+  (void)scene;
+  u64 s0 = tl_counters.shades, x0 = tl_counters.textured;
+  rt_v3 at = rt_v3_make(tint[0], tint[1], tint[2]);
+  rt_v3 em = rt_v3_make(emission[0], emission[1], emission[2]);
+  random_state = *state;
+  bool stop = path_hit(config, ray, hit, &at, &em);
+  *state = random_state;
+  if (!stop) {                             /* (a `break` leaves the loop before its increment) */
+    *bounce += 1;
+    if (*bounce >= max_bounces) stop = true;
+  }
+  tint[0] = at.x; tint[1] = at.y; tint[2] = at.z;
+  emission[0] = em.x; emission[1] = em.y; emission[2] = em.z;
+  *done = stop ? 1 : 0;
+  if (stop) { radiance[0] = em.x; radiance[1] = em.y; radiance[2] = em.z; }
+  counters[0] = tl_counters.shades - s0;
+  counters[1] = tl_counters.textured - x0;
 }
 
 /* driver.c:411-418 on its own */

@@ -127,6 +127,15 @@ u8   oracle_encode_u8(f32 linear);
 int  oracle_set_literal(int on);
 /* raytracer.c:505-558 from a given ray and RNG state, in the mode oracle_set_literal selected */
 void oracle_cast_ray(Scene const *scene, Oracle_Config const *config, Ray const *ray, isize max_bounces, u32 *state, f32 rgb[3]);
+/* raytracer.c:160-186: the fill of `Hit` for a hit the caller names: triangle index, distance t and barycentrics (u, v) =
+ * (t1, t2); the code ray_triangles_hit_8 runs for the hit it accepts */
+void oracle_fill_hit(Scene const *scene, Ray const *ray, f32 t, i32 triangle, f32 u, f32 v, Hit *out);
+/* raytracer.c:515-551 + the `for` of :510: ONE iteration of cast_ray's loop for a ray whose closest hit is `hit` (the very
+ * function cast_ray calls), then the bounce increment and the exhaustion rule.  ray, tint, emission, *state (the RNG) and
+ * *bounce are carried in and out; *done = 1 and radiance = emission when the shader terminated or *bounce reached
+ * max_bounces, else *done = 0 and radiance is left alone.  counters = { shades, textured } added by this step. */
+void oracle_path_step(Scene const *scene, Oracle_Config const *config, Ray *ray, Hit const *hit, f32 tint[3], f32 emission[3],
+                      u32 *state, i32 *bounce, isize max_bounces, i32 *done, f32 radiance[3], u64 counters[2]);
 /* driver.c:411-418 */
 void oracle_debug_shade(PBR_Shader_Data const *data, Shader_Input const *in, Shader_Output *out);
 /* raytracer.c:641-694: the primary ray of (x, y, sample) of a width x height frame, out = position, direction; always in the

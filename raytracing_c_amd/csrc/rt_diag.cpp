@@ -3,6 +3,9 @@
 #include "rt_host.h"
 
 #include <cmath>
+#include <vector>
+
+#include "../../include/rt_math.h"      // rt_dot3: the texture coordinates a hit interpolates, as the device computes them
 
 #ifndef RT_DIAG_VARIANTS
 #error rt_diag.cpp belongs to the diagnostic library only (-DRT_DIAG_VARIANTS)
@@ -27,6 +30,10 @@ int rt_launch_test_trace_stream(const RT_KParams *P, int n, const float *rays, c
 int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const float *uv, float *out, hipStream_t stream);
 int rt_launch_test_shade(const RT_KParams *P, int lds, int n, const int *tri, const float *in, const uint32_t *state_in, float *out,
                          uint32_t *state_out, int *terminate, int *textured, hipStream_t stream);
+int rt_launch_test_shade_hit(const RT_KParams *P, int mode, int n, const int *tri, const float *hit, const float *ray, const float *carry,
+                             const uint32_t *state_in, const int *bounce_in, float *out, uint32_t *iout, hipStream_t stream);
+int rt_launch_test_feature_hit(const RT_KParams *P, int n, const int *tri, const float *hit, const float *ray, float *out, int *flag,
+                               hipStream_t stream);
 int rt_launch_test_brdf(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir, float *brdf,
                         uint32_t *state_out, hipStream_t stream);
 int rt_launch_test_background(const RT_KParams *P, int lds, int n, const float *dir, float *rgb, hipStream_t stream);
@@ -476,6 +483,93 @@ extern "C" int rt_test_shade(RT_Device_Scene *d, i32 mode, i32 n, i32 const *tri
   if (rc == 0) rc = (int)hipMemcpy(terminate, dterm, (size_t)n * 4, hipMemcpyDeviceToHost);
   if (rc == 0) rc = (int)hipMemcpy(textured, dtex, (size_t)n * 4, hipMemcpyDeviceToHost);
   if (rc != 0) return rt_fail("rt_test_shade failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- one path step / one feature hit on hits a test chooses (shade_hit, feature_hit; tests/test_gpu_shade_hit.py) ----------
+
+// What both refuse, as rt_test_shade does: a slot outside the scene or without a material, vertex texture coordinates that are
+// not finite, and barycentrics that carry them to a texture coordinate that is not finite (a NaN converts to a texel index
+// differently on the two sides).  `rec`: the device scene's 28-float triangle records, read back.
+static int check_hit_items(const char *who, RT_Device_Scene *d, const std::vector<float> &rec, i32 n, i32 const *tri, f32 const *hit) {
+  for (i32 i = 0; i < n; i++) {
+    if (tri[i] < 0 || tri[i] >= d->n_triangles) return rt_fail("%s: item %d names triangle slot %d of %d", who, i, tri[i], d->n_triangles);
+    const float *r = &rec[(size_t)tri[i] * 28];
+    int32_t mat;
+    memcpy(&mat, r + 3, 4);
+    if (mat < 0 || mat >= d->n_materials) return rt_fail("%s: item %d triangle slot %d names no material of the scene", who, i, tri[i]);
+    const f32 ux[3] = {r[7], r[15], r[23]}, uy[3] = {r[11], r[19], r[24]};      // Surface::uvx / uvy (rt_dev.hip.h)
+    if (!all_finite(ux, 3) || !all_finite(uy, 3)) return rt_fail("%s: item %d: triangle slot %d has non-finite texture coordinates", who, i, tri[i]);
+    const f32 t1 = hit[(size_t)i * 3 + 1], t2 = hit[(size_t)i * 3 + 2], t0 = 1.0f - t1 - t2;
+    const f32 uv[2] = {rt_dot3(ux[0], t0, ux[1], t1, ux[2], t2), rt_dot3(uy[0], t0, uy[1], t1, uy[2], t2)};
+    if (!all_finite(uv, 2)) return rt_fail("%s: item %d: barycentrics (%g, %g) give non-finite texture coordinates", who, i, (double)t1, (double)t2);
+  }
+  return 0;
+}
+
+extern "C" int rt_test_shade_hit(RT_Device_Scene *d, i32 mode, i32 max_bounces, i32 n, i32 const *tri, f32 const *hit, f32 const *ray,
+                                 f32 const *carry, u32 const *state_in, i32 const *bounce_in, f32 *out, u32 *out_words) {
+  if (!d || n <= 0 || !tri || !hit || !ray || !carry || !state_in || !bounce_in || !out || !out_words) return rt_fail("rt_test_shade_hit: bad arguments");
+  if (mode < 0 || mode > 2) return rt_fail("rt_test_shade_hit: mode %d is not 0 (ShadeParams), 1 (ShadeParamsLds) or 2 (RT_KParams)", mode);
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  std::vector<float> rec((size_t)d->n_triangles * 28);
+  HIP_TRY(hipMemcpy(rec.data(), d->tris, rec.size() * 4, hipMemcpyDeviceToHost));
+  if (check_hit_items("rt_test_shade_hit", d, rec, n, tri, hit) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  K.max_bounces = max_bounces;
+  DevMem<int> dtri, dbounce;
+  DevMem<float> dhit, dray, dcarry, dout;
+  DevMem<uint32_t> ds0, dwords;
+  HIP_TRY(dtri.grow((size_t)n));
+  HIP_TRY(dbounce.grow((size_t)n));
+  HIP_TRY(dhit.grow((size_t)n * 3));
+  HIP_TRY(dray.grow((size_t)n * 6));
+  HIP_TRY(dcarry.grow((size_t)n * 6));
+  HIP_TRY(dout.grow((size_t)n * 15));
+  HIP_TRY(ds0.grow((size_t)n));
+  HIP_TRY(dwords.grow((size_t)n * 5));
+  HIP_TRY(hipMemcpy(dtri, tri, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dbounce, bounce_in, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dhit, hit, (size_t)n * 12, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dray, ray, (size_t)n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dcarry, carry, (size_t)n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ds0, state_in, (size_t)n * 4, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_shade_hit(&K, mode, n, dtri, dhit, dray, dcarry, ds0, dbounce, dout, dwords, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, (size_t)n * 60, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(out_words, dwords, (size_t)n * 20, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_shade_hit failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_test_feature_hit(RT_Device_Scene *d, i32 n, i32 const *tri, f32 const *hit, f32 const *ray, f32 *out, i32 *flag) {
+  if (!d || n <= 0 || !tri || !hit || !ray || !out || !flag) return rt_fail("rt_test_feature_hit: bad arguments");
+  Device &D = *d->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (ensure_device(D) != 0) return -1;
+  std::vector<float> rec((size_t)d->n_triangles * 28);
+  HIP_TRY(hipMemcpy(rec.data(), d->tris, rec.size() * 4, hipMemcpyDeviceToHost));
+  if (check_hit_items("rt_test_feature_hit", d, rec, n, tri, hit) != 0) return -1;
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  DevMem<int> dtri, dflag;
+  DevMem<float> dhit, dray, dout;
+  HIP_TRY(dtri.grow((size_t)n));
+  HIP_TRY(dflag.grow((size_t)n));
+  HIP_TRY(dhit.grow((size_t)n * 3));
+  HIP_TRY(dray.grow((size_t)n * 6));
+  HIP_TRY(dout.grow((size_t)n * 12));
+  HIP_TRY(hipMemcpy(dtri, tri, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dhit, hit, (size_t)n * 12, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dray, ray, (size_t)n * 24, hipMemcpyHostToDevice));
+  int rc = rt_launch_test_feature_hit(&K, n, dtri, dhit, dray, dout, dflag, nullptr);
+  if (rc == 0) rc = (int)hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost);
+  if (rc == 0) rc = (int)hipMemcpy(flag, dflag, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (rc != 0) return rt_fail("rt_test_feature_hit failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 

@@ -5,6 +5,17 @@
 
 #include "rt_dev.hip.h"
 
+// feature_hit() is defined beside its kernel in rt_features.hip.  This unit reads that file as it is, so that
+// rt_test_feature_hit_kernel below instantiates the same feature_hit() text; the diagnostic library links rt_features_dev.o too,
+// which has the real kernels and launchers, so here the kernels go into an unnamed namespace and the two launchers -- declared
+// static first, which their definitions inherit -- stay local to this object.
+namespace {
+static int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
+static int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo,
+                                      float *normal, float *position, hipStream_t stream);
+#include "rt_features.hip"
+}
+
 __global__ void rt_test_math_kernel(int op, int n, const float *x, const float *y, float *out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -286,6 +297,88 @@ __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_shade_kernel(RT_KPar
   textured[i] = (int)cn.textured;
 }
 
+// One path step on a hit a test chooses: shade_hit<PT>() -- face test, surface_at(), shade(), carried tint and emission, the next
+// origin, the bounce count -- for PT = ShadeParams (the wavefront shade kernel's), ShadeParamsLds (the path kernel's: the sRGB
+// scale table in LDS, filled before the barrier) and RT_KParams (cast_ray_lane's, the lightmap).  Item i is lane i & 63 of wave
+// i >> 6 as in rt_test_shade_kernel; the lanes past n have left before shade_hit(), so which lanes are active inside its `else`
+// -- the lanes shade()'s ballot sees -- is decided by the order of the items alone.
+//   hit  t, u, v           ray  origin, direction        carry  tint, emission
+//   out  15 floats: origin, direction, tint, emission, radiance (as they stand afterwards; radiance starts as -1, -2, -3)
+//   iout 5 words: rng, bounce, done, shades increment, textured increment
+template <class PT>
+__device__ __forceinline__ void test_shade_hit_item(const PT &S, int i, const int *tri, const float *hit_in, const float *ray_in,
+                                                    const float *carry, const uint32_t *state_in, const int *bounce_in, float *out,
+                                                    uint32_t *iout) {
+  HitRec hit;
+  hit.t = hit_in[(size_t)i * 3 + 0]; hit.u = hit_in[(size_t)i * 3 + 1]; hit.v = hit_in[(size_t)i * 3 + 2];
+  hit.tri = tri[i];
+  const float *r = ray_in + (size_t)i * 6, *c = carry + (size_t)i * 6;
+  rt_v3 org = rt_v3_make(r[0], r[1], r[2]), dir = rt_v3_make(r[3], r[4], r[5]);
+  rt_v3 tint = rt_v3_make(c[0], c[1], c[2]), emis = rt_v3_make(c[3], c[4], c[5]);
+  rt_v3 radiance = rt_v3_make(-1.0f, -2.0f, -3.0f);
+  uint32_t rng = state_in[i];
+  int bounce = bounce_in[i];
+  LaneCounters cn;
+  cn.rays = cn.nodes = cn.leaves = cn.shades = cn.bgs = cn.textured = cn.paths = 0;
+  const bool done = shade_hit(S, hit, org, dir, tint, emis, rng, bounce, cn, radiance);
+  float *o = out + (size_t)i * 15;
+  o[0] = org.x; o[1] = org.y; o[2] = org.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z;
+  o[6] = tint.x; o[7] = tint.y; o[8] = tint.z; o[9] = emis.x; o[10] = emis.y; o[11] = emis.z;
+  o[12] = radiance.x; o[13] = radiance.y; o[14] = radiance.z;
+  uint32_t *w = iout + (size_t)i * 5;
+  w[0] = rng; w[1] = (uint32_t)bounce; w[2] = done ? 1u : 0u; w[3] = (uint32_t)cn.shades; w[4] = (uint32_t)cn.textured;
+}
+
+template <class SP>
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_shade_hit_kernel(RT_KParams P, int n, const int *tri, const float *hit_in,
+                                                                             const float *ray_in, const float *carry,
+                                                                             const uint32_t *state_in, const int *bounce_in, float *out,
+                                                                             uint32_t *iout) {
+  if (Pow24InLds<SP>::value) {
+    pow24_lds_init((int)threadIdx.x);
+    __syncthreads();
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SP S;
+  shade_params(S, &P, true);
+  test_shade_hit_item(S, i, tri, hit_in, ray_in, carry, state_in, bounce_in, out, iout);
+}
+
+// ... and with the kernel arguments themselves as PT, as cast_ray_lane() has them
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_shade_hit_kparams_kernel(RT_KParams P, int n, const int *tri, const float *hit_in,
+                                                                                     const float *ray_in, const float *carry,
+                                                                                     const uint32_t *state_in, const int *bounce_in,
+                                                                                     float *out, uint32_t *iout) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  test_shade_hit_item(P, i, tri, hit_in, ray_in, carry, state_in, bounce_in, out, iout);
+}
+
+// feature_hit<ShadeParamsLds>() (rt_features.hip), the feature kernel's instance, on the same kind of item.
+//   out 12 floats: origin afterwards, albedo, normal, position (the last three start as 0 and stay so on a back face); flag[n] 0 / 1
+__global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_feature_hit_kernel(RT_KParams P, int n, const int *tri, const float *hit_in,
+                                                                               const float *ray_in, float *out, int *flag) {
+  pow24_lds_init((int)threadIdx.x);
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ShadeParamsLds S;
+  shade_params(S, &P, true);
+  HitRec hit;
+  hit.t = hit_in[(size_t)i * 3 + 0]; hit.u = hit_in[(size_t)i * 3 + 1]; hit.v = hit_in[(size_t)i * 3 + 2];
+  hit.tri = tri[i];
+  const float *r = ray_in + (size_t)i * 6;
+  rt_v3 org = rt_v3_make(r[0], r[1], r[2]);
+  const rt_v3 dir = rt_v3_make(r[3], r[4], r[5]);
+  rt_v3 albedo = rt_v3_make(0, 0, 0), normal = rt_v3_make(0, 0, 0), position = rt_v3_make(0, 0, 0);
+  const bool f = feature_hit(S, hit, org, dir, albedo, normal, position);
+  float *o = out + (size_t)i * 12;
+  o[0] = org.x; o[1] = org.y; o[2] = org.z; o[3] = albedo.x; o[4] = albedo.y; o[5] = albedo.z;
+  o[6] = normal.x; o[7] = normal.y; o[8] = normal.z; o[9] = position.x; o[10] = position.y; o[11] = position.z;
+  flag[i] = f ? 1 : 0;
+}
+
 // sample_disney() on a raw BrdfIn: params = roughness, metalness, sheen, sheen_tint, aniso2, base colour
 __global__ void rt_test_brdf_kernel(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir,
                                     float *brdf, uint32_t *state_out) {
@@ -465,6 +558,24 @@ extern "C" int rt_launch_test_shade(const RT_KParams *P, int lds, int n, const i
   const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
   if (lds) hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
   else hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+  return (int)hipGetLastError();
+}
+
+// mode: 0 = ShadeParams, 1 = ShadeParamsLds, 2 = RT_KParams
+extern "C" int rt_launch_test_shade_hit(const RT_KParams *P, int mode, int n, const int *tri, const float *hit, const float *ray,
+                                        const float *carry, const uint32_t *state_in, const int *bounce_in, float *out, uint32_t *iout,
+                                        hipStream_t stream) {
+  const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
+  if (mode == 0) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  else if (mode == 1) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  else hipLaunchKernelGGL(rt_test_shade_hit_kparams_kernel, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_feature_hit(const RT_KParams *P, int n, const int *tri, const float *hit, const float *ray, float *out,
+                                          int *flag, hipStream_t stream) {
+  const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
+  hipLaunchKernelGGL(rt_test_feature_hit_kernel, grid, block, 0, stream, *P, n, tri, hit, ray, out, flag);
   return (int)hipGetLastError();
 }
 

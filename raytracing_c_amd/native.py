@@ -226,6 +226,8 @@ def _declare_diag(d):
     d.rt_test_trace.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     d.rt_test_texture.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
     d.rt_test_shade.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 7
+    d.rt_test_shade_hit.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 8
+    d.rt_test_feature_hit.argtypes = [vp, C.c_int32] + [vp] * 5
     d.rt_test_brdf.argtypes = [C.c_int32] + [vp] * 6
     d.rt_test_background.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
     d.rt_test_primary_ray.argtypes = [C.POINTER(abi.Camera), C.c_int32, C.c_int32, C.c_int32, vp, vp]

@@ -70,6 +70,13 @@ def load(path=None):
     d.oracle_disney_shade.restype = None
     d.oracle_debug_shade.argtypes = [P(abi.PBR_Shader_Data), P(abi.Shader_Input), P(abi.Shader_Output)]
     d.oracle_debug_shade.restype = None
+    d.oracle_cast_ray.argtypes = [P(abi.Scene), P(Oracle_Config), P(abi.Ray), abi.isize, P(C.c_uint32), vp]
+    d.oracle_cast_ray.restype = None
+    d.oracle_fill_hit.argtypes = [P(abi.Scene), P(abi.Ray), C.c_float, C.c_int32, C.c_float, C.c_float, P(abi.Hit)]
+    d.oracle_fill_hit.restype = None
+    d.oracle_path_step.argtypes = [P(abi.Scene), P(Oracle_Config), P(abi.Ray), P(abi.Hit), vp, vp, P(C.c_uint32), P(C.c_int32), abi.isize,
+                                   P(C.c_int32), vp, vp]
+    d.oracle_path_step.restype = None
     d.oracle_primary_ray.argtypes = [P(abi.Camera)] + [C.c_int32] * 5 + [vp]
     d.oracle_primary_ray.restype = None
     d.oracle_math.argtypes = [C.c_int32, C.c_int32, vp, vp, vp]
