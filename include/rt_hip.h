@@ -111,6 +111,22 @@ extern int scene_init_gpu(Scene *scene, Triangle_Slice src_triangles, Allocator 
  * Scene when it ends.  0 on success, -1 with rt_last_error() otherwise (nothing written after a failed validation). */
 extern int scene_refit_gpu(Scene *scene, Triangle_Slice src_triangles, i32 const *slot_of_source);
 
+/* KEPT GEOMETRY: a snapshot of the device copy's leaf tiles -- per leaf group 72 f32, 9 rows x 8: a, b - a, c - a of its eight
+ * slots -- what THE MOTION of a later feature pass is measured against ("first-hit feature buffers" below).  The refit keeps every
+ * triangle in its slot, so the snapshot and the refitted tiles name the same triangle by the same (group, column).  The snapshot
+ * is made by ONE device-to-device copy, replaces an earlier one, and belongs to the device copy: whatever drops the copy --
+ * rt_scene_invalidate, a re-upload after an edit, rt_scene_free, a scene_refit_gpu that falls back to scene_refit, a device
+ * slot torn down -- drops it too, and rt_scene_has_kept_geometry() says 0 again.  scene_refit_gpu, scene_refit and
+ * rt_scene_touch are what they were.  The host loop of an animation:
+ *     render frame k - 1  ->  rt_scene_keep_geometry  ->  scene_refit_gpu (any number of times)  ->  render frame k
+ * rt_device_scene_keep_geometry(): an explicitly uploaded scene, only enqueues the copy on `stream`.  rt_scene_keep_geometry():
+ * the primary device's cached copy of `scene` (made by the ordinary upload when there is none), under the device lock, on the
+ * NULL stream.  rt_scene_has_kept_geometry(): 1 / 0 for the primary device's cached copy; touches no device.  0 on success,
+ * -1 + rt_last_error(). */
+extern int rt_device_scene_keep_geometry(RT_Device_Scene *dscene, void *stream);
+extern int rt_scene_keep_geometry(Scene const *scene);
+extern int rt_scene_has_kept_geometry(Scene const *scene);
+
 /* ---- rendering -------------------------------------------------------------- */
 
 typedef struct {
@@ -335,6 +351,34 @@ extern int rt_resolve_features(RT_Render_Params const *params, void const *d_sum
 extern int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
                               RT_Features const *out, u64 *sums);
 
+/* THE MOTION: for a deforming mesh, where the surface point of a feature hit WAS minus where it is -- three more sums per pixel,
+ * in a buffer of their own, u64[h][w][RT_MOTION_CHANNELS]; RT_FEATURE_CHANNELS and the ten-channel layout stay.  At a FEATURE HIT
+ * with triangle slot tri and barycentrics (u, v) -- the (t1, t2) the leaf test accepted --: g = tri >> 3, k = tri & 7, l = the
+ * current leaf tile of group g (72 f32: 9 rows x 8, rows a.x, (b - a).x, (c - a).x, a.y, ... as uploaded or refitted), l' = the
+ * KEPT tile of group g ("scene residency" above).  For axis r = 0, 1, 2:
+ *     cur_r    = (l [(3r) * 8 + k] + u * l [(3r + 1) * 8 + k]) + v * l [(3r + 2) * 8 + k]
+ *     was_r    = (l'[(3r) * 8 + k] + u * l'[(3r + 1) * 8 + k]) + v * l'[(3r + 2) * 8 + k]
+ *     motion_r = was_r - cur_r
+ * Plain f32 + - *, every operation rounded on its own, left to right as written, no fused multiply-add (the units are built with
+ * -ffp-contract=off): the same bits under all three numeric contracts.  The motion is a difference of two barycentric evaluations,
+ * NOT was - Shader_Input.position: a triangle whose kept column equals its current column has motion +0 bit for bit.  A miss or
+ * an exhausted loop adds nothing; a back face that is passed through adds nothing for that hit.  Sums: rt_accum_quantize_signed,
+ * 32.32, order-free, one atomic per non-zero channel and pixel group, like position.  Without kept geometry the current tiles
+ * serve as the kept ones and every motion sum is 0: the first frame of a sequence.
+ * rt_render_accumulate_features_motion(): rt_render_accumulate_features() -- its checks, locking, sample_first / sample_count --
+ * by ONE launch of a second kernel on the same loop (rt_features_motion_kernel); d_motion_sums is required and zero on entry; the
+ * ten sums it writes into d_sums equal rt_render_accumulate_features()'s bit for bit.  rt_resolve_motion(): sums -> means over
+ * params->samples (rt_accum_resolve_signed), d_motion f32[h][w][3]; like position it is the sum over the samples that hit divided
+ * by ALL samples: motion / coverage is the mean motion of the first hits.  rt_render_features_motion(): rt_render_features() with
+ * two more optional outputs, motion f32[h][w][3] and motion_sums u64[h][w][3], against the kept geometry of the scene's cached
+ * copy; at least one of the four outputs. */
+#define RT_MOTION_CHANNELS 3
+extern int rt_render_accumulate_features_motion(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums,
+                                                void *d_motion_sums, void *stream);
+extern int rt_resolve_motion(RT_Render_Params const *params, void const *d_motion_sums, void *d_motion, void *stream);
+extern int rt_render_features_motion(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
+                                     RT_Features const *out, u64 *sums, f32 *motion, u64 *motion_sums);
+
 /* ---- guided denoiser ------------------------------------------------------------------ */
 
 /* An edge-stopping a-trous filter (Dammertz et al. 2010) of the linear frame, steered by the feature buffers above: what turns the
@@ -465,10 +509,24 @@ extern int rt_render_denoised(Scene const *scene, Image const *image, isize samp
  *   Two consequences.  Equal cameras over an unchanged scene: hx = x, ax = 0, the centre tap has weight 1 and passes both tests with
  *   0 (the feature pass does not read the seed: old and new guides are the same bits), so the output is the recursion
  *   h + (c - h) * a bit for bit.  No history (first frame, after a reset): out = c_p * m_p and len = 1.
- * Out of scope: MOVING GEOMETRY -- after scene_refit_gpu a surface that moved off its old plane fails the plane test and restarts
- * there, one that slid within its own plane is reused wrongly; a host that deforms the mesh resets the history or accepts that
- * (per-triangle motion vectors need a triangle-id feature channel).  Several devices, view batches, weighting frames by their
- * sample counts.  (Moments and variance: "variance-guided denoising" below.) */
+ *
+ * THE ACCUMULATION WITH MOTION (moving geometry: a mesh deformed by scene_refit_gpu between two frames).  THE ACCUMULATION -- and
+ * THE MOMENTS below -- with one more input, motion f32[h][w][3] as rt_resolve_motion writes it (finite), and these differences and
+ * no others.  For a pixel with cov != 0:
+ *       M_p = motion_p / cov per component;  V_p = W_p + M_p per component      (where the mean surface point WAS)
+ *       (front_c, fxc, fyc, .) = proj(camera, W_p) as before;  (front_v, fxv, fyv, dv) = proj(previous camera, V_p)
+ *       in a tap's plane test:  e = W_q - V_p      (N_p, tn2, tp2 and dv -- now V_p's depth in the old camera -- as before)
+ *       the history record keeps (W_p, 0), not V_p: the next frame measures from where the surface is now
+ *   Consequence: with motion all +0, V_p = W_p and every output equals THE ACCUMULATION's (THE MOMENTS') bit for bit.  THE VARIANCE
+ *   and both filters read no previous frame and are what they were.
+ *   Known limit: the normal test stays on the CURRENT normal, dn = N_p - N_q.  A surface that turned by more than normal_tolerance
+ *   between two frames restarts there (previous normals would need the 28-float shading records kept as well).
+ * Still out of scope: TURNING NORMALS (above); TOPOLOGY CHANGES -- the motion pairs a triangle with what its slot held when the
+ * geometry was kept, so a mesh whose triangles change slots or count is rebuilt, loses the kept geometry with the device copy, and
+ * has motion 0; several devices, view batches, weighting frames by their sample counts.  Without the motion plane, after
+ * scene_refit_gpu a surface that moved off its old plane fails the plane test and restarts, and one that slid within its own plane
+ * is reused wrongly: a host that deforms the mesh uses the motion calls below or resets the history.  (Moments and variance:
+ * "variance-guided denoising" below.) */
 typedef struct {
   f32 alpha;
   i32 max_history;
@@ -513,6 +571,10 @@ typedef struct RT_History RT_History;
 extern RT_History *rt_history_create(i32 width, i32 height);
 extern int         rt_history_reset(RT_History *history);
 extern void        rt_history_destroy(RT_History *history);
+/* on = 1: rt_render_temporal() / rt_render_svgf() on this history run the motion feature pass in place of the plain one (one
+ * launch, not two) against the scene's kept geometry, and THE ACCUMULATION WITH MOTION, in the same scene-checked call.  Default 0:
+ * what they did before.  The history's contents stay.  0, or -1 + rt_last_error() (NULL, on not 0 / 1). */
+extern int         rt_history_set_motion(RT_History *history, int on);
 
 /* An accumulated frame in one call: rt_render_frame()'s frame sequence, the feature pass of the same frame shape, the accumulation
  * against `history` (previous camera = the camera of the last call on this history) and, when guided_params is not NULL, the guided
@@ -603,6 +665,23 @@ extern int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Tempora
                                                RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
                                                f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
                                                f32 *moments_out, f32 *variance);
+
+/* THE ACCUMULATION WITH MOTION ("temporal accumulation" above), kernels of their own (rt_temporal_motion_kernel,
+ * rt_temporal_moments_motion_kernel).  d_motion / motion f32[h][w][3] is required.  vp, d_moments_in, d_moments_out and d_variance
+ * (host level: vp, moments_in, moments_out, variance) all NULL selects the plain accumulation, with rt_temporal_accumulate()'s
+ * rules; any of them given selects the moments form, with rt_temporal_accumulate_moments()'s.  Refusals are those calls' plus a
+ * NULL motion; a refused call leaves its outputs untouched. */
+extern int rt_temporal_accumulate_motion(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                         Camera const *previous_camera, void const *d_color, void const *d_coverage,
+                                         void const *d_albedo, void const *d_normal, void const *d_position, void const *d_history_in,
+                                         void *d_history_out, void *d_out, void *d_length, void *d_image, RT_Variance_Params const *vp,
+                                         void const *d_moments_in, void *d_moments_out, void *d_variance, void *stream,
+                                         void const *d_motion);
+extern int rt_temporal_accumulate_motion_host(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                              Camera const *previous_camera, f32 const *color, RT_Features const *planes,
+                                              RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
+                                              f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
+                                              f32 *moments_out, f32 *variance, f32 const *motion);
 
 /* rt_guided_denoise() / rt_guided_denoise_host() as THE VARIANCE-GUIDED FILTER.  d_variance / variance f32[h][w] is required;
  * d_variance_out / variance_out f32[h][w] is optional and counts as an output.  d_work: rt_guided_variance_work_bytes(width,

@@ -44,6 +44,11 @@ extern i64 rt_diag_device_bytes_live(void);
  * a device slot's teardown does (rt_set_devices remaps slots >= 1 only): waits for the device, then releases.  The next call
  * that needs staging allocates it again.  Not while a frame is in flight.  0 on success. */
 extern int rt_diag_release_staging(void);
+/* The primary device's cached copy of `scene`, NULL when there is none: the copy scene_refit_gpu deforms in place and
+ * rt_scene_keep_geometry snapshots, for tests that run the device-level calls (rt_render_accumulate_features_motion with a sample
+ * range) on a deformed mesh.  The cache keeps owning it: not to be released, and gone with the next re-upload; rt_set_camera()
+ * gives it a camera. */
+extern RT_Device_Scene *rt_diag_cached_scene(Scene const *scene);
 
 /* ---- unit-level device entry points (parity tests call the same device
  * functions the render kernel uses) ------------------------------------------ */

@@ -206,6 +206,15 @@ extern "C" int rt_diag_release_staging(void) {
   return 0;
 }
 
+// The primary device's cached copy of `scene` (NULL: none) -- the copy scene_refit_gpu deforms and rt_scene_keep_geometry
+// snapshots -- so that a test can run the device-level calls on it.  The cache still owns it.
+extern "C" RT_Device_Scene *rt_diag_cached_scene(Scene const *scene) {
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  auto it = D.scene_cache.find(scene);
+  return it == D.scene_cache.end() ? nullptr : it->second;
+}
+
 // ---------------------------------------------------------------------------------
 // unit-level device entry points (include/rt_hip_diag.h; diagnostic library only)
 

@@ -1,11 +1,13 @@
 // rt_features.cpp -- first-hit feature buffers (include/rt_hip.h): coverage, albedo, shading normal and world position of what the
 // camera sees, on the device level (device pointers, one launch on the caller's stream) and on the host level (host arrays, the
 // cached device copy of a Scene through scene_checked, rt_residency.cpp).  The work is rt_features_kernel and
-// rt_features_resolve_kernel (rt_features.hip); nothing here computes a feature on the CPU.
+// rt_features_resolve_kernel (rt_features.hip), and with THE MOTION rt_features_motion_kernel and rt_motion_resolve_kernel; nothing
+// here computes a feature on the CPU.
 
 #include "rt_host.h"
 
 static_assert(RT_FEATURE_CHANNELS == 10, "coverage, albedo rgb, normal xyz, position xyz");
+static_assert(RT_MOTION_CHANNELS == 3, "THE MOTION xyz");
 
 // What can be checked without the device.  `who` prefixes the messages.
 static int check_feature_params(const char *who, RT_Render_Params const *p) {
@@ -20,7 +22,8 @@ static int check_feature_params(const char *who, RT_Render_Params const *p) {
 }
 
 // Enqueues one launch of the feature kernel on `stream`.  D.mutex held, D's GPU current, every pointer on D.
-int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream) {
+int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream,
+                     void *d_motion_sums) {
   RT_KParams K;
   scene_only_kparams(&K, d);
   camera_frame_kparams(&K, cam, p);
@@ -58,7 +61,10 @@ int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render
   uint8_t *sl = D.query.slots + (size_t)slot * 64;
   F.head = (uint32_t *)(sl + 32);
   HIP_TRY(hipMemsetAsync(F.head, 0, 4, stream));                  // (the slot's query counters stay: rt_get_query_counters)
-  int rc = rt_launch_features(&K, &F, (int)blocks, S.smem, stream);
+  // (without kept geometry the current tiles serve as the kept ones: the first frame of a sequence has motion 0)
+  const float *kept = d->has_kept ? d->kept_leaves.get() : d->leaves.get();
+  int rc = d_motion_sums ? rt_launch_features_motion(&K, &F, kept, (unsigned long long *)d_motion_sums, (int)blocks, S.smem, stream)
+                         : rt_launch_features(&K, &F, (int)blocks, S.smem, stream);
   if (rc != 0) return rt_fail("feature kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
   HIP_TRY(hipEventRecord(D.query.done[slot], stream));
   return 0;
@@ -72,19 +78,49 @@ int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_cover
   return 0;
 }
 
+int enqueue_resolve_motion(RT_Render_Params const *p, void const *d_motion_sums, void *d_motion, hipStream_t stream) {
+  int rc = rt_launch_motion_resolve(p->width * p->height, p->samples, (const unsigned long long *)d_motion_sums, (float *)d_motion, stream);
+  if (rc != 0) return rt_fail("motion resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
 // ---- device level -------------------------------------------------------------------------------------------------------------
-extern "C" int rt_render_accumulate_features(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums, void *stream) {
-  const char *who = "rt_render_accumulate_features";
+// rt_render_accumulate_features and rt_render_accumulate_features_motion (with_motion: d_motion_sums is required)
+static int accumulate_device(const char *who, bool with_motion, RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums,
+                             void *d_motion_sums, hipStream_t stream) {
   // (everything that can be checked without the device is checked before it is touched)
   if (!dscene) return rt_fail("%s: device scene is NULL", who);
   if (check_feature_params(who, params) != 0) return -1;
   if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if (with_motion && !d_motion_sums) return rt_fail("%s: d_motion_sums is NULL", who);
   Device &D = *dscene->dev;
   std::lock_guard<std::mutex> lock(D.mutex);
   DeviceGuard guard(D);
   auto it = D.cameras.find(dscene);
   if (it == D.cameras.end()) return rt_fail("%s: no camera set for this scene (rt_set_camera)", who);
-  return enqueue_features(D, dscene, &it->second, params, d_sums, (hipStream_t)stream);
+  return enqueue_features(D, dscene, &it->second, params, d_sums, stream, d_motion_sums);
+}
+
+extern "C" int rt_render_accumulate_features(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums, void *stream) {
+  return accumulate_device("rt_render_accumulate_features", false, dscene, params, d_sums, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rt_render_accumulate_features_motion(RT_Device_Scene *dscene, RT_Render_Params const *params, void *d_sums,
+                                                    void *d_motion_sums, void *stream) {
+  return accumulate_device("rt_render_accumulate_features_motion", true, dscene, params, d_sums, d_motion_sums, (hipStream_t)stream);
+}
+
+extern "C" int rt_resolve_motion(RT_Render_Params const *params, void const *d_motion_sums, void *d_motion, void *stream) {
+  const char *who = "rt_resolve_motion";
+  if (check_feature_params(who, params) != 0) return -1;
+  if (!d_motion_sums) return rt_fail("%s: d_motion_sums is NULL", who);
+  if (!d_motion) return rt_fail("%s: d_motion is NULL", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_resolve_motion(params, d_motion_sums, d_motion, (hipStream_t)stream);
 }
 
 extern "C" int rt_resolve_features(RT_Render_Params const *params, void const *d_sums, void *d_coverage, void *d_albedo,
@@ -102,9 +138,10 @@ extern "C" int rt_resolve_features(RT_Render_Params const *params, void const *d
 }
 
 // ---- host level ---------------------------------------------------------------------------------------------------------------
-extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces, RT_Features const *out,
-                                  u64 *sums) {
-  const char *who = "rt_render_features";
+// rt_render_features and rt_render_features_motion (with_motion: motion and motion_sums are two more optional outputs, and the
+// pass is the motion kernel's)
+static int features_host(const char *who, bool with_motion, Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
+                         RT_Features const *out, u64 *sums, f32 *motion, u64 *motion_sums) {
   if (!scene) return rt_fail("%s: scene is NULL", who);
   if (samples > 0x7fffffff || max_bounces > 0x7fffffff) return rt_fail("%s: samples / max_bounces do not fit 32 bits", who);
   RT_Render_Params p;
@@ -116,7 +153,9 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   p.world = 1;
   if (check_feature_params(who, &p) != 0) return -1;
   const bool planes = out && (out->coverage || out->albedo || out->normal || out->position);
-  if (!planes && !sums) return rt_fail("%s: no output is wanted (every plane of `out` and `sums` are NULL)", who);
+  if (!planes && !sums && !motion && !motion_sums)
+    return rt_fail(with_motion ? "%s: no output is wanted (every plane of `out`, `sums`, `motion` and `motion_sums` are NULL)"
+                               : "%s: no output is wanted (every plane of `out` and `sums` are NULL)", who);
 
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
@@ -127,11 +166,17 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
   const size_t pixels = (size_t)width * height;
   HIP_TRY(S.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(S.planes.grow(pixels * RT_FEATURE_CHANNELS));
+  if (with_motion) {
+    HIP_TRY(S.motion_sums.grow(pixels * RT_MOTION_CHANNELS));
+    if (motion) HIP_TRY(S.motion.grow(pixels * RT_MOTION_CHANNELS));
+  }
   const RT_Features f = split_feature_planes(S.planes, pixels);
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
   auto pass = [&](RT_Device_Scene *d) -> int {
     HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
-    if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream) != 0) return -1;
+    if (with_motion) HIP_TRY(hipMemsetAsync(S.motion_sums, 0, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), stream));
+    if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream, with_motion ? S.motion_sums.get() : nullptr) != 0) return -1;
+    if (motion && enqueue_resolve_motion(&p, S.motion_sums, S.motion, stream) != 0) return -1;
     if (planes && enqueue_resolve(&p, S.sums, out->coverage ? f.coverage : nullptr, out->albedo ? f.albedo : nullptr,
                                   out->normal ? f.normal : nullptr, out->position ? f.position : nullptr, stream) != 0)
       return -1;
@@ -147,5 +192,18 @@ extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isi
     if (out->position) HIP_TRY(hipMemcpy(out->position, f.position, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
   }
   if (sums) HIP_TRY(hipMemcpy(sums, S.sums, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (motion) HIP_TRY(hipMemcpy(motion, S.motion, pixels * RT_MOTION_CHANNELS * sizeof(float), hipMemcpyDeviceToHost));
+  if (motion_sums)
+    HIP_TRY(hipMemcpy(motion_sums, S.motion_sums, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
+}
+
+extern "C" int rt_render_features(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces, RT_Features const *out,
+                                  u64 *sums) {
+  return features_host("rt_render_features", false, scene, width, height, samples, max_bounces, out, sums, nullptr, nullptr);
+}
+
+extern "C" int rt_render_features_motion(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
+                                         RT_Features const *out, u64 *sums, f32 *motion, u64 *motion_sums) {
+  return features_host("rt_render_features_motion", true, scene, width, height, samples, max_bounces, out, sums, motion, motion_sums);
 }

@@ -16,10 +16,15 @@
 // lanes whose segment ended on a back face go into traversal again from the advanced origin.  The samples of a pixel are
 // (1 << shift) neighbouring lanes: their ten sums are reduced in the wave (xor shuffles) and the group's first lane issues one
 // 64-bit atomic per non-zero channel.  No pyramid culling; IEEE division in ray_setup and in the leaf blocks.
+//
+// rt_features_motion_kernel (rt_render_accumulate_features_motion) is the same loop -- one text, rt_features_loop.hip.h -- with
+// THE MOTION of a deforming mesh: at a feature hit, where the point (triangle, u, v) WAS in the kept leaf tiles minus where it is
+// in the current ones, three more sums per pixel in a buffer of their own; rt_motion_resolve_kernel turns them into means.
 
 #include "rt_dev.hip.h"
 
 #define RT_FEATURE_CHANNELS 10      // coverage, albedo rgb, normal xyz, position xyz (include/rt_hip.h)
+#define RT_MOTION_CHANNELS  3       // THE MOTION xyz, in a buffer of its own (include/rt_hip.h)
 
 // rt_accum_quantize_signed() (rt_math.h) on the magnitude path of accum_quantize_dev(): truncation towards zero is symmetric, so
 // the signed value is the negated quantised magnitude; NaN -> 0 in both.
@@ -93,85 +98,37 @@ __device__ __forceinline__ bool feature_hit(const PT &P, const HitRec &hit, rt_v
   return true;
 }
 
+// THE MOTION of one feature hit (include/rt_hip.h): where the surface point (tri, u, v) WAS in the kept leaf tiles minus where it is
+// in the current ones -- two barycentric evaluations of the tiles' (a, b - a, c - a) columns, plain f32, left to right, nothing
+// fused (-ffp-contract=off).  A column that equals its kept column gives +0 bit for bit.
+__device__ __forceinline__ rt_v3 feature_motion(const float *leaves, const float *kept, const HitRec &hit) {
+  const size_t col = (size_t)(hit.tri >> 3) * 72 + (size_t)(hit.tri & 7);
+  const float *l = leaves + col, *lk = kept + col;
+  float m[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const float cur = (l[(3 * r) * 8] + hit.u * l[(3 * r + 1) * 8]) + hit.v * l[(3 * r + 2) * 8];
+    const float was = (lk[(3 * r) * 8] + hit.u * lk[(3 * r + 1) * 8]) + hit.v * lk[(3 * r + 2) * 8];
+    m[r] = was - cur;
+  }
+  return rt_v3_make(m[0], m[1], m[2]);
+}
+
+// Both kernels are one text, rt_features_loop.hip.h (see there why it is not a function).
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64, 1) void rt_features_kernel(RT_KParams P, RT_FParams F) {
-  extern __shared__ float4 smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int n_lds = P.n_lds_nodes;
-  pow24_lds_init((int)threadIdx.x);
-  lds_load_nodes<WAVES * 64>(smem, P.nodes, n_lds);
-  __syncthreads();
-  const int leaf_level = P.depth - 1;
-  // (the wave's slice is the perm stack alone; no pyramid)
-  const TravWave W = {smem, smem, wave_perm(smem, n_lds, perm_stack_f4(P.depth), wave), n_lds, 0, 0, leaf_level, lane};
-  const int shift = F.shift;
-  uint32_t next = 0, end = 0;                                     // the wave's current grab: units [next, end)
-  uint32_t w_nodes = 0, w_leaves = 0;                             // (traversal_blocks counts them; not reported)
-  ShadeParamsLds SP;
-  shade_params(SP, &P, true);
+  constexpr bool MOTION = false;
+  const float *const kept = nullptr;
+  unsigned long long *const motion_sums = nullptr;
+#include "rt_features_loop.hip.h"
+}
 
-  for (;;) {
-    if (next >= end) {
-      uint32_t s = 0;
-      if (lane == 0) s = atomicAdd(F.head, (uint32_t)F.grab);
-      s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
-      if (s >= (uint32_t)F.n_units) break;
-      next = s;
-      end = ((uint32_t)F.n_units - s < (uint32_t)F.grab) ? (uint32_t)F.n_units : s + (uint32_t)F.grab;
-    }
-    const uint32_t unit = next++;
-    // unit -> (tile, pixel group, sample block); lane -> (pixel of the group, sample of the block), pixel-major
-    const uint32_t tile = unit / (uint32_t)F.units_per_tile, r = unit - tile * (uint32_t)F.units_per_tile;
-    const uint32_t grp = r / (uint32_t)F.n_sample_blocks, sb = r - grp * (uint32_t)F.n_sample_blocks;
-    const int tile_y = (int)(tile / (uint32_t)F.tiles_x), tile_x = (int)tile - tile_y * F.tiles_x;
-    const int p = (int)grp * (64 >> shift) + (lane >> shift);     // pixel of the tile, 0 .. 63
-    const int x = tile_x * 8 + (p & 7), y = tile_y * 8 + (p >> 3);
-    const int sm = P.sample_first + (int)(sb << shift) + (lane & ((1 << shift) - 1));
-    const bool valid = x < P.width && y < P.height && sm < P.sample_end && P.max_bounces > 0;
-
-    int   bounce = 0;
-    Ray3  ray;
-    rt_v3 org = rt_v3_make(0, 0, 0), dir = rt_v3_make(0, 0, 1);
-    if (valid) primary_ray(P, x, y, sm, org, dir);
-    TravState T = RT_TRAV_IDLE;
-    float cov = 0.0f;
-    rt_v3 albedo = rt_v3_make(0, 0, 0), normal = rt_v3_make(0, 0, 0), position = rt_v3_make(0, 0, 0);
-    bool start = valid;
-    for (;;) {
-      // a new segment: traversal starts at the root (or at leaf group 0)
-      ray_setup<false>(ray, org, dir);
-      if (start) trav_start(T, leaf_level, P.last_row_offset);
-      const int n_trav0 = (int)__popcll(__ballot(T.phase == PH_NODE || T.phase == PH_LEAF));
-      if (n_trav0 == 0) break;
-      traversal_blocks<true, false, false>(P, W, ray, false, T, 64, n_trav0, w_nodes, w_leaves);
-      // every lane that traversed has ended its segment: a feature hit, a back face (again, while iterations are left), or nothing
-      start = false;
-      if (T.phase == PH_HIT) {
-        if (feature_hit(SP, T.hit, org, dir, albedo, normal, position)) cov = 1.0f;
-        else start = ++bounce < P.max_bounces;
-      }
-      T.phase = PH_NEED;
-    }
-
-    // ---- the unit's sums: the samples of a pixel are (1 << shift) neighbouring lanes ----
-    if (__ballot(cov != 0.0f) == 0ull) continue;                 // (nothing was hit: nothing to add)
-    unsigned long long q[RT_FEATURE_CHANNELS];
-    q[0] = cov != 0.0f ? 1ull << 32 : 0ull;                       // rt_accum_quantize(1.0f)
-    q[1] = accum_quantize_dev(albedo.x); q[2] = accum_quantize_dev(albedo.y); q[3] = accum_quantize_dev(albedo.z);
-    q[4] = accum_quantize_dev(normal.x); q[5] = accum_quantize_dev(normal.y); q[6] = accum_quantize_dev(normal.z);
-    q[7] = accum_quantize_signed_dev(position.x); q[8] = accum_quantize_signed_dev(position.y); q[9] = accum_quantize_signed_dev(position.z);
-    for (int k = 0; k < shift; k++) {
-#pragma unroll
-      for (int c = 0; c < RT_FEATURE_CHANNELS; c++) q[c] += shfl_xor_u64(q[c], 1 << k);
-    }
-    if ((lane & ((1 << shift) - 1)) == 0 && q[0] != 0ull) {       // (q[0] == 0: no sample of this pixel has a feature hit; implies valid pixels only)
-      unsigned long long *dst = F.sums + ((size_t)y * P.width + x) * RT_FEATURE_CHANNELS;
-#pragma unroll
-      for (int c = 0; c < RT_FEATURE_CHANNELS; c++)
-        if (q[c] != 0ull) atomicAdd(dst + c, q[c]);
-    }
-  }
+// ... with THE MOTION: kept = the leaf tiles as rt_device_scene_keep_geometry saved them (or P.leaves itself: every sum is 0)
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 1) void rt_features_motion_kernel(RT_KParams P, RT_FParams F, const float *kept,
+                                                                           unsigned long long *motion_sums) {
+  constexpr bool MOTION = true;
+#include "rt_features_loop.hip.h"
 }
 
 // sums -> means, planar f32: coverage [h][w], albedo / normal / position [h][w][3]; one thread per pixel, NULL = not wanted
@@ -189,6 +146,15 @@ __global__ void rt_features_resolve_kernel(int n_pixels, int samples, const unsi
   }
 }
 
+// motion sums -> means, f32[h][w][3] (what the motion accumulation divides by the coverage); one thread per pixel
+__global__ void rt_motion_resolve_kernel(int n_pixels, int samples, const unsigned long long *sums, float *motion) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pixels) return;
+#pragma unroll
+  for (int c = 0; c < RT_MOTION_CHANNELS; c++)
+    motion[(size_t)i * RT_MOTION_CHANNELS + c] = rt_accum_resolve_signed(sums[(size_t)i * RT_MOTION_CHANNELS + c], (uint32_t)samples);
+}
+
 // `n_blocks` workgroups of 16 waves; smem_bytes = the LDS nodes + 16 perm stacks (lds_split as rt_features.cpp, enqueue_features, calls it)
 extern "C" int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream) {
   static uint32_t attr_devices = 0;
@@ -203,5 +169,21 @@ extern "C" int rt_launch_features_resolve(int n_pixels, int samples, const unsig
                                           float *normal, float *position, hipStream_t stream) {
   hipLaunchKernelGGL(rt_features_resolve_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, samples, sums, coverage,
                      albedo, normal, position);
+  return (int)hipGetLastError();
+}
+
+// rt_launch_features with THE MOTION (the same launch geometry; one launch, not two)
+extern "C" int rt_launch_features_motion(const RT_KParams *P, const RT_FParams *F, const float *kept, unsigned long long *motion_sums,
+                                         int n_blocks, int smem_bytes, hipStream_t stream) {
+  static uint32_t attr_devices = 0;
+  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_features_motion_kernel<16>), &attr_devices, smem_bytes,
+                               RT_LDS_BYTES - RT_LDS_TABLE_BYTES))
+    return rc;
+  hipLaunchKernelGGL((rt_features_motion_kernel<16>), dim3(n_blocks), dim3(16 * 64), smem_bytes, stream, *P, *F, kept, motion_sums);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_motion_resolve(int n_pixels, int samples, const unsigned long long *sums, float *motion, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_motion_resolve_kernel, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, n_pixels, samples, sums, motion);
   return (int)hipGetLastError();
 }

@@ -77,6 +77,9 @@ int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, cons
 int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo, float *normal,
                                float *position, hipStream_t stream);
+int rt_launch_features_motion(const RT_KParams *P, const RT_FParams *F, const float *kept, unsigned long long *motion_sums, int n_blocks,
+                              int smem_bytes, hipStream_t stream);
+int rt_launch_motion_resolve(int n_pixels, int samples, const unsigned long long *sums, float *motion, hipStream_t stream);
 // ... in rt_refit.hip
 int rt_launch_refit(int len, int depth, int n_internal, const void *d_src, const int *d_source_of_slot, float *d_block, float *d_nodes,
                     float *d_leaves, float *d_tris, unsigned char *d_populated, unsigned int *d_max_edge_bits, hipStream_t stream);
@@ -89,12 +92,16 @@ int rt_launch_guided_filter(int width, int height, int step, float k_n, float k_
 // ... in rt_temporal.hip
 int rt_launch_temporal(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out, float *length,
                        uint8_t *image, hipStream_t stream);
+int rt_launch_temporal_motion(const RT_TParams *P, RT_Frame frame, const float *motion, const void *hist_in, void *hist_out, float *out,
+                              float *length, uint8_t *image, hipStream_t stream);
 int rt_launch_temporal_pack(int n_pixels, const float *c, const float *len, const float *cov, const float *n, const float *w, void *hist,
                             hipStream_t stream);
 int rt_launch_temporal_unpack(int n_pixels, const void *hist, float *c, float *len, float *cov, float *n, float *w, hipStream_t stream);
 // ... in rt_variance.hip
 int rt_launch_temporal_moments(const RT_TParams *P, RT_Frame frame, const void *hist_in, void *hist_out, float *out, float *length,
                                uint8_t *image, const void *mom_in, void *mom_out, hipStream_t stream);
+int rt_launch_temporal_moments_motion(const RT_TParams *P, RT_Frame frame, const float *motion, const void *hist_in, void *hist_out,
+                                      float *out, float *length, uint8_t *image, const void *mom_in, void *mom_out, hipStream_t stream);
 int rt_launch_variance(int width, int height, float k_n, float k_p, const void *hist, const void *mom, float *variance,
                        hipStream_t stream);
 int rt_launch_variance_pack(int n_pixels, int demodulate, RT_Frame frame, const float *variance, void *c0, void *g0, void *g1,
@@ -250,6 +257,9 @@ struct QueryState {
 struct FeatureState {
   DevMem<unsigned long long> sums;            // [pixels][RT_FEATURE_CHANNELS]
   DevMem<float>              planes;          // coverage [pixels], then albedo, normal, position [pixels][3] each
+  // the motion feature pass alone (rt_render_features_motion, a history with motion on) grows these:
+  DevMem<unsigned long long> motion_sums;     // [pixels][RT_MOTION_CHANNELS]
+  DevMem<float>              motion;          // [pixels][RT_MOTION_CHANNELS]
 };
 
 // The four planes of such a buffer, to write (the resolve) ...
@@ -289,6 +299,7 @@ struct TemporalState {
   DevMem<uint8_t> mom[2];                     // rt_temporal_moments_bytes() each: read, written
   DevMem<float>   mom_planar;                 // moments as the host has them, [pixels][2]
   DevMem<float>   variance;                   // [pixels]: the variance launch's output, the variance-guided filter's input
+  DevMem<float>   motion;                     // rt_temporal_accumulate_motion_host alone: the staged motion plane [pixels][3]
   std::vector<RT_History *> histories;        // every live RT_History (slot 0 only)
 };
 
@@ -334,6 +345,7 @@ struct RT_History {
   bool            valid = false;              // buf[cur] holds a history and `camera` its camera
   DevMem<uint8_t> mom[2];                     // the moments of the two histories (rt_render_svgf allocates them), ping-ponged with buf
   bool            moments_valid = false;      // mom[cur] holds the moments of buf[cur]: the last frame was rt_render_svgf's
+  bool            motion = false;             // rt_history_set_motion: the motion feature pass and THE ACCUMULATION WITH MOTION
   Camera          camera;
   // Gives the device memory back: the history is empty, as after rt_history_reset().  Slot 0's GPU current.
   void release() {
@@ -391,6 +403,10 @@ struct LaunchState {
 struct RT_Device_Scene {
   Device      *dev = nullptr;
   DevMem<float>       nodes, leaves, tris, mats;
+  // the KEPT GEOMETRY (rt_device_scene_keep_geometry): `leaves` as one device-to-device copy left them, what THE MOTION of a later
+  // feature pass is measured against; it goes with the copy
+  DevMem<float>       kept_leaves;
+  bool                has_kept = false;
   DevMem<RT_DTexture> textures;
   DevMem<uint32_t>    texels;
   int32_t      depth = 0, last_row_offset = 0, bg_texture = -1, n_nodes = 0;
@@ -536,7 +552,11 @@ int  acquire_slot(Device &D, int *slot, bool query = true);
 // rt_features.cpp
 // One launch of the feature kernel / of its resolve on `stream` (what rt_render_features runs; rt_post.cpp runs them behind
 // a frame).  D.mutex held, D's GPU current, every pointer on D.
-int  enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream);
+// d_motion_sums (optional): the motion kernel in place of the plain one -- one launch -- against d's kept geometry (none: the
+// current tiles, every motion sum 0).
+int  enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream,
+                      void *d_motion_sums = nullptr);
+int  enqueue_resolve_motion(RT_Render_Params const *p, void const *d_motion_sums, void *d_motion, hipStream_t stream);
 int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal, void *d_position,
                      hipStream_t stream);
 

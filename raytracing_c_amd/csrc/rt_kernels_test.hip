@@ -7,12 +7,15 @@
 
 // feature_hit() is defined beside its kernel in rt_features.hip.  This unit reads that file as it is, so that
 // rt_test_feature_hit_kernel below instantiates the same feature_hit() text; the diagnostic library links rt_features_dev.o too,
-// which has the real kernels and launchers, so here the kernels go into an unnamed namespace and the two launchers -- declared
+// which has the real kernels and launchers, so here the kernels go into an unnamed namespace and the four launchers -- declared
 // static first, which their definitions inherit -- stay local to this object.
 namespace {
 static int rt_launch_features(const RT_KParams *P, const RT_FParams *F, int n_blocks, int smem_bytes, hipStream_t stream);
 static int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long long *sums, float *coverage, float *albedo,
                                       float *normal, float *position, hipStream_t stream);
+static int rt_launch_features_motion(const RT_KParams *P, const RT_FParams *F, const float *kept, unsigned long long *motion_sums,
+                                     int n_blocks, int smem_bytes, hipStream_t stream);
+static int rt_launch_motion_resolve(int n_pixels, int samples, const unsigned long long *sums, float *motion, hipStream_t stream);
 #include "rt_features.hip"
 }
 

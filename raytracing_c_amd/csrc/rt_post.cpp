@@ -4,6 +4,8 @@
 // estimated from them, and the filter steered by that variance.  Each on the device level (device pointers, launches on the caller's stream), on the host level (host arrays
 // through library-owned staging) and behind a frame (rt_render_denoised, rt_render_temporal, rt_render_svgf: one pipeline -- frame,
 // feature pass, optionally the accumulation, optionally the filter -- in ONE scene-checked call).  Nothing here computes a pixel on the CPU.
+// For a mesh that scene_refit_gpu deforms between the frames the accumulation takes one more plane, the motion of the first hits
+// (rt_temporal_accumulate_motion; behind a frame rt_history_set_motion switches the motion feature pass and that accumulation on).
 //
 // The frame a stage reads is ONE value (RT_Frame, rt_device.h), built by whoever has the pointers: the extern "C" entry points
 // (frame_of), upload_host_frame and render_post from the staging.  What a stage may write, and what its variance / moments form adds,
@@ -29,10 +31,12 @@ struct FilterIO { float *out; uint8_t *image; const float *variance_in; float *v
 
 // What the accumulation may write besides the new history, and what its moments form adds.  moments_out given: THE MOMENTS in the
 // same launch (moments_in exactly when there is a history to read; records on the device, f32[h][w][2] in the host-level calls), and
-// when `variance` is wanted THE VARIANCE behind it, with vp.
+// when `variance` is wanted THE VARIANCE behind it, with vp.  motion given: THE ACCUMULATION WITH MOTION, plain or with the moments
+// (f32[h][w][3] as rt_resolve_motion writes it).
 struct AccumulateIO {
   float *out, *length; uint8_t *image;                                             // [h][w][3], [h][w], [h][w][3]
   const void *moments_in; void *moments_out; float *variance; RT_Variance_Params const *vp;
+  const float *motion;
 };
 
 // A history as a host has it (RT_History_Planes) and as TemporalState::planar stages it: the planes in the order
@@ -178,9 +182,16 @@ static int launch_filter(i32 width, i32 height, RT_Guided_Params const *g, int i
 
 static int launch_accumulate(RT_TParams const &P, RT_Frame const &f, const void *history_in, void *history_out, AccumulateIO const &a,
                              hipStream_t stream) {
+  if (a.moments_out && a.motion)
+    return launched(rt_launch_temporal_moments_motion(&P, f, a.motion, history_in, history_out, a.out, a.length, a.image, a.moments_in,
+                                                      a.moments_out, stream),
+                    "temporal moments kernel launch failed: %s");
   if (a.moments_out)
     return launched(rt_launch_temporal_moments(&P, f, history_in, history_out, a.out, a.length, a.image, a.moments_in, a.moments_out, stream),
                     "temporal moments kernel launch failed: %s");
+  if (a.motion)
+    return launched(rt_launch_temporal_motion(&P, f, a.motion, history_in, history_out, a.out, a.length, a.image, stream),
+                    "temporal kernel launch failed: %s");
   return launched(rt_launch_temporal(&P, f, history_in, history_out, a.out, a.length, a.image, stream), "temporal kernel launch failed: %s");
 }
 
@@ -275,9 +286,9 @@ extern "C" int rt_guided_denoise_variance(i32 width, i32 height, RT_Guided_Param
                        {(float *)d_out, (uint8_t *)d_image, (const float *)d_variance, (float *)d_variance_out}, d_work, (hipStream_t)stream);
 }
 
-// rt_temporal_accumulate and rt_temporal_accumulate_moments (with_moments: a.moments_out is required, a.moments_in goes with
-// d_history_in, a.vp is required when a.variance is wanted)
-static int temporal_device(const char *who, bool with_moments, i32 width, i32 height, RT_Temporal_Params const *params,
+// rt_temporal_accumulate, rt_temporal_accumulate_moments and rt_temporal_accumulate_motion (with_moments: a.moments_out is
+// required, a.moments_in goes with d_history_in, a.vp is required when a.variance is wanted; with_motion: a.motion is required)
+static int temporal_device(const char *who, bool with_moments, bool with_motion, i32 width, i32 height, RT_Temporal_Params const *params,
                            Camera const *camera, Camera const *previous_camera, RT_Frame const &f, void const *d_history_in,
                            void *d_history_out, AccumulateIO const &a, hipStream_t stream) {
   if (check_temporal(who, width, height, params) != 0) return -1;
@@ -285,6 +296,7 @@ static int temporal_device(const char *who, bool with_moments, i32 width, i32 he
   if (!camera) return rt_fail("%s: camera is NULL", who);
   if (d_history_in && !previous_camera) return rt_fail("%s: previous_camera is NULL and a history is given", who);
   if (check_device_frame(who, f, params->demodulate) != 0) return -1;
+  if (with_motion && !a.motion) return rt_fail("%s: d_motion is NULL", who);
   if (!d_history_out) return rt_fail("%s: d_history_out is NULL", who);
   if (((uintptr_t)d_history_out | (uintptr_t)d_history_in) & 15) return rt_fail("%s: the histories must be 16-byte aligned", who);
   const uintptr_t pixels = (uintptr_t)width * height;
@@ -304,7 +316,7 @@ extern "C" int rt_temporal_accumulate(i32 width, i32 height, RT_Temporal_Params 
                                       Camera const *previous_camera, void const *d_color, void const *d_coverage, void const *d_albedo,
                                       void const *d_normal, void const *d_position, void const *d_history_in, void *d_history_out,
                                       void *d_out, void *d_length, void *d_image, void *stream) {
-  return temporal_device("rt_temporal_accumulate", false, width, height, params, camera, previous_camera,
+  return temporal_device("rt_temporal_accumulate", false, false, width, height, params, camera, previous_camera,
                          frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out,
                          {(float *)d_out, (float *)d_length, (uint8_t *)d_image}, (hipStream_t)stream);
 }
@@ -316,7 +328,21 @@ extern "C" int rt_temporal_accumulate_moments(i32 width, i32 height, RT_Temporal
                                               RT_Variance_Params const *vp, void const *d_moments_in, void *d_moments_out,
                                               void *d_variance, void *stream) {
   const AccumulateIO a = {(float *)d_out, (float *)d_length, (uint8_t *)d_image, d_moments_in, d_moments_out, (float *)d_variance, vp};
-  return temporal_device("rt_temporal_accumulate_moments", true, width, height, params, camera, previous_camera,
+  return temporal_device("rt_temporal_accumulate_moments", true, false, width, height, params, camera, previous_camera,
+                         frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out, a, (hipStream_t)stream);
+}
+
+// (vp, d_moments_in, d_moments_out and d_variance all NULL: the plain accumulation; otherwise the moments form, by its rules)
+extern "C" int rt_temporal_accumulate_motion(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                             Camera const *previous_camera, void const *d_color, void const *d_coverage,
+                                             void const *d_albedo, void const *d_normal, void const *d_position,
+                                             void const *d_history_in, void *d_history_out, void *d_out, void *d_length, void *d_image,
+                                             RT_Variance_Params const *vp, void const *d_moments_in, void *d_moments_out,
+                                             void *d_variance, void *stream, void const *d_motion) {
+  const bool with_moments = vp || d_moments_in || d_moments_out || d_variance;
+  const AccumulateIO a = {(float *)d_out, (float *)d_length, (uint8_t *)d_image, d_moments_in, d_moments_out, (float *)d_variance, vp,
+                          (const float *)d_motion};
+  return temporal_device("rt_temporal_accumulate_motion", with_moments, true, width, height, params, camera, previous_camera,
                          frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out, a, (hipStream_t)stream);
 }
 
@@ -391,8 +417,9 @@ static const char *missing_history_plane(RT_History_Planes const *h) {
 }
 
 // rt_temporal_accumulate_host and rt_temporal_accumulate_moments_host (with_moments: h.moments_in goes with history_in,
-// h.moments_out and h.variance are optional outputs, h.vp is required when h.variance is wanted); h holds the host's pointers
-static int temporal_host(const char *who, bool with_moments, i32 width, i32 height, RT_Temporal_Params const *params,
+// h.moments_out and h.variance are optional outputs, h.vp is required when h.variance is wanted) and
+// rt_temporal_accumulate_motion_host (with_motion: h.motion is required); h holds the host's pointers
+static int temporal_host(const char *who, bool with_moments, bool with_motion, i32 width, i32 height, RT_Temporal_Params const *params,
                          Camera const *camera, Camera const *previous_camera, f32 const *color, RT_Features const *planes,
                          RT_History_Planes const *history_in, RT_History_Planes const *history_out, AccumulateIO const &h) {
   if (check_temporal(who, width, height, params) != 0) return -1;
@@ -400,6 +427,7 @@ static int temporal_host(const char *who, bool with_moments, i32 width, i32 heig
   if (!camera) return rt_fail("%s: camera is NULL", who);
   if (history_in && !previous_camera) return rt_fail("%s: previous_camera is NULL and a history is given", who);
   if (check_host_frame(who, color, planes, params->demodulate) != 0) return -1;
+  if (with_motion && !h.motion) return rt_fail("%s: motion is NULL", who);
   if (history_in && missing_history_plane(history_in)) return rt_fail("%s: history_in->%s is NULL", who, missing_history_plane(history_in));
   if (history_out && missing_history_plane(history_out)) return rt_fail("%s: history_out->%s is NULL", who, missing_history_plane(history_out));
   if (with_moments && history_in && !h.moments_in) return rt_fail("%s: a history is given without its moments (moments_in is NULL)", who);
@@ -426,11 +454,13 @@ static int temporal_host(const char *who, bool with_moments, i32 width, i32 heig
     HIP_TRY(S.mom_planar.grow(pixels * 2));
     if (h.variance) HIP_TRY(S.variance.grow(pixels));
   }
+  if (with_motion) HIP_TRY(S.motion.grow(pixels * RT_MOTION_CHANNELS));
   float *pl[5];                                                 // the staged planes, in HISTORY_PLANES' order
   for (int k = 0; k < 5; k++) pl[k] = S.planar + pixels * HISTORY_PLANES[k].offset;
   hipStream_t stream = nullptr;
   RT_Frame f;
   if (upload_host_frame(S.in, pixels, color, planes, &f) != 0) return -1;
+  if (with_motion) HIP_TRY(hipMemcpy(S.motion, h.motion, f3, hipMemcpyHostToDevice));
   if (history_in) {
     for (int k = 0; k < 5; k++)
       HIP_TRY(hipMemcpy(pl[k], history_in->*HISTORY_PLANES[k].member, f1 * HISTORY_PLANES[k].floats, hipMemcpyHostToDevice));
@@ -444,7 +474,7 @@ static int temporal_host(const char *who, bool with_moments, i32 width, i32 heig
   }
   const AccumulateIO d = {h.out ? S.out.get() : nullptr, h.length ? S.length.get() : nullptr, h.image ? S.image.get() : nullptr,
                           with_moments && history_in ? S.mom[0].get() : nullptr, with_moments ? S.mom[1].get() : nullptr,
-                          h.variance ? S.variance.get() : nullptr, h.vp};
+                          h.variance ? S.variance.get() : nullptr, h.vp, with_motion ? S.motion.get() : nullptr};
   if (enqueue_temporal(width, height, params, camera, previous_camera, f, history_in ? S.hist[0].get() : nullptr, S.hist[1], d,
                        stream) != 0)
     return -1;
@@ -469,7 +499,7 @@ extern "C" int rt_temporal_accumulate_host(i32 width, i32 height, RT_Temporal_Pa
                                            Camera const *previous_camera, f32 const *color, RT_Features const *planes,
                                            RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
                                            f32 *length, u8 *image) {
-  return temporal_host("rt_temporal_accumulate_host", false, width, height, params, camera, previous_camera, color, planes, history_in,
+  return temporal_host("rt_temporal_accumulate_host", false, false, width, height, params, camera, previous_camera, color, planes, history_in,
                        history_out, {out, length, image});
 }
 
@@ -478,8 +508,19 @@ extern "C" int rt_temporal_accumulate_moments_host(i32 width, i32 height, RT_Tem
                                                    RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
                                                    f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
                                                    f32 *moments_out, f32 *variance) {
-  return temporal_host("rt_temporal_accumulate_moments_host", true, width, height, params, camera, previous_camera, color, planes,
+  return temporal_host("rt_temporal_accumulate_moments_host", true, false, width, height, params, camera, previous_camera, color, planes,
                        history_in, history_out, {out, length, image, moments_in, moments_out, variance, vp});
+}
+
+// (vp, moments_in, moments_out and variance all NULL: the plain accumulation; otherwise the moments form, by its rules)
+extern "C" int rt_temporal_accumulate_motion_host(i32 width, i32 height, RT_Temporal_Params const *params, Camera const *camera,
+                                                  Camera const *previous_camera, f32 const *color, RT_Features const *planes,
+                                                  RT_History_Planes const *history_in, RT_History_Planes const *history_out, f32 *out,
+                                                  f32 *length, u8 *image, RT_Variance_Params const *vp, f32 const *moments_in,
+                                                  f32 *moments_out, f32 *variance, f32 const *motion) {
+  const bool with_moments = vp || moments_in || moments_out || variance;
+  return temporal_host("rt_temporal_accumulate_motion_host", with_moments, true, width, height, params, camera, previous_camera, color,
+                       planes, history_in, history_out, {out, length, image, moments_in, moments_out, variance, vp, motion});
 }
 
 // ---- the history a host keeps ---------------------------------------------------------------------------------------------------
@@ -510,6 +551,15 @@ extern "C" int rt_history_reset(RT_History *history) {
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
   history->valid = history->moments_valid = false;              // (the memory stays for the next frame)
+  return 0;
+}
+
+extern "C" int rt_history_set_motion(RT_History *history, int on) {
+  if (!history) return rt_fail("rt_history_set_motion: history is NULL");
+  if (on != 0 && on != 1) return rt_fail("rt_history_set_motion: on must be 0 or 1 (got %d)", on);
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  history->motion = on != 0;                                    // (the history itself stays: W_p is kept either way)
   return 0;
 }
 
@@ -546,7 +596,9 @@ struct PostOutputs { f32 *linear_noisy, *linear_out, *length, *variance; };
 // filter (s.g) -- in one scene-checked call.  W.linear is the noisy frame, D.temporal.out / length serve the accumulation,
 // D.guided.work / out the filter, and W.image receives the encoding of the LAST stage.  s.vp (with history and g): rt_render_svgf
 // -- the accumulation carries the history's moments, the variance launch follows it into D.temporal.variance, and the filter is
-// the variance-guided one.
+// the variance-guided one.  A history with motion on (rt_history_set_motion): the feature pass is the motion kernel's -- one
+// launch -- against the scene's kept geometry, its motion sums are resolved into F.motion, and the accumulation is THE ACCUMULATION
+// WITH MOTION.
 static int render_post(const char *who, PostFrame const &kind, Scene const *scene, Image const *image, isize samples, isize max_bounces,
                        PostStages const &s, PostOutputs const &o) {
   // before the device lock: the image's size before it goes into 32 bits, the stages' parameters, the rest of the frame's
@@ -590,6 +642,11 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
   if (ensure_ws_buffers(W, p.width, p.height, 0, 0) != 0) return -1;
   HIP_TRY(F.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(F.planes.grow(pixels * RT_FEATURE_CHANNELS));
+  const bool motion = history && history->motion;
+  if (motion) {
+    HIP_TRY(F.motion_sums.grow(pixels * RT_MOTION_CHANNELS));
+    HIP_TRY(F.motion.grow(pixels * RT_MOTION_CHANNELS));
+  }
   const bool want_accumulated = history && (g || o.linear_out);   // the accumulation's f32 output: the filter's input, or the caller's
   const uint8_t *h_in = nullptr;
   uint8_t *h_out = nullptr;
@@ -612,6 +669,7 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
       a.variance = S.variance;
       a.vp = s.vp;
     }
+    a.motion = motion ? F.motion.get() : nullptr;
   }
   if (g) {
     HIP_TRY(G.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
@@ -623,8 +681,10 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
   auto pass = [&](RT_Device_Scene *d) -> int {
     if (enqueue_frame(D, d, &scene->camera, &p, W, stream, 0, nullptr, nullptr, W.linear) != 0) return -1;
     HIP_TRY(hipMemsetAsync(F.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
-    if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream) != 0) return -1;
+    if (motion) HIP_TRY(hipMemsetAsync(F.motion_sums, 0, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), stream));
+    if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream, motion ? F.motion_sums.get() : nullptr) != 0) return -1;
     if (enqueue_resolve(&p, F.sums, planes.coverage, planes.albedo, planes.normal, planes.position, stream) != 0) return -1;
+    if (motion && enqueue_resolve_motion(&p, F.motion_sums, F.motion, stream) != 0) return -1;
     if (history && enqueue_temporal(p.width, p.height, s.t, &scene->camera, &history->camera, device_frame(W.linear, planes), h_in, h_out,
                                     a, stream) != 0)
       return -1;

@@ -504,6 +504,48 @@ extern "C" void rt_scene_invalidate(Scene const *scene) {
 
 extern "C" i64 rt_scene_device_bytes(RT_Device_Scene const *dscene) { return dscene ? dscene->bytes : 0; }
 
+// ---- kept geometry ---------------------------------------------------------------------------------------------------------
+// What THE MOTION of a feature pass is measured against (include/rt_hip.h): the copy's leaf tiles as they are now, saved by ONE
+// device-to-device copy before the host deforms the mesh (scene_refit_gpu rewrites d->leaves in place and keeps every triangle in
+// its slot).  The snapshot is a member of the copy: whatever drops the copy -- invalidate, a re-upload, rt_scene_free, a refit that
+// falls back to scene_refit, release_staging -- drops it too.
+
+// D.mutex held, D's GPU current.
+static int keep_geometry_locked(RT_Device_Scene *d, hipStream_t stream) {
+  const size_t n = d->leaves.cap;                                 // 72 f32 per leaf group
+  d->has_kept = false;
+  HIP_TRY(d->kept_leaves.grow(n));
+  if (n) HIP_TRY(hipMemcpyAsync(d->kept_leaves, d->leaves, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  d->has_kept = true;
+  return 0;
+}
+
+extern "C" int rt_device_scene_keep_geometry(RT_Device_Scene *dscene, void *stream) {
+  if (!dscene) return rt_fail("rt_device_scene_keep_geometry: device scene is NULL");
+  Device &D = dscene->dev ? *dscene->dev : dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  return keep_geometry_locked(dscene, (hipStream_t)stream);
+}
+
+extern "C" int rt_scene_keep_geometry(Scene const *scene) {
+  if (!scene) return rt_fail("rt_scene_keep_geometry: scene is NULL");
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  RT_Device_Scene *d = cached_scene_locked(D, scene, nullptr, nullptr);      // (the ordinary upload when there is no copy)
+  if (!d) return -1;
+  return keep_geometry_locked(d, nullptr);                        // (a refit that follows waits for the device before it writes)
+}
+
+extern "C" int rt_scene_has_kept_geometry(Scene const *scene) {
+  if (!scene) return 0;
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  auto it = D.scene_cache.find(scene);
+  return it != D.scene_cache.end() && it->second->has_kept ? 1 : 0;
+}
+
 // ---- in-place edits of a resident scene ------------------------------------------------------------------------------------
 // The reference reads the live Scene every frame (raytracer.c:596-612).  Here a frame renders from the device copy, and
 // three things keep the two equal:

@@ -25,6 +25,15 @@ __global__ __launch_bounds__(TP_TX * TP_TY) void rt_temporal_kernel(RT_TParams P
   temporal_pixel<false>(P, color, coverage, albedo, normal, position, hist_in, hist_out, out, length, image, nullptr, nullptr);
 }
 
+// ... with one more plane, the motion of the first hits (include/rt_hip.h, "THE ACCUMULATION WITH MOTION")
+__global__ __launch_bounds__(TP_TX * TP_TY) void rt_temporal_motion_kernel(RT_TParams P, const float *color, const float *coverage,
+                                                                            const float *albedo, const float *normal,
+                                                                            const float *position, const float *motion,
+                                                                            const float4 *hist_in, float4 *hist_out, float *out,
+                                                                            float *length, uint8_t *image) {
+  temporal_pixel<false, true>(P, color, coverage, albedo, normal, position, hist_in, hist_out, out, length, image, nullptr, nullptr, motion);
+}
+
 // planar (colour [n][3], length [n], coverage [n], N [n][3], W [n][3]) -> the three float4 planes
 __global__ __launch_bounds__(256) void rt_temporal_pack_history(int n_pixels, const float *c, const float *len, const float *cov,
                                                                 const float *n, const float *w, float4 *hist) {
@@ -55,6 +64,14 @@ extern "C" int rt_launch_temporal(const RT_TParams *P, RT_Frame frame, const voi
   const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
   hipLaunchKernelGGL(rt_temporal_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage, frame.albedo, frame.normal,
                      frame.position, (const float4 *)hist_in, (float4 *)hist_out, out, length, image);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_temporal_motion(const RT_TParams *P, RT_Frame frame, const float *motion, const void *hist_in, void *hist_out,
+                                         float *out, float *length, uint8_t *image, hipStream_t stream) {
+  const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
+  hipLaunchKernelGGL(rt_temporal_motion_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage, frame.albedo,
+                     frame.normal, frame.position, motion, (const float4 *)hist_in, (float4 *)hist_out, out, length, image);
   return (int)hipGetLastError();
 }
 

@@ -3,7 +3,10 @@
 // reprojection, shared by rt_temporal_kernel (rt_temporal.hip: MOMENTS = false) and rt_temporal_moments_kernel (rt_variance.hip:
 // MOMENTS = true), which carries the first and second moment of the demodulated luminance through the same taps with the same
 // weights ("THE MOMENTS") and writes the 16-byte moments record next to the history.  With MOMENTS = false nothing of the moments
-// is compiled: rt_temporal_kernel pays nothing for them.
+// is compiled: rt_temporal_kernel pays nothing for them.  MOTION = true ("THE ACCUMULATION WITH MOTION": rt_temporal_motion_kernel,
+// rt_temporal_moments_motion_kernel) reads one more plane, the mean motion of the pixel's first hits, projects where the surface
+// point WAS into the previous camera and measures a tap's plane distance from there; with MOTION = false nothing of that is compiled
+// either, and the two instances above are what they were.
 
 #pragma once
 
@@ -38,11 +41,13 @@ __device__ __forceinline__ bool temporal_project(const RT_TCamera &c, float aspe
 }
 
 // The pixel of thread (threadIdx.x, threadIdx.y) of block blockIdx.x.  mom_in / mom_out: planes of float4 (m1, m2, 0, 0), read and
-// written only when MOMENTS; mom_in is given exactly when hist_in is.
-template <bool MOMENTS>
+// written only when MOMENTS; mom_in is given exactly when hist_in is.  motion: f32[h][w][3] as rt_resolve_motion writes it, read only
+// when MOTION.
+template <bool MOMENTS, bool MOTION = false>
 __device__ __forceinline__ void temporal_pixel(const RT_TParams &P, const float *color, const float *coverage, const float *albedo,
                                                const float *normal, const float *position, const float4 *hist_in, float4 *hist_out,
-                                               float *out, float *length, uint8_t *image, const float4 *mom_in, float4 *mom_out) {
+                                               float *out, float *length, uint8_t *image, const float4 *mom_in, float4 *mom_out,
+                                               const float *motion = nullptr) {
   // (a one-dimensional grid: an image of one column may be 2^28 rows high)
   const int tile_x = (int)(blockIdx.x % (unsigned)P.tiles_x), tile_y = (int)(blockIdx.x / (unsigned)P.tiles_x);
   const int x = tile_x * TP_TX + (int)threadIdx.x, y = tile_y * TP_TY + (int)threadIdx.y;
@@ -76,7 +81,14 @@ __device__ __forceinline__ void temporal_pixel(const RT_TParams &P, const float 
     const float wx = position[p3] / cov, wy = position[p3 + 1] / cov, wz = position[p3 + 2] / cov;
     float fxc, fyc, dc, fxv, fyv, dv;
     const bool front_c = temporal_project(P.cur, P.aspect, P.half_w, P.half_h, wx, wy, wz, fxc, fyc, dc);
-    const bool front_v = temporal_project(P.prev, P.aspect, P.half_w, P.half_h, wx, wy, wz, fxv, fyv, dv);
+    // V_p: where the mean surface point was (MOTION: W_p + M_p, M_p = motion_p / cov; otherwise W_p itself)
+    float vx = wx, vy = wy, vz = wz;
+    if (MOTION) {
+      vx = wx + motion[p3] / cov;
+      vy = wy + motion[p3 + 1] / cov;
+      vz = wz + motion[p3 + 2] / cov;
+    }
+    const bool front_v = temporal_project(P.prev, P.aspect, P.half_w, P.half_h, vx, vy, vz, fxv, fyv, dv);
     const float hx = (float)x + (fxv - fxc), hy = (float)y + (fyv - fyc);
     // (every comparison is false for NaN)
     const bool usable = hist_in != nullptr && front_c && front_v && hx >= -1.0f && hx < (float)width && hy >= -1.0f && hy < (float)height;
@@ -98,7 +110,7 @@ __device__ __forceinline__ void temporal_pixel(const RT_TParams &P, const float 
         const float b = bx[k & 1] * by[k >> 1];
         const float dnx = nx - q1.x, dny = ny - q1.y, dnz = nz - q1.z;
         const float dn2 = dnx * dnx + dny * dny + dnz * dnz;
-        const float ex = q2.x - wx, ey = q2.y - wy, ez = q2.z - wz;
+        const float ex = q2.x - vx, ey = q2.y - vy, ez = q2.z - vz;
         const float pl = nx * ex + ny * ey + nz * ez;                           // distance of the old point from p's tangent plane
         if (dn2 <= P.tn2 && pl * pl <= plane_bound) {
           sw = sw + b;

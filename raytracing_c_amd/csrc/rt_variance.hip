@@ -5,7 +5,8 @@
 // operation by operation: f32 + - * / only, every operation rounded on its own (-ffp-contract=off), sums left to right, taps in a
 // fixed order -- a float32 restatement on the CPU (tests/_variance.py) equals the result bit for bit.
 //
-// rt_temporal_moments_kernel: rt_temporal_kernel with the moments, ONE launch and ONE reprojection (rt_temporal_pixel.hip.h).
+// rt_temporal_moments_kernel: rt_temporal_kernel with the moments, ONE launch and ONE reprojection (rt_temporal_pixel.hip.h);
+// rt_temporal_moments_motion_kernel: the same with the motion plane of a deforming mesh.
 //
 // rt_variance_kernel: one thread per pixel, a 32 x 8 tile per workgroup, a one-dimensional grid.  A pixel whose new history is at
 // least 4 frames long takes the temporal variance from its own moments record.  Only a workgroup that has a shorter pixel stages
@@ -32,6 +33,16 @@ __global__ __launch_bounds__(TP_TX * TP_TY) void rt_temporal_moments_kernel(RT_T
                                                                              float4 *hist_out, float *out, float *length, uint8_t *image,
                                                                              const float4 *mom_in, float4 *mom_out) {
   temporal_pixel<true>(P, color, coverage, albedo, normal, position, hist_in, hist_out, out, length, image, mom_in, mom_out);
+}
+
+// ... with the motion plane ("THE ACCUMULATION WITH MOTION"): the moments ride through the taps the motion chose
+__global__ __launch_bounds__(TP_TX * TP_TY) void rt_temporal_moments_motion_kernel(RT_TParams P, const float *color, const float *coverage,
+                                                                                    const float *albedo, const float *normal,
+                                                                                    const float *position, const float *motion,
+                                                                                    const float4 *hist_in, float4 *hist_out, float *out,
+                                                                                    float *length, uint8_t *image, const float4 *mom_in,
+                                                                                    float4 *mom_out) {
+  temporal_pixel<true, true>(P, color, coverage, albedo, normal, position, hist_in, hist_out, out, length, image, mom_in, mom_out, motion);
 }
 
 // hist: the NEW history's three planes; mom: the NEW moments.  Block b is tile (b % tiles_x, b / tiles_x).
@@ -146,6 +157,16 @@ extern "C" int rt_launch_temporal_moments(const RT_TParams *P, RT_Frame frame, c
   const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
   hipLaunchKernelGGL(rt_temporal_moments_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage, frame.albedo,
                      frame.normal, frame.position, (const float4 *)hist_in, (float4 *)hist_out, out, length, image,
+                     (const float4 *)mom_in, (float4 *)mom_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_temporal_moments_motion(const RT_TParams *P, RT_Frame frame, const float *motion, const void *hist_in,
+                                                 void *hist_out, float *out, float *length, uint8_t *image, const void *mom_in,
+                                                 void *mom_out, hipStream_t stream) {
+  const unsigned blocks = (unsigned)P->tiles_x * (unsigned)((P->height + TP_TY - 1) / TP_TY);
+  hipLaunchKernelGGL(rt_temporal_moments_motion_kernel, dim3(blocks), dim3(TP_TX, TP_TY), 0, stream, *P, frame.color, frame.coverage,
+                     frame.albedo, frame.normal, frame.position, motion, (const float4 *)hist_in, (float4 *)hist_out, out, length, image,
                      (const float4 *)mom_in, (float4 *)mom_out);
   return (int)hipGetLastError();
 }

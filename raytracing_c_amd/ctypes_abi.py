@@ -155,6 +155,7 @@ class RT_Features(C.Structure):  # rt_hip.h: the planes rt_render_features fills
 
 
 RT_FEATURE_CHANNELS = 10          # coverage, albedo rgb, normal xyz, position xyz
+RT_MOTION_CHANNELS = 3            # THE MOTION xyz, a buffer of its own (rt_render_features_motion)
 
 
 class RT_Guided_Params(C.Structure):  # rt_hip.h: the guided denoiser's parameters
@@ -224,14 +225,17 @@ EXPORTED_SYMBOLS = [
     "rt_set_devices", "rt_device_count", "rt_math_contract",
     "rt_scene_verify", "rt_scene_touch", "rt_scene_set_static", "rt_get_frame_timing",
     "rt_scene_upload", "rt_scene_release", "rt_scene_invalidate", "rt_scene_device_bytes", "rt_set_camera",
+    "rt_device_scene_keep_geometry", "rt_scene_keep_geometry", "rt_scene_has_kept_geometry",
     "rt_chunk_count", "rt_chunk_owner", "rt_local_chunk_count", "rt_max_local_chunk_count", "rt_local_chunk_list", "rt_render_accumulate", "rt_resolve", "rt_untile",
     "rt_denoise", "rt_render_frame", "rt_frame_begin", "rt_frame_end", "rt_render_views", "rt_render_accumulate_views",
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
+    "rt_render_accumulate_features_motion", "rt_resolve_motion", "rt_render_features_motion",
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
-    "rt_history_destroy", "rt_render_temporal",
+    "rt_history_destroy", "rt_history_set_motion", "rt_render_temporal",
     "rt_temporal_moments_bytes", "rt_temporal_accumulate_moments", "rt_temporal_accumulate_moments_host",
+    "rt_temporal_accumulate_motion", "rt_temporal_accumulate_motion_host",
     "rt_guided_variance_work_bytes", "rt_guided_denoise_variance", "rt_guided_denoise_variance_host", "rt_render_svgf",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_fused_root_visits", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
@@ -240,7 +244,7 @@ EXPORTED_SYMBOLS = [
 # NOT carry them (tests/test_abi.py)
 DIAG_ONLY_SYMBOLS = [
     "rt_diag_set_tokens", "rt_diag_multi_fault", "rt_set_pipeline", "rt_get_pipeline", "rt_set_wavefront_capacity", "rt_get_wave_times", "rt_get_ledger",
-    "rt_diag_device_bytes_live", "rt_diag_release_staging",
+    "rt_diag_device_bytes_live", "rt_diag_release_staging", "rt_diag_cached_scene",
     "rt_test_math", "rt_test_rcp_sweep", "rt_test_srgb_sweep", "rt_test_env_sweep", "rt_test_quantize_sweep", "rt_test_group_sum", "rt_test_sky_add_group", "rt_test_node_order", "rt_test_trace", "rt_test_trace_stream",
     "rt_test_tile_order", "rt_test_texture", "rt_test_shade", "rt_test_shade_hit", "rt_test_feature_hit", "rt_test_brdf", "rt_test_background", "rt_test_primary_ray",
 ]

@@ -179,6 +179,19 @@ def _declare(d):
                                                       vp]
         d.rt_render_svgf.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, vp, P(abi.RT_Temporal_Params),
                                      P(abi.RT_Variance_Params), P(abi.RT_Guided_Params), vp, vp, vp, vp]
+    if hasattr(d, "rt_scene_keep_geometry"):               # (absent from older builds loaded as A/B partners)
+        d.rt_device_scene_keep_geometry.argtypes = [vp, vp]
+        d.rt_scene_keep_geometry.argtypes = [P(abi.Scene)]
+        d.rt_scene_has_kept_geometry.argtypes = [P(abi.Scene)]
+        d.rt_render_accumulate_features_motion.argtypes = [vp, P(abi.RT_Render_Params), vp, vp, vp]
+        d.rt_resolve_motion.argtypes = [P(abi.RT_Render_Params), vp, vp, vp]
+        d.rt_render_features_motion.argtypes = [P(abi.Scene), C.c_int32, C.c_int32, abi.isize, abi.isize, P(abi.RT_Features), vp, vp, vp]
+        d.rt_temporal_accumulate_motion.argtypes = ([C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera)]
+                                                    + [vp] * 10 + [P(abi.RT_Variance_Params)] + [vp] * 5)
+        d.rt_temporal_accumulate_motion_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Temporal_Params), P(abi.Camera), P(abi.Camera),
+                                                         vp, P(abi.RT_Features), P(abi.RT_History_Planes), P(abi.RT_History_Planes),
+                                                         vp, vp, vp, P(abi.RT_Variance_Params), vp, vp, vp, vp]
+        d.rt_history_set_motion.argtypes = [vp, C.c_int]
     d.rt_get_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_get_skipped_root_visits"):           # (absent from older builds that tools/exp_small_ab.sh loads as A/B partners)
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
@@ -242,6 +255,8 @@ def _declare_diag(d):
     d.rt_diag_device_bytes_live.argtypes = []
     d.rt_diag_device_bytes_live.restype = C.c_int64
     d.rt_diag_release_staging.argtypes = []
+    d.rt_diag_cached_scene.argtypes = [C.POINTER(abi.Scene)]
+    d.rt_diag_cached_scene.restype = vp
     d.rt_diag_multi_fault.argtypes = [C.c_int32, C.c_int32]
     d.rt_diag_multi_fault.restype = None
     d.rt_diag_set_tokens.argtypes = [vp, vp, vp]

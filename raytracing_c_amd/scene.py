@@ -149,6 +149,17 @@ class HostScene:
             raise RuntimeError(("scene_refit_gpu: " if device == "gpu" else "scene_refit: ") + last_error())
         self.source_triangles[...] = tri
 
+    def keep_geometry(self):
+        """rt_scene_keep_geometry: the device copy's geometry as it is now becomes what THE MOTION of later feature passes
+        (features.render_features(motion=True), temporal.History(motion=True)) is measured against.  The animation loop is
+        render -> keep_geometry() -> refit(...) -> render."""
+        if lib.rt_scene_keep_geometry(C.byref(self.scene)) != 0:
+            raise RuntimeError("rt_scene_keep_geometry: " + last_error())
+
+    @property
+    def has_kept_geometry(self):
+        return bool(lib.rt_scene_has_kept_geometry(C.byref(self.scene)))
+
     def free(self):
         if not self._freed:
             try:

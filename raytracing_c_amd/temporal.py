@@ -44,12 +44,14 @@ def _history_planes(h, w, given=None):
 
 
 def temporal_accumulate(color, coverage, albedo, normal, position, camera, previous_camera=None, history=None, alpha=0.05,
-                        max_history=64, normal_tolerance=0.3, plane_tolerance=0.02, demodulate=True, image=False, lib=None) -> dict:
+                        max_history=64, normal_tolerance=0.3, plane_tolerance=0.02, demodulate=True, image=False, lib=None,
+                        motion=None) -> dict:
     """One accumulation step: dict(out float32 (h, w, 3), length float32 (h, w), history, and with image=True image uint8 (h, w, 3)).
     numpy arrays go through rt_temporal_accumulate_host, and a history is a dict of the planes HISTORY_PLANES; torch GPU tensors go
     through rt_temporal_accumulate on torch's current stream (the call only enqueues), and a history is a float32 tensor
     (3, h, w, 4): the three planes of float4 records.  history=None: no history (previous_camera is not read).  `albedo` may be
-    None when demodulate is False.  Cameras: abi.Camera or (view matrix, focal_length)."""
+    None when demodulate is False.  Cameras: abi.Camera or (view matrix, focal_length).  motion: None, or the (h, w, 3) float32
+    motion plane of render_features(motion=True) -- THE ACCUMULATION WITH MOTION, through rt_temporal_accumulate_motion(_host)."""
     lib = lib or _lib
     params = _params(alpha, max_history, normal_tolerance, plane_tolerance, demodulate)
     cam = as_camera(camera)
@@ -62,7 +64,14 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
         out = np.zeros((h, w, 3), np.float32)
         length = np.zeros((h, w), np.float32)
         img = np.zeros((h, w, 3), np.uint8) if image else None
-        if lib.rt_temporal_accumulate_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col,
+        if motion is not None:
+            mot = _host_plane(motion, (h, w, 3), "motion")
+            if lib.rt_temporal_accumulate_motion_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col,
+                                                      C.byref(planes), None if h_in is None else C.byref(h_in), C.byref(h_out),
+                                                      out.ctypes.data, length.ctypes.data, img.ctypes.data if image else None,
+                                                      None, None, None, None, mot.ctypes.data) != 0:
+                raise RuntimeError("rt_temporal_accumulate_motion_host failed: " + last_error(lib))
+        elif lib.rt_temporal_accumulate_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col,
                                            C.byref(planes), None if h_in is None else C.byref(h_in), C.byref(h_out), out.ctypes.data,
                                            length.ctypes.data, img.ctypes.data if image else None) != 0:
             raise RuntimeError("rt_temporal_accumulate_host failed: " + last_error(lib))
@@ -74,13 +83,19 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
     dev = color.device
     frame = _device_frame(color, coverage, albedo, normal, position)
     h_in = None if history is None else _device_plane(history, (3, h, w, 4), "history", dev)
+    mot = None if motion is None else _device_plane(motion, (h, w, 3), "motion", dev)
     with torch.cuda.device(dev):
         new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
         out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         length = torch.empty((h, w), dtype=torch.float32, device=dev)
         img = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if image else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if lib.rt_temporal_accumulate(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame, h_in,
+        if motion is not None:
+            if lib.rt_temporal_accumulate_motion(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame,
+                                                 h_in, new.data_ptr(), out.data_ptr(), length.data_ptr(),
+                                                 img.data_ptr() if image else None, None, None, None, None, stream, mot) != 0:
+                raise RuntimeError("rt_temporal_accumulate_motion failed: " + last_error(lib))
+        elif lib.rt_temporal_accumulate(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame, h_in,
                                       new.data_ptr(), out.data_ptr(), length.data_ptr(), img.data_ptr() if image else None, stream) != 0:
             raise RuntimeError("rt_temporal_accumulate failed: " + last_error(lib))
     res = dict(out=out, length=length, history=new)
@@ -90,14 +105,23 @@ def temporal_accumulate(color, coverage, albedo, normal, position, camera, previ
 
 
 class History:
-    """rt_history_create / rt_history_reset / rt_history_destroy: the history of one sequence, for render_temporal()."""
+    """rt_history_create / rt_history_reset / rt_history_destroy: the history of one sequence, for render_temporal().
+    motion=True: for a mesh deformed between the frames (rt_history_set_motion)."""
 
-    def __init__(self, width, height, lib=None):
+    def __init__(self, width, height, lib=None, motion=False):
         self.lib = lib or _lib
         self.width, self.height = int(width), int(height)
         self.handle = self.lib.rt_history_create(self.width, self.height)
         if not self.handle:
             raise RuntimeError("rt_history_create failed: " + last_error(self.lib))
+        if motion:
+            self.set_motion(True)
+
+    def set_motion(self, on):
+        """rt_history_set_motion: frames on this history use the motion feature pass and THE ACCUMULATION WITH MOTION, against the
+        scene's kept geometry (HostScene.keep_geometry)."""
+        if self.lib.rt_history_set_motion(self.handle, 1 if on else 0) != 0:
+            raise RuntimeError("rt_history_set_motion failed: " + last_error(self.lib))
 
     def reset(self):
         if self.lib.rt_history_reset(self.handle) != 0:

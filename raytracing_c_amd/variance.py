@@ -19,12 +19,13 @@ def _variance_params(sigma_normal, sigma_position):
 
 def temporal_accumulate_moments(color, coverage, albedo, normal, position, camera, previous_camera=None, history=None, moments=None,
                                 alpha=0.05, max_history=64, normal_tolerance=0.3, plane_tolerance=0.02, demodulate=True,
-                                sigma_normal=0.2, sigma_position=None, image=False, lib=None) -> dict:
+                                sigma_normal=0.2, sigma_position=None, image=False, lib=None, motion=None) -> dict:
     """temporal_accumulate() with the moments and the variance: dict(out, length, history, moments, variance float32 (h, w), and
     with image=True image).  numpy arrays go through rt_temporal_accumulate_moments_host and moments are float32 (h, w, 2); torch
     GPU tensors go through rt_temporal_accumulate_moments on torch's current stream and moments are float32 (h, w, 4): the records
     (m1, m2, 0, 0).  history and moments are given both or neither.  sigma_position=None: default_sigma_position(position,
-    coverage)."""
+    coverage).  motion: None, or the (h, w, 3) float32 motion plane of render_features(motion=True) -- the moments form of THE
+    ACCUMULATION WITH MOTION, through rt_temporal_accumulate_motion(_host)."""
     lib = lib or _lib
     if sigma_position is None:
         sigma_position = default_sigma_position(position, coverage)
@@ -43,11 +44,15 @@ def temporal_accumulate_moments(color, coverage, albedo, normal, position, camer
         m_out = np.zeros((h, w, 2), np.float32)
         var = np.zeros((h, w), np.float32)
         img = np.zeros((h, w, 3), np.uint8) if image else None
-        if lib.rt_temporal_accumulate_moments_host(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col,
-                                                   C.byref(planes), None if h_in is None else C.byref(h_in), C.byref(h_out),
-                                                   out.ctypes.data, length.ctypes.data, img.ctypes.data if image else None,
-                                                   C.byref(vparams), None if m_in is None else m_in.ctypes.data, m_out.ctypes.data,
-                                                   var.ctypes.data) != 0:
+        args = (w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), col, C.byref(planes),
+                None if h_in is None else C.byref(h_in), C.byref(h_out), out.ctypes.data, length.ctypes.data,
+                img.ctypes.data if image else None, C.byref(vparams), None if m_in is None else m_in.ctypes.data, m_out.ctypes.data,
+                var.ctypes.data)
+        if motion is not None:
+            mot = _host_plane(motion, (h, w, 3), "motion")
+            if lib.rt_temporal_accumulate_motion_host(*args, mot.ctypes.data) != 0:
+                raise RuntimeError("rt_temporal_accumulate_motion_host failed: " + last_error(lib))
+        elif lib.rt_temporal_accumulate_moments_host(*args) != 0:
             raise RuntimeError("rt_temporal_accumulate_moments_host failed: " + last_error(lib))
         res = dict(out=out, length=length, history=new, moments=m_out, variance=var)
         if image:
@@ -58,6 +63,7 @@ def temporal_accumulate_moments(color, coverage, albedo, normal, position, camer
     frame = _device_frame(color, coverage, albedo, normal, position)
     h_in = None if history is None else _device_plane(history, (3, h, w, 4), "history", dev)
     m_in = None if moments is None else _device_plane(moments, (h, w, 4), "moments", dev)
+    mot = None if motion is None else _device_plane(motion, (h, w, 3), "motion", dev)
     with torch.cuda.device(dev):
         new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
         m_out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
@@ -66,9 +72,13 @@ def temporal_accumulate_moments(color, coverage, albedo, normal, position, camer
         var = torch.empty((h, w), dtype=torch.float32, device=dev)
         img = torch.empty((h, w, 3), dtype=torch.uint8, device=dev) if image else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if lib.rt_temporal_accumulate_moments(w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame, h_in,
-                                              new.data_ptr(), out.data_ptr(), length.data_ptr(), img.data_ptr() if image else None,
-                                              C.byref(vparams), m_in, m_out.data_ptr(), var.data_ptr(), stream) != 0:
+        args = (w, h, C.byref(params), C.byref(cam), None if prev is None else C.byref(prev), *frame, h_in, new.data_ptr(),
+                out.data_ptr(), length.data_ptr(), img.data_ptr() if image else None, C.byref(vparams), m_in, m_out.data_ptr(),
+                var.data_ptr(), stream)
+        if motion is not None:
+            if lib.rt_temporal_accumulate_motion(*args, mot) != 0:
+                raise RuntimeError("rt_temporal_accumulate_motion failed: " + last_error(lib))
+        elif lib.rt_temporal_accumulate_moments(*args) != 0:
             raise RuntimeError("rt_temporal_accumulate_moments failed: " + last_error(lib))
     res = dict(out=out, length=length, history=new, moments=m_out, variance=var)
     if image:
