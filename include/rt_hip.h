@@ -410,7 +410,7 @@ extern int rt_render_features_motion(Scene const *scene, i32 width, i32 height, 
  *     c'_p = sum_c / sum_w (the centre tap has wgt = 0.140625, so sum_w > 0)
  *     a pixel with coverage_p == 0 keeps c_p: sky is not noisy, and the features say nothing about it
  *   Output: out_p = c_p * m_p; where coverage_p == 0, out_p = color_p bit for bit.  The u8 image is rt_encode_u8(out) per channel
- *     (rt_math.h), under the library's numeric contract like rt_resolve's.
+ *     (rt_math.h), under the library's numeric contract like rt_resolve's; a NaN encodes to 0, here and in every pass below.
  * Not done: several devices, view batches.  (Reuse over time: temporal accumulation below; a luminance term measured in the pixel's
  * own variance: "variance-guided denoising" further below.) */
 typedef struct {

@@ -77,6 +77,12 @@ extern int rt_test_env_sweep(i32 which, u32 seed, u64 out[4]);
 /* the tile-stream kernel's fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit patterns:
  * out[0] differing patterns (0 expected), out[1] first differing pattern + 1 */
 extern int rt_test_quantize_sweep(u64 out[2]);
+/* rt_encode_u8() (rt_math.h: the last step of every image, rt_resolve's and the post passes') on the device over all 2^32 bit
+ * patterns: out[k], k < 256, the lowest pattern in [0, 0x3F800000] -- the floats of [0, 1] -- that encodes to k (2^32 when none
+ * does); out[256] patterns of that range, in ascending order, whose byte is below that of the pattern before (0 expected);
+ * out[257] patterns in (1.0, +inf] that do not give 255, out[258] negative patterns, -0 and -inf included, that do not give 0,
+ * out[259] NaN patterns that do not give 0 (0 expected each).  The CPU counterpart of the table is oracle_encode_steps(). */
+extern int rt_test_encode_sweep(u64 out[260]);
 /* the sky loop's sample reduction (group_sum3_u64, rt_dev.hip.h) on lanes a test chooses: three channels of n = n_waves x 64
  * values, channel c of lane i & 63 of wave i >> 6 at in[c * n + i]; a lane with valid[i] == 0 contributes 0.  out[c * n + i] = the
  * sum mod 2^64 of channel c over lane i's aligned group of `group` lanes (4, 16 or 64), which every lane of the group must hold. */

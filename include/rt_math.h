@@ -435,9 +435,13 @@ RT_FN float rt_accum_resolve_signed(uint64_t sum, uint32_t samples) {
   return (float)mean;
 }
 
-/* average -> clamp -> sRGB -> u8, raytracer.c:700-716 */
+/* average -> clamp -> sRGB -> u8, raytracer.c:700-716.  The clamp is written so that NaN FAILS it, as in rt_accum_quantize():
+ * a NaN pixel encodes to 0 (deviation D11, oracle/oracle.h).  rt_clampf() lets NaN through, rt_powf() turns it into 0, the
+ * sRGB formula into -0.055, and the conversion of -14.08f to uint8_t is undefined in C.  Every other input keeps its byte:
+ * -0 becomes +0 here, and 12.92f * 0 * 255.999f truncates to 0 with either sign. */
 RT_FN uint8_t rt_encode_u8(float linear) {
-  float c = rt_clampf(linear, 0.0f, 1.0f);
+  float c = (linear > 0.0f) ? linear : 0.0f;
+  c = (c > 1.0f) ? 1.0f : c;
   c = rt_linear_to_srgb(c);
   c = c * 255.999f;
   return (uint8_t)c;

@@ -1016,6 +1016,74 @@ void oracle_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out) {
 
 u8 oracle_encode_u8(f32 linear) { return rt_encode_u8(linear); }
 
+void oracle_encode_u8_array(isize n, f32 const *linear, u8 *out) {
+  for (isize i = 0; i < n; i++) out[i] = rt_encode_u8(linear[i]);
+}
+
+/* The step table of rt_encode_u8() over every float in [0, 1]: bit patterns 0 .. 0x3F800000 in ascending order, threads claim
+ * chunks of 2^20 patterns as oracle_render's claim 32x32 pixels.  A chunk starts from the byte of the pattern before it, so a
+ * descent across a chunk boundary counts. */
+#define ENCODE_STEPS_LAST  0x3F800000u
+#define ENCODE_STEPS_CHUNK (1u << 20)
+
+typedef struct {
+  atomic_int      current_chunk;
+  pthread_mutex_t lock;
+  u64             first[256];      /* lowest pattern per byte, 2^32 = none */
+  u64             descents;
+} Encode_Steps_Job;
+
+static void *encode_steps_worker(void *arg) {
+  Encode_Steps_Job *job = (Encode_Steps_Job *)arg;
+  u64 first[256], descents = 0;
+  for (int k = 0; k < 256; k++) first[k] = 1ull << 32;
+  i32 n_chunks = (i32)(ENCODE_STEPS_LAST / ENCODE_STEPS_CHUNK) + 1;
+  for (;;) {
+    i32 c = atomic_fetch_add(&job->current_chunk, 1);
+    if (c >= n_chunks) break;
+    u32 b0 = (u32)c * ENCODE_STEPS_CHUNK;
+    u32 b1 = b0 + (ENCODE_STEPS_CHUNK - 1u);
+    if (b1 > ENCODE_STEPS_LAST) b1 = ENCODE_STEPS_LAST;
+    i32 prev = b0 ? (i32)rt_encode_u8(rt_u2f(b0 - 1u)) : -1;
+    for (u32 b = b0; b <= b1; b++) {
+      i32 v = (i32)rt_encode_u8(rt_u2f(b));
+      if (v != prev) {
+        if ((u64)b < first[v]) first[v] = b;
+        if (v < prev) descents += 1;
+        prev = v;
+      }
+    }
+  }
+  pthread_mutex_lock(&job->lock);
+  for (int k = 0; k < 256; k++) if (first[k] < job->first[k]) job->first[k] = first[k];
+  job->descents += descents;
+  pthread_mutex_unlock(&job->lock);
+  return NULL;
+}
+
+int oracle_encode_steps(u32 first[256], u64 *descents, i32 n_threads) {
+  if (!first || !descents) return -1;
+  Encode_Steps_Job job;
+  atomic_init(&job.current_chunk, 0);
+  pthread_mutex_init(&job.lock, NULL);
+  for (int k = 0; k < 256; k++) job.first[k] = 1ull << 32;
+  job.descents = 0;
+  i32 n = n_threads < 1 ? 1 : n_threads;
+  if (n > 256) n = 256;
+  pthread_t threads[256];
+  for (i32 i = 1; i < n; i++) pthread_create(&threads[i], NULL, encode_steps_worker, &job);
+  encode_steps_worker(&job);
+  for (i32 i = 1; i < n; i++) pthread_join(threads[i], NULL);
+  pthread_mutex_destroy(&job.lock);
+  i32 seen = 0;
+  for (int k = 0; k < 256; k++) {
+    seen += job.first[k] <= ENCODE_STEPS_LAST ? 1 : 0;
+    first[k] = job.first[k] <= ENCODE_STEPS_LAST ? (u32)job.first[k] : 0xFFFFFFFFu;
+  }
+  *descents = job.descents;
+  return seen;
+}
+
 /* Test-only switch (tests/test_reference_pin.py): the unit-level entry points above run with the default semantics
  * (oracle_render resets the flag); 1 makes the CALLING thread evaluate the D8 sites as ORACLE_LITERAL does, until it is set
  * back or oracle_render runs.  Returns the previous mode. */

@@ -39,6 +39,12 @@
  *   D10 (lightmap) a texel is stored as (u8) of the mean clamped to [0, 255], NaN as 0; the reference converts the raw
  *      float (raytracer.c:777-779), which C leaves undefined outside [0, 256).  Inside that range the two are the same
  *      conversion, and tests/test_reference_pin.py compares whole lightmaps there.
+ *   D11 (u8 store) rt_encode_u8()'s clamp is written so that NaN fails it (v > 0 ? v : 0, then the upper bound, as
+ *      rt_accum_quantize() clamps): a NaN mean encodes to 0.  The reference clamps with comparisons NaN passes
+ *      (raytracer.c:700-716), its power and sRGB formula turn NaN into -0.055, and the conversion of -14.08f to u8 is
+ *      undefined in C (242 from gcc here, 0 from a saturating conversion).  A rendered frame's fixed-point sums are
+ *      never NaN; the post passes take f32 planes from the host, where it can be.  Every other float keeps its byte:
+ *      tests/golden/encode_u8_steps.npz is the step table of the function before the change, per numeric contract.
  *
  * ORACLE_LITERAL (Oracle_Config.literal = 1) switches D1, D2, D6 and D8 back to the reference's literal semantics:
  * ONE thread whose RNG state is seeded once (frame seed in place of time_now(), raytracer.c:597) and runs on across
@@ -122,6 +128,12 @@ void oracle_disney_shade(PBR_Shader_Data const *data, Shader_Input const *in, u3
 /* rt_math.h wrappers: op 0 log,1 exp,2 pow(x,y),3 sin,4 cos,5 atan2(x=y,y=x),6 asin,7 srgb_to_linear,8 linear_to_srgb,9 sqrt, 10 1/x */
 void oracle_math(i32 op, i32 n, f32 const *x, f32 const *y, f32 *out);
 u8   oracle_encode_u8(f32 linear);
+void oracle_encode_u8_array(isize n, f32 const *linear, u8 *out);
+/* rt_encode_u8() on every float of [0, 1] -- bit patterns 0 .. 0x3F800000 -- in ascending order, on n_threads threads:
+ * first[k] = the lowest pattern that encodes to k (0xFFFFFFFF: none), *descents = patterns whose byte is below that of the
+ * pattern before.  Returns how many of the 256 bytes occur, -1 on NULL.  With no descent and all 256 present the table IS
+ * the function on [0, 1]. */
+int  oracle_encode_steps(u32 first[256], u64 *descents, i32 n_threads);
 /* test-only: 1 = the calling thread's unit-level entry points evaluate the D8 sites as ORACLE_LITERAL does (they default
  * to 0, and oracle_render sets 0 again); returns the previous mode */
 int  oracle_set_literal(int on);

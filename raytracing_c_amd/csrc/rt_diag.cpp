@@ -18,6 +18,7 @@ int rt_launch_test_rcp_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_srgb_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_env_sweep(int which, uint32_t seed, unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream);
+int rt_launch_test_encode_sweep(unsigned long long *counts, hipStream_t stream);
 int rt_launch_test_sky_add_group(void);
 int rt_launch_test_group_sum(int group, int n_waves, const unsigned long long *in, const unsigned char *valid, unsigned long long *out,
                               hipStream_t stream);
@@ -284,6 +285,15 @@ extern "C" int rt_test_env_sweep(i32 which, u32 seed, u64 out[4]) {
 // The tile-stream kernel's shift-based fixed-point conversion of a sample against rt_accum_quantize() over all 2^32 bit
 // patterns: out[0] differing patterns (0 expected), out[1] first differing pattern + 1.
 extern "C" int rt_test_quantize_sweep(u64 out[2]) { return run_sweep(rt_launch_test_quantize_sweep, "rt_test_quantize_sweep", out, 2); }
+
+// rt_encode_u8() on the device over all 2^32 bit patterns (rt_hip_diag.h): out[0 .. 255] the lowest pattern of [0, 0x3F800000] per
+// byte (2^32: the byte does not occur), out[256] descents over that range, out[257 .. 259] patterns above 1.0 that do not give 255,
+// negative ones and NaNs that do not give 0.
+extern "C" int rt_test_encode_sweep(u64 out[260]) {
+  if (int rc = run_sweep(rt_launch_test_encode_sweep, "rt_test_encode_sweep", out, 260)) return rc;
+  for (int k = 0; k < 256; k++) out[k] = 0x100000000ull - out[k];       // the kernel keeps 2^32 - the lowest pattern, 0 = none
+  return 0;
+}
 
 // The sky loop's sample reduction on crafted lanes (rt_hip_diag.h): three channels of n_waves x 64 values, out[c * n + i] = the sum of
 // channel c over lane i's aligned group of `group` lanes.

@@ -92,6 +92,36 @@ __global__ void rt_test_quantize_sweep_kernel(unsigned long long *counts) {
   if (first) atomicMax(&counts[1], (unsigned long long)first);
 }
 
+// rt_encode_u8(x) -- the last step of every image: rt_resolve, the post passes -- on all 2^32 bit patterns, 256 consecutive ones
+// per thread.  counts[k], k < 256: 2^32 - the LOWEST pattern in [0, 0x3F800000] (the floats of [0, 1]) that encodes to k, 0 when
+// there is none (a maximum over the threads; rt_test_encode_sweep turns it into the pattern); counts[256] = patterns of that range
+// whose byte is below that of the pattern before, counts[257] = patterns in (1.0, +inf] that do not give 255, counts[258] =
+// negative patterns, -0 and -inf included, that do not give 0, counts[259] = NaN patterns that do not give 0.  A byte's lowest
+// pattern is one whose predecessor has another byte (or pattern 0), so only those reach the atomics.
+__global__ void rt_test_encode_sweep_kernel(unsigned long long *counts) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t b0 = tid * 256u;
+  uint32_t descents = 0, above = 0, negative = 0, nan = 0;
+  int prev = (b0 != 0u && b0 <= 0x3F800000u) ? (int)rt_encode_u8(__uint_as_float(b0 - 1u)) : -1;
+  for (uint32_t k = 0; k < 256u; k++) {
+    const uint32_t b = b0 + k;
+    const int v = (int)rt_encode_u8(__uint_as_float(b));
+    if (b <= 0x3F800000u) {
+      if (v != prev) {
+        atomicMax(&counts[v], 0x100000000ull - (unsigned long long)b);
+        descents += v < prev ? 1u : 0u;
+        prev = v;
+      }
+    } else if (b <= 0x7F800000u) above += v != 255 ? 1u : 0u;
+    else if ((b & 0x7FFFFFFFu) > 0x7F800000u) nan += v != 0 ? 1u : 0u;
+    else negative += v != 0 ? 1u : 0u;
+  }
+  if (descents) atomicAdd(&counts[256], (unsigned long long)descents);
+  if (above) atomicAdd(&counts[257], (unsigned long long)above);
+  if (negative) atomicAdd(&counts[258], (unsigned long long)negative);
+  if (nan) atomicAdd(&counts[259], (unsigned long long)nan);
+}
+
 // group_sum3_u64<G> (the sky loop's sample reduction, three values at once) on values a test chooses: one wave per block, lane
 // i & 63 of wave i >> 6, channel c at [c * n + i]; a lane that is not valid contributes 0, as in the loop.  Every lane writes
 // what it holds afterwards.
@@ -534,6 +564,11 @@ extern "C" int rt_launch_test_sky_add_group(void) { return RT_SKY_ADD_GROUP; }
 
 extern "C" int rt_launch_test_quantize_sweep(unsigned long long *counts, hipStream_t stream) {
   hipLaunchKernelGGL(rt_test_quantize_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rt_launch_test_encode_sweep(unsigned long long *counts, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_test_encode_sweep_kernel, dim3(65536), dim3(256), 0, stream, counts);
   return (int)hipGetLastError();
 }
 

@@ -245,6 +245,6 @@ EXPORTED_SYMBOLS = [
 DIAG_ONLY_SYMBOLS = [
     "rt_diag_set_tokens", "rt_diag_multi_fault", "rt_set_pipeline", "rt_get_pipeline", "rt_set_wavefront_capacity", "rt_get_wave_times", "rt_get_ledger",
     "rt_diag_device_bytes_live", "rt_diag_release_staging", "rt_diag_cached_scene",
-    "rt_test_math", "rt_test_rcp_sweep", "rt_test_srgb_sweep", "rt_test_env_sweep", "rt_test_quantize_sweep", "rt_test_group_sum", "rt_test_sky_add_group", "rt_test_node_order", "rt_test_trace", "rt_test_trace_stream",
+    "rt_test_math", "rt_test_rcp_sweep", "rt_test_srgb_sweep", "rt_test_env_sweep", "rt_test_quantize_sweep", "rt_test_encode_sweep", "rt_test_group_sum", "rt_test_sky_add_group", "rt_test_node_order", "rt_test_trace", "rt_test_trace_stream",
     "rt_test_tile_order", "rt_test_texture", "rt_test_shade", "rt_test_shade_hit", "rt_test_feature_hit", "rt_test_brdf", "rt_test_background", "rt_test_primary_ray",
 ]

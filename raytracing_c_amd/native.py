@@ -233,6 +233,7 @@ def _declare_diag(d):
     d.rt_test_srgb_sweep.argtypes = [vp]
     d.rt_test_env_sweep.argtypes = [C.c_int32, C.c_uint32, vp]
     d.rt_test_quantize_sweep.argtypes = [vp]
+    d.rt_test_encode_sweep.argtypes = [vp]
     d.rt_test_group_sum.argtypes = [C.c_int32, C.c_int32, vp, vp, vp]
     d.rt_test_sky_add_group.argtypes = []
     d.rt_test_node_order.argtypes = [C.c_int32, vp, vp, vp]

@@ -82,10 +82,13 @@ def guided(color, coverage, albedo, normal, position, iterations=4, sigma_color=
 
 
 def encode_u8(x):
-    """rt_encode_u8 per element (rt_math.h): clamp, the oracle's rt_linear_to_srgb, x 255.999, truncate."""
+    """rt_encode_u8 per element (rt_math.h): the clamp that NaN fails (x > 0 ? x : 0, then the upper bound: NaN encodes to 0),
+    the oracle's rt_linear_to_srgb, x 255.999, truncate."""
     from tests import _oracle
     x = np.ascontiguousarray(x, F)
-    c = np.where(x < 0, F(0.0), np.where(x > 1, F(1.0), x)).astype(F)
+    with np.errstate(invalid="ignore"):
+        c = np.where(x > 0, x, F(0.0)).astype(F)
+    c = np.where(c > 1, F(1.0), c).astype(F)
     return (_oracle.math(8, c) * F(255.999)).astype(np.uint8)
 
 

@@ -87,6 +87,10 @@ def load(path=None):
     d.oracle_denoise_image.restype = None
     d.oracle_encode_u8.argtypes = [C.c_float]
     d.oracle_encode_u8.restype = C.c_uint8
+    d.oracle_encode_u8_array.argtypes = [abi.isize, vp, vp]
+    d.oracle_encode_u8_array.restype = None
+    d.oracle_encode_steps.argtypes = [vp, P(C.c_uint64), C.c_int32]
+    d.oracle_encode_steps.restype = C.c_int
     d.oracle_have_avx2.restype = C.c_int
     d.oracle_set_simd.argtypes = [C.c_int]
     d.oracle_set_simd.restype = C.c_int
@@ -142,3 +146,22 @@ def math(op, x, y=None, lib=None):
         yp = y.ctypes.data
     d.oracle_math(op, x.size, x.ctypes.data, yp, out.ctypes.data)
     return out
+
+
+def encode_u8(x, lib=None):
+    """oracle_encode_u8 (rt_encode_u8 of include/rt_math.h) per element -> u8 array of x's shape."""
+    d = lib or load()
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros(x.shape, np.uint8)
+    d.oracle_encode_u8_array(x.size, x.ctypes.data, out.ctypes.data)
+    return out
+
+
+def encode_steps(n_threads=8, lib=None):
+    """oracle_encode_steps -> (first u32[256], descents, bytes that occur)."""
+    d = lib or load()
+    first = np.zeros(256, np.uint32)
+    descents = C.c_uint64(0)
+    seen = d.oracle_encode_steps(first.ctypes.data, C.byref(descents), n_threads)
+    assert seen >= 0
+    return first, int(descents.value), int(seen)

@@ -118,6 +118,49 @@ def test_texture_srgb_decode_equals_the_division(rt, oracle, diag):
     assert np.array_equal(_bits(want)[:-1], _bits(got)[:-1]) and np.isnan(got[-1]) == np.isnan(want[-1])
 
 
+def test_encode_u8_equals_the_oracle_on_every_float(rt, oracle, diag):
+    """rt_encode_u8 -- the byte of every image: rt_resolve, the guided, temporal and variance passes -- on the device over all 2^32
+    bit patterns (rt_test_encode_sweep) against the oracle's sweep of [0, 1] (oracle_encode_steps).  Both step tables are equal,
+    neither function ever descends and all 256 bytes occur: so the two agree on every one of the 1 065 353 217 floats of [0, 1].
+    Outside it the device gives 255 above 1.0 up to +inf, 0 for every negative pattern, -0 and -inf included, and 0 for every
+    NaN (deviation D11, oracle/oracle.h)."""
+    from tests.test_encode_cpu import oracle_steps
+    out = (C.c_uint64 * 260)()
+    assert rt.diag.rt_test_encode_sweep(out) == 0, rt.last_error(rt.diag)
+    got = np.array([int(v) for v in out], np.uint64)
+    first, descents, above, negative, nan = got[:256], int(got[256]), int(got[257]), int(got[258]), int(got[259])
+    want, want_descents, want_seen, _ = oracle_steps()
+    print("descents %d / %d, outside: %d above, %d negative, %d NaN; differing steps %d"
+          % (descents, want_descents, above, negative, nan, int((first != want.astype(np.uint64)).sum())))
+    assert (first < (1 << 32)).all(), np.nonzero(first >= (1 << 32))[0][:8].tolist()           # all 256 values occur
+    assert want_seen == 256
+    bad = np.nonzero(first != want.astype(np.uint64))[0]
+    assert bad.size == 0, [(int(k), hex(int(first[k])), hex(int(want[k]))) for k in bad[:4]]
+    assert descents == 0 and want_descents == 0
+    assert above == 0 and negative == 0 and nan == 0
+
+
+def test_linear_to_srgb_at_its_threshold_and_at_the_steps(rt, oracle, diag):
+    """rt_linear_to_srgb as a FLOAT, where the byte cannot see it: at 0.0031308f the linear segment and the power law differ by nine
+    ulps and both truncate to byte 10, so a threshold off by one ulp leaves the step table alone.  256 patterns either side of the
+    threshold, and four either side of each step of tests/golden/encode_u8_steps.npz, have the oracle's bits."""
+    from tests import _oracle
+    from tests.test_encode_cpu import steps_fixture
+    threshold = int(np.array([0.0031308], np.float32).view(np.uint32)[0])
+    near = np.arange(-256, 257, dtype=np.int64)
+    first = steps_fixture()["first"][1:].astype(np.int64)
+    bits = np.concatenate([threshold + near, (first[:, None] + np.arange(-4, 5)[None, :]).reshape(-1)]).astype(np.uint32)
+    x = bits.view(np.float32)
+    want = _oracle.math(8, x)
+    at = 256
+    assert bits[at] == threshold and _bits(want)[at + 1] < _bits(want)[at]             # (the power law starts BELOW the linear segment)
+    assert _bits(want)[at] - _bits(want)[at + 1] == 9
+    got = np.zeros_like(x)
+    assert rt.diag.rt_test_math(8, x.size, x.ctypes.data, None, got.ctypes.data) == 0, rt.last_error(rt.diag)
+    bad = np.nonzero(_bits(want) != _bits(got))[0]
+    assert bad.size == 0, [(hex(int(bits[i])), hex(int(_bits(want)[i])), hex(int(_bits(got)[i]))) for i in bad[:4]]
+
+
 # ---------------------------------------------------------------------------------------
 # traversal + intersection
 
