@@ -705,6 +705,92 @@ extern int rt_render_svgf(Scene const *scene, Image const *image, isize samples,
                           RT_Temporal_Params const *temporal_params, RT_Variance_Params const *variance_params,
                           RT_Guided_Params const *guided_params, f32 *linear_noisy, f32 *linear_out, f32 *length, f32 *variance);
 
+/* ---- half-resolution frames: feature-guided upsampling ------------------------------------ */
+
+/* The one stage behind a frame that takes path-tracing work away: the frame is traced at half the width and half the height -- a
+ * quarter of the paths -- and brought to full size over FULL-resolution feature buffers ("first-hit feature buffers" above: their
+ * edge-aware upscaler).  The albedo is taken at full resolution, so texture detail does not come from the path frame: only the
+ * demodulated colour is interpolated, and a low pixel contributes to a full pixel as far as their first hits agree.  One kernel of
+ * its own (rt_upsample_kernel, csrc/rt_upsample.hip) behind the filter's pack kernel; rt_guided_denoise*, rt_render_denoised,
+ * rt_render_temporal and rt_render_svgf return what they returned.
+ *
+ * THE UPSAMPLING.  Only + - * / , comparisons and selects in f32, every operation rounded on its own (no fused multiply-add, no
+ * reciprocal, exp or sqrt), a fixed tap order: a float32 restatement on the CPU is equal bit for bit (tests/_upsample.py).
+ *   Sizes: the full size W x H, both even and >= 2; the low size wl = W / 2, hl = H / 2.
+ *   Geometry: a primary ray goes through uvx = ((x + jitter - 0.5) * 2) / width - 1 (and uvy likewise), so the centre of low pixel
+ *     X lies on the centre of full pixel 2 X (both at 2 X / wl - 1), and width / height is the same f32 for both sizes: ONE camera
+ *     serves both frames.  With an odd size neither holds, which is why odd sizes are refused.
+ *   Inputs (all finite): low -- color f32[hl][wl][3] the linear mean radiance, coverage f32[hl][wl], albedo, normal, position
+ *     f32[hl][wl][3]; full -- coverage f32[H][W], albedo, normal, position f32[H][W][3].  normal is the encoded n * 0.5 + 0.5 mean
+ *     exactly as rt_resolve_features writes it.
+ *   Parameters: sigma_normal, sigma_position > 0 and not NaN, +inf switches that term off; demodulate 0 or 1.  The host computes
+ *     k_n = 1.0f / (sigma_normal * sigma_normal) and k_p likewise, in f32.
+ *   Per low pixel q and per full pixel p, exactly as THE FILTER has them:
+ *     N = normal * 2.0f - coverage per component
+ *     m = albedo + ((1.0f - coverage) + 1e-3f) per channel when demodulate is set, otherwise 1
+ *     and for low pixels c_q = color_q / m_q
+ *   Taps: a separable quadratic B-spline on the low lattice (its weights at whole and half lattice steps are dyadic).  For full
+ *     pixel (x, y): X0 = x >> 1, Y0 = y >> 1; along x the taps are X0 - 1 + (x & 1) + i, i = 0, 1, 2, with the weights
+ *     Hx = {0.125f, 0.75f, 0.125f} for even x and {0.5f, 0.5f, 0} for odd x; along y likewise with j and Hy; j is the outer loop
+ *     and i the inner one.  A tap with a zero spline weight is skipped.  A tap outside the low image is skipped, not clamped.  For
+ *     every tap q = (X, Y) that is left:
+ *       dn = N_p - N_q;  dn2 = dn.x * dn.x + dn.y * dn.y + dn.z * dn.z
+ *       dcov = cov_p - cov_q
+ *       e = P_q - P_p;  pl = N_p.x * e.x + N_p.y * e.y + N_p.z * e.z      (the distance of q from p's tangent plane)
+ *       D = dn2 * k_n + dcov * dcov * k_n + pl * pl * k_p, evaluated left to right
+ *       r = 1.0f / (1.0f + D)
+ *       wgt = ((Hy * Hx) * r) * r
+ *       sum_c = sum_c + wgt * c_q per channel;  sum_w = sum_w + wgt
+ *   Result: c_p = sum_c / sum_w where sum_w > 0, otherwise c_p = c of low pixel (X0, Y0).  (sum_w > 0 can fail although the low
+ *     pixel (X0, Y0) is always a tap: pl * pl overflows to +inf for positions around 3e19 and every r is 0 -- or NaN, with k_p = 0.)
+ *   Sky needs no case of its own: with cov_p == 0, N_p is 0 and the plane term vanishes; the normal and the coverage term then
+ *     prefer the sky taps.
+ *   Output: out_p = c_p * m_p.  The u8 image is rt_encode_u8(out) per channel (rt_math.h), under the library's numeric contract; a
+ *     NaN encodes to 0.
+ * Not done: factors other than 2, odd sizes, several devices, view batches; an upsampled frame in front of rt_render_temporal /
+ * rt_render_svgf (the upsampled frame is an ordinary linear frame: the natural next step); low-resolution guides derived from the
+ * full-resolution planes in place of a second feature pass. */
+typedef struct {
+  f32 sigma_normal, sigma_position;
+  i32 demodulate;
+  i32 guide_samples;   /* rt_render_upsampled alone reads it: samples of the full-resolution feature pass, 1 .. samples; 0 = samples */
+} RT_Upsample_Params;                                                                            /* 16 bytes */
+
+/* Device level, like rt_guided_denoise(): every pointer is a DEVICE pointer owned by the caller, the call only enqueues work on
+ * `stream` (the pack launch over the low frame, then the upsampling launch).
+ *   d_color_low, d_coverage_low, d_albedo_low, d_normal_low, d_position_low : the low frame, (width / 2) x (height / 2)
+ *   d_coverage, d_albedo, d_normal, d_position : the full-resolution planes, width x height
+ *   d_out   : f32[height][width][3] or NULL      d_image : u8[height][width][3] or NULL      (at least one of them)
+ *   d_work  : rt_guided_upsample_work_bytes(width, height) bytes of scratch, 16-byte aligned: 48 B per LOW pixel = 12 B per full
+ *             pixel -- the packed low frame, three planes of float4: (c, L), (N, cov), (P, 0)
+ * d_out and d_image must not overlap any input nor d_work (refused).  Both albedo planes may be NULL only when demodulate == 0.
+ * Host level: rt_guided_upsample_host() from host memory to host memory through library-owned staging (kept between calls); it takes
+ * the library's device lock and runs on the NULL stream like rt_guided_denoise_host().  low / full: all four planes (albedo may be
+ * NULL when demodulate == 0); out f32[height][width][3] and / or image u8[height][width][3].
+ * Checked before the GPU is touched, by all of them: NULL pointers, width and height even and >= 2, width x height <= 2^28, sigmas
+ * > 0 and not NaN, demodulate 0 or 1, at least one output.  0 on success, -1 + rt_last_error() (rt_guided_upsample_work_bytes: the
+ * size, -1 + rt_last_error()); a refused call leaves its outputs untouched. */
+extern i64 rt_guided_upsample_work_bytes(i32 width, i32 height);
+extern int rt_guided_upsample(i32 width, i32 height, RT_Upsample_Params const *params, void const *d_color_low,
+                              void const *d_coverage_low, void const *d_albedo_low, void const *d_normal_low,
+                              void const *d_position_low, void const *d_coverage, void const *d_albedo, void const *d_normal,
+                              void const *d_position, void *d_out, void *d_image, void *d_work, void *stream);
+extern int rt_guided_upsample_host(i32 width, i32 height, RT_Upsample_Params const *params, f32 const *color_low,
+                                   RT_Features const *low, RT_Features const *full, f32 *out, u8 *image);
+/* An upsampled frame in one call: rt_render_frame()'s frame sequence at (W / 2) x (H / 2), the feature pass of that frame (the
+ * same samples), the feature pass at W x H with upsample_params->guide_samples samples -- guides are geometric and need few --,
+ * the upsampling and, when guided_params is not NULL, the guided filter at W x H over the upsampled frame, in ONE scene-checked call
+ * (the scene check and the device lock are rt_render_frame()'s; seed and camera are read as it reads them).  `image` is W x H and
+ * receives the encoding of the LAST stage with rt_render_frame()'s layout rules (pixels.data may be NULL when linear_upsampled or
+ * linear_out is given); linear_low (optional) f32[H / 2][W / 2][3] = what rt_render_frame() returns as `linear` at the low size,
+ * linear_upsampled (optional) f32[H][W][3] = the upsampling's output, linear_out (optional, only with guided_params) f32[H][W][3] =
+ * the filter's.  Refused besides what the stages refuse: W or H odd or < 2, guide_samples outside 0 .. samples, linear_out without
+ * guided_params.  rt_get_counters() afterwards describes the LOW frame; rt_get_frame_timing()'s gpu_copy_ms then also covers the
+ * feature passes, the upsampling and the filter.  One device only: with rt_device_count() > 1 the call fails. */
+extern int rt_render_upsampled(Scene const *scene, Image const *image, isize samples, isize max_bounces,
+                               RT_Upsample_Params const *upsample_params, RT_Guided_Params const *guided_params, f32 *linear_low,
+                               f32 *linear_upsampled, f32 *linear_out);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

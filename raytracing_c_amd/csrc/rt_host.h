@@ -12,7 +12,8 @@
 //   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
 //   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter), temporal accumulation (the
 //                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline);
-//                     a stage reads one RT_Frame (rt_device.h) and is launched in one place, which chooses its plain or variance / moments kernel
+//                     a stage reads one RT_Frame (rt_device.h) and is launched in one place, which chooses its plain or variance / moments kernel;
+//                     and feature-guided upsampling of a half-resolution frame, on the same three levels (rt_render_upsampled)
 //   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
@@ -111,6 +112,9 @@ int rt_launch_variance_filter(int width, int height, int step, float k_n, float 
                               float *var_out, hipStream_t stream);
 int rt_launch_moments_pack(int n_pixels, const float *planar, void *mom, hipStream_t stream);
 int rt_launch_moments_unpack(int n_pixels, const void *mom, float *planar, hipStream_t stream);
+// ... in rt_upsample.hip (c0, g0, g1: the low frame as rt_launch_guided_pack packs it; full: the full-resolution planes, no colour)
+int rt_launch_upsample(int width, int height, float k_n, float k_p, int demodulate, const void *c0, const void *g0, const void *g1,
+                       RT_Frame full, float *out, uint8_t *image, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -303,6 +307,19 @@ struct TemporalState {
   std::vector<RT_History *> histories;        // every live RT_History (slot 0 only)
 };
 
+// Feature-guided upsampling (rt_post.cpp): the device staging of rt_guided_upsample_host -- the low frame and the full-resolution
+// planes (two RT_Frames, the second without a colour) -- kept between calls, given back with the device slot (release_staging).
+// rt_render_upsampled upsamples the workspace's linear frame, rendered at the low size, from low_planes over FeatureState's planes:
+// it uses low_planes, work and out.
+struct UpsampleState {
+  DevMem<float>   in_low;                     // the host-level call's low RT_Frame: color [low pixels][3], then planes as FeatureState's
+  DevMem<float>   in_full;                    // ... and its full-resolution planes, as FeatureState's
+  DevMem<float>   low_planes;                 // rt_render_upsampled: the low frame's planes, as FeatureState's
+  DevMem<uint8_t> work;                       // rt_guided_upsample_work_bytes()
+  DevMem<float>   out;                        // [pixels][3]
+  DevMem<uint8_t> image;                      // [pixels][3]
+};
+
 // scene_refit_gpu (rt_extras.cpp): the device staging of a refit, kept between calls -- a deforming mesh is refitted every frame --
 // and given back with the device slot (release_staging).
 struct RefitState {
@@ -334,6 +351,7 @@ struct Device {
   GuidedState guided;
   RefitState refit;
   TemporalState temporal;
+  UpsampleState upsample;
 };
 
 // rt_history_create's object.  Guarded by slot 0's mutex like the staging it belongs to.

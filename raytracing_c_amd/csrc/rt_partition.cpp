@@ -82,6 +82,7 @@ void release_staging(Device &D) {
   D.features = FeatureState();
   D.guided = GuidedState();
   D.refit = RefitState();
+  D.upsample = UpsampleState();
   release_temporal_state(D);                    // (also empties every live RT_History; the list of them stays)
 }
 

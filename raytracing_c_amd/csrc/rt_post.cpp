@@ -6,6 +6,8 @@
 // feature pass, optionally the accumulation, optionally the filter -- in ONE scene-checked call).  Nothing here computes a pixel on the CPU.
 // For a mesh that scene_refit_gpu deforms between the frames the accumulation takes one more plane, the motion of the first hits
 // (rt_temporal_accumulate_motion; behind a frame rt_history_set_motion switches the motion feature pass and that accumulation on).
+// And, at the end of this file, feature-guided upsampling of a frame rendered at half the size (rt_upsample.hip), on the same three
+// levels: rt_guided_upsample, rt_guided_upsample_host, rt_render_upsampled.
 //
 // The frame a stage reads is ONE value (RT_Frame, rt_device.h), built by whoever has the pointers: the extern "C" entry points
 // (frame_of), upload_host_frame and render_post from the staging.  What a stage may write, and what its variance / moments form adds,
@@ -17,6 +19,7 @@
 static_assert(sizeof(RT_Guided_Params) == 20, "iterations, three sigmas, demodulate");
 static_assert(sizeof(RT_Temporal_Params) == 20, "alpha, max_history, two tolerances, demodulate");
 static_assert(sizeof(RT_Variance_Params) == 8, "two sigmas");
+static_assert(sizeof(RT_Upsample_Params) == 16, "two sigmas, demodulate, guide_samples");
 
 #define RT_GUIDED_WORK_PER_PIXEL 64        // two colour buffers (r, g, b, L) and the guides (N, coverage), (P, 0): four float4
 #define RT_TEMPORAL_HISTORY_PER_PIXEL 48   // (c, len), (N, coverage), (W, 0): three float4
@@ -729,4 +732,230 @@ extern "C" int rt_render_svgf(Scene const *scene, Image const *image, isize samp
                               RT_Guided_Params const *guided_params, f32 *linear_noisy, f32 *linear_out, f32 *length, f32 *variance) {
   return render_post("rt_render_svgf", SVGF, scene, image, samples, max_bounces,
                      {guided_params, history, temporal_params, variance_params}, {linear_noisy, linear_out, length, variance});
+}
+
+// ---- half-resolution frames: feature-guided upsampling ------------------------------------------------------------------------------
+// THE UPSAMPLING (include/rt_hip.h; rt_upsample.hip): device level, host level and behind a frame, like the stages above.
+
+#define RT_UPSAMPLE_WORK_PER_LOW_PIXEL 48   // the packed low frame: (c, L), (N, coverage), (P, 0), three float4
+
+// What can be checked without the device: the full size -- even, >= 2, at most RT_MAX_PIXELS -- and the parameters but guide_samples.
+static int check_upsample_size(const char *who, i64 width, i64 height) {
+  if (width < 2 || height < 2 || width > 0x7fffffff || height > 0x7fffffff)
+    return rt_fail("%s: image size %ldx%ld is invalid (an upsampled frame is at least 2x2)", who, (long)width, (long)height);
+  if ((width | height) & 1)
+    return rt_fail("%s: image size %ldx%ld is odd (the low frame is width / 2 x height / 2)", who, (long)width, (long)height);
+  return check_image_size(who, (i32)width, (i32)height);
+}
+
+static int check_upsample(const char *who, i64 width, i64 height, RT_Upsample_Params const *u) {
+  if (check_upsample_size(who, width, height) != 0) return -1;
+  if (!u) return rt_fail("%s: upsample params are NULL", who);
+  // (written so that NaN fails)
+  if (!(u->sigma_normal > 0.0f)) return rt_fail("%s: sigma_normal must be > 0 (got %g)", who, (double)u->sigma_normal);
+  if (!(u->sigma_position > 0.0f)) return rt_fail("%s: sigma_position must be > 0 (got %g)", who, (double)u->sigma_position);
+  if (u->demodulate != 0 && u->demodulate != 1) return rt_fail("%s: demodulate must be 0 or 1 (got %d)", who, u->demodulate);
+  return 0;
+}
+
+extern "C" i64 rt_guided_upsample_work_bytes(i32 width, i32 height) {
+  if (check_upsample_size("rt_guided_upsample_work_bytes", width, height) != 0) return -1;
+  return (i64)(width / 2) * (height / 2) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL;
+}
+
+// An array an entry point reads or writes, by the name its message has for it; p NULL: not given.
+struct Range { const char *name; const void *p; uintptr_t bytes; };
+// Refuses an output that overlaps an input: the upsampling writes a pixel while other pixels still read.
+template <int N, int M> static int check_ranges_apart(const char *who, const Range (&outs)[N], const Range (&ins)[M]) {
+  for (const Range &o : outs)
+    for (const Range &i : ins) {
+      if (!o.p || !i.p) continue;
+      const uintptr_t a = (uintptr_t)o.p, b = (uintptr_t)i.p;
+      if (a < b + i.bytes && b < a + o.bytes) return rt_fail("%s: %s overlaps %s", who, o.name, i.name);
+    }
+  return 0;
+}
+
+// Enqueues the pack launch over the low frame and the upsampling launch.  `full`: the full-resolution planes (its colour is not
+// read).  Every pointer is on the current device.
+static int enqueue_upsample(i32 width, i32 height, RT_Upsample_Params const *u, RT_Frame const &low, RT_Frame const &full, float *out,
+                            uint8_t *image, void *d_work, hipStream_t stream) {
+  const size_t low_pixels = (size_t)(width / 2) * (height / 2);
+  uint8_t *b = (uint8_t *)d_work;
+  const GuidedWork w = {{b, nullptr}, b + low_pixels * 16, b + low_pixels * 32};
+  if (launch_pack(low_pixels, u->demodulate, low, nullptr, w, stream) != 0) return -1;
+  const float k_n = 1.0f / (u->sigma_normal * u->sigma_normal), k_p = 1.0f / (u->sigma_position * u->sigma_position);
+  return launched(rt_launch_upsample(width, height, k_n, k_p, u->demodulate, w.buf[0], w.g0, w.g1, full, out, image, stream),
+                  "upsample kernel launch failed: %s");
+}
+
+extern "C" int rt_guided_upsample(i32 width, i32 height, RT_Upsample_Params const *params, void const *d_color_low,
+                                  void const *d_coverage_low, void const *d_albedo_low, void const *d_normal_low,
+                                  void const *d_position_low, void const *d_coverage, void const *d_albedo, void const *d_normal,
+                                  void const *d_position, void *d_out, void *d_image, void *d_work, void *stream) {
+  const char *who = "rt_guided_upsample";
+  if (check_upsample(who, width, height, params) != 0) return -1;
+  const RT_Frame low = frame_of(d_color_low, d_coverage_low, d_albedo_low, d_normal_low, d_position_low);
+  const RT_Frame full = frame_of(nullptr, d_coverage, d_albedo, d_normal, d_position);
+  if (!low.color) return rt_fail("%s: d_color_low is NULL", who);
+  if (!low.coverage) return rt_fail("%s: d_coverage_low is NULL", who);
+  if (!low.albedo && params->demodulate) return rt_fail("%s: d_albedo_low is NULL and demodulate is set", who);
+  if (!low.normal) return rt_fail("%s: d_normal_low is NULL", who);
+  if (!low.position) return rt_fail("%s: d_position_low is NULL", who);
+  if (!full.coverage) return rt_fail("%s: d_coverage is NULL", who);
+  if (!full.albedo && params->demodulate) return rt_fail("%s: d_albedo is NULL and demodulate is set", who);
+  if (!full.normal) return rt_fail("%s: d_normal is NULL", who);
+  if (!full.position) return rt_fail("%s: d_position is NULL", who);
+  const Output wanted[] = {{"d_out", d_out}, {"d_image", d_image}};
+  if (check_wanted(who, wanted) != 0) return -1;
+  if (!d_work) return rt_fail("%s: d_work is NULL", who);
+  if ((uintptr_t)d_work & 15) return rt_fail("%s: d_work must be 16-byte aligned", who);
+  const uintptr_t pixels = (uintptr_t)width * height, f1 = pixels * sizeof(float), l1 = f1 / 4;
+  const Range outs[] = {{"d_out", d_out, f1 * 3}, {"d_image", d_image, pixels * 3}};
+  const Range ins[] = {{"d_color_low", low.color, l1 * 3}, {"d_coverage_low", low.coverage, l1}, {"d_albedo_low", low.albedo, l1 * 3},
+                       {"d_normal_low", low.normal, l1 * 3}, {"d_position_low", low.position, l1 * 3}, {"d_coverage", full.coverage, f1},
+                       {"d_albedo", full.albedo, f1 * 3}, {"d_normal", full.normal, f1 * 3}, {"d_position", full.position, f1 * 3},
+                       {"d_work", d_work, (uintptr_t)(pixels / 4) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL}};
+  if (check_ranges_apart(who, outs, ins) != 0) return -1;
+  const Range image_range[] = {{"d_image", d_image, pixels * 3}}, out_range[] = {{"d_out", d_out, f1 * 3}};
+  if (check_ranges_apart(who, image_range, out_range) != 0) return -1;
+  if (device_ready() != 0) return -1;
+  return enqueue_upsample(width, height, params, low, full, (float *)d_out, (uint8_t *)d_image, d_work, (hipStream_t)stream);
+}
+
+// Copies the four planes of a host frame into `in` (RT_FEATURE_CHANNELS f32 per pixel, as FeatureState keeps them); *f is the
+// planes on the device, without a colour; f->albedo is NULL when the host gave none.
+static int upload_host_planes(float *in, size_t pixels, RT_Features const *planes, RT_Frame *f) {
+  const size_t f3 = pixels * 3 * sizeof(float), f1 = pixels * sizeof(float);
+  RT_Features d = split_feature_planes(in, pixels);
+  HIP_TRY(hipMemcpy(d.coverage, planes->coverage, f1, hipMemcpyHostToDevice));
+  if (planes->albedo) HIP_TRY(hipMemcpy(d.albedo, planes->albedo, f3, hipMemcpyHostToDevice));
+  else d.albedo = nullptr;
+  HIP_TRY(hipMemcpy(d.normal, planes->normal, f3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.position, planes->position, f3, hipMemcpyHostToDevice));
+  *f = device_frame(nullptr, d);
+  return 0;
+}
+
+extern "C" int rt_guided_upsample_host(i32 width, i32 height, RT_Upsample_Params const *params, f32 const *color_low,
+                                       RT_Features const *low, RT_Features const *full, f32 *out, u8 *image) {
+  const char *who = "rt_guided_upsample_host";
+  if (check_upsample(who, width, height, params) != 0) return -1;
+  if (!color_low) return rt_fail("%s: color_low is NULL", who);
+  if (!low) return rt_fail("%s: low is NULL", who);
+  if (!full) return rt_fail("%s: full is NULL", who);
+  const struct { const char *name; RT_Features const *planes; } frames[2] = {{"low", low}, {"full", full}};
+  for (const auto &fr : frames) {
+    if (!fr.planes->coverage) return rt_fail("%s: %s->coverage is NULL", who, fr.name);
+    if (!fr.planes->albedo && params->demodulate) return rt_fail("%s: %s->albedo is NULL and demodulate is set", who, fr.name);
+    if (!fr.planes->normal) return rt_fail("%s: %s->normal is NULL", who, fr.name);
+    if (!fr.planes->position) return rt_fail("%s: %s->position is NULL", who, fr.name);
+  }
+  const Output wanted[] = {{"out", out}, {"image", image}};
+  if (check_wanted(who, wanted) != 0) return -1;
+
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  UpsampleState &S = D.upsample;
+  const size_t pixels = (size_t)width * height, low_pixels = pixels / 4;
+  HIP_TRY(S.in_low.grow(low_pixels * RT_HOST_FRAME_F32));
+  HIP_TRY(S.in_full.grow(pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(S.work.grow(low_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
+  if (out) HIP_TRY(S.out.grow(pixels * 3));
+  if (image) HIP_TRY(S.image.grow(pixels * 3));
+  hipStream_t stream = nullptr;
+  RT_Frame fl, ff;
+  if (upload_host_frame(S.in_low, low_pixels, color_low, low, &fl) != 0) return -1;
+  if (upload_host_planes(S.in_full, pixels, full, &ff) != 0) return -1;
+  if (enqueue_upsample(width, height, params, fl, ff, out ? S.out.get() : nullptr, image ? S.image.get() : nullptr, S.work, stream) != 0)
+    return -1;
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  if (out) HIP_TRY(hipMemcpy(out, S.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (image) HIP_TRY(hipMemcpy(image, S.image, pixels * 3, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The low frame (W.linear, at half the Image's size), its feature pass into D.upsample.low_planes, the full-resolution feature pass
+// with guide_samples into D.features.planes, the upsampling into D.upsample.out and, when g is given, the filter over that
+// (D.guided.work / out) -- in one scene-checked call.  W.image receives the encoding of the LAST stage.
+extern "C" int rt_render_upsampled(Scene const *scene, Image const *image, isize samples, isize max_bounces,
+                                   RT_Upsample_Params const *upsample_params, RT_Guided_Params const *guided_params, f32 *linear_low,
+                                   f32 *linear_upsampled, f32 *linear_out) {
+  const char *who = "rt_render_upsampled";
+  RT_Upsample_Params const *const u = upsample_params;
+  RT_Guided_Params const *const g = guided_params;
+  // before the device lock: the image's size before it goes into 32 bits, the stages' parameters, the rest of the frame's
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  if (!image) return rt_fail("%s: image is NULL", who);
+  if (check_upsample(who, image->width, image->height, u) != 0) return -1;
+  const i32 width = (i32)image->width, height = (i32)image->height;
+  if (g && check_guided(who, width, height, g) != 0) return -1;
+  if (check_image_layout(image, who) != 0) return -1;
+  if (samples <= 0 || samples > 0x7fffffff) return rt_fail("%s: samples must be positive and fit 32 bits (got %ld)", who, (long)samples);
+  if (max_bounces < 0 || max_bounces > 0x7fffffff) return rt_fail("%s: max_bounces must be >= 0 and fit 32 bits (got %ld)", who, (long)max_bounces);
+  if (u->guide_samples < 0 || u->guide_samples > samples)
+    return rt_fail("%s: guide_samples must be 0 .. samples (got %d, samples %ld)", who, u->guide_samples, (long)samples);
+  if (linear_out && !g) return rt_fail("%s: linear_out is the filter's output and guided params are NULL", who);
+  if (!image->pixels.data && !linear_upsampled && !linear_out)
+    return rt_fail("%s: no output is wanted (no pixels, no linear_upsampled, no linear_out)", who);
+
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  const double t_start = now_ms();
+  if (ensure_device(D) != 0) return -1;
+  if (rt_device_count() > 1)
+    return rt_fail("%s: an upsampled frame renders on one device, and %d are set (rt_set_devices)", who, rt_device_count());
+  Image low_image = *image;                                        // (the low frame's size alone is read from it)
+  low_image.width = width / 2;
+  low_image.height = height / 2;
+  RT_Render_Params pl, pf;                                         // the low frame and its feature pass; the full-resolution feature pass
+  if (fill_frame_params(&pl, &low_image, samples, max_bounces, g_seed.load()) != 0) return -1;
+  if (fill_frame_params(&pf, image, u->guide_samples ? u->guide_samples : samples, max_bounces, g_seed.load()) != 0) return -1;
+  forget_multi_counters();
+
+  FrameTiming T;
+  Workspace &W = D.ws;
+  FeatureState &F = D.features;
+  GuidedState &G = D.guided;
+  UpsampleState &U = D.upsample;
+  const size_t pixels = (size_t)width * height, low_pixels = pixels / 4;
+  if (ensure_ws_buffers(W, pl.width, pl.height, 0, 0) != 0) return -1;
+  HIP_TRY(W.image.grow(pixels * 3));
+  HIP_TRY(F.sums.grow(pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(F.planes.grow(pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(U.low_planes.grow(low_pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(U.work.grow(low_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
+  const bool want_upsampled = g || linear_upsampled;               // the upsampling's f32 output: the filter's input, or the caller's
+  if (want_upsampled) HIP_TRY(U.out.grow(pixels * 3));
+  if (g) {
+    HIP_TRY(G.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
+    if (linear_out) HIP_TRY(G.out.grow(pixels * 3));
+  }
+  const RT_Features low_planes = split_feature_planes(U.low_planes, low_pixels), planes = split_feature_planes(F.planes, pixels);
+  hipStream_t stream = nullptr;
+  auto features = [&](RT_Device_Scene *d, RT_Render_Params const &p, RT_Features const &to) -> int {
+    HIP_TRY(hipMemsetAsync(F.sums, 0, (size_t)p.width * p.height * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
+    if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream) != 0) return -1;
+    return enqueue_resolve(&p, F.sums, to.coverage, to.albedo, to.normal, to.position, stream);
+  };
+  auto pass = [&](RT_Device_Scene *d) -> int {
+    if (enqueue_frame(D, d, &scene->camera, &pl, W, stream, 0, nullptr, nullptr, W.linear) != 0) return -1;
+    if (features(d, pl, low_planes) != 0 || features(d, pf, planes) != 0) return -1;
+    if (enqueue_upsample(width, height, u, device_frame(W.linear, low_planes), device_frame(nullptr, planes),
+                         want_upsampled ? U.out.get() : nullptr, g ? nullptr : W.image.get(), U.work, stream) != 0)
+      return -1;
+    if (!g) return 0;
+    const FilterIO f = {linear_out ? G.out.get() : nullptr, W.image};
+    return enqueue_guided(width, height, g, device_frame(U.out, planes), f, G.work, stream);
+  };
+  if (!scene_checked(D, scene, stream, &T, pass)) return -1;         // (a scene edited since the copy: uploaded and rendered again)
+
+  if (copy_image_out(image, W.image, width, height, stream) != 0) return -1;
+  HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
+  if (linear_low) HIP_TRY(hipMemcpy(linear_low, W.linear, low_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (linear_upsampled) HIP_TRY(hipMemcpy(linear_upsampled, U.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (linear_out) HIP_TRY(hipMemcpy(linear_out, G.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  return finish_frame(D, W, stream, T, t_start);
 }

@@ -179,6 +179,14 @@ def _declare(d):
                                                       vp]
         d.rt_render_svgf.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, vp, P(abi.RT_Temporal_Params),
                                      P(abi.RT_Variance_Params), P(abi.RT_Guided_Params), vp, vp, vp, vp]
+    if hasattr(d, "rt_render_upsampled"):                  # (absent from older builds loaded as A/B partners)
+        d.rt_guided_upsample_work_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_guided_upsample_work_bytes.restype = C.c_int64
+        d.rt_guided_upsample.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Upsample_Params)] + [vp] * 13
+        d.rt_guided_upsample_host.argtypes = [C.c_int32, C.c_int32, P(abi.RT_Upsample_Params), vp, P(abi.RT_Features),
+                                              P(abi.RT_Features), vp, vp]
+        d.rt_render_upsampled.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, P(abi.RT_Upsample_Params),
+                                          P(abi.RT_Guided_Params), vp, vp, vp]
     if hasattr(d, "rt_scene_keep_geometry"):               # (absent from older builds loaded as A/B partners)
         d.rt_device_scene_keep_geometry.argtypes = [vp, vp]
         d.rt_scene_keep_geometry.argtypes = [P(abi.Scene)]
