@@ -21,9 +21,10 @@ static int check_feature_params(const char *who, RT_Render_Params const *p) {
   return 0;
 }
 
-// Enqueues one launch of the feature kernel on `stream`.  D.mutex held, D's GPU current, every pointer on D.
-int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream,
-                     void *d_motion_sums) {
+// Enqueues one launch of the feature kernel on `stream` (d_motion_sums given: of the motion kernel, against d's kept geometry).
+// D.mutex held, D's GPU current, every pointer on D.
+static int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream,
+                            void *d_motion_sums) {
   RT_KParams K;
   scene_only_kparams(&K, d);
   camera_frame_kparams(&K, cam, p);
@@ -70,18 +71,31 @@ int enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render
   return 0;
 }
 
-int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal,
-                    void *d_position, hipStream_t stream) {
+static int enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal,
+                           void *d_position, hipStream_t stream) {
   int rc = rt_launch_features_resolve(p->width * p->height, p->samples, (const unsigned long long *)d_sums, (float *)d_coverage,
                                       (float *)d_albedo, (float *)d_normal, (float *)d_position, stream);
   if (rc != 0) return rt_fail("feature resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 
-int enqueue_resolve_motion(RT_Render_Params const *p, void const *d_motion_sums, void *d_motion, hipStream_t stream) {
+static int enqueue_resolve_motion(RT_Render_Params const *p, void const *d_motion_sums, void *d_motion, hipStream_t stream) {
   int rc = rt_launch_motion_resolve(p->width * p->height, p->samples, (const unsigned long long *)d_motion_sums, (float *)d_motion, stream);
   if (rc != 0) return rt_fail("motion resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
+}
+
+// THE FEATURE PASS of one frame on `stream` (rt_host.h): the sums zeroed, the one launch, the resolves that are wanted.
+int enqueue_feature_pass(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, RT_Features const &to,
+                         hipStream_t stream, void *d_motion_sums, void *d_motion) {
+  const size_t pixels = (size_t)p->width * p->height;
+  HIP_TRY(hipMemsetAsync(d_sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
+  if (d_motion_sums) HIP_TRY(hipMemsetAsync(d_motion_sums, 0, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), stream));
+  if (enqueue_features(D, d, cam, p, d_sums, stream, d_motion_sums) != 0) return -1;
+  if ((to.coverage || to.albedo || to.normal || to.position) &&
+      enqueue_resolve(p, d_sums, to.coverage, to.albedo, to.normal, to.position, stream) != 0)
+    return -1;
+  return d_motion ? enqueue_resolve_motion(p, d_motion_sums, d_motion, stream) : 0;
 }
 
 // ---- device level -------------------------------------------------------------------------------------------------------------
@@ -171,16 +185,14 @@ static int features_host(const char *who, bool with_motion, Scene const *scene, 
     if (motion) HIP_TRY(S.motion.grow(pixels * RT_MOTION_CHANNELS));
   }
   const RT_Features f = split_feature_planes(S.planes, pixels);
+  // (only the planes the caller asked for are resolved)
+  const RT_Features to = planes ? RT_Features{out->coverage ? f.coverage : nullptr, out->albedo ? f.albedo : nullptr,
+                                              out->normal ? f.normal : nullptr, out->position ? f.position : nullptr}
+                                : RT_Features{};
   hipStream_t stream = nullptr;                                 // (does not wait for the lane streams of frames in flight)
   auto pass = [&](RT_Device_Scene *d) -> int {
-    HIP_TRY(hipMemsetAsync(S.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
-    if (with_motion) HIP_TRY(hipMemsetAsync(S.motion_sums, 0, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), stream));
-    if (enqueue_features(D, d, &scene->camera, &p, S.sums, stream, with_motion ? S.motion_sums.get() : nullptr) != 0) return -1;
-    if (motion && enqueue_resolve_motion(&p, S.motion_sums, S.motion, stream) != 0) return -1;
-    if (planes && enqueue_resolve(&p, S.sums, out->coverage ? f.coverage : nullptr, out->albedo ? f.albedo : nullptr,
-                                  out->normal ? f.normal : nullptr, out->position ? f.position : nullptr, stream) != 0)
-      return -1;
-    return 0;
+    return enqueue_feature_pass(D, d, &scene->camera, &p, S.sums, to, stream, with_motion ? S.motion_sums.get() : nullptr,
+                                motion ? S.motion.get() : nullptr);
   };
   if (!scene_checked(D, scene, stream, nullptr, pass)) return -1;      // (a scene edited since the copy: uploaded and traced again)
   HIP_TRY(hipStreamSynchronize(stream));

@@ -276,8 +276,9 @@ static inline RT_Frame device_frame(const float *color, RT_Features const &plane
 }
 
 // Guided denoiser (rt_post.cpp): the device staging of the host-level calls, kept between calls, given back with the device slot
-// (release_staging).  rt_render_denoised filters the workspace's linear frame over FeatureState's planes (one RT_Frame): it uses
-// work and out.
+// (release_staging).  Behind a frame (rt_post.cpp's render_post) the filter is the optional last stage over FeatureState's planes
+// -- of the workspace's linear frame (rt_render_denoised), of TemporalState's out or of UpsampleState's out (one RT_Frame each):
+// it uses work and out.
 struct GuidedState {
   DevMem<float>   in;                         // the host-level calls' RT_Frame: color [pixels][3], then planes as FeatureState's
   DevMem<float>   out;                        // [pixels][3]
@@ -308,13 +309,14 @@ struct TemporalState {
 };
 
 // Feature-guided upsampling (rt_post.cpp): the device staging of rt_guided_upsample_host -- the low frame and the full-resolution
-// planes (two RT_Frames, the second without a colour) -- kept between calls, given back with the device slot (release_staging).
-// rt_render_upsampled upsamples the workspace's linear frame, rendered at the low size, from low_planes over FeatureState's planes:
+// planes (two RT_Frames through the one upload, the second without a colour) -- kept between calls, given back with the device slot
+// (release_staging).  Behind a frame the upsampling is a stage of render_post (rt_render_upsampled): the workspace's linear frame,
+// rendered at the low size, and low_planes, the planes of its feature pass, are upsampled over FeatureState's planes at full size:
 // it uses low_planes, work and out.
 struct UpsampleState {
   DevMem<float>   in_low;                     // the host-level call's low RT_Frame: color [low pixels][3], then planes as FeatureState's
   DevMem<float>   in_full;                    // ... and its full-resolution planes, as FeatureState's
-  DevMem<float>   low_planes;                 // rt_render_upsampled: the low frame's planes, as FeatureState's
+  DevMem<float>   low_planes;                 // render_post: the low frame's planes, as FeatureState's
   DevMem<uint8_t> work;                       // rt_guided_upsample_work_bytes()
   DevMem<float>   out;                        // [pixels][3]
   DevMem<uint8_t> image;                      // [pixels][3]
@@ -568,15 +570,13 @@ int  ensure_query_state(Device &D);                                             
 int  acquire_slot(Device &D, int *slot, bool query = true);
 
 // rt_features.cpp
-// One launch of the feature kernel / of its resolve on `stream` (what rt_render_features runs; rt_post.cpp runs them behind
-// a frame).  D.mutex held, D's GPU current, every pointer on D.
-// d_motion_sums (optional): the motion kernel in place of the plain one -- one launch -- against d's kept geometry (none: the
-// current tiles, every motion sum 0).
-int  enqueue_features(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, hipStream_t stream,
-                      void *d_motion_sums = nullptr);
-int  enqueue_resolve_motion(RT_Render_Params const *p, void const *d_motion_sums, void *d_motion, hipStream_t stream);
-int  enqueue_resolve(RT_Render_Params const *p, void const *d_sums, void *d_coverage, void *d_albedo, void *d_normal, void *d_position,
-                     hipStream_t stream);
+// THE FEATURE PASS of one frame on `stream` (what rt_render_features runs; rt_post.cpp runs it behind a frame): d_sums zeroed, one
+// launch of the feature kernel over p's image, and the resolve into the planes of `to` that are given (none: no resolve).
+// d_motion_sums (optional): zeroed too, and the motion kernel in place of the plain one -- one launch -- against d's kept geometry
+// (none: the current tiles, every motion sum 0); d_motion (optional, with d_motion_sums): they are resolved into it.
+// D.mutex held, D's GPU current, every pointer on D.
+int  enqueue_feature_pass(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, RT_Features const &to,
+                          hipStream_t stream, void *d_motion_sums = nullptr, void *d_motion = nullptr);
 
 // rt_post.cpp
 void release_temporal_state(Device &D);                                             // release_staging()'s part here

@@ -1,18 +1,21 @@
 // rt_post.cpp -- what runs on a frame and its first-hit feature planes (include/rt_hip.h): the guided denoiser (the edge-stopping
 // a-trous filter, rt_guided.hip) and temporal accumulation (the frame blended with the reprojected history of the frames before it,
 // rt_temporal.hip), and what SVGF adds to the two (rt_variance.hip): the luminance moments carried through the accumulation, the variance
-// estimated from them, and the filter steered by that variance.  Each on the device level (device pointers, launches on the caller's stream), on the host level (host arrays
-// through library-owned staging) and behind a frame (rt_render_denoised, rt_render_temporal, rt_render_svgf: one pipeline -- frame,
-// feature pass, optionally the accumulation, optionally the filter -- in ONE scene-checked call).  Nothing here computes a pixel on the CPU.
+// estimated from them, and the filter steered by that variance; and feature-guided upsampling of a frame rendered at half the size
+// (rt_upsample.hip).  Each on the device level (device pointers, launches on the caller's stream), on the host level (host arrays
+// through library-owned staging) and behind a frame (rt_render_denoised, rt_render_temporal, rt_render_svgf, rt_render_upsampled:
+// one pipeline, render_post -- frame, feature pass, optionally the accumulation or the upsampling, optionally the filter -- in ONE
+// scene-checked call).  Nothing here computes a pixel on the CPU.
 // For a mesh that scene_refit_gpu deforms between the frames the accumulation takes one more plane, the motion of the first hits
 // (rt_temporal_accumulate_motion; behind a frame rt_history_set_motion switches the motion feature pass and that accumulation on).
-// And, at the end of this file, feature-guided upsampling of a frame rendered at half the size (rt_upsample.hip), on the same three
-// levels: rt_guided_upsample, rt_guided_upsample_host, rt_render_upsampled.
 //
 // The frame a stage reads is ONE value (RT_Frame, rt_device.h), built by whoever has the pointers: the extern "C" entry points
-// (frame_of), upload_host_frame and render_post from the staging.  What a stage may write, and what its variance / moments form adds,
-// is one struct per stage (FilterIO, AccumulateIO; absent = NULL).  Every stage is launched in ONE place (launch_pack, launch_filter,
-// launch_accumulate), which chooses the plain kernel or its variance / moments form by whether the optional pointer is given.
+// (frame_of), upload_host_frame and render_post from the staging; the upsampling reads two, the low frame and the planes at full
+// size.  That a frame's planes are there is ONE check (check_frame), whatever the entry point calls its pointers; that two arrays
+// lie apart is ONE predicate (overlap).  What a stage may write, and what its variance / moments form adds, is one struct per
+// stage (FilterIO, AccumulateIO; absent = NULL).  Every stage is launched in ONE place (launch_pack, launch_filter,
+// launch_accumulate, enqueue_upsample), which chooses the plain kernel or its variance / moments form by whether the optional
+// pointer is given.
 
 #include "rt_host.h"
 
@@ -24,6 +27,7 @@ static_assert(sizeof(RT_Upsample_Params) == 16, "two sigmas, demodulate, guide_s
 #define RT_GUIDED_WORK_PER_PIXEL 64        // two colour buffers (r, g, b, L) and the guides (N, coverage), (P, 0): four float4
 #define RT_TEMPORAL_HISTORY_PER_PIXEL 48   // (c, len), (N, coverage), (W, 0): three float4
 #define RT_TEMPORAL_MOMENTS_PER_PIXEL 16   // (m1, m2, 0, 0): one float4
+#define RT_UPSAMPLE_WORK_PER_LOW_PIXEL 48   // the packed low frame: (c, L), (N, coverage), (P, 0), three float4
 #define RT_TEMPORAL_MAX_HISTORY (1 << 20)
 #define RT_HOST_FRAME_F32 (3 + RT_FEATURE_CHANNELS)   // a staged host frame, f32 per pixel: the colour, then the planes as FeatureState keeps them
 
@@ -87,25 +91,49 @@ static int check_variance(const char *who, RT_Variance_Params const *v) {
   return 0;
 }
 
-// A frame on the device (the albedo only where `demodulate` reads it).
-static int check_device_frame(const char *who, RT_Frame const &f, int demodulate) {
-  if (!f.color) return rt_fail("%s: d_color is NULL", who);
-  if (!f.coverage) return rt_fail("%s: d_coverage is NULL", who);
-  if (!f.albedo && demodulate) return rt_fail("%s: d_albedo is NULL and demodulate is set", who);
-  if (!f.normal) return rt_fail("%s: d_normal is NULL", who);
-  if (!f.position) return rt_fail("%s: d_position is NULL", who);
+// What can be checked of an upsampled frame: the full size -- even, >= 2, at most RT_MAX_PIXELS -- and the parameters but
+// guide_samples.
+static int check_upsample_size(const char *who, i64 width, i64 height) {
+  if (width < 2 || height < 2 || width > 0x7fffffff || height > 0x7fffffff)
+    return rt_fail("%s: image size %ldx%ld is invalid (an upsampled frame is at least 2x2)", who, (long)width, (long)height);
+  if ((width | height) & 1)
+    return rt_fail("%s: image size %ldx%ld is odd (the low frame is width / 2 x height / 2)", who, (long)width, (long)height);
+  return check_image_size(who, (i32)width, (i32)height);
+}
+
+static int check_upsample(const char *who, i64 width, i64 height, RT_Upsample_Params const *u) {
+  if (check_upsample_size(who, width, height) != 0) return -1;
+  if (!u) return rt_fail("%s: upsample params are NULL", who);
+  // (written so that NaN fails)
+  if (!(u->sigma_normal > 0.0f)) return rt_fail("%s: sigma_normal must be > 0 (got %g)", who, (double)u->sigma_normal);
+  if (!(u->sigma_position > 0.0f)) return rt_fail("%s: sigma_position must be > 0 (got %g)", who, (double)u->sigma_position);
+  if (u->demodulate != 0 && u->demodulate != 1) return rt_fail("%s: demodulate must be 0 or 1 (got %d)", who, u->demodulate);
   return 0;
 }
 
-// ... and in host arrays.
+// The planes of a frame are there -- its colour when `with_color`, the albedo only where `demodulate` reads it -- wherever the
+// pointers are.  A message names a pointer as the entry point's arguments do: in a struct `owner` of host arrays "owner->plane",
+// among device pointers (owner NULL) "d_plane" with `suffix` behind it ("", "_low").
+static int check_frame(const char *who, RT_Frame const &f, bool with_color, int demodulate, const char *owner, const char *suffix = "") {
+  char n[48];
+  auto name = [&](const char *plane) {
+    if (owner) snprintf(n, sizeof n, "%s->%s", owner, plane);
+    else snprintf(n, sizeof n, "d_%s%s", plane, suffix);
+    return n;
+  };
+  if (with_color && !f.color) return rt_fail("%s: %s is NULL", who, name("color"));
+  if (!f.coverage) return rt_fail("%s: %s is NULL", who, name("coverage"));
+  if (!f.albedo && demodulate) return rt_fail("%s: %s is NULL and demodulate is set", who, name("albedo"));
+  if (!f.normal) return rt_fail("%s: %s is NULL", who, name("normal"));
+  if (!f.position) return rt_fail("%s: %s is NULL", who, name("position"));
+  return 0;
+}
+
+// A frame in host arrays: the colour, then the struct of its planes.
 static int check_host_frame(const char *who, f32 const *color, RT_Features const *planes, int demodulate) {
   if (!color) return rt_fail("%s: color is NULL", who);
   if (!planes) return rt_fail("%s: planes is NULL", who);
-  if (!planes->coverage) return rt_fail("%s: planes->coverage is NULL", who);
-  if (!planes->albedo && demodulate) return rt_fail("%s: planes->albedo is NULL and demodulate is set", who);
-  if (!planes->normal) return rt_fail("%s: planes->normal is NULL", who);
-  if (!planes->position) return rt_fail("%s: planes->position is NULL", who);
-  return 0;
+  return check_frame(who, device_frame(nullptr, *planes), false, demodulate, "planes");
 }
 
 // An output an entry point offers, by the name its message has for it; name NULL: this form of the entry point does not offer it.
@@ -123,11 +151,26 @@ template <int N> static int check_wanted(const char *who, const Output (&outs)[N
   return rt_fail("%s: no output is wanted (%s are NULL)", who, names);
 }
 
+// An array an entry point reads or writes, by the name its message has for it; p NULL: not given.
+struct Range { const char *name; const void *p; uintptr_t bytes; };
+// Two arrays that are given share a byte.
+static bool overlap(Range const &x, Range const &y) {
+  const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+  return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+}
+
 // d_<what>_in (optional) and d_<what>_out, `bytes` each, must lie apart: a pixel reads records that other pixels write.
 static int check_apart(const char *who, const char *what, const void *in, const void *out, uintptr_t bytes) {
-  if (!in) return 0;
-  const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-  if ((a <= b ? b - a : a - b) < bytes) return rt_fail("%s: d_%s_in and d_%s_out overlap (the reads are gathers)", who, what, what);
+  if (overlap({nullptr, in, bytes}, {nullptr, out, bytes}))
+    return rt_fail("%s: d_%s_in and d_%s_out overlap (the reads are gathers)", who, what, what);
+  return 0;
+}
+
+// No output may overlap an input: the upsampling writes a pixel while other pixels still read.
+template <int N, int M> static int check_ranges_apart(const char *who, const Range (&outs)[N], const Range (&ins)[M]) {
+  for (const Range &o : outs)
+    for (const Range &i : ins)
+      if (overlap(o, i)) return rt_fail("%s: %s overlaps %s", who, o.name, i.name);
   return 0;
 }
 
@@ -146,6 +189,11 @@ extern "C" i64 rt_guided_work_bytes(i32 w, i32 h) { return bytes_of("rt_guided_w
 extern "C" i64 rt_temporal_history_bytes(i32 w, i32 h) { return bytes_of("rt_temporal_history_bytes", w, h, RT_TEMPORAL_HISTORY_PER_PIXEL); }
 extern "C" i64 rt_guided_variance_work_bytes(i32 w, i32 h) { return bytes_of("rt_guided_variance_work_bytes", w, h, RT_GUIDED_WORK_PER_PIXEL); }
 extern "C" i64 rt_temporal_moments_bytes(i32 w, i32 h) { return bytes_of("rt_temporal_moments_bytes", w, h, RT_TEMPORAL_MOMENTS_PER_PIXEL); }
+// (its sizes are the upsampling's, with their own messages)
+extern "C" i64 rt_guided_upsample_work_bytes(i32 width, i32 height) {
+  if (check_upsample_size("rt_guided_upsample_work_bytes", width, height) != 0) return -1;
+  return (i64)(width / 2) * (height / 2) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL;
+}
 
 // ---------------------------------------------------------------------------------
 // the stages.  Every pointer is on the current device; the launches go on `stream`.
@@ -211,6 +259,19 @@ static int enqueue_guided(i32 width, i32 height, RT_Guided_Params const *g, RT_F
   return 0;
 }
 
+// Enqueues the pack launch over the low frame and the upsampling launch (d_work: rt_guided_upsample_work_bytes).  `full`: the
+// full-resolution planes (its colour is not read).
+static int enqueue_upsample(i32 width, i32 height, RT_Upsample_Params const *u, RT_Frame const &low, RT_Frame const &full, float *out,
+                            uint8_t *image, void *d_work, hipStream_t stream) {
+  const size_t low_pixels = (size_t)(width / 2) * (height / 2);
+  uint8_t *b = (uint8_t *)d_work;
+  const GuidedWork w = {{b, nullptr}, b + low_pixels * 16, b + low_pixels * 32};
+  if (launch_pack(low_pixels, u->demodulate, low, nullptr, w, stream) != 0) return -1;
+  const float k_n = 1.0f / (u->sigma_normal * u->sigma_normal), k_p = 1.0f / (u->sigma_position * u->sigma_position);
+  return launched(rt_launch_upsample(width, height, k_n, k_p, u->demodulate, w.buf[0], w.g0, w.g1, full, out, image, stream),
+                  "upsample kernel launch failed: %s");
+}
+
 static void temporal_camera(RT_TCamera *c, Camera const *cam) {
   for (int i = 0; i < 3; i++) {
     for (int k = 0; k < 3; k++) c->r[i][k] = cam->view_matrix.rows[i][k];
@@ -264,7 +325,7 @@ static int device_ready() {
 static int guided_device(const char *who, bool with_variance, i32 width, i32 height, RT_Guided_Params const *params, RT_Frame const &f,
                          FilterIO const &o, void *d_work, hipStream_t stream) {
   if (check_guided(who, width, height, params) != 0) return -1;
-  if (check_device_frame(who, f, params->demodulate) != 0) return -1;
+  if (check_frame(who, f, true, params->demodulate, nullptr) != 0) return -1;
   if (with_variance && !o.variance_in) return rt_fail("%s: d_variance is NULL", who);
   const Output outs[] = {{"d_out", o.out}, {"d_image", o.image}, {with_variance ? "d_variance_out" : nullptr, o.variance_out}};
   if (check_wanted(who, outs) != 0) return -1;
@@ -298,7 +359,7 @@ static int temporal_device(const char *who, bool with_moments, bool with_motion,
   if (with_moments && (a.vp || a.variance) && check_variance(who, a.vp) != 0) return -1;
   if (!camera) return rt_fail("%s: camera is NULL", who);
   if (d_history_in && !previous_camera) return rt_fail("%s: previous_camera is NULL and a history is given", who);
-  if (check_device_frame(who, f, params->demodulate) != 0) return -1;
+  if (check_frame(who, f, true, params->demodulate, nullptr) != 0) return -1;
   if (with_motion && !a.motion) return rt_fail("%s: d_motion is NULL", who);
   if (!d_history_out) return rt_fail("%s: d_history_out is NULL", who);
   if (((uintptr_t)d_history_out | (uintptr_t)d_history_in) & 15) return rt_fail("%s: the histories must be 16-byte aligned", who);
@@ -349,21 +410,49 @@ extern "C" int rt_temporal_accumulate_motion(i32 width, i32 height, RT_Temporal_
                          frame_of(d_color, d_coverage, d_albedo, d_normal, d_position), d_history_in, d_history_out, a, (hipStream_t)stream);
 }
 
+// No output may lie over an input or the work area (or the image over the f32 output): the launch writes pixels while others read.
+extern "C" int rt_guided_upsample(i32 width, i32 height, RT_Upsample_Params const *params, void const *d_color_low,
+                                  void const *d_coverage_low, void const *d_albedo_low, void const *d_normal_low,
+                                  void const *d_position_low, void const *d_coverage, void const *d_albedo, void const *d_normal,
+                                  void const *d_position, void *d_out, void *d_image, void *d_work, void *stream) {
+  const char *who = "rt_guided_upsample";
+  if (check_upsample(who, width, height, params) != 0) return -1;
+  const RT_Frame low = frame_of(d_color_low, d_coverage_low, d_albedo_low, d_normal_low, d_position_low);
+  const RT_Frame full = frame_of(nullptr, d_coverage, d_albedo, d_normal, d_position);
+  if (check_frame(who, low, true, params->demodulate, nullptr, "_low") != 0) return -1;
+  if (check_frame(who, full, false, params->demodulate, nullptr) != 0) return -1;
+  const Output wanted[] = {{"d_out", d_out}, {"d_image", d_image}};
+  if (check_wanted(who, wanted) != 0) return -1;
+  if (!d_work) return rt_fail("%s: d_work is NULL", who);
+  if ((uintptr_t)d_work & 15) return rt_fail("%s: d_work must be 16-byte aligned", who);
+  const uintptr_t pixels = (uintptr_t)width * height, f1 = pixels * sizeof(float), l1 = f1 / 4;
+  const Range outs[] = {{"d_out", d_out, f1 * 3}, {"d_image", d_image, pixels * 3}};
+  const Range ins[] = {{"d_color_low", low.color, l1 * 3}, {"d_coverage_low", low.coverage, l1}, {"d_albedo_low", low.albedo, l1 * 3},
+                       {"d_normal_low", low.normal, l1 * 3}, {"d_position_low", low.position, l1 * 3}, {"d_coverage", full.coverage, f1},
+                       {"d_albedo", full.albedo, f1 * 3}, {"d_normal", full.normal, f1 * 3}, {"d_position", full.position, f1 * 3},
+                       {"d_work", d_work, (uintptr_t)(pixels / 4) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL}};
+  if (check_ranges_apart(who, outs, ins) != 0) return -1;
+  if (overlap(outs[1], outs[0])) return rt_fail("%s: d_image overlaps d_out", who);
+  if (device_ready() != 0) return -1;
+  return enqueue_upsample(width, height, params, low, full, (float *)d_out, (uint8_t *)d_image, d_work, (hipStream_t)stream);
+}
+
 // ---- host level ---------------------------------------------------------------------------------------------------------------
 // The host-level calls run on the NULL stream: it does not wait for the lane streams of frames in flight.
 
-// Copies a host frame into `in` (RT_HOST_FRAME_F32 f32 per pixel): the colour at `in` itself, behind it the planes.  *f is the frame
-// on the device; f->albedo is NULL when the host gave none.
+// Copies a host frame into `in`: the colour (optional) at `in` itself, behind it the planes as FeatureState keeps them -- with a
+// colour RT_HOST_FRAME_F32 f32 per pixel, without one RT_FEATURE_CHANNELS.  *f is the frame on the device; f->color is NULL
+// without a colour, f->albedo when the host gave none.
 static int upload_host_frame(float *in, size_t pixels, f32 const *color, RT_Features const *planes, RT_Frame *f) {
   const size_t f3 = pixels * 3 * sizeof(float), f1 = pixels * sizeof(float);
-  RT_Features d = split_feature_planes(in + pixels * 3, pixels);
-  HIP_TRY(hipMemcpy(in, color, f3, hipMemcpyHostToDevice));
+  RT_Features d = split_feature_planes(color ? in + pixels * 3 : in, pixels);
+  if (color) HIP_TRY(hipMemcpy(in, color, f3, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d.coverage, planes->coverage, f1, hipMemcpyHostToDevice));
   if (planes->albedo) HIP_TRY(hipMemcpy(d.albedo, planes->albedo, f3, hipMemcpyHostToDevice));
   else d.albedo = nullptr;
   HIP_TRY(hipMemcpy(d.normal, planes->normal, f3, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d.position, planes->position, f3, hipMemcpyHostToDevice));
-  *f = device_frame(in, d);
+  *f = device_frame(color ? in : nullptr, d);
   return 0;
 }
 
@@ -411,6 +500,41 @@ extern "C" int rt_guided_denoise_host(i32 width, i32 height, RT_Guided_Params co
 extern "C" int rt_guided_denoise_variance_host(i32 width, i32 height, RT_Guided_Params const *params, f32 const *color,
                                                RT_Features const *planes, f32 *out, u8 *image, f32 const *variance, f32 *variance_out) {
   return guided_host("rt_guided_denoise_variance_host", true, width, height, params, color, planes, {out, image, variance, variance_out});
+}
+
+extern "C" int rt_guided_upsample_host(i32 width, i32 height, RT_Upsample_Params const *params, f32 const *color_low,
+                                       RT_Features const *low, RT_Features const *full, f32 *out, u8 *image) {
+  const char *who = "rt_guided_upsample_host";
+  if (check_upsample(who, width, height, params) != 0) return -1;
+  if (!color_low) return rt_fail("%s: color_low is NULL", who);
+  if (!low) return rt_fail("%s: low is NULL", who);
+  if (!full) return rt_fail("%s: full is NULL", who);
+  if (check_frame(who, device_frame(nullptr, *low), false, params->demodulate, "low") != 0) return -1;
+  if (check_frame(who, device_frame(nullptr, *full), false, params->demodulate, "full") != 0) return -1;
+  const Output wanted[] = {{"out", out}, {"image", image}};
+  if (check_wanted(who, wanted) != 0) return -1;
+
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  UpsampleState &S = D.upsample;
+  const size_t pixels = (size_t)width * height, low_pixels = pixels / 4;
+  HIP_TRY(S.in_low.grow(low_pixels * RT_HOST_FRAME_F32));
+  HIP_TRY(S.in_full.grow(pixels * RT_FEATURE_CHANNELS));
+  HIP_TRY(S.work.grow(low_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
+  if (out) HIP_TRY(S.out.grow(pixels * 3));
+  if (image) HIP_TRY(S.image.grow(pixels * 3));
+  hipStream_t stream = nullptr;
+  RT_Frame fl, ff;
+  if (upload_host_frame(S.in_low, low_pixels, color_low, low, &fl) != 0) return -1;
+  if (upload_host_frame(S.in_full, pixels, nullptr, full, &ff) != 0) return -1;
+  if (enqueue_upsample(width, height, params, fl, ff, out ? S.out.get() : nullptr, image ? S.image.get() : nullptr, S.work, stream) != 0)
+    return -1;
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  if (out) HIP_TRY(hipMemcpy(out, S.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (image) HIP_TRY(hipMemcpy(image, S.image, pixels * 3, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 static const char *missing_history_plane(RT_History_Planes const *h) {
@@ -582,33 +706,42 @@ extern "C" void rt_history_destroy(RT_History *history) {
 
 // ---- behind a frame -----------------------------------------------------------------------------------------------------------
 
-// The three entry points: their word for the frame in the one-device refusal; their stages -- `history`: the accumulation,
-// `variance`: it carries the moments and the filter is the variance-guided one, `must_filter`: the filter's params are required --;
-// their list of the outputs in the refusal of a call that wants none.
-struct PostFrame { const char *what; bool history, variance, must_filter; const char *outputs; };
-static const PostFrame DENOISED = {"a denoised frame", false, false, true, "no pixels and no linear_denoised"};
-static const PostFrame ACCUMULATED = {"an accumulated frame", true, false, false, "no pixels, no linear_out, no length"};
-static const PostFrame SVGF = {"a variance-guided frame", true, true, true, "no pixels, no linear_out, no length, no variance"};
+// The four entry points: their word for the frame in the one-device refusal; their stages -- `history`: the accumulation,
+// `variance`: it carries the moments and the filter is the variance-guided one, `upsample`: the frame is rendered at half the size
+// and upsampled, `must_filter`: the filter's params are required --; their list of the outputs in the refusal of a call that wants
+// none.  (No entry point has both a history and the upsampling.)
+struct PostFrame { const char *what; bool history, variance, upsample, must_filter; const char *outputs; };
+static const PostFrame DENOISED = {"a denoised frame", false, false, false, true, "no pixels and no linear_denoised"};
+static const PostFrame ACCUMULATED = {"an accumulated frame", true, false, false, false, "no pixels, no linear_out, no length"};
+static const PostFrame SVGF = {"a variance-guided frame", true, true, false, true, "no pixels, no linear_out, no length, no variance"};
+static const PostFrame UPSAMPLED = {"an upsampled frame", false, false, true, false, "no pixels, no linear_upsampled, no linear_out"};
 
 // The stages' arguments (NULL: the entry point has no such stage, or g: the caller wants no filter), and what the caller wants back
-// besides the Image (f32, each optional): the frame as rendered, the last stage's output, the history lengths, the filter's variance.
-struct PostStages { RT_Guided_Params const *g; RT_History *history; RT_Temporal_Params const *t; RT_Variance_Params const *vp; };
-struct PostOutputs { f32 *linear_noisy, *linear_out, *length, *variance; };
+// besides the Image (f32, each optional): the frame as rendered (at half the size when it is upsampled), the last stage's output,
+// the history lengths, the filter's variance, the upsampling's output.
+struct PostStages {
+  RT_Guided_Params const *g; RT_History *history; RT_Temporal_Params const *t; RT_Variance_Params const *vp; RT_Upsample_Params const *u;
+};
+struct PostOutputs { f32 *linear_noisy, *linear_out, *length, *variance, *linear_upsampled; };
 
-// The frame, the four planes of its feature pass, then the stages that are given -- the accumulation against s.history (s.t), the
-// filter (s.g) -- in one scene-checked call.  W.linear is the noisy frame, D.temporal.out / length serve the accumulation,
-// D.guided.work / out the filter, and W.image receives the encoding of the LAST stage.  s.vp (with history and g): rt_render_svgf
-// -- the accumulation carries the history's moments, the variance launch follows it into D.temporal.variance, and the filter is
-// the variance-guided one.  A history with motion on (rt_history_set_motion): the feature pass is the motion kernel's -- one
-// launch -- against the scene's kept geometry, its motion sums are resolved into F.motion, and the accumulation is THE ACCUMULATION
-// WITH MOTION.
+// The frame, the four planes of its feature pass, then the stages that are given -- the accumulation against s.history (s.t) or
+// the upsampling (s.u), the filter (s.g) -- in one scene-checked call.  W.linear is the noisy frame, D.temporal.out / length serve
+// the accumulation, D.upsample.work / out the upsampling, D.guided.work / out the filter, and W.image receives the encoding of the
+// LAST stage.  s.vp (with history and g): rt_render_svgf -- the accumulation carries the history's moments, the variance launch
+// follows it into D.temporal.variance, and the filter is the variance-guided one.  A history with motion on
+// (rt_history_set_motion): the feature pass is the motion kernel's -- one launch -- against the scene's kept geometry, its motion
+// sums are resolved into F.motion, and the accumulation is THE ACCUMULATION WITH MOTION.  s.u: rt_render_upsampled -- the frame
+// and its feature pass (into D.upsample.low_planes) are at half the Image's size, a second feature pass with guide_samples fills
+// D.features.planes at full size, and the upsampling and the filter run at full size.
 static int render_post(const char *who, PostFrame const &kind, Scene const *scene, Image const *image, isize samples, isize max_bounces,
                        PostStages const &s, PostOutputs const &o) {
   // before the device lock: the image's size before it goes into 32 bits, the stages' parameters, the rest of the frame's
   if (!scene) return rt_fail("%s: scene is NULL", who);
   if (!image) return rt_fail("%s: image is NULL", who);
   if (kind.history && !s.history) return rt_fail("%s: history is NULL", who);
-  if (image->width <= 0 || image->height <= 0 || image->width > 0x7fffffff || image->height > 0x7fffffff)
+  if (kind.upsample) {
+    if (check_upsample(who, image->width, image->height, s.u) != 0) return -1;
+  } else if (image->width <= 0 || image->height <= 0 || image->width > 0x7fffffff || image->height > 0x7fffffff)
     return rt_fail("%s: image size %ldx%ld is invalid", who, (long)image->width, (long)image->height);
   const i32 width = (i32)image->width, height = (i32)image->height;
   if (kind.history && check_temporal(who, width, height, s.t) != 0) return -1;
@@ -617,10 +750,17 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
   if (check_image_layout(image, who) != 0) return -1;
   if (samples <= 0 || samples > 0x7fffffff) return rt_fail("%s: samples must be positive and fit 32 bits (got %ld)", who, (long)samples);
   if (max_bounces < 0 || max_bounces > 0x7fffffff) return rt_fail("%s: max_bounces must be >= 0 and fit 32 bits (got %ld)", who, (long)max_bounces);
-  if (!image->pixels.data && !o.linear_out && !o.length && !o.variance) return rt_fail("%s: no output is wanted (%s)", who, kind.outputs);
+  if (kind.upsample) {
+    if (s.u->guide_samples < 0 || s.u->guide_samples > samples)
+      return rt_fail("%s: guide_samples must be 0 .. samples (got %d, samples %ld)", who, s.u->guide_samples, (long)samples);
+    if (o.linear_out && !s.g) return rt_fail("%s: linear_out is the filter's output and guided params are NULL", who);
+  }
+  if (!image->pixels.data && !o.linear_out && !o.length && !o.variance && !o.linear_upsampled)
+    return rt_fail("%s: no output is wanted (%s)", who, kind.outputs);
 
   RT_History *const history = s.history;
   RT_Guided_Params const *const g = s.g;
+  RT_Upsample_Params const *const u = s.u;
   Device &D = dev0();
   std::lock_guard<std::mutex> lock(D.mutex);
   if (history && (image->width != history->width || image->height != history->height))
@@ -632,8 +772,15 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
   if (ensure_device(D) != 0) return -1;
   if (rt_device_count() > 1)
     return rt_fail("%s: %s renders on one device, and %d are set (rt_set_devices)", who, kind.what, rt_device_count());
-  RT_Render_Params p;
-  if (fill_frame_params(&p, image, samples, max_bounces, g_seed.load()) != 0) return -1;
+  // p: the frame and its feature pass -- at half the Image's size when it is upsampled, and then pf: the full-size feature pass
+  Image frame_image = *image;                                      // (the frame's size alone is read from it)
+  if (u) {
+    frame_image.width = width / 2;
+    frame_image.height = height / 2;
+  }
+  RT_Render_Params p, pf;
+  if (fill_frame_params(&p, &frame_image, samples, max_bounces, g_seed.load()) != 0) return -1;
+  if (u && fill_frame_params(&pf, image, u->guide_samples ? u->guide_samples : samples, max_bounces, g_seed.load()) != 0) return -1;
   forget_multi_counters();
 
   FrameTiming T;
@@ -641,10 +788,18 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
   FeatureState &F = D.features;
   GuidedState &G = D.guided;
   TemporalState &S = D.temporal;
-  const size_t pixels = (size_t)p.width * p.height;
+  UpsampleState &U = D.upsample;
+  const size_t pixels = (size_t)width * height, frame_pixels = (size_t)p.width * p.height;
   if (ensure_ws_buffers(W, p.width, p.height, 0, 0) != 0) return -1;
   HIP_TRY(F.sums.grow(pixels * RT_FEATURE_CHANNELS));
   HIP_TRY(F.planes.grow(pixels * RT_FEATURE_CHANNELS));
+  const bool want_upsampled = u && (g || o.linear_upsampled);       // the upsampling's f32 output: the filter's input, or the caller's
+  if (u) {
+    HIP_TRY(W.image.grow(pixels * 3));                              // (the workspace is the low frame's)
+    HIP_TRY(U.low_planes.grow(frame_pixels * RT_FEATURE_CHANNELS));
+    HIP_TRY(U.work.grow(frame_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
+    if (want_upsampled) HIP_TRY(U.out.grow(pixels * 3));
+  }
   const bool motion = history && history->motion;
   if (motion) {
     HIP_TRY(F.motion_sums.grow(pixels * RT_MOTION_CHANNELS));
@@ -678,22 +833,27 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
     HIP_TRY(G.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
     if (o.linear_out) HIP_TRY(G.out.grow(pixels * 3));
   }
+  // the planes at the Image's size, and those of the frame: the same, but for a frame that is upsampled
   const RT_Features planes = split_feature_planes(F.planes, pixels);
+  const RT_Features frame_planes = u ? split_feature_planes(U.low_planes, frame_pixels) : planes;
+  const float *const filter_in = history ? S.out.get() : u ? U.out.get() : W.linear.get();   // the stage before the filter wrote it
   hipStream_t stream = nullptr;
   // (a pass that is run again after a scene edit reads the same old history and writes the same new one)
   auto pass = [&](RT_Device_Scene *d) -> int {
     if (enqueue_frame(D, d, &scene->camera, &p, W, stream, 0, nullptr, nullptr, W.linear) != 0) return -1;
-    HIP_TRY(hipMemsetAsync(F.sums, 0, pixels * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
-    if (motion) HIP_TRY(hipMemsetAsync(F.motion_sums, 0, pixels * RT_MOTION_CHANNELS * sizeof(unsigned long long), stream));
-    if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream, motion ? F.motion_sums.get() : nullptr) != 0) return -1;
-    if (enqueue_resolve(&p, F.sums, planes.coverage, planes.albedo, planes.normal, planes.position, stream) != 0) return -1;
-    if (motion && enqueue_resolve_motion(&p, F.motion_sums, F.motion, stream) != 0) return -1;
-    if (history && enqueue_temporal(p.width, p.height, s.t, &scene->camera, &history->camera, device_frame(W.linear, planes), h_in, h_out,
-                                    a, stream) != 0)
+    if (enqueue_feature_pass(D, d, &scene->camera, &p, F.sums, frame_planes, stream, motion ? F.motion_sums.get() : nullptr,
+                             motion ? F.motion.get() : nullptr) != 0)
+      return -1;
+    if (history && enqueue_temporal(width, height, s.t, &scene->camera, &history->camera, device_frame(W.linear, planes), h_in, h_out, a,
+                                    stream) != 0)
+      return -1;
+    if (u && (enqueue_feature_pass(D, d, &scene->camera, &pf, F.sums, planes, stream) != 0 ||
+              enqueue_upsample(width, height, u, device_frame(W.linear, frame_planes), device_frame(nullptr, planes),
+                               want_upsampled ? U.out.get() : nullptr, g ? nullptr : W.image.get(), U.work, stream) != 0))
       return -1;
     if (!g) return 0;
     const FilterIO f = {o.linear_out ? G.out.get() : nullptr, W.image, a.variance};
-    return enqueue_guided(p.width, p.height, g, device_frame(history ? S.out.get() : W.linear.get(), planes), f, G.work, stream);
+    return enqueue_guided(width, height, g, device_frame(filter_in, planes), f, G.work, stream);
   };
   if (!scene_checked(D, scene, stream, &T, pass)) {                // (a scene edited since the copy: uploaded and rendered again)
     if (history) history->valid = history->moments_valid = false;   // (the new history may be half written, the old one is not current)
@@ -706,9 +866,10 @@ static int render_post(const char *who, PostFrame const &kind, Scene const *scen
     history->camera = scene->camera;
   }
 
-  if (copy_image_out(image, W.image, p.width, p.height, stream) != 0) return -1;
+  if (copy_image_out(image, W.image, width, height, stream) != 0) return -1;
   HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
-  if (o.linear_noisy) HIP_TRY(hipMemcpy(o.linear_noisy, W.linear, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.linear_noisy) HIP_TRY(hipMemcpy(o.linear_noisy, W.linear, frame_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (o.linear_upsampled) HIP_TRY(hipMemcpy(o.linear_upsampled, U.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
   if (o.linear_out) HIP_TRY(hipMemcpy(o.linear_out, g ? G.out.get() : S.out.get(), pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
   if (o.length) HIP_TRY(hipMemcpy(o.length, S.length, pixels * sizeof(float), hipMemcpyDeviceToHost));
   if (o.variance) HIP_TRY(hipMemcpy(o.variance, S.variance, pixels * sizeof(float), hipMemcpyDeviceToHost));
@@ -734,228 +895,9 @@ extern "C" int rt_render_svgf(Scene const *scene, Image const *image, isize samp
                      {guided_params, history, temporal_params, variance_params}, {linear_noisy, linear_out, length, variance});
 }
 
-// ---- half-resolution frames: feature-guided upsampling ------------------------------------------------------------------------------
-// THE UPSAMPLING (include/rt_hip.h; rt_upsample.hip): device level, host level and behind a frame, like the stages above.
-
-#define RT_UPSAMPLE_WORK_PER_LOW_PIXEL 48   // the packed low frame: (c, L), (N, coverage), (P, 0), three float4
-
-// What can be checked without the device: the full size -- even, >= 2, at most RT_MAX_PIXELS -- and the parameters but guide_samples.
-static int check_upsample_size(const char *who, i64 width, i64 height) {
-  if (width < 2 || height < 2 || width > 0x7fffffff || height > 0x7fffffff)
-    return rt_fail("%s: image size %ldx%ld is invalid (an upsampled frame is at least 2x2)", who, (long)width, (long)height);
-  if ((width | height) & 1)
-    return rt_fail("%s: image size %ldx%ld is odd (the low frame is width / 2 x height / 2)", who, (long)width, (long)height);
-  return check_image_size(who, (i32)width, (i32)height);
-}
-
-static int check_upsample(const char *who, i64 width, i64 height, RT_Upsample_Params const *u) {
-  if (check_upsample_size(who, width, height) != 0) return -1;
-  if (!u) return rt_fail("%s: upsample params are NULL", who);
-  // (written so that NaN fails)
-  if (!(u->sigma_normal > 0.0f)) return rt_fail("%s: sigma_normal must be > 0 (got %g)", who, (double)u->sigma_normal);
-  if (!(u->sigma_position > 0.0f)) return rt_fail("%s: sigma_position must be > 0 (got %g)", who, (double)u->sigma_position);
-  if (u->demodulate != 0 && u->demodulate != 1) return rt_fail("%s: demodulate must be 0 or 1 (got %d)", who, u->demodulate);
-  return 0;
-}
-
-extern "C" i64 rt_guided_upsample_work_bytes(i32 width, i32 height) {
-  if (check_upsample_size("rt_guided_upsample_work_bytes", width, height) != 0) return -1;
-  return (i64)(width / 2) * (height / 2) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL;
-}
-
-// An array an entry point reads or writes, by the name its message has for it; p NULL: not given.
-struct Range { const char *name; const void *p; uintptr_t bytes; };
-// Refuses an output that overlaps an input: the upsampling writes a pixel while other pixels still read.
-template <int N, int M> static int check_ranges_apart(const char *who, const Range (&outs)[N], const Range (&ins)[M]) {
-  for (const Range &o : outs)
-    for (const Range &i : ins) {
-      if (!o.p || !i.p) continue;
-      const uintptr_t a = (uintptr_t)o.p, b = (uintptr_t)i.p;
-      if (a < b + i.bytes && b < a + o.bytes) return rt_fail("%s: %s overlaps %s", who, o.name, i.name);
-    }
-  return 0;
-}
-
-// Enqueues the pack launch over the low frame and the upsampling launch.  `full`: the full-resolution planes (its colour is not
-// read).  Every pointer is on the current device.
-static int enqueue_upsample(i32 width, i32 height, RT_Upsample_Params const *u, RT_Frame const &low, RT_Frame const &full, float *out,
-                            uint8_t *image, void *d_work, hipStream_t stream) {
-  const size_t low_pixels = (size_t)(width / 2) * (height / 2);
-  uint8_t *b = (uint8_t *)d_work;
-  const GuidedWork w = {{b, nullptr}, b + low_pixels * 16, b + low_pixels * 32};
-  if (launch_pack(low_pixels, u->demodulate, low, nullptr, w, stream) != 0) return -1;
-  const float k_n = 1.0f / (u->sigma_normal * u->sigma_normal), k_p = 1.0f / (u->sigma_position * u->sigma_position);
-  return launched(rt_launch_upsample(width, height, k_n, k_p, u->demodulate, w.buf[0], w.g0, w.g1, full, out, image, stream),
-                  "upsample kernel launch failed: %s");
-}
-
-extern "C" int rt_guided_upsample(i32 width, i32 height, RT_Upsample_Params const *params, void const *d_color_low,
-                                  void const *d_coverage_low, void const *d_albedo_low, void const *d_normal_low,
-                                  void const *d_position_low, void const *d_coverage, void const *d_albedo, void const *d_normal,
-                                  void const *d_position, void *d_out, void *d_image, void *d_work, void *stream) {
-  const char *who = "rt_guided_upsample";
-  if (check_upsample(who, width, height, params) != 0) return -1;
-  const RT_Frame low = frame_of(d_color_low, d_coverage_low, d_albedo_low, d_normal_low, d_position_low);
-  const RT_Frame full = frame_of(nullptr, d_coverage, d_albedo, d_normal, d_position);
-  if (!low.color) return rt_fail("%s: d_color_low is NULL", who);
-  if (!low.coverage) return rt_fail("%s: d_coverage_low is NULL", who);
-  if (!low.albedo && params->demodulate) return rt_fail("%s: d_albedo_low is NULL and demodulate is set", who);
-  if (!low.normal) return rt_fail("%s: d_normal_low is NULL", who);
-  if (!low.position) return rt_fail("%s: d_position_low is NULL", who);
-  if (!full.coverage) return rt_fail("%s: d_coverage is NULL", who);
-  if (!full.albedo && params->demodulate) return rt_fail("%s: d_albedo is NULL and demodulate is set", who);
-  if (!full.normal) return rt_fail("%s: d_normal is NULL", who);
-  if (!full.position) return rt_fail("%s: d_position is NULL", who);
-  const Output wanted[] = {{"d_out", d_out}, {"d_image", d_image}};
-  if (check_wanted(who, wanted) != 0) return -1;
-  if (!d_work) return rt_fail("%s: d_work is NULL", who);
-  if ((uintptr_t)d_work & 15) return rt_fail("%s: d_work must be 16-byte aligned", who);
-  const uintptr_t pixels = (uintptr_t)width * height, f1 = pixels * sizeof(float), l1 = f1 / 4;
-  const Range outs[] = {{"d_out", d_out, f1 * 3}, {"d_image", d_image, pixels * 3}};
-  const Range ins[] = {{"d_color_low", low.color, l1 * 3}, {"d_coverage_low", low.coverage, l1}, {"d_albedo_low", low.albedo, l1 * 3},
-                       {"d_normal_low", low.normal, l1 * 3}, {"d_position_low", low.position, l1 * 3}, {"d_coverage", full.coverage, f1},
-                       {"d_albedo", full.albedo, f1 * 3}, {"d_normal", full.normal, f1 * 3}, {"d_position", full.position, f1 * 3},
-                       {"d_work", d_work, (uintptr_t)(pixels / 4) * RT_UPSAMPLE_WORK_PER_LOW_PIXEL}};
-  if (check_ranges_apart(who, outs, ins) != 0) return -1;
-  const Range image_range[] = {{"d_image", d_image, pixels * 3}}, out_range[] = {{"d_out", d_out, f1 * 3}};
-  if (check_ranges_apart(who, image_range, out_range) != 0) return -1;
-  if (device_ready() != 0) return -1;
-  return enqueue_upsample(width, height, params, low, full, (float *)d_out, (uint8_t *)d_image, d_work, (hipStream_t)stream);
-}
-
-// Copies the four planes of a host frame into `in` (RT_FEATURE_CHANNELS f32 per pixel, as FeatureState keeps them); *f is the
-// planes on the device, without a colour; f->albedo is NULL when the host gave none.
-static int upload_host_planes(float *in, size_t pixels, RT_Features const *planes, RT_Frame *f) {
-  const size_t f3 = pixels * 3 * sizeof(float), f1 = pixels * sizeof(float);
-  RT_Features d = split_feature_planes(in, pixels);
-  HIP_TRY(hipMemcpy(d.coverage, planes->coverage, f1, hipMemcpyHostToDevice));
-  if (planes->albedo) HIP_TRY(hipMemcpy(d.albedo, planes->albedo, f3, hipMemcpyHostToDevice));
-  else d.albedo = nullptr;
-  HIP_TRY(hipMemcpy(d.normal, planes->normal, f3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.position, planes->position, f3, hipMemcpyHostToDevice));
-  *f = device_frame(nullptr, d);
-  return 0;
-}
-
-extern "C" int rt_guided_upsample_host(i32 width, i32 height, RT_Upsample_Params const *params, f32 const *color_low,
-                                       RT_Features const *low, RT_Features const *full, f32 *out, u8 *image) {
-  const char *who = "rt_guided_upsample_host";
-  if (check_upsample(who, width, height, params) != 0) return -1;
-  if (!color_low) return rt_fail("%s: color_low is NULL", who);
-  if (!low) return rt_fail("%s: low is NULL", who);
-  if (!full) return rt_fail("%s: full is NULL", who);
-  const struct { const char *name; RT_Features const *planes; } frames[2] = {{"low", low}, {"full", full}};
-  for (const auto &fr : frames) {
-    if (!fr.planes->coverage) return rt_fail("%s: %s->coverage is NULL", who, fr.name);
-    if (!fr.planes->albedo && params->demodulate) return rt_fail("%s: %s->albedo is NULL and demodulate is set", who, fr.name);
-    if (!fr.planes->normal) return rt_fail("%s: %s->normal is NULL", who, fr.name);
-    if (!fr.planes->position) return rt_fail("%s: %s->position is NULL", who, fr.name);
-  }
-  const Output wanted[] = {{"out", out}, {"image", image}};
-  if (check_wanted(who, wanted) != 0) return -1;
-
-  Device &D = dev0();
-  std::lock_guard<std::mutex> lock(D.mutex);
-  if (ensure_device(D) != 0) return -1;
-  UpsampleState &S = D.upsample;
-  const size_t pixels = (size_t)width * height, low_pixels = pixels / 4;
-  HIP_TRY(S.in_low.grow(low_pixels * RT_HOST_FRAME_F32));
-  HIP_TRY(S.in_full.grow(pixels * RT_FEATURE_CHANNELS));
-  HIP_TRY(S.work.grow(low_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
-  if (out) HIP_TRY(S.out.grow(pixels * 3));
-  if (image) HIP_TRY(S.image.grow(pixels * 3));
-  hipStream_t stream = nullptr;
-  RT_Frame fl, ff;
-  if (upload_host_frame(S.in_low, low_pixels, color_low, low, &fl) != 0) return -1;
-  if (upload_host_planes(S.in_full, pixels, full, &ff) != 0) return -1;
-  if (enqueue_upsample(width, height, params, fl, ff, out ? S.out.get() : nullptr, image ? S.image.get() : nullptr, S.work, stream) != 0)
-    return -1;
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(hipGetLastError());
-  if (out) HIP_TRY(hipMemcpy(out, S.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (image) HIP_TRY(hipMemcpy(image, S.image, pixels * 3, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The low frame (W.linear, at half the Image's size), its feature pass into D.upsample.low_planes, the full-resolution feature pass
-// with guide_samples into D.features.planes, the upsampling into D.upsample.out and, when g is given, the filter over that
-// (D.guided.work / out) -- in one scene-checked call.  W.image receives the encoding of the LAST stage.
 extern "C" int rt_render_upsampled(Scene const *scene, Image const *image, isize samples, isize max_bounces,
                                    RT_Upsample_Params const *upsample_params, RT_Guided_Params const *guided_params, f32 *linear_low,
                                    f32 *linear_upsampled, f32 *linear_out) {
-  const char *who = "rt_render_upsampled";
-  RT_Upsample_Params const *const u = upsample_params;
-  RT_Guided_Params const *const g = guided_params;
-  // before the device lock: the image's size before it goes into 32 bits, the stages' parameters, the rest of the frame's
-  if (!scene) return rt_fail("%s: scene is NULL", who);
-  if (!image) return rt_fail("%s: image is NULL", who);
-  if (check_upsample(who, image->width, image->height, u) != 0) return -1;
-  const i32 width = (i32)image->width, height = (i32)image->height;
-  if (g && check_guided(who, width, height, g) != 0) return -1;
-  if (check_image_layout(image, who) != 0) return -1;
-  if (samples <= 0 || samples > 0x7fffffff) return rt_fail("%s: samples must be positive and fit 32 bits (got %ld)", who, (long)samples);
-  if (max_bounces < 0 || max_bounces > 0x7fffffff) return rt_fail("%s: max_bounces must be >= 0 and fit 32 bits (got %ld)", who, (long)max_bounces);
-  if (u->guide_samples < 0 || u->guide_samples > samples)
-    return rt_fail("%s: guide_samples must be 0 .. samples (got %d, samples %ld)", who, u->guide_samples, (long)samples);
-  if (linear_out && !g) return rt_fail("%s: linear_out is the filter's output and guided params are NULL", who);
-  if (!image->pixels.data && !linear_upsampled && !linear_out)
-    return rt_fail("%s: no output is wanted (no pixels, no linear_upsampled, no linear_out)", who);
-
-  Device &D = dev0();
-  std::lock_guard<std::mutex> lock(D.mutex);
-  const double t_start = now_ms();
-  if (ensure_device(D) != 0) return -1;
-  if (rt_device_count() > 1)
-    return rt_fail("%s: an upsampled frame renders on one device, and %d are set (rt_set_devices)", who, rt_device_count());
-  Image low_image = *image;                                        // (the low frame's size alone is read from it)
-  low_image.width = width / 2;
-  low_image.height = height / 2;
-  RT_Render_Params pl, pf;                                         // the low frame and its feature pass; the full-resolution feature pass
-  if (fill_frame_params(&pl, &low_image, samples, max_bounces, g_seed.load()) != 0) return -1;
-  if (fill_frame_params(&pf, image, u->guide_samples ? u->guide_samples : samples, max_bounces, g_seed.load()) != 0) return -1;
-  forget_multi_counters();
-
-  FrameTiming T;
-  Workspace &W = D.ws;
-  FeatureState &F = D.features;
-  GuidedState &G = D.guided;
-  UpsampleState &U = D.upsample;
-  const size_t pixels = (size_t)width * height, low_pixels = pixels / 4;
-  if (ensure_ws_buffers(W, pl.width, pl.height, 0, 0) != 0) return -1;
-  HIP_TRY(W.image.grow(pixels * 3));
-  HIP_TRY(F.sums.grow(pixels * RT_FEATURE_CHANNELS));
-  HIP_TRY(F.planes.grow(pixels * RT_FEATURE_CHANNELS));
-  HIP_TRY(U.low_planes.grow(low_pixels * RT_FEATURE_CHANNELS));
-  HIP_TRY(U.work.grow(low_pixels * RT_UPSAMPLE_WORK_PER_LOW_PIXEL));
-  const bool want_upsampled = g || linear_upsampled;               // the upsampling's f32 output: the filter's input, or the caller's
-  if (want_upsampled) HIP_TRY(U.out.grow(pixels * 3));
-  if (g) {
-    HIP_TRY(G.work.grow(pixels * RT_GUIDED_WORK_PER_PIXEL));
-    if (linear_out) HIP_TRY(G.out.grow(pixels * 3));
-  }
-  const RT_Features low_planes = split_feature_planes(U.low_planes, low_pixels), planes = split_feature_planes(F.planes, pixels);
-  hipStream_t stream = nullptr;
-  auto features = [&](RT_Device_Scene *d, RT_Render_Params const &p, RT_Features const &to) -> int {
-    HIP_TRY(hipMemsetAsync(F.sums, 0, (size_t)p.width * p.height * RT_FEATURE_CHANNELS * sizeof(unsigned long long), stream));
-    if (enqueue_features(D, d, &scene->camera, &p, F.sums, stream) != 0) return -1;
-    return enqueue_resolve(&p, F.sums, to.coverage, to.albedo, to.normal, to.position, stream);
-  };
-  auto pass = [&](RT_Device_Scene *d) -> int {
-    if (enqueue_frame(D, d, &scene->camera, &pl, W, stream, 0, nullptr, nullptr, W.linear) != 0) return -1;
-    if (features(d, pl, low_planes) != 0 || features(d, pf, planes) != 0) return -1;
-    if (enqueue_upsample(width, height, u, device_frame(W.linear, low_planes), device_frame(nullptr, planes),
-                         want_upsampled ? U.out.get() : nullptr, g ? nullptr : W.image.get(), U.work, stream) != 0)
-      return -1;
-    if (!g) return 0;
-    const FilterIO f = {linear_out ? G.out.get() : nullptr, W.image};
-    return enqueue_guided(width, height, g, device_frame(U.out, planes), f, G.work, stream);
-  };
-  if (!scene_checked(D, scene, stream, &T, pass)) return -1;         // (a scene edited since the copy: uploaded and rendered again)
-
-  if (copy_image_out(image, W.image, width, height, stream) != 0) return -1;
-  HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
-  if (linear_low) HIP_TRY(hipMemcpy(linear_low, W.linear, low_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (linear_upsampled) HIP_TRY(hipMemcpy(linear_upsampled, U.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (linear_out) HIP_TRY(hipMemcpy(linear_out, G.out, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  return finish_frame(D, W, stream, T, t_start);
+  return render_post("rt_render_upsampled", UPSAMPLED, scene, image, samples, max_bounces,
+                     {guided_params, nullptr, nullptr, nullptr, upsample_params}, {linear_low, linear_out, nullptr, nullptr, linear_upsampled});
 }
