@@ -807,6 +807,17 @@ extern int rt_get_leafless_paths(u64 *out);
  * depth 0 and rays that are not NaN-free take the node block as before: 0 for such a frame).  The visits are executed and counted;
  * what they skip is a traversal round.  Equals rays - skipped root visits - leafless paths when every ray is NaN-free.  For tests. */
 extern int rt_get_fused_root_visits(u64 *out);
+/* Which form of the shade block's texture stage the last path-kernel launch of rt_render_accumulate / rt_render_accumulate_views /
+ * rt_render_frame on the primary device ran: 1 = shared, one set of bilinear taps per hit for the material's four textures;
+ * 0 = general, one set per texture; -1 = no launch yet.  A launch is shared when rt_materials_share_taps() holds for the resident
+ * copy's material table and a material names a texture; decided at upload and again when rt_scene_touch() patches a material.
+ * Same frames either way, bit for bit.  For tests and profile notes. */
+extern int rt_get_shade_taps_form(void);
+/* The predicate behind it, on a table a caller supplies: n_materials packed material rows of 36 words each -- words 12 .. 15 the
+ * slot indices of the albedo, normal, metal-roughness and emission textures as int bits (< 0: none), words 20 + 4 k .. 23 + 4 k
+ * the descriptor (offset, width, height, stride) of texture k as int bits.  1 when, in every row, all the textures the row names
+ * have equal width, height and stride (no texture, one texture, an empty or NULL table: 1), else 0.  Touches no device. */
+extern int rt_materials_share_taps(f32 const *mats, i32 n_materials);
 
 /* Where the time of the last frame behind render_thread_proc / render / rt_render_frame went, in milliseconds.
  * Host clock: stamp = the per-frame scene check, upload = the scene upload when one was needed, enqueue = launching the

@@ -124,8 +124,12 @@ extern int rt_test_texture(RT_Device_Scene *dscene, i32 tex, i32 n, f32 const *u
 /* ---- the shade block, item by item (tests/test_gpu_shade.py; the CPU counterparts are oracle_disney_shade, oracle_debug_shade,
  * oracle_sample_disney_brdf, oracle_sample_background and oracle_primary_ray of oracle/oracle.h).  Host arrays. */
 
+#define RT_TEST_SHARED_TAPS 4      /* mode bit of rt_test_shade / rt_test_shade_hit */
 /* shade() -- disney_shader_proc / debug_shader_proc, driver.c:350-418 -- on n inputs a test chooses.
- *   mode      0 = shade<ShadeParams>, 1 = shade<ShadeParamsLds>: the path kernel's instance, the sRGB scale table in LDS
+ *   mode      0 = shade<ShadeParams>, 1 = shade<ShadeParamsLds>: the path kernel's instance, the sRGB scale table in LDS;
+ *             either + RT_TEST_SHARED_TAPS: the form with ONE set of bilinear taps per item (what the path kernel runs on a scene
+ *             whose materials' textures agree in size, rt_get_shade_taps_form); refused on a scene where
+ *             rt_materials_share_taps() does not hold
  *   tri[n]    triangle slot of the uploaded scene whose MATERIAL is evaluated: float 3 of its 28-float record, as shade_hit()
  *             reads it.  Nothing else of the triangle is used.
  *   in        14 floats per item: direction, normal, tangent, bitangent (3 each), texture coordinates (2, finite)
@@ -141,7 +145,7 @@ extern int rt_test_shade(RT_Device_Scene *dscene, i32 mode, i32 n, i32 const *tr
  * hit (surface_at), shade(), carried tint and emission, the next origin, the bounce count.  CPU counterpart: oracle_fill_hit +
  * oracle_path_step (tests/test_gpu_shade_hit.py).
  *   mode        0 = shade_hit<ShadeParams> (the wavefront shade kernel's), 1 = <ShadeParamsLds> (the path kernel's), 2 =
- *               <RT_KParams> (cast_ray_lane's, the lightmap)
+ *               <RT_KParams> (cast_ray_lane's, the lightmap); 0 or 1 + RT_TEST_SHARED_TAPS as for rt_test_shade
  *   max_bounces what the step's exhaustion rule compares with
  *   tri[n]      triangle slot of the hit; hit = 3 floats per item: t, u, v; ray = 6: origin, direction; carry = 6: tint, emission;
  *               state_in[n] the RNG state, bounce_in[n] the bounce count before the step

@@ -819,7 +819,13 @@ __device__ __forceinline__ rt_v3 tex_bilinear(const PT &P, int tex, float tx, fl
 // caller (Pow24InLds<PT>): only a kernel that fills the table may.
 static __shared__ float rt_pow24_lds[8];
 template <class PT> struct Pow24InLds { static constexpr bool value = false; };
-__device__ __forceinline__ void pow24_lds_init(int tid) {        // before a __syncthreads() of the kernel
+// SharedTaps<PT>: shade() computes tex_taps() ONCE for a material's four textures.  tex_taps() reads width, height and stride of
+// a descriptor and the texture coordinates, nothing else, and the four textures are sampled at the same coordinates: where every
+// texture a material names has the same three numbers, the four results are the same six values.  Whether that holds for every
+// material of the resident scene is decided by the host (rt_materials_share_taps, rt_residency.cpp); only a launch on such a scene
+// may ask for it, through the parameter struct as above.
+template <class PT> struct SharedTaps { static constexpr bool value = false; };
+__device__ __forceinline__ void pow24_lds_init(int tid) {      // before a __syncthreads() of the kernel
   const float scales[8] = RT_POW24_SCALES;
   if (tid < 8) {
     float v = 0.0f;
@@ -1042,8 +1048,28 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
   const bool ha = tex_albedo >= 0 && !dbg, hn = tex_normal >= 0, hm = tex_mr >= 0 && !dbg, he = tex_em >= 0 && !dbg;
   TexTaps tn, ta, tm, te;
   TexQuad qn, qa, qm, qe;
-  if (hn) { tn = tex_taps(D[1], in.uvx, in.uvy); qn = tex_fetch(P.texels + D[1].offset, tn); }
-  if (ha) { ta = tex_taps(D[0], in.uvx, in.uvy); qa = tex_fetch(P.texels + D[0].offset, ta); }
+  if (SharedTaps<PT>::value) {
+    // one set of taps, from the dimensions of the first texture the material names in the order normal, albedo, metal-roughness,
+    // emission (every one it names has the same three: SharedTaps).  Selects on the three fields, not an index into D[]: a
+    // runtime index puts the array into scratch.
+    RT_DTexture S;
+    S.offset = 0;
+    S.width = D[3].width; S.height = D[3].height; S.stride = D[3].stride;
+    if (tex_mr >= 0)     { S.width = D[2].width; S.height = D[2].height; S.stride = D[2].stride; }
+    if (tex_albedo >= 0) { S.width = D[0].width; S.height = D[0].height; S.stride = D[0].stride; }
+    if (tex_normal >= 0) { S.width = D[1].width; S.height = D[1].height; S.stride = D[1].stride; }
+    // (unconditionally: a material without a texture gets taps of a 0 x 0 image that nothing fetches with -- behind a test for
+    // "any texture" the 16-wave instance spills 36 VGPRs instead of 24, profiles/r14_shade_taps.md)
+    tn = tex_taps(S, in.uvx, in.uvy);
+    ta = tm = te = tn;
+    if (hn) qn = tex_fetch(P.texels + D[1].offset, tn);
+    if (ha) qa = tex_fetch(P.texels + D[0].offset, ta);
+    // (the other two stay behind the debug material's return: all sixteen loads in one batch here measured 0.13 ms SLOWER per
+    // launch of the default frame than two batches of eight, profiles/r14_shade_taps.md)
+  } else {
+    if (hn) { tn = tex_taps(D[1], in.uvx, in.uvy); qn = tex_fetch(P.texels + D[1].offset, tn); }
+    if (ha) { ta = tex_taps(D[0], in.uvx, in.uvy); qa = tex_fetch(P.texels + D[0].offset, ta); }
+  }
 
   rt_v3 normal = normal_map(hn, hn ? tex_combine(qn, tn) : rt_v3_make(0, 0, 0), m2.x, in);
   terminate = false;
@@ -1058,8 +1084,13 @@ __device__ __forceinline__ void shade(const PT &P, int mat, const ShadeIn &in, u
 
   if (tex_albedo >= 0 || tex_normal >= 0 || tex_mr >= 0 || tex_em >= 0) cn.textured += 1;
 
-  if (hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
-  if (he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
+  if (SharedTaps<PT>::value) {
+    if (hm) qm = tex_fetch(P.texels + D[2].offset, tm);
+    if (he) qe = tex_fetch(P.texels + D[3].offset, te);
+  } else {
+    if (hm) { tm = tex_taps(D[2], in.uvx, in.uvy); qm = tex_fetch(P.texels + D[2].offset, tm); }
+    if (he) { te = tex_taps(D[3], in.uvx, in.uvy); qe = tex_fetch(P.texels + D[3].offset, te); }
+  }
   rt_v3 base_color = rt_v3_make(m0.x, m0.y, m0.z);
   if (ha) base_color = rt_v3_mul(base_color, srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_combine(qa, ta)));
 
@@ -1942,6 +1973,15 @@ __device__ __forceinline__ void shade_params(SPT &SP, const ARGS A, const bool w
 
 struct ShadeParamsLds : ShadeParams {};      // ... of a kernel that keeps the sRGB scale table in LDS (pow24_lds_init)
 template <> struct Pow24InLds<ShadeParamsLds> { static constexpr bool value = RT_MATH_POW24 != 0; };
+
+// ... of a launch on a scene whose materials' textures agree in size (RT_KParams.shared_taps): one set of bilinear taps per hit
+struct ShadeParamsShared : ShadeParams {};
+struct ShadeParamsLdsShared : ShadeParamsLds {};
+template <> struct SharedTaps<ShadeParamsShared> { static constexpr bool value = true; };
+template <> struct SharedTaps<ShadeParamsLdsShared> { static constexpr bool value = true; };
+template <> struct Pow24InLds<ShadeParamsLdsShared> { static constexpr bool value = RT_MATH_POW24 != 0; };
+template <bool SHARED_TAPS> struct PathShadeParams { typedef ShadeParamsLds type; };      // the path kernel's, by its template argument
+template <> struct PathShadeParams<true> { typedef ShadeParamsLdsShared type; };
 
 struct PrimaryParams {          // what primary_ray reads
   float cam[3][4];

@@ -112,7 +112,9 @@ typedef struct {
   uint32_t seed;
   int32_t chunks_x, n_chunks;
   int32_t rank, world, n_local_chunks;
-  int32_t unused_pad[3];       /* no kernel reads these (work items of retired kernels): they keep the offsets below; zero */
+  int32_t shared_taps;         /* host only, no kernel reads it: 1 = launch the path-kernel instance that computes one set of bilinear
+                                * taps per hit -- every material's textures agree in width, height and stride (rt_residency.cpp) */
+  int32_t unused_pad[2];       /* no kernel reads these (work items of retired kernels): they keep the offsets below; zero */
   int32_t sched_thresh;        /* lanes waiting for shade / environment / regeneration that trigger that block */
   int32_t n_lds_nodes;         /* BVH nodes [0, n) are also in the workgroup's LDS   */
   /* outputs */

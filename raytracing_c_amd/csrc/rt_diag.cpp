@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/rt_math.h"      // rt_dot3: the texture coordinates a hit interpolates, as the device computes them
+#include "../../include/rt_hip_diag.h"
 
 #ifndef RT_DIAG_VARIANTS
 #error rt_diag.cpp belongs to the diagnostic library only (-DRT_DIAG_VARIANTS)
@@ -471,7 +472,10 @@ static bool all_finite(f32 const *v, size_t n) {
 extern "C" int rt_test_shade(RT_Device_Scene *d, i32 mode, i32 n, i32 const *tri, f32 const *in, u32 const *state_in, f32 *out,
                              u32 *state_out, i32 *terminate, i32 *textured) {
   if (!d || n <= 0 || !tri || !in || !state_in || !out || !state_out || !terminate || !textured) return rt_fail("rt_test_shade: bad arguments");
-  if (mode != 0 && mode != 1) return rt_fail("rt_test_shade: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds)", mode);
+  if ((mode & ~RT_TEST_SHARED_TAPS) != 0 && (mode & ~RT_TEST_SHARED_TAPS) != 1)
+    return rt_fail("rt_test_shade: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds), with or without RT_TEST_SHARED_TAPS", mode);
+  if ((mode & RT_TEST_SHARED_TAPS) && !rt_materials_share_taps(d->mats_host.data(), d->n_materials))
+    return rt_fail("rt_test_shade: RT_TEST_SHARED_TAPS on a scene with a material whose textures differ in size");
   for (i32 i = 0; i < n; i++) {
     if (tri[i] < 0 || tri[i] >= d->n_triangles) return rt_fail("rt_test_shade: item %d names triangle slot %d of %d", i, tri[i], d->n_triangles);
     // texture coordinates index texels: finite only (a NaN converts to an index differently on the two sides)
@@ -529,7 +533,10 @@ static int check_hit_items(const char *who, RT_Device_Scene *d, const std::vecto
 extern "C" int rt_test_shade_hit(RT_Device_Scene *d, i32 mode, i32 max_bounces, i32 n, i32 const *tri, f32 const *hit, f32 const *ray,
                                  f32 const *carry, u32 const *state_in, i32 const *bounce_in, f32 *out, u32 *out_words) {
   if (!d || n <= 0 || !tri || !hit || !ray || !carry || !state_in || !bounce_in || !out || !out_words) return rt_fail("rt_test_shade_hit: bad arguments");
-  if (mode < 0 || mode > 2) return rt_fail("rt_test_shade_hit: mode %d is not 0 (ShadeParams), 1 (ShadeParamsLds) or 2 (RT_KParams)", mode);
+  if ((mode < 0 || mode > 2) && mode != (0 | RT_TEST_SHARED_TAPS) && mode != (1 | RT_TEST_SHARED_TAPS))
+    return rt_fail("rt_test_shade_hit: mode %d is not 0 (ShadeParams), 1 (ShadeParamsLds) or 2 (RT_KParams), nor one of the first two with RT_TEST_SHARED_TAPS", mode);
+  if ((mode & RT_TEST_SHARED_TAPS) && !rt_materials_share_taps(d->mats_host.data(), d->n_materials))
+    return rt_fail("rt_test_shade_hit: RT_TEST_SHARED_TAPS on a scene with a material whose textures differ in size");
   Device &D = *d->dev;
   std::lock_guard<std::mutex> lock(D.mutex);
   DeviceGuard guard(D);

@@ -434,6 +434,10 @@ struct RT_Device_Scene {
   int64_t      bytes = 0;
   float        max_edge = 0.0f;   // largest |component| of an edge b - a, c - a in the leaf tiles (NaN if one is NaN)
   bool         boxes_ordered = true;      // every child box of every node has min <= max on every axis (no NaN either)
+  // the material table as uploaded and patched since (rt_scene_touch), and what it says about the textures: every material's agree
+  // in width, height and stride (rt_materials_share_taps) and one names a texture -> the path kernel's shared-taps instance
+  std::vector<float> mats_host;
+  bool         shared_taps = false;
   // what the host Scene looked like at upload: the per-frame stamp (scene_stamp) re-reads exactly this much of it
   uint64_t     stamp = 0;
   std::vector<const void *> mat_ptrs;     // distinct shader.data pointers, upload order

@@ -62,7 +62,7 @@ __global__ void rt_ledger_reduce_kernel(unsigned long long *counters) {
 }
 #endif
 
-template <int WAVES, bool LDSN, int MIN_WAVES_PER_SIMD, bool SHORT_DIV, bool VIEWS>
+template <int WAVES, bool LDSN, int MIN_WAVES_PER_SIMD, bool SHORT_DIV, bool VIEWS, bool SHARED_TAPS>
 __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel_stream(RT_KParams P) {
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
         rt_v3 radiance = rt_v3_make(0, 0, 0);
         rt_v3 org = ray.o, dir = ray.d;
         RT_KArgs A = cold_args();
-        ShadeParamsLds SP;
+        typename PathShadeParams<SHARED_TAPS>::type SP;      // (SHARED_TAPS: one set of bilinear taps per hit, rt_dev.hip.h)
         shade_params(SP, A, true);
         // ---- environment for the paths that left the scene ----
 #ifdef RT_LEDGER
@@ -889,10 +889,10 @@ extern "C" int rt_launch_prepare(int n_tiles, uint32_t *tile_next, uint32_t *ope
 // ---------------------------------------------------------------------------------
 // launchers (called from rt_launch.cpp, rt_residency.cpp, rt_extras.cpp)
 
-template <int WAVES, bool LDSN, int MINW, bool SHORT_DIV, bool VIEWS>
+template <int WAVES, bool LDSN, int MINW, bool SHORT_DIV, bool VIEWS, bool SHARED_TAPS>
 static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipStream_t stream) {
   static uint32_t attr_devices = 0;
-  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>), &attr_devices,
+  if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS, SHARED_TAPS>), &attr_devices,
                                smem_bytes, RT_LDS_BYTES - RT_LDS_TABLE_BYTES))      // (the kernel has the sRGB scale table)
     return rc;
 #ifdef RT_LEDGER
@@ -904,7 +904,7 @@ static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipSt
     if (e != hipSuccess) return (int)e;
   }
 #endif
-  hipLaunchKernelGGL((rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS>), dim3((n_waves + WAVES - 1) / WAVES),
+  hipLaunchKernelGGL((rt_path_kernel_stream<WAVES, LDSN, MINW, SHORT_DIV, VIEWS, SHARED_TAPS>), dim3((n_waves + WAVES - 1) / WAVES),
                      dim3(WAVES * 64), smem_bytes, stream, *P);
 #ifdef RT_LEDGER
   hipLaunchKernelGGL(rt_ledger_reduce_kernel, dim3(1), dim3(RT_LEDGER_ROW), 0, stream, P->counters);
@@ -914,23 +914,27 @@ static int launch_stream(const RT_KParams *P, int n_waves, int smem_bytes, hipSt
 
 extern "C" int rt_math_contract(void) { return RT_MATH_CONTRACT; }      // include/rt_math.h: 2 = explicit FMA, 1 = -DRT_MATH_NO_FMA
 
-template <bool VIEWS>
+template <bool VIEWS, bool SHARED_TAPS>
 static int launch_stream_wg(const RT_KParams *P, int n_waves, int smem_bytes, int wg_waves, hipStream_t stream) {
   if (wg_waves == 8)
-    return P->short_div ? launch_stream<8, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<8, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
+    return P->short_div ? launch_stream<8, true, 1, true, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<8, true, 1, false, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream);
   if (wg_waves == 12)
-    return P->short_div ? launch_stream<12, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                        : launch_stream<12, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
-  return P->short_div ? launch_stream<16, true, 1, true, VIEWS>(P, n_waves, smem_bytes, stream)
-                      : launch_stream<16, true, 1, false, VIEWS>(P, n_waves, smem_bytes, stream);
+    return P->short_div ? launch_stream<12, true, 1, true, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream)
+                        : launch_stream<12, true, 1, false, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream);
+  return P->short_div ? launch_stream<16, true, 1, true, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream)
+                      : launch_stream<16, true, 1, false, VIEWS, SHARED_TAPS>(P, n_waves, smem_bytes, stream);
 }
 
 // `wg_waves` = waves per workgroup, 8 / 12 / 16 (one workgroup per CU: 2 / 3 / 4 waves per SIMD), chosen by rt_launch.cpp from the
 // size of the launch; the same kernel source, three instances of its launch geometry.
 extern "C" int rt_launch_path_kernel(const RT_KParams *P, int n_waves, int smem_bytes, int wg_waves, hipStream_t stream) {
-  if (P->n_views > 0) return launch_stream_wg<true>(P, n_waves, smem_bytes, wg_waves, stream);      // one launch, K views
-  return launch_stream_wg<false>(P, n_waves, smem_bytes, wg_waves, stream);
+  // (shared_taps: the host found every material's textures of one size, rt_launch.cpp -- the instance with one set of taps per hit)
+  if (P->n_views > 0)                                                                                // one launch, K views
+    return P->shared_taps ? launch_stream_wg<true, true>(P, n_waves, smem_bytes, wg_waves, stream)
+                          : launch_stream_wg<true, false>(P, n_waves, smem_bytes, wg_waves, stream);
+  return P->shared_taps ? launch_stream_wg<false, true>(P, n_waves, smem_bytes, wg_waves, stream)
+                        : launch_stream_wg<false, false>(P, n_waves, smem_bytes, wg_waves, stream);
 }
 
 extern "C" int rt_launch_resolve(int width, int height, int samples, int chunks_x, const int32_t *local_chunks,

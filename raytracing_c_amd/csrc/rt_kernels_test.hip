@@ -590,21 +590,28 @@ extern "C" int rt_launch_test_texture(const RT_KParams *P, int tex, int n, const
   return (int)hipGetLastError();
 }
 
-// lds: 0 = ShadeParams, 1 = ShadeParamsLds (the instance of the path kernel)
-extern "C" int rt_launch_test_shade(const RT_KParams *P, int lds, int n, const int *tri, const float *in, const uint32_t *state_in,
+// mode: 0 = ShadeParams, 1 = ShadeParamsLds (the instance of the path kernel); + RT_TEST_SHARED_TAPS (4): the same two with one set
+// of bilinear taps per item (ShadeParamsShared, ShadeParamsLdsShared) -- the caller has checked that the scene's materials qualify
+extern "C" int rt_launch_test_shade(const RT_KParams *P, int mode, int n, const int *tri, const float *in, const uint32_t *state_in,
                                     float *out, uint32_t *state_out, int *terminate, int *textured, hipStream_t stream) {
   const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
-  if (lds) hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+  const int lds = mode & 1;
+  if (mode & 4) {
+    if (lds) hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsLdsShared>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+    else hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsShared>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
+  } else if (lds) hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
   else hipLaunchKernelGGL(rt_test_shade_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, in, state_in, out, state_out, terminate, textured);
   return (int)hipGetLastError();
 }
 
-// mode: 0 = ShadeParams, 1 = ShadeParamsLds, 2 = RT_KParams
+// mode: 0 = ShadeParams, 1 = ShadeParamsLds, 2 = RT_KParams; 4, 5 = the first two with shared taps (see rt_launch_test_shade)
 extern "C" int rt_launch_test_shade_hit(const RT_KParams *P, int mode, int n, const int *tri, const float *hit, const float *ray,
                                         const float *carry, const uint32_t *state_in, const int *bounce_in, float *out, uint32_t *iout,
                                         hipStream_t stream) {
   const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
-  if (mode == 0) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  if (mode == 4) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParamsShared>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  else if (mode == 5) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParamsLdsShared>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
+  else if (mode == 0) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParams>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
   else if (mode == 1) hipLaunchKernelGGL(rt_test_shade_hit_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
   else hipLaunchKernelGGL(rt_test_shade_hit_kparams_kernel, grid, block, 0, stream, *P, n, tri, hit, ray, carry, state_in, bounce_in, out, iout);
   return (int)hipGetLastError();

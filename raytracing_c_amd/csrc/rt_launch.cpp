@@ -2,6 +2,8 @@
 
 #include "rt_host.h"
 
+static std::atomic<int> g_taps_form{-1};      // rt_get_shade_taps_form(): the texture stage of the last path-kernel launch
+
 int check_params(RT_Render_Params const *p) {
   if (!p) return rt_fail("render params are NULL");
   if (p->width <= 0 || p->height <= 0) return rt_fail("image size %dx%d is invalid", p->width, p->height);
@@ -277,6 +279,9 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
       }
   K.short_div = (d->max_edge <= 0x1p38f && cam_max <= 0x1p16f) ? 1 : 0;
   if (knob_int("RT_SHORT_DIV", 1) == 0) K.short_div = 0;
+  // The shade block with one set of bilinear taps per hit (SharedTaps, rt_dev.hip.h): where every material's textures agree in
+  // width, height and stride -- a property of the resident copy, kept current by rt_residency.cpp.  Same frames.
+  K.shared_taps = (d->shared_taps && knob_int("RT_SHARED_TAPS", 1) != 0) ? 1 : 0;
   // hits parked until a dense shade block can be made of them: RT_PARK_RECORD_DWORDS = 18 fields x 128 records per wave
   K.park = nullptr;
   if (!wavefront && knob_int("RT_PARK", 1) != 0 && K.max_bounces < (1 << 26)) {      // (a parked record keeps the bounce count in 26 bits)
@@ -323,6 +328,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   {
     int rc = rt_launch_path_kernel(&K, n_waves, smem, wg_waves, stream);
     if (rc != 0) return rt_fail("path kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    g_taps_form.store(K.shared_taps);
   }
   HIP_TRY(hipEventRecord(D.ws.ev1[slot], stream));
   D.ws.n_timed += 1;
@@ -464,6 +470,9 @@ extern "C" int rt_get_leafless_paths(u64 *out) { return get_counter("rt_get_leaf
 // rounds (rt_kernels.hip): every NaN-free ray that the sky / leafless loop does not serve, when the root has at most four populated
 // children.
 extern "C" int rt_get_fused_root_visits(u64 *out) { return get_counter("rt_get_fused_root_visits", RT_CNT_FUSED_ROOT, out); }
+
+// The texture stage of the last path-kernel launch: 1 = shared taps, 0 = general, -1 = none yet (include/rt_hip.h).
+extern "C" int rt_get_shade_taps_form(void) { return g_taps_form.load(); }
 
 int read_counters(Device &D, unsigned long long c[RT_N_COUNTERS]) {
   HIP_TRY(hipDeviceSynchronize());

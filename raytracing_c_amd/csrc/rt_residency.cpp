@@ -327,6 +327,39 @@ static void build_material_row(const PBR_Shader_Data *d, int ta, int tn, int tm,
   }
 }
 
+// May a shade block compute ONE set of bilinear taps for a material's four textures (SharedTaps, rt_dev.hip.h)?  Yes when, in
+// every one of the n packed material rows (RT_MAT_FLOATS floats each, rt_device.h), all the textures the row names -- slot index
+// >= 0 -- have the same width, height and stride in the descriptors embedded in the row.  A material with no texture or one
+// agrees with itself; so does an empty table.  Conservative: one mixed material and the whole scene renders with the general form.
+extern "C" int rt_materials_share_taps(const float *mats, i32 n_materials) {
+  if (!mats || n_materials <= 0) return 1;
+  for (i32 m = 0; m < n_materials; m++) {
+    int32_t w[RT_MAT_FLOATS];
+    memcpy(w, mats + (size_t)m * RT_MAT_FLOATS, sizeof w);
+    int first = -1;
+    for (int k = 0; k < 4; k++) {
+      if (w[12 + k] < 0) continue;
+      if (first < 0) { first = k; continue; }
+      for (int f = 1; f < 4; f++)                                        // width, height, stride; not the offset
+        if (w[20 + 4 * k + f] != w[20 + 4 * first + f]) return 0;
+    }
+  }
+  return 1;
+}
+
+// ... of the copy's material table as it is now; and whether any material names a texture at all (a scene without one has no taps
+// to share and keeps the general instance).  After every write to d->mats_host.
+static void refresh_shared_taps(RT_Device_Scene *d) {
+  bool any = false;
+  for (size_t m = 0; m < d->mats_host.size() / RT_MAT_FLOATS && !any; m++)
+    for (int k = 0; k < 4; k++) {
+      int32_t t;
+      memcpy(&t, &d->mats_host[m * RT_MAT_FLOATS + 12 + k], 4);
+      if (t >= 0) any = true;
+    }
+  d->shared_taps = any && rt_materials_share_taps(d->mats_host.data(), (i32)(d->mats_host.size() / RT_MAT_FLOATS)) != 0;
+}
+
 bool node_boxes_ordered(const float *nodes, size_t n_nodes) {
   for (size_t nd = 0; nd < n_nodes; nd++)
     for (int k = 0; k < 24; k++)
@@ -456,6 +489,8 @@ static RT_Device_Scene *upload_scene_locked(Device &D, Scene const *scene) {
   d->max_edge = max_edge;
   d->boxes_ordered = boxes_ordered;
   d->n_materials = (int32_t)(mats.size() / RT_MAT_FLOATS);
+  d->mats_host = mats;
+  refresh_shared_taps(d);
   d->n_textures = (int32_t)pool.descs.size();
   d->mat_ptrs = mat_ptrs;
   d->mat_first_tri = mat_first_tri;
@@ -649,8 +684,10 @@ static int touch_device_scene(RT_Device_Scene *d, Scene const *scene, const void
       float row[RT_MAT_FLOATS];
       build_material_row(m, ta, tn, tm, te, (int)(kv.first & 1u), d->tex_descs, row);
       HIP_TRY(hipMemcpy(d->mats + (size_t)kv.second * RT_MAT_FLOATS, row, sizeof row, hipMemcpyHostToDevice));
+      memcpy(&d->mats_host[(size_t)kv.second * RT_MAT_FLOATS], row, sizeof row);
       any = true;
     }
+    if (any) refresh_shared_taps(d);      // the material may name other textures of the pool now: the next launch picks its instance anew
     return any ? 1 : 0;
   }
   // texels of a texture (or of the background): the touched rows are packed again

@@ -207,6 +207,9 @@ def _declare(d):
         d.rt_get_leafless_paths.argtypes = [P(C.c_uint64)]
     if hasattr(d, "rt_get_fused_root_visits"):
         d.rt_get_fused_root_visits.argtypes = [P(C.c_uint64)]
+    if hasattr(d, "rt_get_shade_taps_form"):               # (absent from older builds loaded as A/B partners)
+        d.rt_get_shade_taps_form.argtypes = []
+        d.rt_materials_share_taps.argtypes = [vp, C.c_int32]
     d.rt_math_contract.restype = C.c_int
     d.rt_last_kernel_ms.restype = C.c_float
     d.rt_kernel_timing_reset.restype = None

@@ -16,7 +16,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = os.environ.get("RT_LEDGER_KERNEL", "_Z21rt_path_kernel_streamILi16ELb1ELi1ELb1ELb0EEv10RT_KParams")
+KERNEL = os.environ.get("RT_LEDGER_KERNEL", "_Z21rt_path_kernel_streamILi16ELb1ELi1ELb1ELb0ELb1EEv10RT_KParams")      # (the last Lb: 1 = shared taps, 0 = general)
 
 
 def kernel_asm(path=None):
