@@ -791,6 +791,84 @@ extern int rt_render_upsampled(Scene const *scene, Image const *image, isize sam
                                RT_Upsample_Params const *upsample_params, RT_Guided_Params const *guided_params, f32 *linear_low,
                                f32 *linear_upsampled, f32 *linear_out);
 
+/* ---- adaptive sampling: chunks double their samples until the error settles ------------------ */
+
+/* The one stage that decides WHERE samples go: sky and flat surfaces stop early, glossy edges go on.  The scheme is Dammertz et
+ * al. 2010, "A hierarchical automatic stopping condition for Monte Carlo methods", restricted to the 32x32 chunks of the frame and
+ * to doubling: a chunk that holds n samples per pixel in `accum` receives samples [n, 2n) into a second buffer `fresh`; the two
+ * buffers are independent halves of equal size, their difference estimates the chunk's error and their sum is the chunk's
+ * 2n-sample frame; a chunk whose error is at or under a threshold stops, the others double again, up to a cap.  One launch of the
+ * path kernel per round over a shrinking chunk list; the path kernel is what it was (it finds its pixels through a chunk table),
+ * and since a path's seed depends on (frame seed, pixel, sample) alone and the sums are order-free, a chunk that ends with n_c
+ * samples holds the sums rt_render_frame(samples = n_c) gives its pixels, bit for bit.  Two kernels of their own
+ * (rt_adaptive_merge_kernel, rt_resolve_adaptive_kernel, csrc/rt_adaptive.hip); every other entry point returns what it returned.
+ *
+ * A CHUNK LIST: a HOST array of n_list >= 0 global chunk indices (chunk c = cx + cy * ceil(width / 32)), every one in
+ * [0, rt_chunk_count(width, height)), strictly ascending (a duplicate would add a chunk twice).  Checked on the host before the
+ * device is touched -- a wrong index would be a write outside the caller's buffers -- and copied to the device before the call
+ * returns: the caller may reuse the array at once.  Calls that take a list serve ONE stream at a time.
+ *
+ * rt_render_accumulate_chunks(): rt_render_accumulate() with the caller's list in place of the partition's: rank 0 of world 1 only.
+ * Chunks not listed are neither read nor written; n_list == 0 enqueues the launch's preparation and renders nothing.  These launches
+ * have a launch state of their own, run their tiles in list order and keep no schedule feedback: ordinary frames, before and
+ * after, are scheduled as if the call had not been made.  rt_get_counters() afterwards describes this launch.
+ *
+ * THE MERGE.  rt_accum_resolve (rt_math.h), then f32 + - / and sqrt, every operation rounded on its own (no fused multiply-add),
+ * evaluated as written; the chunk's sum in integers: a numpy restatement is equal bit for bit (tests/_adaptive.py).  For every pixel
+ * of a listed chunk that lies inside the image, n = the samples each buffer holds per pixel:
+ *     a_c = min(rt_accum_resolve(accum_c, n), 1.0f),  b_c = min(rt_accum_resolve(fresh_c, n), 1.0f)     per channel c = r, g, b
+ *       (the output stage clamps at 1: error above that is invisible)
+ *     d = (|a_r - b_r| + |a_g - b_g|) + |a_b - b_b|
+ *     m = ((a_r + b_r) + (a_g + b_g)) + (a_b + b_b)
+ *     e = d / rt_sqrtf(m + 1e-4f)
+ *     q = (u64)(e * 4294967296.0f)      (e <= 300: the product is exact, the conversion truncates)
+ *     accum_c = accum_c + fresh_c in u64;  fresh_c = 0
+ *   err[chunk] = the sum of the chunk's q, in u64 (stored, not added: no need to clear err).
+ * rt_adaptive_merge(): d_accum, d_fresh u64[height][width][3], d_err u64[rt_chunk_count(width, height)] on the primary device;
+ * chunks not listed, and their err entries, are neither read nor written.  Only enqueues work on `stream`.
+ *
+ * rt_resolve_adaptive(): rt_resolve() for rank 0 of 1 with the divisor read per chunk: d_chunk_samples i32[rt_chunk_count(width,
+ * height)] on the device, every entry >= 1 (the library cannot check device memory).  Outputs, each optional, at least one:
+ * d_image u8[height][width][3], d_linear f32[height][width][3], d_sample_map i32[height][width] -- every pixel's divisor, what a
+ * viewer or a later variance-aware stage reads.  Only enqueues work on `stream`.
+ * Checked before the GPU is touched, by all three: NULL pointers, the image size, the list, n >= 1, no output. */
+extern int rt_render_accumulate_chunks(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_list, i32 const *chunks,
+                                       void *d_accum, void *stream);
+extern int rt_adaptive_merge(i32 width, i32 height, i32 n, i32 n_list, i32 const *chunks, void *d_accum, void *d_fresh, void *d_err,
+                             void *stream);
+extern int rt_resolve_adaptive(i32 width, i32 height, void const *d_chunk_samples, void const *d_accum, void *d_image, void *d_linear,
+                               void *d_sample_map, void *stream);
+
+typedef struct {
+  i32 min_samples;   /* first launch: samples [0, min) of every pixel; >= 1                                */
+  i32 max_samples;   /* cap; min_samples * 2^k, k >= 1                                                     */
+  f32 threshold;     /* a chunk stops when its mean per-pixel error <= threshold; finite, >= 0             */
+  i32 reserved;      /* 0 */
+} RT_Adaptive_Params;                                                                            /* 16 bytes */
+
+/* An adaptive frame in one call, from host memory to host memory like rt_render_frame() (its scene check, device lock, seed,
+ * camera and Image layout rules; pixels.data may be NULL when another output is given):
+ *   1. samples [0, min_samples) of every chunk;
+ *   2. rounds with n = min_samples, 2 min_samples, ...: samples [n, 2n) of the active chunks into `fresh`, THE MERGE, the errors
+ *      copied to the host (one synchronisation per round); in double, err_c = err[c] / 2^32 / (pixels of chunk c inside the
+ *      image); chunk c stays active iff err_c > (double)threshold && 2n < max_samples;
+ *   3. when no chunk is active: rt_resolve_adaptive and the copies out.
+ * Every chunk ends with 2 min_samples .. max_samples samples, a power-of-two multiple of min_samples.  linear (optional)
+ * f32[height][width][3], accum (optional) u64[height][width][3] as rt_render_frame() returns them; chunk_samples (optional)
+ * i32[rt_chunk_count(width, height)] = n_c.  What is needed by every frame -- step 1 and the first round -- is enqueued before the
+ * full content check of the host scene, which runs while the GPU traces them.
+ * Afterwards rt_get_counters() is the SUM over the frame's launches (paths = the sum over the chunks of pixels inside the image x
+ * n_c); rt_get_skipped_root_visits(), rt_get_leafless_paths(), rt_get_fused_root_visits() and the kernel timing describe single
+ * launches, the LAST one where they describe one.  rt_get_frame_timing(): gpu_prep = the clears and the first preparation, gpu_path
+ * = from there to the end of the last merge, the host's decisions between the rounds included.  Every launch ends with the tail
+ * rt_frame_begin() describes: a frame of up to 1 + log2(max_samples / min_samples) launches pays it that often.
+ * Refused before the GPU is touched: NULL scene, image or params, min_samples < 1, max_samples not min_samples * 2^k with k >= 1,
+ * a threshold that is negative, infinite or NaN, reserved != 0, the image's size and layout, max_bounces < 0, no output.  One device
+ * only: with rt_device_count() > 1 the call fails.  Not done: view batches, the wavefront pipeline, an adaptive frame in front of
+ * the post passes, granularity finer than a chunk, the next list built on the device, schedule costs carried across rounds. */
+extern int rt_render_adaptive(Scene const *scene, Image const *image, RT_Adaptive_Params const *ap, isize max_bounces, f32 *linear,
+                              u64 *accum, i32 *chunk_samples);
+
 /* Counters of the last rt_render_accumulate / rt_render_frame on this process
  * (read back synchronously; summed over the devices of a multi-device frame). */
 extern int rt_get_counters(RT_Counters *out);

@@ -15,3 +15,4 @@ from .guided import guided_denoise, render_denoised   # noqa: F401
 from .temporal import temporal_accumulate, render_temporal, History   # noqa: F401
 from .variance import temporal_accumulate_moments, guided_denoise_variance, render_svgf   # noqa: F401
 from .upsample import guided_upsample, render_upsampled   # noqa: F401
+from .adaptive import render_adaptive, render_accumulate_chunks, adaptive_merge, resolve_adaptive   # noqa: F401

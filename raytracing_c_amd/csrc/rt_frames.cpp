@@ -1,6 +1,9 @@
-// rt_frames.cpp -- the one-device frame sequence, blocking frames, frames in flight, frame timing, completion protocol.
+// rt_frames.cpp -- the one-device frame sequence, blocking frames, frames in flight, frame timing, completion protocol, the adaptive
+// frame and its two device-level calls.
 
 #include "rt_host.h"
+
+#include <cmath>
 
 void forget_multi_counters() {
   std::lock_guard<std::mutex> lk(g_multi_mutex);
@@ -284,4 +287,208 @@ extern "C" bool rendering_context_is_finished(Rendering_Context *context) {
 
 extern "C" void rendering_context_finish(Rendering_Context *context) {
   while (__atomic_load_n(&context->n_threads, __ATOMIC_SEQ_CST) > 0) std::this_thread::yield();
+}
+
+// ---------------------------------------------------------------------------------
+// adaptive sampling (include/rt_hip.h): the merge of two equal halves of a chunk's samples and the per-chunk resolve on the device
+// level, and the blocking frame whose chunks double their samples until their error settles (rt_render_adaptive): one launch of the
+// path kernel per round over a shrinking chunk list (rt_launch.cpp: a launch with the caller's chunk table).
+
+// ---- the device level -------------------------------------------------------------------------------------------------------------
+
+// The merge of `list` on `stream`, the list staged through D.adaptive.merge_list.  D.mutex held, D's GPU current, list checked.
+static int enqueue_merge(Device &D, i32 width, i32 height, i32 n, ChunkList const &list, void *d_accum, void *d_fresh, void *d_err,
+                         hipStream_t stream) {
+  const int32_t *d_list = nullptr;
+  if (stage_chunk_list(D.adaptive.merge_list, list, stream, &d_list) != 0) return -1;
+  int rc = rt_launch_adaptive_merge(width, height, n, list.n, d_list, (unsigned long long *)d_accum, (unsigned long long *)d_fresh,
+                                    (unsigned long long *)d_err, stream);
+  if (rc != 0) return rt_fail("adaptive merge kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rt_adaptive_merge(i32 width, i32 height, i32 n, i32 n_list, i32 const *chunks, void *d_accum, void *d_fresh, void *d_err,
+                                 void *stream) {
+  const char *who = "rt_adaptive_merge";
+  if (check_image_size(who, width, height) != 0) return -1;
+  if (n < 1) return rt_fail("%s: n must be >= 1, the samples each buffer holds per pixel (got %d)", who, n);
+  if (check_chunk_list(who, width, height, n_list, chunks) != 0) return -1;
+  if (!d_accum) return rt_fail("%s: d_accum is NULL", who);
+  if (!d_fresh) return rt_fail("%s: d_fresh is NULL", who);
+  if (!d_err) return rt_fail("%s: d_err is NULL", who);
+  if (d_accum == d_fresh) return rt_fail("%s: d_accum and d_fresh are one buffer", who);
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  DeviceGuard guard(D);
+  ChunkList list;
+  list.n = n_list;
+  list.chunks = chunks;
+  return enqueue_merge(D, width, height, n, list, d_accum, d_fresh, d_err, (hipStream_t)stream);
+}
+
+extern "C" int rt_resolve_adaptive(i32 width, i32 height, void const *d_chunk_samples, void const *d_accum, void *d_image, void *d_linear,
+                                   void *d_sample_map, void *stream) {
+  const char *who = "rt_resolve_adaptive";
+  if (check_image_size(who, width, height) != 0) return -1;
+  if (!d_chunk_samples) return rt_fail("%s: d_chunk_samples is NULL", who);
+  if (!d_accum) return rt_fail("%s: d_accum is NULL", who);
+  if (!d_image && !d_linear && !d_sample_map) return rt_fail("%s: no output is wanted (no d_image, no d_linear, no d_sample_map)", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  DeviceGuard guard(D);
+  int rc = rt_launch_resolve_adaptive(width, height, (const int32_t *)d_chunk_samples, (const unsigned long long *)d_accum,
+                                      (uint8_t *)d_image, (float *)d_linear, (int32_t *)d_sample_map, (hipStream_t)stream);
+  if (rc != 0) return rt_fail("adaptive resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- the frame --------------------------------------------------------------------------------------------------------------------
+
+static int check_adaptive(const char *who, RT_Adaptive_Params const *ap) {
+  if (!ap) return rt_fail("%s: adaptive params are NULL", who);
+  if (ap->min_samples < 1) return rt_fail("%s: min_samples must be >= 1 (got %d)", who, ap->min_samples);
+  bool doubled = false;
+  for (int64_t m = (int64_t)ap->min_samples * 2; m <= (int64_t)0x7fffffff; m *= 2)
+    if (m == ap->max_samples) doubled = true;
+  if (!doubled)
+    return rt_fail("%s: max_samples must be min_samples * 2^k with k >= 1 (got %d and min_samples %d)", who, ap->max_samples, ap->min_samples);
+  if (!(ap->threshold >= 0.0f) || std::isinf(ap->threshold))
+    return rt_fail("%s: threshold must be finite and >= 0 (got %g)", who, (double)ap->threshold);
+  if (ap->reserved != 0) return rt_fail("%s: reserved must be 0 (got %d)", who, ap->reserved);
+  return 0;
+}
+
+// The host's decision after a round (rt_hip.h): the chunk's mean per-pixel error, in double, over its pixels inside the image.
+static double chunk_error(unsigned long long sum, i32 width, i32 height, i32 chunk) {
+  const int chunks_x = (width + RT_CHUNK_SIZE - 1) / RT_CHUNK_SIZE;
+  const int x0 = (chunk % chunks_x) * RT_CHUNK_SIZE, y0 = (chunk / chunks_x) * RT_CHUNK_SIZE;
+  const int w = width - x0 < RT_CHUNK_SIZE ? width - x0 : RT_CHUNK_SIZE, h = height - y0 < RT_CHUNK_SIZE ? height - y0 : RT_CHUNK_SIZE;
+  return (double)sum / 4294967296.0 / (double)(w * h);
+}
+
+extern "C" int rt_render_adaptive(Scene const *scene, Image const *image, RT_Adaptive_Params const *ap, isize max_bounces, f32 *linear,
+                                  u64 *accum, i32 *chunk_samples) {
+  const char *who = "rt_render_adaptive";
+  // before the device lock: everything the arguments alone decide
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  if (!image) return rt_fail("%s: image is NULL", who);
+  if (check_adaptive(who, ap) != 0) return -1;
+  if (image->width <= 0 || image->height <= 0 || image->width > 0x7fffffff || image->height > 0x7fffffff)
+    return rt_fail("%s: image size %ldx%ld is invalid", who, (long)image->width, (long)image->height);
+  if (check_image_size(who, (i32)image->width, (i32)image->height) != 0) return -1;
+  if (check_image_layout(image, who) != 0) return -1;
+  if (max_bounces < 0 || max_bounces > 0x7fffffff) return rt_fail("%s: max_bounces must be >= 0 and fit 32 bits (got %ld)", who, (long)max_bounces);
+  if (!image->pixels.data && !linear && !accum && !chunk_samples)
+    return rt_fail("%s: no output is wanted (no pixels, no linear, no accum, no chunk_samples)", who);
+
+  Device &D = dev0();
+  std::lock_guard<std::mutex> lock(D.mutex);
+  const double t_start = now_ms();
+  if (ensure_device(D) != 0) return -1;
+  if (rt_device_count() > 1)
+    return rt_fail("%s: an adaptive frame renders on one device, and %d are set (rt_set_devices)", who, rt_device_count());
+  RT_Render_Params p;      // (samples: the cap -- every launch traces a sample range inside [0, max_samples))
+  if (fill_frame_params(&p, image, ap->max_samples, max_bounces, g_seed.load()) != 0) return -1;
+  forget_multi_counters();
+
+  FrameTiming T;
+  Workspace &W = D.ws;
+  AdaptiveState &A = D.adaptive;
+  const i32 width = p.width, height = p.height, n_chunks = rt_chunk_count(width, height);
+  const size_t pixels = (size_t)width * height;
+  if (ensure_ws_buffers(W, width, height, 0, 0, linear != nullptr) != 0) return -1;
+  HIP_TRY(A.fresh.grow(pixels * 3));
+  HIP_TRY(A.err.grow((size_t)n_chunks));
+  HIP_TRY(A.err_host.grow((size_t)n_chunks));
+  HIP_TRY(A.chunk_samples.grow((size_t)n_chunks));
+  HIP_TRY(A.counters_host.grow((size_t)RT_ADAPTIVE_MAX_LAUNCHES * RT_N_COUNTERS));
+
+  hipStream_t stream = nullptr;
+  std::vector<i32> active, counts((size_t)n_chunks, 0);
+  int n_launches = 0;
+  // one launch of the path kernel over the active chunks, samples [first, first + count) into `dst`; its counters go to the host
+  // behind it (the next launch's preparation clears them)
+  auto launch = [&](RT_Device_Scene *d, i32 first, i32 count, void *dst, hipEvent_t ev_prep) -> int {
+    if (n_launches >= RT_ADAPTIVE_MAX_LAUNCHES) return rt_fail("%s: more than %d launches", who, RT_ADAPTIVE_MAX_LAUNCHES);
+    RT_Render_Params q = p;
+    q.sample_first = first;
+    q.sample_count = count;
+    ChunkList list;
+    list.n = (int)active.size();
+    list.chunks = active.data();
+    if (render_accumulate_locked(D, d, &scene->camera, &q, dst, stream, ev_prep, RT_ADAPTIVE_STATE, nullptr, &list) != 0) return -1;
+    HIP_TRY(hipMemcpyAsync(A.counters_host + (size_t)n_launches * RT_N_COUNTERS, d->ls[RT_ADAPTIVE_STATE].counters,
+                           RT_N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    n_launches++;
+    return 0;
+  };
+  // a round: the active chunks hold n samples; samples [n, 2n) into `fresh`, the merge, the errors on their way to the host
+  auto round = [&](RT_Device_Scene *d, i32 n) -> int {
+    if (launch(d, n, n, A.fresh, nullptr) != 0) return -1;
+    ChunkList list;
+    list.n = (int)active.size();
+    list.chunks = active.data();
+    if (enqueue_merge(D, width, height, n, list, W.accum, A.fresh, A.err, stream) != 0) return -1;
+    HIP_TRY(hipMemcpyAsync(A.err_host, A.err, (size_t)n_chunks * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(W.ev_frame[2], stream));
+    return 0;
+  };
+  // what every frame needs -- samples [0, min) and the first round, over all chunks -- is enqueued inside the scene-checked call:
+  // the full content check of the host scene runs while the GPU traces them (a scene edited since the copy: all of it once more)
+  auto begin = [&](RT_Device_Scene *d) -> int {
+    n_launches = 0;
+    active.resize((size_t)n_chunks);
+    for (i32 c = 0; c < n_chunks; c++) active[(size_t)c] = c;
+    HIP_TRY(hipEventRecord(W.ev_frame[0], stream));
+    HIP_TRY(hipMemsetAsync(W.accum, 0, pixels * 3 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(A.fresh, 0, pixels * 3 * sizeof(unsigned long long), stream));      // (once: the merge re-zeroes what it consumed)
+    if (launch(d, 0, ap->min_samples, W.accum, W.ev_frame[1]) != 0) return -1;
+    return round(d, ap->min_samples);
+  };
+  RT_Device_Scene *d = scene_checked(D, scene, stream, &T, begin);
+  if (!d) return -1;
+
+  for (i32 n = ap->min_samples;; n *= 2) {
+    HIP_TRY(hipStreamSynchronize(stream));            // the round's errors are on the host
+    std::vector<i32> next;
+    for (i32 c : active) {
+      counts[(size_t)c] = 2 * n;
+      if (chunk_error(A.err_host[c], width, height, c) > (double)ap->threshold && (int64_t)2 * n < ap->max_samples) next.push_back(c);
+    }
+    active.swap(next);
+    if (active.empty()) break;
+    if (round(d, 2 * n) != 0) return -1;
+  }
+
+  HIP_TRY(hipMemcpyAsync(A.chunk_samples, counts.data(), (size_t)n_chunks * sizeof(i32), hipMemcpyHostToDevice, stream));
+  {
+    int rc = rt_launch_resolve_adaptive(width, height, A.chunk_samples, W.accum, W.image, linear ? W.linear.get() : nullptr, nullptr, stream);
+    if (rc != 0) return rt_fail("adaptive resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  }
+  HIP_TRY(hipEventRecord(W.ev_frame[3], stream));
+  if (copy_image_out(image, W.image, width, height, stream) != 0) return -1;
+  HIP_TRY(hipEventRecord(W.ev_frame[4], stream));
+  if (linear) HIP_TRY(hipMemcpy(linear, W.linear, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (accum) HIP_TRY(hipMemcpy(accum, W.accum, pixels * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (finish_frame(D, W, stream, T, t_start) != 0) return -1;
+  if (chunk_samples) memcpy(chunk_samples, counts.data(), (size_t)n_chunks * sizeof(i32));
+
+  // rt_get_counters(): the sum over the frame's launches, kept where a multi-device frame keeps its sum
+  unsigned long long c[RT_N_COUNTERS] = {};
+  for (int l = 0; l < n_launches; l++)
+    for (int k = 0; k < RT_N_COUNTERS; k++) c[k] += A.counters_host[(size_t)l * RT_N_COUNTERS + k];
+  std::lock_guard<std::mutex> lk(g_multi_mutex);
+  g_multi_counters.paths = c[RT_CNT_PATHS];
+  g_multi_counters.rays = c[RT_CNT_RAYS];
+  g_multi_counters.node_visits = c[RT_CNT_NODES];
+  g_multi_counters.leaf_visits = c[RT_CNT_LEAVES];
+  g_multi_counters.shades = c[RT_CNT_SHADES];
+  g_multi_counters.backgrounds = c[RT_CNT_BG];
+  g_multi_counters.textured = c[RT_CNT_TEXTURED];
+  g_multi_counters_valid = true;
+  return 0;
 }

@@ -7,7 +7,9 @@
 //   rt_launch.cpp     launch set-up (fill_kparams, render_accumulate_locked), the LDS split and the camera / frame fields every
 //                     kernel on traversal_blocks() is launched with (lds_split, camera_frame_kparams), resolve / untile, workspace
 //                     buffers, counters, kernel timing
-//   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers
+//   rt_frames.cpp     the one-device frame sequence, blocking frames, frame lanes (rt_frame_begin / rt_frame_end), completion helpers;
+//                     adaptive sampling: the merge and the per-chunk resolve on the device level, the frame whose chunks double their
+//                     samples until their error settles (rt_render_adaptive)
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
 //   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
 //   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter), temporal accumulation (the
@@ -115,6 +117,11 @@ int rt_launch_moments_unpack(int n_pixels, const void *mom, float *planar, hipSt
 // ... in rt_upsample.hip (c0, g0, g1: the low frame as rt_launch_guided_pack packs it; full: the full-resolution planes, no colour)
 int rt_launch_upsample(int width, int height, float k_n, float k_p, int demodulate, const void *c0, const void *g0, const void *g1,
                        RT_Frame full, float *out, uint8_t *image, hipStream_t stream);
+// ... in rt_adaptive.hip (chunks: n_list global chunk indices on the device, every one inside the image's chunk grid)
+int rt_launch_adaptive_merge(int width, int height, int samples, int n_list, const int32_t *chunks, unsigned long long *accum,
+                             unsigned long long *fresh, unsigned long long *err, hipStream_t stream);
+int rt_launch_resolve_adaptive(int width, int height, const int32_t *chunk_samples, const unsigned long long *accum, uint8_t *image,
+                               float *linear, int32_t *sample_map, hipStream_t stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -185,11 +192,19 @@ struct FrameTiming {          // the most recent frame through render_thread_pro
 #endif
 #define RT_LAUNCH_STATES (1 + RT_FRAME_LANES)
 #define RT_VIEWS_STATE   RT_LAUNCH_STATES        // the launch state of view batches (rt_render_views, rt_render_accumulate_views)
+#define RT_ADAPTIVE_STATE (RT_VIEWS_STATE + 1)   // the launch state of chunk-list launches (rt_render_accumulate_chunks, rt_render_adaptive)
 
 // K views of one frame (rt_render_views): one launch, the tiles of every view in one work queue.
 struct ViewBatch {
   int            n = 0;
   RT_View const *views = nullptr;
+};
+
+// The chunks of one launch, chosen by the caller (rt_render_accumulate_chunks): a HOST array of global chunk indices that
+// check_chunk_list() has passed.
+struct ChunkList {
+  int        n = 0;
+  i32 const *chunks = nullptr;
 };
 
 // (hidden, here and at LaunchState: the structs made of owners have destructors and move assignments now, and none of them joins
@@ -332,6 +347,28 @@ struct RefitState {
   DevMem<uint32_t> max_edge_bits;             // one word
 };
 
+// A chunk list on its way to the device: the pinned copy is rewritten only once the copy queued from it is done (as the view table
+// of a batch is, rt_launch.cpp).
+struct ChunkListStage {
+  DevMem<int32_t>    dev;
+  PinnedMem<int32_t> host;
+  DevEvent           copied;                  // recorded after the list's copy: `host` may be rewritten once it completed
+};
+
+// Adaptive sampling (rt_frames.cpp): the chunk list of rt_adaptive_merge, and what rt_render_adaptive keeps between calls -- the
+// second sum buffer, the chunks' errors and sample counts, the sample map, the counters of the frame's launches -- given back with
+// the device slot (release_staging).
+struct AdaptiveState {
+  ChunkListStage                merge_list;
+  DevMem<unsigned long long>    fresh;        // [pixels][3]
+  DevMem<unsigned long long>    err;          // [chunks]
+  PinnedMem<unsigned long long> err_host;     // [chunks]
+  DevMem<int32_t>               chunk_samples;   // [chunks]
+  DevMem<int32_t>               sample_map;   // [pixels]
+  PinnedMem<unsigned long long> counters_host;   // [RT_ADAPTIVE_MAX_LAUNCHES][RT_N_COUNTERS]
+};
+#define RT_ADAPTIVE_MAX_LAUNCHES 32           // the first launch and at most 30 doublings of min_samples >= 1 within 2^31
+
 #pragma GCC visibility pop
 
 struct Device {
@@ -354,6 +391,7 @@ struct Device {
   RefitState refit;
   TemporalState temporal;
   UpsampleState upsample;
+  AdaptiveState adaptive;
 };
 
 // rt_history_create's object.  Guarded by slot 0's mutex like the staging it belongs to.
@@ -416,6 +454,8 @@ struct LaunchState {
   DevMem<RT_KView>    views;
   PinnedMem<RT_KView> views_host;
   DevEvent            views_copied;            // recorded after the table's copy: views_host may be rewritten once it completed
+  // chunk-list launches ([RT_ADAPTIVE_STATE] only): the device copy of the caller's list
+  ChunkListStage      list;
 };
 
 #pragma GCC visibility pop
@@ -450,11 +490,12 @@ struct RT_Device_Scene {
   std::unordered_map<uint64_t, int> mat_map;            // (shader.data, kind) -> material id
   std::vector<const Image *>        tex_sources;        // Image of texture k (pool order; the background is one of them)
   std::vector<RT_DTexture>          tex_descs;          // its slot in the texel pool
-  // launch state: RT_LAUNCH_STATES + 1 of them, so that launches of ONE device scene can be in flight on several streams at once
+  // launch state: RT_LAUNCH_STATES + 2 of them, so that launches of ONE device scene can be in flight on several streams at once
   // ([0]: the blocking entry points and rt_render_accumulate; [1 + k]: frame lane k of rt_frame_begin / rt_frame_end;
   // [RT_VIEWS_STATE]: view batches -- their tile list is K times as long, and a state of their own keeps the schedule feedback
-  // of single frames and of batches from replacing each other)
-  LaunchState ls[RT_LAUNCH_STATES + 1];
+  // of single frames and of batches from replacing each other; [RT_ADAPTIVE_STATE]: chunk-list launches -- their tile list has
+  // another length every time, they run in identity order and keep no schedule feedback at all)
+  LaunchState ls[RT_LAUNCH_STATES + 2];
   // wavefront pipeline (rt_wavefront.hip): record queues between the camera / shade / trace kernels
   DevMem<uint32_t>    wf_hit0, wf_hit, wf_ray[2];
   DevMem<uint32_t>    wf_cnt;                  // records per chunk: hit0 | hit | ray[0] | ray[1]
@@ -524,6 +565,12 @@ int  device_owner_table(Device &D, int width, int height, int world, const int32
 int check_params(RT_Render_Params const *p);
 int check_image_size(const char *who, i32 width, i32 height);                       // `who`: not positive / more than RT_MAX_PIXELS
 int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const char *who);   // the batch's sizes; no device needed
+// A caller's chunk list for a width x height image: n_list >= 0, a list when n_list > 0, every index in [0, rt_chunk_count), strictly
+// ascending.  No device needed.
+int check_chunk_list(const char *who, i32 width, i32 height, i32 n_list, i32 const *chunks);
+// The list's device copy, enqueued on `stream` through S's pinned copy; *d_list stays valid for what is enqueued behind it on that
+// stream.  The owning device's mutex held, its GPU current.
+int stage_chunk_list(ChunkListStage &S, ChunkList const &list, hipStream_t stream, const int32_t **d_list);
 // How a workgroup's LDS is split (rt_device.h): as many leading BVH nodes as fit beside `wg_waves` perm stacks of `depth` levels and
 // `wave_extra_bytes` more per wave, when `wgs_per_cu` workgroups share a CU and -- `static_table` -- the kernel's sRGB table takes
 // RT_LDS_TABLE_BYTES of it (launches that never counted the table say false).  No node when a child box has min > max (the LDS
@@ -537,10 +584,11 @@ void camera_rows(float dst[3][4], Camera const *cam);                           
 void camera_frame_kparams(RT_KParams *K, Camera const *cam, RT_Render_Params const *p);   // the camera and frame fields of K
 // Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
 // ev_prep (optional): recorded between the per-launch preparation and the path kernel.  batch (optional): K views in one launch
-// (cam and p->seed are ignored; d_accum holds K images).
+// (cam and p->seed are ignored; d_accum holds K images).  list (optional, launch state RT_ADAPTIVE_STATE, rank 0 of 1, no batch): the
+// launch renders the list's chunks in place of the partition's, in identity order, and keeps no schedule feedback.
 int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
                              hipStream_t stream, hipEvent_t ev_prep = nullptr, int launch_state = 0,
-                             ViewBatch const *batch = nullptr);
+                             ViewBatch const *batch = nullptr, ChunkList const *list = nullptr);
 int resolve_on(Device &D, RT_Render_Params const *p, void const *d_accum, void *d_tiles, void *d_image, void *d_linear,
                hipStream_t stream);                                                 // D's GPU current
 int untile_on(Device &D, i32 width, i32 height, i32 world, void const *d_all_tiles, void *d_image, hipStream_t stream);   // D's GPU current

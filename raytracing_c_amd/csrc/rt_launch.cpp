@@ -34,6 +34,20 @@ int check_views(i32 n_views, RT_View const *views, i32 width, i32 height, const 
   return 0;
 }
 
+int check_chunk_list(const char *who, i32 width, i32 height, i32 n_list, i32 const *chunks) {
+  if (n_list < 0) return rt_fail("%s: n_list must be >= 0 (got %d)", who, n_list);
+  if (n_list > 0 && !chunks) return rt_fail("%s: chunks is NULL", who);
+  const i32 n_chunks = rt_chunk_count(width, height);
+  for (i32 k = 0; k < n_list; k++) {
+    if (chunks[k] < 0 || chunks[k] >= n_chunks)
+      return rt_fail("%s: chunks[%d] = %d is outside [0, %d), the chunks of a %dx%d image", who, k, chunks[k], n_chunks, width, height);
+    if (k > 0 && chunks[k] <= chunks[k - 1])
+      return rt_fail("%s: chunks[%d] = %d after chunks[%d] = %d: the list must be strictly ascending", who, k, chunks[k], k - 1,
+                     chunks[k - 1]);
+  }
+  return 0;
+}
+
 // The size limit of one launch, unchanged since a launch was cut into (tile x block of samples) items counted in 32 bits: blocks
 // of p->slab samples, or by default the largest of 32 / 16 / 8 that leaves 24 items per wave of a full grid.  No kernel counts
 // such items any more, but the limit still decides which launches are refused: check_params / check_views bound pixels and
@@ -86,7 +100,7 @@ LdsSplit lds_split(const RT_Device_Scene *d, int depth, int wg_waves, int wave_e
 
 // Scene, camera, frame, partition and sample range of the launch; what depends on the launch state comes later.
 static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p,
-                        void *d_accum, ViewBatch const *batch) {
+                        void *d_accum, ViewBatch const *batch, ChunkList const *list) {
   const int nv = batch ? batch->n : 1;
   if (batch) cam = &batch->views[0].camera;      // (the kernel reads every view's camera from the view table)
   scene_only_kparams(K, d);
@@ -96,7 +110,10 @@ static int fill_kparams(Device &D, RT_KParams *K, RT_Device_Scene *d, Camera con
   K->n_chunks = rt_chunk_count(p->width, p->height);
   K->rank = p->rank;
   K->world = p->world;
-  {
+  if (list) {
+    K->local_chunks = nullptr;       // (the caller's table: staged once the launch state is known)
+    K->n_local_chunks = list->n;
+  } else {
     int n_local = 0;
     if (device_chunk_list(D, p->width, p->height, p->rank, p->world, &K->local_chunks, &n_local) != 0) return -1;
     K->n_local_chunks = n_local;
@@ -197,19 +214,40 @@ static int upload_view_table(LaunchState &L, RT_KParams &K, ViewBatch const *bat
   return 0;
 }
 
+// ---- a chunk list: like the view table, through a pinned copy that is rewritten only once the previous list's copy is done ----
+int stage_chunk_list(ChunkListStage &S, ChunkList const &list, hipStream_t stream, const int32_t **d_list) {
+  if (!S.copied) HIP_TRY(S.copied.ensure(hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(S.copied));
+  // (a list that outgrows the device copy frees it: what was queued from the old block must be done first)
+  if (S.dev && S.dev.cap < (size_t)list.n) HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(S.dev.grow((size_t)list.n));
+  HIP_TRY(S.host.grow((size_t)list.n));
+  if (list.n > 0) {
+    memcpy(S.host.get(), list.chunks, (size_t)list.n * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(S.dev, S.host, (size_t)list.n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(S.copied, stream));
+  }
+  *d_list = S.dev;
+  return 0;
+}
+
 // Enqueues one launch of the path tracer for p's rank / sample range.  D.mutex held, D's GPU current.
 // ev_prep (optional): recorded between the per-launch preparation and the path kernel.
 int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_accum,
-                             hipStream_t stream, hipEvent_t ev_prep, int launch_state, ViewBatch const *batch) {
+                             hipStream_t stream, hipEvent_t ev_prep, int launch_state, ViewBatch const *batch, ChunkList const *list) {
   if (ensure_device(D) != 0) return -1;
   if (check_params(p) != 0) return -1;
   if (!d || !d_accum) return rt_fail("rt_render_accumulate: NULL scene or accumulation buffer");
   if (d->dev != &D) return rt_fail("rt_render_accumulate: the scene was uploaded to another device");
   if (batch && check_views(batch->n, batch->views, p->width, p->height, "view batch") != 0) return -1;
+  if (list && (batch || launch_state != RT_ADAPTIVE_STATE || p->rank != 0 || p->world != 1 ||
+               check_chunk_list("chunk list", p->width, p->height, list->n, list->chunks) != 0))
+    return rt_fail("rt_render_accumulate: a chunk list needs rank 0 of 1, no view batch, its own launch state and a valid list");
   const int nv = batch ? batch->n : 1;
   RT_KParams K;
-  if (fill_kparams(D, &K, d, cam, p, d_accum, batch) != 0) return -1;
-  if (launch_state < 0 || launch_state > RT_VIEWS_STATE) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
+  if (fill_kparams(D, &K, d, cam, p, d_accum, batch, list) != 0) return -1;
+  if (launch_state < 0 || launch_state > RT_ADAPTIVE_STATE) return rt_fail("rt_render_accumulate: launch state %d out of range", launch_state);
+  if (!list && launch_state == RT_ADAPTIVE_STATE) return rt_fail("rt_render_accumulate: launch state %d serves chunk lists only", launch_state);
   LaunchState &L = d->ls[launch_state];
   HIP_TRY(L.counters.grow(RT_N_COUNTERS));
   HIP_TRY(L.work_head.grow(16));
@@ -232,8 +270,12 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   K.drain_thresh = knob_int("RT_DRAIN_THRESH", K.sched_thresh);
   if (K.drain_thresh < 1 || K.drain_thresh > 64) K.drain_thresh = K.sched_thresh;
 
+  // (a chunk list: identity order and no costs -- the list has another length every time, and schedule_feedback gives its buffers
+  //  back whenever the number of tiles changes)
   const uint32_t *cost_prev = nullptr;
-  if (schedule_feedback(L, K, &cost_prev) != 0) return -1;
+  K.order = nullptr;
+  K.tile_cost = nullptr;
+  if (!list && schedule_feedback(L, K, &cost_prev) != 0) return -1;
 
   // unit = 2 neighbouring pixels x `slab` samples, default 64 (128 paths, pixel-major: the 64 lanes of a wave sit on one
   // pixel, then on its neighbour); it is also the granularity at which waves share a tile at the end of a launch.
@@ -245,11 +287,13 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
   K.chunk_shift = cshift;
   K.n_sample_blocks = (n_samples + (1 << cshift) - 1) >> cshift;
   K.n_chunks_tile = 32 * K.n_sample_blocks;          // units: 8 rows x sample blocks x 4 pixel pairs
-  if (L.tile_next_n < K.n_tiles) {
+  // (a chunk list: sized once for every chunk of the image, whatever the list's length)
+  const int tiles_room = list ? K.n_chunks * 16 : K.n_tiles;
+  if (L.tile_next_n < tiles_room) {
     L.tile_next_n = 0;
     // [n_tiles] chunk counters, then [ceil(n_tiles / 64)] open-tile counts of the groups
-    HIP_TRY(L.tile_next.grow((size_t)K.n_tiles + (size_t)((K.n_tiles + 63) / 64)));
-    L.tile_next_n = K.n_tiles;
+    HIP_TRY(L.tile_next.grow((size_t)tiles_room + (size_t)((tiles_room + 63) / 64)));
+    L.tile_next_n = tiles_room;
   }
   K.tile_next = L.tile_next;
   K.open_groups = L.tile_next + L.tile_next_n;
@@ -293,6 +337,7 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
 
   K.views = nullptr;
   if (batch && upload_view_table(L, K, batch, stream) != 0) return -1;
+  if (list && stage_chunk_list(L.list, *list, stream, &K.local_chunks) != 0) return -1;
 
   // ---- ONE preparation launch: counters, work head, tile / unit counters, this launch's cost buffer, tile order ----
   {
@@ -353,6 +398,28 @@ extern "C" int rt_render_accumulate(RT_Device_Scene *dscene, RT_Render_Params co
   if (it == D.cameras.end()) return rt_fail("rt_render_accumulate: no camera set for this scene (rt_set_camera)");
   forget_multi_counters();             // rt_get_counters() now means THIS launch, not an older multi-device frame
   return render_accumulate_locked(D, dscene, &it->second, params, d_accum, (hipStream_t)stream);
+}
+
+// rt_render_accumulate with the caller's chunk table (rt_hip.h).  Everything that can be checked without the device is checked
+// before dscene is read: a wrong index would be a write outside the accumulation buffer.
+extern "C" int rt_render_accumulate_chunks(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_list, i32 const *chunks,
+                                           void *d_accum, void *stream) {
+  const char *who = "rt_render_accumulate_chunks";
+  if (!dscene || !d_accum) return rt_fail("%s: NULL scene or accumulation buffer", who);
+  if (check_params(params) != 0) return -1;
+  if (params->world != 1 || params->rank != 0)
+    return rt_fail("%s: a chunk list replaces the partition: rank 0 of world 1 only (got %d of %d)", who, params->rank, params->world);
+  if (check_chunk_list(who, params->width, params->height, n_list, chunks) != 0) return -1;
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  auto it = D.cameras.find(dscene);
+  if (it == D.cameras.end()) return rt_fail("%s: no camera set for this scene (rt_set_camera)", who);
+  forget_multi_counters();
+  ChunkList list;
+  list.n = n_list;
+  list.chunks = chunks;
+  return render_accumulate_locked(D, dscene, &it->second, params, d_accum, (hipStream_t)stream, nullptr, RT_ADAPTIVE_STATE, nullptr, &list);
 }
 
 extern "C" int rt_render_accumulate_views(RT_Device_Scene *dscene, RT_Render_Params const *params, i32 n_views,

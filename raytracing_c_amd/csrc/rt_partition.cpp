@@ -83,6 +83,7 @@ void release_staging(Device &D) {
   D.guided = GuidedState();
   D.refit = RefitState();
   D.upsample = UpsampleState();
+  D.adaptive = AdaptiveState();
   release_temporal_state(D);                    // (also empties every live RT_History; the list of them stays)
 }
 

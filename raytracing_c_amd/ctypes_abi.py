@@ -195,6 +195,13 @@ assert C.sizeof(RT_Upsample_Params) == 16
 RT_UPSAMPLE_WORK_PER_LOW_PIXEL = 48   # three float4 records per pixel of the (w / 2) x (h / 2) frame
 
 
+class RT_Adaptive_Params(C.Structure):  # rt_hip.h: the adaptive frame's parameters
+    _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("threshold", f32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(RT_Adaptive_Params) == 16
+
+
 # numpy views of RT_Ray_Hit[] / RT_Device_Hit[] / Hit[]
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<i4"), ("u", "<f4"), ("v", "<f4")])
 _HIT_HEAD = [("distance", "<f4"), ("normal", "<f4", (3,)), ("normal_geo", "<f4", (3,)), ("point", "<f4", (3,)),
@@ -246,6 +253,7 @@ EXPORTED_SYMBOLS = [
     "rt_temporal_accumulate_motion", "rt_temporal_accumulate_motion_host",
     "rt_guided_variance_work_bytes", "rt_guided_denoise_variance", "rt_guided_denoise_variance_host", "rt_render_svgf",
     "rt_guided_upsample_work_bytes", "rt_guided_upsample", "rt_guided_upsample_host", "rt_render_upsampled",
+    "rt_render_accumulate_chunks", "rt_adaptive_merge", "rt_resolve_adaptive", "rt_render_adaptive",
     "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_fused_root_visits", "rt_get_shade_taps_form", "rt_materials_share_taps", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 

@@ -187,6 +187,11 @@ def _declare(d):
                                               P(abi.RT_Features), vp, vp]
         d.rt_render_upsampled.argtypes = [P(abi.Scene), P(abi.Image), abi.isize, abi.isize, P(abi.RT_Upsample_Params),
                                           P(abi.RT_Guided_Params), vp, vp, vp]
+    if hasattr(d, "rt_render_adaptive"):                   # (absent from older builds loaded as A/B partners)
+        d.rt_render_accumulate_chunks.argtypes = [vp, P(abi.RT_Render_Params), C.c_int32, vp, vp, vp]
+        d.rt_adaptive_merge.argtypes = [C.c_int32] * 4 + [vp] * 5
+        d.rt_resolve_adaptive.argtypes = [C.c_int32, C.c_int32] + [vp] * 6
+        d.rt_render_adaptive.argtypes = [P(abi.Scene), P(abi.Image), P(abi.RT_Adaptive_Params), abi.isize, vp, vp, vp]
     if hasattr(d, "rt_scene_keep_geometry"):               # (absent from older builds loaded as A/B partners)
         d.rt_device_scene_keep_geometry.argtypes = [vp, vp]
         d.rt_scene_keep_geometry.argtypes = [P(abi.Scene)]
