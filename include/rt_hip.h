@@ -877,9 +877,14 @@ extern int rt_get_counters(RT_Counters *out);
  * finds no candidate for any of them; the kernel proves that per tile and skips the block).  The oracle counts them too. */
 extern int rt_get_skipped_root_visits(u64 *out);
 /* Camera paths of the last rt_render_accumulate launch (single device) that the path kernel's leafless loop served: paths of 8x8
- * tiles whose pixel pyramid, pruned through the tree from the root, reaches no leaf group.  Their node visits ARE executed (and
+ * tiles whose pixel pyramid, pruned through the tree from the root, reaches no leaf group, or only groups none of whose
+ * triangles it can touch (rt_get_triangleless_paths() counts the latter).  Their node visits ARE executed (and
  * are not among the skipped root visits); what they skip is the traversal state machine.  For tests and profile notes. */
 extern int rt_get_leafless_paths(u64 *out);
+/* Of rt_get_leafless_paths(): the camera paths of TRIANGLE-LESS tiles, whose pyramid does reach leaf groups, but every triangle of
+ * every reached group lies outside it (an all-zero padding slot counts as outside).  Their leaf visits are counted like their node
+ * visits: one per group whose box the ray enters.  Paths of tiles that reach no leaf group are not among them. */
+extern int rt_get_triangleless_paths(u64 *out);
 /* Rays of the last rt_render_accumulate launch (single device) whose root visit the path kernel ran at the top of a traversal call,
  * in front of the traversal rounds, over the populated children of the root only (at most four of them; a root with more, a tree of
  * depth 0 and rays that are not NaN-free take the node block as before: 0 for such a frame).  The visits are executed and counted;

@@ -1309,7 +1309,7 @@ __device__ __forceinline__ void lds_load_nodes(float4 *smem, const float *nodes,
 // A wave's slice of the kernels that render tiles (path kernel, wavefront camera and trace kernels): the perm stack, one row of 64
 // words per tree level (at least one), then the 8x8-pixel accumulator tile, 3 x u64 per pixel.  The perm row of the deepest node
 // level is never written (a leaf-level node has no node below it): it is the PYRAMID AREA, the RT_PYR_* words below.  Row 0 is free
-// while no lane of the wave traverses: the tile set-up keeps the node list of a leafless tile there (RT_LL_*, rt_tile.hip.h).
+// while no lane of the wave traverses: the tile set-up keeps the list of a leafless or triangle-less tile there, all 64 words (RT_LL_*, rt_tile.hip.h).
 #define RT_LDS_PERM_LEVEL_F4 (RT_LDS_PERM_LEVEL_BYTES / 16)
 #define RT_LDS_ACC_TILE_F4   (RT_LDS_ACC_TILE_BYTES / 16)
 struct WaveLds {
@@ -1562,7 +1562,9 @@ __device__ __forceinline__ uint32_t node_enter_few(const Ray3 &r, const float4 *
 // of the distance are there for that; that they suffice is NOT proved, it rests on the frames of tests/test_gpu_pyramid.py
 // (ratios up to 1e4, bit for bit).  (Vertices b, c are a + (b - a), a + (c - a) here, an ulp off the reference's: the `coarse`
 // term of the margin covers a thousand of those.)
-__device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const float *pyr, int g) {
+// PADDING (leafless_walk): *padding = the 8-bit mask of the group's all-zero triangles, from the same nine floats.
+template <bool PADDING = false>
+__device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const float *pyr, int g, uint32_t *padding = nullptr) {
   const int lane = lane_now();
   const float *tb = leaves + (size_t)g * 72 + (lane & 7);
   const float *pl = pyr + RT_PYR_PLANE + ((lane >> 3) & 3) * 4;
@@ -1583,6 +1585,10 @@ __device__ __forceinline__ uint32_t pyramid_cull_tris(const float *leaves, const
     outside = outside && (val - band > 1e-3f * extent + 1e-6f * coarse);              // (NaN compares false: not outside)
   }
   const uint32_t m = (uint32_t)__ballot(outside);                                     // lanes 0..31: 4 planes x 8 triangles
+  if (PADDING) {
+    const bool zero = ax == 0.0f && e1x == 0.0f && e2x == 0.0f && ay == 0.0f && e1y == 0.0f && e2y == 0.0f && az == 0.0f && e1z == 0.0f && e2z == 0.0f;
+    *padding = (uint32_t)__ballot(zero) & 0xFFu;                                      // (lanes 0..7: one per triangle)
+  }
   return (m | (m >> 8) | (m >> 16) | (m >> 24)) & 0xFFu;
 }
 

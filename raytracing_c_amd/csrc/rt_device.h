@@ -45,8 +45,9 @@ enum {
   RT_CNT_PATHS = 0, RT_CNT_RAYS, RT_CNT_NODES, RT_CNT_LEAVES, RT_CNT_SHADES, RT_CNT_BG, RT_CNT_TEXTURED,
   RT_CNT_SKIPPED_ROOT,         /* of RT_CNT_NODES: root visits of camera paths whose tile's pyramid misses the root -- counted, not executed */
   RT_CNT_LEDGER,               /* .. + RT_CNT_LEDGER_SLOTS: the block ledger of the path kernel (-DRT_LEDGER builds, LG_* slots in rt_dev.hip.h) */
-  RT_CNT_LEAFLESS = 136,       /* camera paths served by the leafless loop (rt_kernels.hip) */
+  RT_CNT_LEAFLESS = 136,       /* camera paths served by the leafless loop (rt_kernels.hip), those of triangle-less tiles included */
   RT_CNT_FUSED_ROOT,           /* rays whose root visit ran in front of the traversal rounds (rt_kernels.hip) */
+  RT_CNT_TRIANGLELESS,         /* of RT_CNT_LEAFLESS: paths of tiles whose pyramid reaches leaf groups, but no triangle of them */
   RT_N_COUNTERS
 };
 #define RT_CNT_LEDGER_SLOTS (RT_CNT_LEAFLESS - RT_CNT_LEDGER)

@@ -533,6 +533,9 @@ extern "C" int rt_get_skipped_root_visits(u64 *out) { return get_counter("rt_get
 // Camera paths of the last rt_render_accumulate launch that the leafless loop of the path kernel served (rt_kernels.hip).
 extern "C" int rt_get_leafless_paths(u64 *out) { return get_counter("rt_get_leafless_paths", RT_CNT_LEAFLESS, out); }
 
+// Of those: the paths of triangle-less tiles, whose pyramid reaches leaf groups but no triangle of them.
+extern "C" int rt_get_triangleless_paths(u64 *out) { return get_counter("rt_get_triangleless_paths", RT_CNT_TRIANGLELESS, out); }
+
 // Rays of the last rt_render_accumulate launch whose root visit ran at the top of a traversal call, in front of the traversal
 // rounds (rt_kernels.hip): every NaN-free ray that the sky / leafless loop does not serve, when the root has at most four populated
 // children.

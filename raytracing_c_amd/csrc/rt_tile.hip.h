@@ -5,7 +5,7 @@
 //   take_queue_tile / join_open_tile   a tile of its own from the queue, or one that still has units
 //   tile_origin                        where the tile lies in the image (and in which view)
 //   tile_pyramid                       the tile's camera-ray pyramid into the wave's LDS slice; can a camera ray touch the root's children?
-//   leafless_walk                      (path kernel) does the pyramid, pruned through the tree, reach a leaf group at all?
+//   leafless_walk                      (path kernel) does the pyramid, pruned through the tree, reach a triangle at all?
 //   grab_units / unit_decode           the tile's units, one or more per atomic, and the pixels and samples of a unit
 //   regen_paths                        the wave's idle lanes take the next paths of the tile's units
 //   flush_tile                         the wave's accumulator tile to the frame
@@ -182,42 +182,65 @@ __device__ __forceinline__ bool tile_pyramid(const CAM S, const float *nodes, fl
   return __ballot(may_hit) == 0ull;
 }
 
-// ---- does the pyramid, pruned through the tree, reach a leaf group at all? ----
+// ---- does the pyramid, pruned through the tree, reach a triangle at all? ----
 // Breadth-first from the root with the node blocks' own plane test (pyramid_cull_mask on the LDS nodes): the surviving
-// children of a listed node join the list; a surviving child that is a leaf group ends the walk.  A tile whose walk ends
-// without one is LEAFLESS: every child box that a NaN-free camera ray of the tile can enter is a listed node, none of them
-// leads to a triangle, so the ray's outcome is known -- no hit -- and only its node visits remain to be counted (the
-// leafless form of the path kernel's batch loop).  Caps: RT_LL_MAX listed nodes, 4 survivors per node (node_enter_few's
-// limit), every listed node LDS resident; a tile over a cap is an ordinary tile.
-// The list lives in row 0 of the wave's perm stack, which is free while no lane of the wave traverses (leafless_list): entry
-// i >= 1 at [RT_LL_ENTRY + i] = byte offset of (parent node, child slot) in the LDS node image | index of the parent in the list
-// << 20 | 1 << 31 (marks an entry), the node itself at [RT_LL_NODE + i].
-// Returns the number of listed nodes (the root counts), 0 for a tile that is not leafless.  levels = depth - 1 >= 1, n_nodes =
-// pyr_nodes > 0, leaf0 = last_row_offset.  Writes every visited node's mask into the (tile, node) cache of the node blocks: the
-// root visit in front of the traversal finds the root's there.
-#define RT_LL_MAX   8
+// children of a listed node join the list.  A surviving child that is a leaf group gets the leaf blocks' triangle test
+// (pyramid_cull_tris): a triangle that survives ends the walk, a group without one joins the list as a group.  A tile whose walk
+// ends without a triangle is LEAFLESS (no group listed) or TRIANGLE-LESS: every child box that a NaN-free camera ray of the tile
+// can enter is a listed node or group, no listed group holds a triangle the ray can be accepted by, so the ray's outcome is known
+// -- no hit -- and only its node and leaf visits remain to be counted (the leafless form of the path kernel's batch loop).
+// An all-zero triangle, the padding of a partly filled group of the reference's builder, counts as culled whatever the planes say
+// (the camera may stand on the origin's side of all four): its edges are zero, so det = 0, the reciprocal is infinite or NaN,
+// s . (d x e2) = 0 and u = inv_det * 0 is NaN, as is t.  No comparison with a NaN holds: tri_test_uniform and
+// leaf_test_short_div find `miss` false and then `t < best` false, leaf_test turns the NaN distance into +infinity (dist > 0 is
+// false) and `dist < best` is false.  None of the three accepts it.
+// Caps: RT_LL_MAX listed nodes and groups together, 4 survivors per node (node_enter_few's limit), every listed node -- and the
+// parent of every listed group -- LDS resident; a tile over a cap is an ordinary tile.
+// The list lives in row 0 of the wave's perm stack, which is free while no lane of the wave traverses (leafless_list) and has 64
+// words: entry i >= 1 at [RT_LL_ENTRY + i] = byte offset of (parent node, child slot) in the LDS node image | index of the parent
+// in the list << 20 (5 bits) | RT_LL_GROUP for a leaf group | 1 << 31 (marks an entry), the node or group itself, in the tree's
+// implicit numbering, at [RT_LL_NODE + i].
+// Returns the number of listed nodes and groups (the root counts), 0 for a tile that is neither.  levels = depth - 1 >= 1,
+// n_nodes = pyr_nodes > 0, leaf0 = last_row_offset, leaves = the launch's leaf groups.  Writes every visited node's mask into the
+// (tile, node) cache of the node blocks -- the root visit in front of the traversal finds the root's there -- and every tested
+// group's into the leaf blocks' (by group & 7, the later of two groups that share a slot).
+#define RT_LL_MAX   32
 #define RT_LL_ENTRY 0
 #define RT_LL_NODE  RT_LL_MAX
+#define RT_LL_GROUP 0x40000000u
+static_assert(2 * RT_LL_MAX * 4 <= RT_LDS_PERM_LEVEL_BYTES && RT_LL_MAX <= 32, "the list is one row of the perm stack, `entered` one word");
 __device__ __forceinline__ uint32_t *leafless_list(float4 *smem, const int pyr_off, const int levels) {
   return reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off) - levels * (RT_LDS_PERM_LEVEL_BYTES / 4));      // the pyramid area is row `levels`
 }
 __device__ __forceinline__ int leafless_walk(float4 *smem, const float4 *lds_nodes, const int pyr_off, const int levels, const int n_nodes,
-                                             const int leaf0) {
+                                             const int leaf0, const float *leaves) {
   const float *pyr = lds_at(smem, pyr_off);
   uint32_t *list = leafless_list(smem, pyr_off, levels);
   int n_list = 1;
   for (int head = 0; head < n_list; head++) {
     const int nd = head ? __builtin_amdgcn_readfirstlane((int)list[RT_LL_NODE + head]) : 0;
+    if (nd >= leaf0) continue;              // a listed group: nothing below it
     const uint32_t surv = 0xFFu & ~pyramid_cull_mask(lds_nodes, pyr, nd);
     if (lane_now() == 0) reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off))[RT_PYR_NODE_CACHE + (nd & 31)] = ((uint32_t)(nd + 1) << 8) | (0xFFu & ~surv);
     if (surv) {
       const int ns = (int)__popc(surv);
-      // children that are leaf groups, or nodes outside the LDS image (its last node's children at the most), or a cap
-      if (8 * nd + 1 >= leaf0 || 8 * nd + 8 >= n_nodes || ns > 4 || n_list + ns > RT_LL_MAX) return 0;
+      const bool groups = 8 * nd + 1 >= leaf0;      // the children are leaf groups
+      // children that are nodes outside the LDS image (its last node's children at the most), or a cap
+      if ((!groups && 8 * nd + 8 >= n_nodes) || ns > 4 || n_list + ns > RT_LL_MAX) return 0;
+      if (groups) {
+        for (uint32_t m = surv; m; m &= m - 1u) {
+          const int g = 8 * nd + 1 + (int)__builtin_ctz(m) - leaf0;
+          if ((uint32_t)g >= 0x800000u) return 0;   // (the leaf cache's key has 23 bits)
+          uint32_t padding = 0u;            // the group's all-zero triangles
+          const uint32_t cull = pyramid_cull_tris<true>(leaves, pyr, g, &padding);
+          if (lane_now() == 0) reinterpret_cast<uint32_t *>(lds_at(smem, pyr_off))[RT_PYR_LEAF_CACHE + (g & 7)] = ((0x800000u | (uint32_t)g) << 8) | cull;
+          if ((0xFFu & ~(cull | padding)) != 0u) return 0;      // a triangle the pyramid can touch: an ordinary tile
+        }
+      }
       const int k = lane_now();             // lane k < 8: child k
       if (k < 8 && ((surv >> k) & 1u)) {
         const int at = n_list + (int)__popc(surv & ((1u << k) - 1u));
-        list[RT_LL_ENTRY + at] = (uint32_t)(nd * RT_LDS_NODE_BYTES + k * 4) | ((uint32_t)head << 20) | 0x80000000u;
+        list[RT_LL_ENTRY + at] = (uint32_t)(nd * RT_LDS_NODE_BYTES + k * 4) | ((uint32_t)head << 20) | (groups ? RT_LL_GROUP : 0u) | 0x80000000u;
         list[RT_LL_NODE + at] = (uint32_t)(8 * nd + 1 + k);
       }
       n_list += ns;

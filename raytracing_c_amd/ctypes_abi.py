@@ -254,7 +254,7 @@ EXPORTED_SYMBOLS = [
     "rt_guided_variance_work_bytes", "rt_guided_denoise_variance", "rt_guided_denoise_variance_host", "rt_render_svgf",
     "rt_guided_upsample_work_bytes", "rt_guided_upsample", "rt_guided_upsample_host", "rt_render_upsampled",
     "rt_render_accumulate_chunks", "rt_adaptive_merge", "rt_resolve_adaptive", "rt_render_adaptive",
-    "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_fused_root_visits", "rt_get_shade_taps_form", "rt_materials_share_taps", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
+    "rt_get_counters", "rt_get_skipped_root_visits", "rt_get_leafless_paths", "rt_get_triangleless_paths", "rt_get_fused_root_visits", "rt_get_shade_taps_form", "rt_materials_share_taps", "rt_last_kernel_ms", "rt_kernel_timing_reset", "rt_kernel_timing_mean_ms",
 ]
 
 # include/rt_hip_diag.h: exported by librt_hip_diag.so only (which also exports everything above); the product library must

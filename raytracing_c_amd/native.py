@@ -210,6 +210,8 @@ def _declare(d):
         d.rt_get_skipped_root_visits.argtypes = [P(C.c_uint64)]
     if hasattr(d, "rt_get_leafless_paths"):
         d.rt_get_leafless_paths.argtypes = [P(C.c_uint64)]
+    if hasattr(d, "rt_get_triangleless_paths"):
+        d.rt_get_triangleless_paths.argtypes = [P(C.c_uint64)]
     if hasattr(d, "rt_get_fused_root_visits"):
         d.rt_get_fused_root_visits.argtypes = [P(C.c_uint64)]
     if hasattr(d, "rt_get_shade_taps_form"):               # (absent from older builds loaded as A/B partners)
