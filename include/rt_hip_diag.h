@@ -165,7 +165,12 @@ extern int rt_test_feature_hit(RT_Device_Scene *dscene, i32 n, i32 const *tri, f
 /* sample_disney() (driver.c:287-348) on raw parameters: params = 8 floats per item (roughness, metalness, sheen, sheen_tint,
  * aniso2, base colour), in_dir = 3; out_dir = 3, brdf = 4 per item (rgb and the weight-pdf; <= 0 ends the path) */
 extern int rt_test_brdf(i32 n, f32 const *params, f32 const *in_dir, u32 const *state_in, f32 *out_dir, f32 *brdf, u32 *state_out);
-/* background_lookup() (driver.c:95-104) of n finite directions (3 floats each) on the scene's environment image; mode as above */
+#define RT_TEST_BG_IMAGE 8         /* mode bit of rt_test_background */
+/* background_lookup() (driver.c:95-104) of n directions (3 floats each) on the scene's environment image.
+ *   mode      0 = <ShadeParams>, 1 = <ShadeParamsLds>, on the RGBA8 texel pool; either + RT_TEST_BG_IMAGE: background_lookup_image()
+ *             on the float copy of the background, what the path kernel's batch loop runs
+ * Any float is taken: both forms turn a coordinate that is NaN into texel 0 and a NaN colour, and no direction makes either read
+ * outside the image.  The oracle's function is a partner for finite directions only (it converts a NaN coordinate another way). */
 extern int rt_test_background(RT_Device_Scene *dscene, i32 mode, i32 n, f32 const *dir, f32 *rgb);
 /* primary_ray() (raytracer.c:641-694) of n (x, y, sample) triples of a width x height frame, with the frame constants the host
  * computes for a real frame (1 / width, 1 / height, width / height); rays = 6 floats per item: origin, direction */

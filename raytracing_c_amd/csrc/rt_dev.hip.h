@@ -880,6 +880,38 @@ __device__ __forceinline__ rt_v3 background_lookup(const PT &P, rt_v3 dir) {
   return srgb_to_linear_tex<Pow24InLds<PT>::value>(tex_bilinear<false>(P, P.bg_texture, u, v));
 }
 
+// The same lookup on the background's float image (rt_device.h: RT_KParams.bg_image, made at upload by rt_pack_bg_image_kernel),
+// for a caller whose lanes all sample THE background: the descriptor comes through the scalar cache without a ballot, the texel at
+// (u, v) is word v * pitch + u of a row-major image whose pad column and pad row stand for tex_taps' clamp to the edge (du = 0,
+// dv = 0 there: the neighbour IS the texel, and so is the pad's copy of it), and a texel holds the three products texel_rgb()
+// forms from its bytes.  Coordinates, fract, scale, truncation, upper clamps and weights are tex_taps<false>'s expressions, the
+// lerps tex_combine's in its order: every operation gets the operands it gets in background_lookup(), hence the same bits.
+struct BgTexel { float r, g, b, pad; };      // RT_BG_TEXEL_FLOATS
+template <class PT>
+__device__ __forceinline__ rt_v3 background_lookup_image(const PT &P, rt_v3 dir) {
+  const float tx = tex_wrap_fract<false>(bg_coord_u(atan2_dev(dir.z, dir.x)));
+  const float ty = tex_wrap_fract<false>(bg_coord_v(asin_dev(dir.y)));
+  typedef const RT_DTexture __attribute__((address_space(4))) CT;
+  CT *tp = (CT *)(unsigned long long)(P.textures + P.bg_texture);
+  const int width = tp->width, height = tp->height;
+  const float px = tx * (float)width;
+  const float py = ty * (float)height;
+  int u = (int)px, v = (int)py;
+  if (u > width - 1) u = width - 1;
+  if (v > height - 1) v = height - 1;
+  const float a = px - (float)u;
+  const float b = py - (float)v;
+  // (byte offsets in 32 bits, which the upload guarantees: one base in scalar registers, the neighbours at immediate offsets)
+  const uint32_t row = (uint32_t)P.bg_pitch * (uint32_t)sizeof(BgTexel);
+  const uint32_t o = (uint32_t)(v * P.bg_pitch + u) * (uint32_t)sizeof(BgTexel);
+  const char *base = reinterpret_cast<const char *>(P.bg_image);
+  const BgTexel *r0 = reinterpret_cast<const BgTexel *>(base + o), *r1 = reinterpret_cast<const BgTexel *>(base + (o + row));
+  const BgTexel q00 = r0[0], q10 = r0[1], q01 = r1[0], q11 = r1[1];
+  const rt_v3 c0 = rt_v3_lerp(rt_v3_make(q00.r, q00.g, q00.b), rt_v3_make(q10.r, q10.g, q10.b), a);
+  const rt_v3 c1 = rt_v3_lerp(rt_v3_make(q01.r, q01.g, q01.b), rt_v3_make(q11.r, q11.g, q11.b), a);
+  return srgb_to_linear_tex<Pow24InLds<PT>::value>(rt_v3_lerp(c0, c1, b));
+}
+
 // ---------------------------------------------------------------------------------
 // Disney-style BSDF, driver.c:118-348.  Expression order matches oracle/oracle.c.
 
@@ -1988,6 +2020,19 @@ template <> struct SharedTaps<ShadeParamsLdsShared> { static constexpr bool valu
 template <> struct Pow24InLds<ShadeParamsLdsShared> { static constexpr bool value = RT_MATH_POW24 != 0; };
 template <bool SHARED_TAPS> struct PathShadeParams { typedef ShadeParamsLds type; };      // the path kernel's, by its template argument
 template <> struct PathShadeParams<true> { typedef ShadeParamsLdsShared type; };
+
+struct BgImageParams {          // what background_lookup_image reads (same field names as RT_KParams)
+  const RT_DTexture *textures;
+  const float *bg_image;
+  int32_t bg_texture, bg_pitch;
+};
+template <class ARGS>
+__device__ __forceinline__ void bg_image_params(BgImageParams &BP, const ARGS A) {
+  BP.textures = A->textures; BP.bg_image = A->bg_image;
+  BP.bg_texture = A->bg_texture; BP.bg_pitch = A->bg_pitch;
+}
+struct BgImageParamsLds : BgImageParams {};      // ... of a kernel that keeps the sRGB scale table in LDS
+template <> struct Pow24InLds<BgImageParamsLds> { static constexpr bool value = RT_MATH_POW24 != 0; };
 
 struct PrimaryParams {          // what primary_ray reads
   float cam[3][4];

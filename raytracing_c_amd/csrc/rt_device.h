@@ -82,6 +82,14 @@ typedef struct {
 } RT_DTexture;
 #define RT_TEX_TILE_INDEX(x, y, tpr) ((((y) >> 2) * (tpr) + ((x) >> 2)) * 16 + (((y) & 3) << 2) + ((x) & 3))
 
+/* The background image a second time, as floats (RT_KParams.bg_image; background_lookup_image(), rt_dev.hip.h): row-major,
+ * (width + 1) x (height + 1) texels of 16 bytes -- r, g, b as u8 * (1.0f / 255.999f), the product texel_rgb() forms, and a zero.
+ * Column `width` repeats column width - 1 and row `height` repeats row height - 1: the clamp-to-edge rule of tex_taps() as data,
+ * so the right and lower neighbours of texel (u, v) sit at +1 and +pitch whatever u and v.  A texel's byte offset is kept in 32
+ * bits, which bounds the image (rt_scene_upload refuses a larger background). */
+#define RT_BG_TEXEL_FLOATS 4
+#define RT_BG_IMAGE_MAX_BYTES 0xFFFFFFFFull
+
 /* One view of a multi-view launch: what RT_KParams.cam / focal_length / seed are to a one-view launch.  64 bytes, so that a
  * view's record is one aligned block of scalar loads. */
 typedef struct RT_KView {
@@ -155,6 +163,10 @@ typedef struct {
   int32_t n_views;             /* views of this launch; 0 = one view, the camera / seed above                                */
   int32_t tiles_per_view;      /* n_local_chunks * 16                                                                         */
   int32_t pixels_per_view;     /* width * height: view v accumulates into accum + v * pixels_per_view * 3                    */
+  /* the background once more, as floats (RT_BG_IMAGE_* above): what the path kernel's batch loop reads.  Appended likewise. */
+  const float *bg_image;       /* bg_pitch x (height + 1) texels of RT_BG_TEXEL_FLOATS floats                                */
+  int32_t bg_pitch;            /* texels per row: the background's width + 1                                                  */
+  int32_t bg_pad;
 } RT_KParams;
 
 /* Batch ray queries (rt_query_kernel, rt_hit_attributes_kernel; include/rt_hip.h rt_query_closest / rt_query_occluded): what one

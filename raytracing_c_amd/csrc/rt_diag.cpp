@@ -38,7 +38,7 @@ int rt_launch_test_feature_hit(const RT_KParams *P, int n, const int *tri, const
                                hipStream_t stream);
 int rt_launch_test_brdf(int n, const float *params, const float *in_dir, const uint32_t *state_in, float *out_dir, float *brdf,
                         uint32_t *state_out, hipStream_t stream);
-int rt_launch_test_background(const RT_KParams *P, int lds, int n, const float *dir, float *rgb, hipStream_t stream);
+int rt_launch_test_background(const RT_KParams *P, int mode, int n, const float *dir, float *rgb, hipStream_t stream);
 int rt_launch_test_primary_ray(const RT_KParams *P, int n, const int *xys, float *rays, hipStream_t stream);
 int rt_wf_launch_camera(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
 int rt_wf_launch_trace(const RT_KParams *P, int n_blocks, int geometry, int smem_bytes, hipStream_t stream);
@@ -625,8 +625,8 @@ extern "C" int rt_test_brdf(i32 n, f32 const *params, f32 const *in_dir, u32 con
 
 extern "C" int rt_test_background(RT_Device_Scene *d, i32 mode, i32 n, f32 const *dir, f32 *rgb) {
   if (!d || n <= 0 || !dir || !rgb) return rt_fail("rt_test_background: bad arguments");
-  if (mode != 0 && mode != 1) return rt_fail("rt_test_background: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds)", mode);
-  if (!all_finite(dir, (size_t)n * 3)) return rt_fail("rt_test_background: non-finite direction");
+  if ((mode & ~RT_TEST_BG_IMAGE) != 0 && (mode & ~RT_TEST_BG_IMAGE) != 1)
+    return rt_fail("rt_test_background: mode %d is not 0 (ShadeParams) or 1 (ShadeParamsLds), with or without RT_TEST_BG_IMAGE", mode);
   Device &D = *d->dev;
   std::lock_guard<std::mutex> lock(D.mutex);
   DeviceGuard guard(D);

@@ -74,6 +74,8 @@ int rt_launch_denoise(int width, int height, int src_stride, int src_comp, int d
                       const uint8_t *src, uint8_t *dst, hipStream_t stream);
 int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, int y0, int stride, int comp, uint32_t *out,
                            hipStream_t stream);
+int rt_launch_pack_bg_image(const uint8_t *raw, int width, int height, int rows, int y0, int stride, int comp, float *out,
+                            hipStream_t stream);
 int rt_launch_query(const RT_KParams *P, const RT_QParams *Q, int any, int wg_waves, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_hit_attributes(const RT_KParams *P, int n, const float *rays, const float *hits, float *out, hipStream_t stream);
 // ... in rt_features.hip
@@ -469,6 +471,7 @@ struct RT_Device_Scene {
   bool                has_kept = false;
   DevMem<RT_DTexture> textures;
   DevMem<uint32_t>    texels;
+  DevMem<float>       bg_image;                // the background as padded floats (rt_device.h), made from the rows that fill `texels`
   int32_t      depth = 0, last_row_offset = 0, bg_texture = -1, n_nodes = 0;
   int32_t      n_triangles = 0, n_materials = 0, n_textures = 0;
   int64_t      bytes = 0;

@@ -206,8 +206,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       const uint32_t n_sb = (uint32_t)A->n_sample_blocks, gmax = (uint32_t)A->grab_max;
       PrimaryParams PP;
       primary_params(PP, S, A);
-      ShadeParamsLds SP;
-      shade_params(SP, A, false);
+      BgImageParamsLds BP;                // (the environment from its float image: background_lookup_image, rt_dev.hip.h)
+      bg_image_params(BP, A);
       uint32_t *tile_next = A->tile_next, *open_groups = A->open_groups;
       uint32_t n_sky = 0;                 // paths served here: their root visit is COUNTED (like the oracle's) but not executed
       // lane i: entry i of the tile's node list, 0 past its end (the pass below stops there: no count in a scalar register)
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           // registers and one lane adds (tile_add_samples_grouped); with fewer samples per pixel every lane adds its own, as before.
           unsigned long long qr = 0ull, qg = 0ull, qb = 0ull;
           if (valid[q]) {
-            const rt_v3 bg = background_lookup(SP, dirs[q]);
+            const rt_v3 bg = background_lookup_image(BP, dirs[q]);
             const rt_v3 radiance = rt_v3_mul_add(bg, rt_v3_make(1, 1, 1), rt_v3_make(0, 0, 0));      // tint 1, emission 0 (raytracer.c:554)
             qr = accum_quantize_dev(radiance.x); qg = accum_quantize_dev(radiance.y); qb = accum_quantize_dev(radiance.z);
           }
@@ -986,6 +986,31 @@ extern "C" int rt_launch_pack_texture(const uint8_t *raw, int width, int rows, i
   size_t n = (size_t)width * rows;
   hipLaunchKernelGGL(rt_pack_texture_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, raw, width, rows, y0, stride,
                      comp, out);
+  return (int)hipGetLastError();
+}
+
+// The same raw rows -> the float image of the background (rt_device.h: RT_KParams.bg_image): texel (x, y) of the (width + 1) x
+// (height + 1) image is texel (min(x, width - 1), y) of the source, r g b as texel_rgb() converts them and a zero; a thread of the
+// source's last row writes the pad row below it as well.  `rows` rows starting at row y0, as above.
+__global__ void rt_pack_bg_image_kernel(const uint8_t *raw, int width, int height, int rows, int y0, int stride, int comp, float4 *out) {
+  const int pitch = width + 1;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)pitch * rows) return;
+  int yl = (int)(i / pitch), x = (int)(i % pitch);
+  const int xs = x < width ? x : width - 1;
+  const uint8_t *p = raw + ((size_t)yl * stride + xs) * comp;
+  const int y = y0 + yl;
+  const rt_v3 c = texel_rgb((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+  const float4 t = make_float4(c.x, c.y, c.z, 0.0f);
+  out[(size_t)y * pitch + x] = t;
+  if (y == height - 1) out[(size_t)height * pitch + x] = t;
+}
+
+extern "C" int rt_launch_pack_bg_image(const uint8_t *raw, int width, int height, int rows, int y0, int stride, int comp, float *out,
+                                       hipStream_t stream) {
+  size_t n = (size_t)(width + 1) * rows;
+  hipLaunchKernelGGL(rt_pack_bg_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, raw, width, height, rows, y0,
+                     stride, comp, reinterpret_cast<float4 *>(out));
   return (int)hipGetLastError();
 }
 

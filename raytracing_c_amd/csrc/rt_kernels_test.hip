@@ -430,6 +430,7 @@ __global__ void rt_test_brdf_kernel(int n, const float *params, const float *in_
   state_out[i] = rng;
 }
 
+// SP = BgImageParams / BgImageParamsLds: background_lookup_image() on the float image; any other: background_lookup() on the texel pool
 template <class SP>
 __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_background_kernel(RT_KParams P, int n, const float *dir, float *rgb) {
   if (Pow24InLds<SP>::value) {
@@ -439,8 +440,15 @@ __global__ __launch_bounds__(RT_BLOCK_THREADS) void rt_test_background_kernel(RT
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   SP S;
-  shade_params(S, &P, false);
-  const rt_v3 c = background_lookup(S, rt_v3_make(dir[i * 3 + 0], dir[i * 3 + 1], dir[i * 3 + 2]));
+  const rt_v3 d = rt_v3_make(dir[i * 3 + 0], dir[i * 3 + 1], dir[i * 3 + 2]);
+  rt_v3 c;
+  if constexpr (std::is_base_of<BgImageParams, SP>::value) {
+    bg_image_params(S, &P);
+    c = background_lookup_image(S, d);
+  } else {
+    shade_params(S, &P, false);
+    c = background_lookup(S, d);
+  }
   rgb[i * 3 + 0] = c.x; rgb[i * 3 + 1] = c.y; rgb[i * 3 + 2] = c.z;
 }
 
@@ -630,9 +638,14 @@ extern "C" int rt_launch_test_brdf(int n, const float *params, const float *in_d
   return (int)hipGetLastError();
 }
 
-extern "C" int rt_launch_test_background(const RT_KParams *P, int lds, int n, const float *dir, float *rgb, hipStream_t stream) {
+// mode: 0 = ShadeParams, 1 = ShadeParamsLds; + RT_TEST_BG_IMAGE (8): the lookup on the float image, BgImageParams / BgImageParamsLds
+extern "C" int rt_launch_test_background(const RT_KParams *P, int mode, int n, const float *dir, float *rgb, hipStream_t stream) {
   const dim3 grid((n + RT_BLOCK_THREADS - 1) / RT_BLOCK_THREADS), block(RT_BLOCK_THREADS);
-  if (lds) hipLaunchKernelGGL(rt_test_background_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, dir, rgb);
+  const int lds = mode & 1;
+  if (mode & 8) {
+    if (lds) hipLaunchKernelGGL(rt_test_background_kernel<BgImageParamsLds>, grid, block, 0, stream, *P, n, dir, rgb);
+    else hipLaunchKernelGGL(rt_test_background_kernel<BgImageParams>, grid, block, 0, stream, *P, n, dir, rgb);
+  } else if (lds) hipLaunchKernelGGL(rt_test_background_kernel<ShadeParamsLds>, grid, block, 0, stream, *P, n, dir, rgb);
   else hipLaunchKernelGGL(rt_test_background_kernel<ShadeParams>, grid, block, 0, stream, *P, n, dir, rgb);
   return (int)hipGetLastError();
 }

@@ -55,9 +55,16 @@ static int texture_index(Image const *img, TexturePool &pool) {
   return idx;
 }
 
-static int upload_textures(const TexturePool &pool, DevMem<uint32_t> &d_texels, int64_t *bytes) {
+// ... and, from the staged rows of the background (texture `bg` of the pool), rt_pack_bg_image_kernel: its float copy (rt_device.h)
+static int upload_textures(const TexturePool &pool, DevMem<uint32_t> &d_texels, int bg, DevMem<float> &d_bg_image, int64_t *bytes) {
   HIP_TRY(d_texels.grow(pool.texels));
   *bytes += (int64_t)d_texels.bytes();
+  const size_t bg_texels = ((size_t)pool.descs[bg].width + 1) * ((size_t)pool.descs[bg].height + 1);
+  if (bg_texels * RT_BG_TEXEL_FLOATS * sizeof(float) > RT_BG_IMAGE_MAX_BYTES)
+    return rt_fail("rt_scene_upload: the background (%d x %d) is too large for its float copy", pool.descs[bg].width, pool.descs[bg].height);
+  if (d_bg_image.grow(bg_texels * RT_BG_TEXEL_FLOATS) != hipSuccess)
+    return rt_fail("rt_scene_upload: out of device memory for the float copy of the background (%zu bytes)", bg_texels * RT_BG_TEXEL_FLOATS * sizeof(float));
+  *bytes += (int64_t)d_bg_image.bytes();
   size_t max_raw = 0;
   for (const Image *img : pool.sources) {
     size_t raw = (size_t)img->stride * img->height * img->components;
@@ -73,6 +80,8 @@ static int upload_textures(const TexturePool &pool, DevMem<uint32_t> &d_texels, 
     rc = (int)hipMemcpy(stage, img->pixels.data, raw, hipMemcpyHostToDevice);
     if (rc == 0) rc = rt_launch_pack_texture(stage, (int)img->width, (int)img->height, 0, (int)img->stride, (int)img->components,
                                              d_texels + pool.descs[k].offset, nullptr);
+    if (rc == 0 && (int)k == bg) rc = rt_launch_pack_bg_image(stage, (int)img->width, (int)img->height, (int)img->height, 0, (int)img->stride,
+                                                              (int)img->components, d_bg_image, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();        // the staging buffer is reused by the next texture
   }
   if (rc != 0) return rt_fail("texture upload failed: %s", hipGetErrorString((hipError_t)rc));
@@ -477,7 +486,7 @@ static RT_Device_Scene *upload_scene_locked(Device &D, Scene const *scene) {
   }
   if (upload(d->nodes, nodes, &d->bytes) || upload(d->leaves, leaves, &d->bytes) ||
       upload(d->tris, tris, &d->bytes) || upload(d->mats, mats, &d->bytes) ||
-      upload(d->textures, pool.descs, &d->bytes) || upload_textures(pool, d->texels, &d->bytes)) {
+      upload(d->textures, pool.descs, &d->bytes) || upload_textures(pool, d->texels, bg, d->bg_image, &d->bytes)) {
     free_device_scene(d);
     return nullptr;
   }
@@ -704,6 +713,9 @@ static int touch_device_scene(RT_Device_Scene *d, Scene const *scene, const void
     uint32_t *tex_base = d->texels + desc.offset;
     int rc = rt_launch_pack_texture(stage, (int)img->width, (int)(r1 - r0), (int)r0, (int)img->stride,
                                     (int)img->components, tex_base, nullptr);
+    // (the background's float copy: the same rows, each with its pad column, and the pad row with the last one)
+    if (rc == 0 && (int)t == d->bg_texture) rc = rt_launch_pack_bg_image(stage, (int)img->width, (int)img->height, (int)(r1 - r0), (int)r0,
+                                                                         (int)img->stride, (int)img->components, d->bg_image, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();
     if (rc != 0) return rt_fail("rt_scene_touch: texture rows: %s", hipGetErrorString((hipError_t)rc));
     return 1;
@@ -833,6 +845,8 @@ void scene_only_kparams(RT_KParams *K, RT_Device_Scene *d) {
   K->last_row_offset = d->last_row_offset;
   K->bg_texture = d->bg_texture;
   K->n_nodes = d->n_nodes;
+  K->bg_image = d->bg_image;
+  K->bg_pitch = d->tex_descs[(size_t)d->bg_texture].width + 1;
 }
 
 RT_Device_Scene *cached_scene_locked(Device &D, Scene const *scene, float *stamp_ms, float *upload_ms) {
