@@ -379,6 +379,83 @@ extern int rt_resolve_motion(RT_Render_Params const *params, void const *d_motio
 extern int rt_render_features_motion(Scene const *scene, i32 width, i32 height, isize samples, isize max_bounces,
                                      RT_Features const *out, u64 *sums, f32 *motion, u64 *motion_sums);
 
+/* ---- light probes ---------------------------------------------------------------------- */
+
+/* The incoming light at points in space: what lights everything that is not baked into a lightmap -- moving objects, particles,
+ * volumetrics, characters sample a probe grid laid through the level.  For probe i of the caller's array, global index
+ * g = probe_first + i, position o_i, and sample s of `samples`:
+ *     state = rt_path_seed(seed, (u32)g, (u32)s)
+ *     d     = rt_rand_unit_vec3(&state)                      rt_math.h; common.h:30-42: uniform on the sphere by rejection,
+ *                                                            RT_EPS < |p|^2 <= 1, then p * (1 / rt_sqrtf(|p|^2))
+ *     L     = cast_ray(Ray{o_i, d}, max_bounces, &state)     raytracer.c:505-558 unchanged, the RNG stream going on where the
+ *                                                            direction left it: back faces pass through at the price of an
+ *                                                            iteration, the background is looked up on a miss, exhaustion
+ *                                                            returns the emission
+ *     t     = the distance of the FIRST segment's closest hit (ray_scene_hit with entry distance F32_INFINITY): +inf on a miss
+ *             and when max_bounces <= 0 (no ray is cast; L = 0)
+ * The position is taken AS GIVEN: a NaN or infinite coordinate gives whatever the reference's arithmetic gives.
+ *
+ * THE RECORD of a sample, 32 bytes, written with two 16-byte stores: */
+typedef struct { f32 radiance[3]; f32 t; f32 direction[3]; u32 pad; /* 0 */ } RT_Probe_Sample;
+/* THE PROJECTION onto the nine real spherical harmonics of bands 0-2, d = (x, y, z) -- rt_sh9_basis() of rt_math.h: plain f32
+ * * + -, every operation rounded on its own, left to right as written, no fused multiply-add (the units are built with
+ * -ffp-contract=off, like THE MOTION): the same bits under all three numeric contracts.
+ *     Y0 = 0.282095f
+ *     Y1 = 0.488603f*y        Y2 = 0.488603f*z        Y3 = 0.488603f*x
+ *     Y4 = 1.092548f*(x*y)    Y5 = 1.092548f*(y*z)    Y7 = 1.092548f*(x*z)
+ *     Y6 = 0.315392f*((3.0f*(z*z)) - 1.0f)
+ *     Y8 = 0.546274f*((x*x) - (y*y))
+ * THE SUMS: sums[i][k][c] += rt_accum_quantize_signed(radiance[c] * Y_k) -- 27 u64 per probe, k-major, 32.32, two's complement,
+ * order-free; NaN counts as 0, as everywhere.  THE COEFFICIENTS: coeff[i][k][c] = rt_accum_resolve_signed(sum, samples) *
+ * 12.566371f -- the mean over ALL `samples`, rounded once, then one f32 multiply by 4 pi: the Monte-Carlo estimate of the integral
+ * of L Y_k over the sphere.  A buffer of sums can be filled by sample ranges and resolved once; radiance(d) ~ sum_k coeff_k Y_k(d),
+ * irradiance by the cosine convolution (band factors pi, 2 pi / 3, pi / 4).
+ *
+ * Three kernels of their own (csrc/rt_probes.hip): rt_probe_kernel, persistent, in the query kernel's launch geometry on the path
+ * kernel's traversal and shade blocks, lanes refilled from ONE list of n x sample_count paths; rt_probe_project_kernel, one
+ * workgroup per probe; rt_probe_resolve_kernel.  Every record, sum and coefficient equals the reference's arithmetic bit for bit.
+ * Frames, views, queries, features and their counters are not affected by probe calls. */
+#define RT_PROBE_COEFFS 9
+#define RT_PROBE_MAX_PATHS ((i64)1 << 30)
+typedef struct {
+  i32 samples;                 /* samples per probe: what the coefficients are the mean over                                  */
+  i32 sample_first;            /* this call traces samples [sample_first, sample_first + sample_count) of every probe ...     */
+  i32 sample_count;            /* ... 0 = all of them                                                                        */
+  i32 max_bounces;
+  u32 seed;
+  u32 probe_first;             /* global index of positions[0]: a slice of a probe array equals the matching part of the whole */
+} RT_Probe_Params;             /* 24 bytes */
+
+/* Device level, like rt_render_accumulate(): every pointer is a DEVICE pointer owned by the caller, on the device the scene was
+ * uploaded to (project and resolve: the primary device); the calls only enqueue work on `stream` (NULL = default stream).
+ *   d_positions : f32[n][3]                                    d_samples : RT_Probe_Sample[n][sample_count], 16-byte aligned
+ *   d_sums      : u64[n][9][3], zero before the first range    d_coeffs  : f32[n][9][3]
+ * rt_probe_trace() writes every record of the range; rt_probe_project() ADDS the range's 27 sums per probe to d_sums (atomics: a
+ * buffer is filled progressively by sample ranges); rt_probe_resolve() turns sums into coefficients.
+ * Refused before a device is touched, each with a text of its own in rt_last_error(): a NULL scene, params, positions or output;
+ * n <= 0; samples <= 0; a sample range outside [0, samples]; max_bounces < 0; n x sample_count > 2^30 (RT_PROBE_MAX_PATHS: the
+ * kernel holds path indices in 32-bit integers); (u64)probe_first + n > 2^32; d_samples not 16-byte aligned.  A refused call
+ * leaves its outputs untouched.  0 on success, -1 + rt_last_error(). */
+extern int rt_probe_trace(RT_Device_Scene *dscene, RT_Probe_Params const *params, i64 n, void const *d_positions, void *d_samples,
+                          void *stream);
+extern int rt_probe_project(RT_Probe_Params const *params, i64 n, void const *d_samples, void *d_sums, void *stream);
+extern int rt_probe_resolve(RT_Probe_Params const *params, i64 n, void const *d_sums, void *d_coeffs, void *stream);
+
+/* Host level: the three steps from host memory to host memory, on the cached device copy of `scene` with rt_render_frame()'s scene
+ * check and device lock, on the NULL stream, on the PRIMARY device only (as the queries).  coeffs f32[n][9][3], sums u64[n][9][3]
+ * (the sums of THIS call's sample range, from zero), samples RT_Probe_Sample[n][sample_count]: each optional, at least one.  The
+ * probes are traced in slices of at most 2^21 paths (RT_PROBE_SLICE: 64 MB of records on the device; the staging is kept for the
+ * next call); a single probe whose sample_count exceeds the slice is split by sample range; probe_first and sample_first make
+ * every slice equal to the matching part of the whole.  The same refusals (n x sample_count is not bounded here). */
+#define RT_PROBE_SLICE ((i64)1 << 21)
+extern int rt_scene_probes(Scene const *scene, RT_Probe_Params const *params, i64 n, Vec3 const *positions, f32 *coeffs, u64 *sums,
+                           RT_Probe_Sample *samples);
+
+/* Counters of the last probe call of this process (device or host level; a host call's slices summed): paths, rays, 8-box slab
+ * tests, 8-triangle tests, shader evaluations, background lookups, textured shader evaluations.  Synchronises.  rt_get_counters()
+ * and rt_get_query_counters() are not affected. */
+extern int rt_get_probe_counters(RT_Counters *out);
+
 /* ---- guided denoiser ------------------------------------------------------------------ */
 
 /* An edge-stopping a-trous filter (Dammertz et al. 2010) of the linear frame, steered by the feature buffers above: what turns the

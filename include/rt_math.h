@@ -435,6 +435,38 @@ RT_FN float rt_accum_resolve_signed(uint64_t sum, uint32_t samples) {
   return (float)mean;
 }
 
+/* ---- light probes (include/rt_hip.h, "light probes") ----------------------------------
+ * common.h:30-42: a uniform direction by rejection from the cube -- three draws per try, accepted when
+ * RT_EPS < |p|^2 <= 1 -- normalised as p * (1 / sqrt(|p|^2)).  The state goes on where the accepted try left it. */
+RT_FN rt_v3 rt_rand_unit_vec3(uint32_t *state) {
+  for (;;) {
+    rt_v3 p;
+    p.x = rt_rand_f32(state) * (1.0f - -1.0f) + -1.0f;
+    p.y = rt_rand_f32(state) * (1.0f - -1.0f) + -1.0f;
+    p.z = rt_rand_f32(state) * (1.0f - -1.0f) + -1.0f;
+    float lensq = rt_v3_dot(p, p);
+    if (RT_EPS < lensq && lensq <= 1.0f) return rt_v3_scale(p, 1.0f / rt_sqrtf(lensq));
+  }
+}
+
+/* The nine real spherical harmonics of bands 0-2 at the direction d: plain f32 * + -, every operation rounded on its own, left
+ * to right as written, nothing fused under any contract (the units that use it are built with -ffp-contract=off). */
+#define RT_SH9 9
+RT_FN void rt_sh9_basis(rt_v3 d, float y[RT_SH9]) {
+  const float x = d.x, yy = d.y, z = d.z;
+  y[0] = 0.282095f;
+  y[1] = 0.488603f * yy;
+  y[2] = 0.488603f * z;
+  y[3] = 0.488603f * x;
+  y[4] = 1.092548f * (x * yy);
+  y[5] = 1.092548f * (yy * z);
+  y[6] = 0.315392f * ((3.0f * (z * z)) - 1.0f);
+  y[7] = 1.092548f * (x * z);
+  y[8] = 0.546274f * ((x * x) - (yy * yy));
+}
+/* 4 pi, the sphere's solid angle: a mean over uniform directions times this is the Monte-Carlo estimate of the integral */
+#define RT_FOUR_PI 12.566371f
+
 /* average -> clamp -> sRGB -> u8, raytracer.c:700-716.  The clamp is written so that NaN FAILS it, as in rt_accum_quantize():
  * a NaN pixel encodes to 0 (deviation D11, oracle/oracle.h).  rt_clampf() lets NaN through, rt_powf() turns it into 0, the
  * sRGB formula into -0.055, and the conversion of -14.08f to uint8_t is undefined in C.  Every other input keeps its byte:

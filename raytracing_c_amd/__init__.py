@@ -11,6 +11,8 @@ from .loaders import load_model, default_camera, camera_from_trs   # noqa: F401
 from .render import render_frame, render_views, render_context, frame_begin, frame_end, Counters   # noqa: F401
 from .query import closest_hits, occluded, closest_hits_device, occluded_device, get_query_counters, QueryCounters   # noqa: F401
 from .features import render_features   # noqa: F401
+from .probes import (bake_probes, bake_probes_device, probe_grid, sh9_basis, sh9_radiance, sh9_irradiance, probe_visibility,   # noqa: F401
+                     get_probe_counters)
 from .guided import guided_denoise, render_denoised   # noqa: F401
 from .temporal import temporal_accumulate, render_temporal, History   # noqa: F401
 from .variance import temporal_accumulate_moments, guided_denoise_variance, render_svgf   # noqa: F401

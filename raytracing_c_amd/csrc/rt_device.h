@@ -200,6 +200,23 @@ typedef struct {
   int32_t      units_per_tile; /* (1 << shift) pixel groups x n_sample_blocks                                             */
 } RT_FParams;
 
+/* Light probes (rt_probe_kernel, rt_probes.hip; include/rt_hip.h rt_probe_trace): what one launch reads and writes besides the
+ * scene fields of RT_KParams (max_bounces and seed among them).  The work list is the path index j in [0, n_paths): probe
+ * j / sample_count of the caller's array, sample sample_first + j % sample_count; record j is the path's. */
+typedef struct {
+  const float *positions;      /* [n][3] probe positions -- taken as given                                                */
+  float       *records;        /* RT_Probe_Sample[n_paths]: radiance, t, direction, 0 -- two float4 per path              */
+  uint32_t    *head;           /* paths handed out so far (zero at launch)                                                */
+  unsigned long long *counters;/* RT_Counters layout (RT_CNT_PATHS .. RT_CNT_TEXTURED) -- added to                        */
+  int32_t      n_paths;        /* n * sample_count, at most 2^30                                                          */
+  int32_t      sample_count, sample_first;
+  uint32_t     probe_first;    /* global index of probe 0: the seed rule's pixel index is probe_first + probe             */
+  int32_t      grab;           /* paths a wave takes per atomic on `head`                                                 */
+  int32_t      exit_lanes;     /* finished lanes that end a traversal call while paths are left to hand out               */
+} RT_PParams;
+#define RT_PROBE_RECORD_F4 2   /* float4 per RT_Probe_Sample */
+#define RT_PROBE_SUMS      27  /* u64 per probe: 9 coefficients x rgb, k-major */
+
 /* Temporal accumulation (rt_temporal_kernel, rt_temporal.hip; include/rt_hip.h rt_temporal_accumulate): a camera as proj() of the
  * contract reads it, and what the host computes once per launch. */
 typedef struct {

@@ -16,7 +16,8 @@
 //                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline);
 //                     a stage reads one RT_Frame (rt_device.h) and is launched in one place, which chooses its plain or variance / moments kernel;
 //                     and feature-guided upsampling of a half-resolution frame, on the same three levels (rt_render_upsampled)
-//   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level)
+//   rt_query.cpp      batch ray queries: closest hit, occlusion, full hit records (device level and host level); light probes: path-traced
+//                     samples at points a host supplies and their SH projection, on the queries' ring and slicing (device level and host level)
 //   rt_features.cpp   first-hit feature buffers: coverage, albedo, normal, position (device level and host level)
 //   rt_diag.cpp       the diagnostic library only (-DRT_DIAG_VARIANTS): wavefront pipeline, unit-test entry points, fault hooks
 //   rt_mem.h          the owners of device memory, pinned memory and events (DevMem, PinnedMem, DevEvent): what a struct below
@@ -85,6 +86,10 @@ int rt_launch_features_resolve(int n_pixels, int samples, const unsigned long lo
 int rt_launch_features_motion(const RT_KParams *P, const RT_FParams *F, const float *kept, unsigned long long *motion_sums, int n_blocks,
                               int smem_bytes, hipStream_t stream);
 int rt_launch_motion_resolve(int n_pixels, int samples, const unsigned long long *sums, float *motion, hipStream_t stream);
+// ... in rt_probes.hip
+int rt_launch_probes(const RT_KParams *P, const RT_PParams *R, int n_blocks, int smem_bytes, hipStream_t stream);
+int rt_launch_probe_project(int n_probes, int sample_count, const float *records, unsigned long long *sums, hipStream_t stream);
+int rt_launch_probe_resolve(long long n_coeffs, int samples, const unsigned long long *sums, float *coeffs, hipStream_t stream);
 // ... in rt_refit.hip
 int rt_launch_refit(int len, int depth, int n_internal, const void *d_src, const int *d_source_of_slot, float *d_block, float *d_nodes,
                     float *d_leaves, float *d_tris, unsigned char *d_populated, unsigned int *d_max_edge_bits, hipStream_t stream);
@@ -283,6 +288,21 @@ struct FeatureState {
   DevMem<float>              motion;          // [pixels][RT_MOTION_CHANNELS]
 };
 
+// Light probes (rt_query.cpp).  What a probe launch writes besides its records -- the seven counters and the work counter -- is one
+// 128-byte slot of a ring of its own, indexed like the query ring and taken with it (acquire_slot: the slot's event orders its
+// reuse), so that rt_get_query_counters() and rt_get_probe_counters() never share a word.  The staging buffers serve the host-level
+// call, one slice of at most RT_PROBE_SLICE paths at a time; they are kept between calls and given back with the device slot
+// (release_staging).
+#define RT_PROBE_SLOT_BYTES 128
+struct ProbeState {
+  DevMem<uint8_t>            slots;           // [RT_QUERY_SLOTS][128]: counters u64[8] at +0 (RT_CNT_PATHS .. RT_CNT_TEXTURED), work counter u32 at +64
+  int                        last = -1;       // slot of the most recent probe call (rt_get_probe_counters)
+  DevMem<float>              positions;       // [probes of a slice][3]
+  DevMem<float>              records;         // [paths of a slice][8]
+  DevMem<unsigned long long> sums;            // [probes of a slice][27]
+  DevMem<float>              coeffs;          // [probes of a slice][27]
+};
+
 // The four planes of such a buffer, to write (the resolve) ...
 static inline RT_Features split_feature_planes(float *planes, size_t pixels) {
   return {planes, planes + pixels, planes + pixels * 4, planes + pixels * 7};
@@ -389,6 +409,7 @@ struct Device {
   FrameLane  lanes[RT_FRAME_LANES];           // slot 0 only
   QueryState query;
   FeatureState features;
+  ProbeState probes;
   GuidedState guided;
   RefitState refit;
   TemporalState temporal;
@@ -632,6 +653,9 @@ int  acquire_slot(Device &D, int *slot, bool query = true);
 // D.mutex held, D's GPU current, every pointer on D.
 int  enqueue_feature_pass(Device &D, RT_Device_Scene *d, Camera const *cam, RT_Render_Params const *p, void *d_sums, RT_Features const &to,
                           hipStream_t stream, void *d_motion_sums = nullptr, void *d_motion = nullptr);
+
+// rt_query.cpp, light probes
+void release_probe_state(Device &D);                                                // release_staging()'s part here
 
 // rt_post.cpp
 void release_temporal_state(Device &D);                                             // release_staging()'s part here

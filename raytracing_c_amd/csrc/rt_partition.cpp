@@ -80,6 +80,7 @@ static void drop_device_partitions(const Partition *q) {        // g_partition_m
 void release_staging(Device &D) {
   release_query_state(D);                       // (also forgets that D was the last device to answer a query)
   D.features = FeatureState();
+  release_probe_state(D);                       // (also forgets that D was the last device to trace probes)
   D.guided = GuidedState();
   D.refit = RefitState();
   D.upsample = UpsampleState();

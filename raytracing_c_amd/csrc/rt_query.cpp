@@ -1,7 +1,7 @@
 // rt_query.cpp -- batch ray queries (include/rt_hip.h): closest hit, occlusion and full hit records for rays the host supplies,
 // on the device level (device pointers, one launch on the caller's stream) and on the host level (host arrays, the cached device
 // copy of a Scene through scene_checked, rt_residency.cpp, slices of RT_QUERY_SLICE rays).  The work is rt_query_kernel and
-// rt_hit_attributes_kernel (rt_kernels.hip); nothing here computes a hit on the CPU.
+// rt_hit_attributes_kernel (rt_kernels.hip); nothing here computes a hit on the CPU.  Behind them, the light probes (below).
 
 #include "rt_host.h"
 
@@ -239,5 +239,254 @@ extern "C" int rt_get_query_counters(RT_Query_Counters *out) {
   out->hits = c[RT_QCNT_HITS];
   out->node_visits = c[RT_QCNT_NODES];
   out->leaf_visits = c[RT_QCNT_LEAVES];
+  return 0;
+}
+
+// ==== light probes (include/rt_hip.h, "light probes") ==========================================================================
+// Path-traced samples of the incoming radiance at points the host supplies and their projection onto nine spherical harmonics, on
+// the device level (device pointers, launches on the caller's stream) and on the host level (host arrays, the cached device copy of
+// a Scene through scene_checked, slices of RT_PROBE_SLICE paths).  They live in this unit because they are the queries' shape -- a
+// list the host supplies, one persistent kernel with one work counter, a ring slot per call, staged slices -- and take their ring
+// slot from the ring above.  The work is rt_probe_kernel, rt_probe_project_kernel and rt_probe_resolve_kernel (rt_probes.hip);
+// nothing here traces a path or forms a sum on the CPU.
+
+static_assert(sizeof(RT_Probe_Sample) == 32 && sizeof(RT_Probe_Sample) == RT_PROBE_RECORD_F4 * 16, "RT_Probe_Sample is two 16-byte stores");
+static_assert(sizeof(RT_Probe_Params) == 24, "RT_Probe_Params");
+static_assert(RT_PROBE_COEFFS * 3 == RT_PROBE_SUMS, "nine coefficients x rgb");
+static_assert(sizeof(Vec3) == 12, "a position is f32[3]");
+static_assert(RT_CNT_TEXTURED < 8, "the probe counters fit the slot's eight words");
+
+static std::atomic<Device *> g_probe_dev{nullptr};      // the device of the most recent probe call (rt_get_probe_counters)
+
+// What can be checked without the device.  `who` prefixes the messages; *count = the sample range's length (0 = all resolved).
+static int check_probe_params(const char *who, RT_Probe_Params const *p, i64 n, i32 *count) {
+  if (!p) return rt_fail("%s: probe params are NULL", who);
+  if (n <= 0) return rt_fail("%s: n must be positive (got %lld)", who, (long long)n);
+  if (p->samples <= 0) return rt_fail("%s: samples must be positive (got %d)", who, p->samples);
+  if (p->sample_first < 0 || p->sample_count < 0 || (i64)p->sample_first + p->sample_count > p->samples)
+    return rt_fail("%s: sample range [%d, +%d) outside [0, %d]", who, p->sample_first, p->sample_count, p->samples);
+  if (p->max_bounces < 0) return rt_fail("%s: max_bounces must be >= 0 (got %d)", who, p->max_bounces);
+  if ((u64)p->probe_first + (u64)n > ((u64)1 << 32))
+    return rt_fail("%s: probe_first %u + n %lld exceeds the 32-bit probe index", who, p->probe_first, (long long)n);
+  *count = p->sample_count ? p->sample_count : p->samples - p->sample_first;
+  return 0;
+}
+
+// ... and of a device-level call: one launch holds every path
+static int check_probe_paths(const char *who, i64 n, i32 count) {
+  if (n * (i64)count > RT_PROBE_MAX_PATHS)
+    return rt_fail("%s: too many paths (%lld probes x %d samples > 2^30 per call)", who, (long long)n, count);
+  return 0;
+}
+
+static int ensure_probe_state(Device &D) {              // D.mutex held, D's GPU current
+  if (ensure_query_state(D) != 0) return -1;
+  HIP_TRY(D.probes.slots.grow(RT_QUERY_SLOTS * RT_PROBE_SLOT_BYTES));
+  return 0;
+}
+
+// The ring slot of a new probe call: the query ring's next slot (its event orders the reuse) and the probe ring's words of it.
+static int acquire_probe_slot(Device &D, int *slot) {
+  if (ensure_probe_state(D) != 0 || acquire_slot(D, slot, false) != 0) return -1;
+  D.probes.last = *slot;
+  g_probe_dev.store(&D);
+  return 0;
+}
+
+void release_probe_state(Device &D) {
+  D.probes = ProbeState();
+  Device *self = &D;
+  g_probe_dev.compare_exchange_strong(self, nullptr);
+}
+
+// Enqueues one launch of the probe kernel on `stream`: n probes x count samples from q->sample_first.  `fresh`: the slot's counters
+// start at zero (the first launch of a call); its work counter always does.  D.mutex held, D's GPU current, every pointer on D.
+static int enqueue_trace(Device &D, RT_Device_Scene *d, RT_Probe_Params const *q, i32 count, i64 n, const float *positions,
+                         float *records, hipStream_t stream, int slot, bool fresh) {
+  uint8_t *sl = D.probes.slots + (size_t)slot * RT_PROBE_SLOT_BYTES;
+  if (fresh) HIP_TRY(hipMemsetAsync(sl, 0, RT_PROBE_SLOT_BYTES, stream));
+  else HIP_TRY(hipMemsetAsync(sl + 64, 0, 4, stream));
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  K.max_bounces = q->max_bounces;
+  K.seed = q->seed;
+  RT_PParams R;
+  memset(&R, 0, sizeof R);
+  R.positions = positions;
+  R.records = records;
+  R.counters = (unsigned long long *)sl;
+  R.head = (uint32_t *)(sl + 64);
+  const int64_t n_paths = n * (int64_t)count;
+  R.n_paths = (int32_t)n_paths;
+  R.sample_count = count;
+  R.sample_first = q->sample_first;
+  R.probe_first = q->probe_first;
+
+  // launch geometry: the query kernel's (rt_query.cpp) -- one workgroup of 16 waves per CU, the tree fills the LDS beside the waves'
+  // perm stacks and the kernel's static sRGB scale table
+  const int wg_waves = 16, wg_lanes = wg_waves * 64;
+  const LdsSplit S = lds_split(d, K.depth, wg_waves, 0, 1, true);
+  K.n_lds_nodes = S.n_lds_nodes;
+  int64_t blocks = (n_paths + wg_lanes - 1) / wg_lanes;
+  if (blocks > D.num_cus) blocks = D.num_cus;
+  if (blocks < 1) blocks = 1;
+  // paths per grab: an eighth of a wave's mean share, in whole wave-fulls, within [64, 512] (why: rt_query_kernel)
+  const int64_t grab = n_paths / (blocks * wg_waves * 8) / 64 * 64;
+  R.grab = grab < 64 ? 64 : (grab > 512 ? 512 : (int)grab);
+  // finished lanes that end a traversal call while paths are left: what follows is the path kernel's S block, whose threshold it is
+  R.exit_lanes = knob_int("RT_PROBE_EXIT", 48);
+  if (R.exit_lanes < 1 || R.exit_lanes > 64) R.exit_lanes = 48;
+  int rc = rt_launch_probes(&K, &R, (int)blocks, S.smem, stream);
+  if (rc != 0) return rt_fail("probe kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  HIP_TRY(hipEventRecord(D.query.done[slot], stream));
+  return 0;
+}
+
+static int enqueue_project(i64 n, i32 count, const void *records, void *sums, hipStream_t stream) {
+  int rc = rt_launch_probe_project((int)n, count, (const float *)records, (unsigned long long *)sums, stream);
+  if (rc != 0) return rt_fail("probe projection kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int enqueue_resolve(i64 n, i32 samples, const void *sums, void *coeffs, hipStream_t stream) {
+  int rc = rt_launch_probe_resolve((long long)n * RT_PROBE_SUMS, samples, (const unsigned long long *)sums, (float *)coeffs, stream);
+  if (rc != 0) return rt_fail("probe resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- device level -------------------------------------------------------------------------------------------------------------
+extern "C" int rt_probe_trace(RT_Device_Scene *dscene, RT_Probe_Params const *params, i64 n, void const *d_positions, void *d_samples,
+                              void *stream) {
+  const char *who = "rt_probe_trace";
+  // (everything that can be checked without the device is checked before it is touched)
+  if (!dscene) return rt_fail("%s: device scene is NULL", who);
+  i32 count = 0;
+  if (check_probe_params(who, params, n, &count) != 0 || check_probe_paths(who, n, count) != 0) return -1;
+  if (!d_positions) return rt_fail("%s: d_positions is NULL", who);
+  if (!d_samples) return rt_fail("%s: d_samples is NULL", who);
+  if ((uintptr_t)d_samples & 15) return rt_fail("%s: d_samples is not 16-byte aligned", who);
+  if (count == 0) return 0;                                     // (an empty range at the end of the samples: nothing to trace)
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  int slot = 0;
+  if (acquire_probe_slot(D, &slot) != 0) return -1;
+  return enqueue_trace(D, dscene, params, count, n, (const float *)d_positions, (float *)d_samples, (hipStream_t)stream, slot, true);
+}
+
+extern "C" int rt_probe_project(RT_Probe_Params const *params, i64 n, void const *d_samples, void *d_sums, void *stream) {
+  const char *who = "rt_probe_project";
+  i32 count = 0;
+  if (check_probe_params(who, params, n, &count) != 0 || check_probe_paths(who, n, count) != 0) return -1;
+  if (!d_samples) return rt_fail("%s: d_samples is NULL", who);
+  if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if ((uintptr_t)d_samples & 15) return rt_fail("%s: d_samples is not 16-byte aligned", who);
+  if (count == 0) return 0;
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_project(n, count, d_samples, d_sums, (hipStream_t)stream);
+}
+
+extern "C" int rt_probe_resolve(RT_Probe_Params const *params, i64 n, void const *d_sums, void *d_coeffs, void *stream) {
+  const char *who = "rt_probe_resolve";
+  i32 count = 0;
+  if (check_probe_params(who, params, n, &count) != 0) return -1;
+  if (n > RT_PROBE_MAX_PATHS) return rt_fail("%s: too many probes (%lld > 2^30 per call)", who, (long long)n);
+  if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if (!d_coeffs) return rt_fail("%s: d_coeffs is NULL", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_resolve(n, params->samples, d_sums, d_coeffs, (hipStream_t)stream);
+}
+
+// ---- host level ---------------------------------------------------------------------------------------------------------------
+// Probes go through the device in GROUPS of as many whole probes as one slice holds; a probe whose sample range is longer than a
+// slice is a group of its own, traced in several launches by sample range.  The group's 27 sums per probe are zeroed in front of
+// its first launch, added to by every launch's projection, and resolved and copied out behind its last.
+extern "C" int rt_scene_probes(Scene const *scene, RT_Probe_Params const *params, i64 n, Vec3 const *positions, f32 *coeffs, u64 *sums,
+                               RT_Probe_Sample *samples) {
+  const char *who = "rt_scene_probes";
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  i32 count = 0;
+  if (check_probe_params(who, params, n, &count) != 0) return -1;
+  if (!positions) return rt_fail("%s: positions is NULL", who);
+  if (!coeffs && !sums && !samples) return rt_fail("%s: no output is wanted (coeffs, sums and samples are NULL)", who);
+
+  Device &D = dev0();                                            // (the primary device only, whatever rt_device_count() says)
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  ProbeState &S = D.probes;
+  const i64 per = count > 0 && count <= RT_PROBE_SLICE ? RT_PROBE_SLICE / count : 1;      // probes of a group
+  const i32 chunk = count <= RT_PROBE_SLICE ? count : (i32)RT_PROBE_SLICE;                  // samples of a launch
+  const i64 group = n < per ? n : per;
+  HIP_TRY(S.positions.grow((size_t)group * 3));
+  HIP_TRY(S.records.grow((size_t)group * (size_t)(chunk > 0 ? chunk : 1) * 8));
+  HIP_TRY(S.sums.grow((size_t)group * RT_PROBE_SUMS));
+  if (coeffs) HIP_TRY(S.coeffs.grow((size_t)group * RT_PROBE_SUMS));
+  int slot = 0;
+  if (acquire_probe_slot(D, &slot) != 0) return -1;
+  hipStream_t stream = nullptr;
+  RT_Device_Scene *d = nullptr;
+  bool first = true;
+  for (i64 b = 0; b < n; b += per) {
+    const i64 m = n - b < per ? n - b : per;
+    if (count == 0) HIP_TRY(hipMemsetAsync(S.sums, 0, (size_t)m * RT_PROBE_SUMS * 8, stream));      // (an empty range: zero sums)
+    for (i32 f = 0; f < count; f += chunk) {
+      RT_Probe_Params q = *params;
+      q.sample_first = params->sample_first + f;
+      q.sample_count = count - f < chunk ? count - f : chunk;
+      q.probe_first = params->probe_first + (u32)b;
+      auto trace_slice = [&](RT_Device_Scene *ds) -> int {
+        if (f == 0) {
+          HIP_TRY(hipMemcpy(S.positions, positions + b, (size_t)m * 12, hipMemcpyHostToDevice));
+          HIP_TRY(hipMemsetAsync(S.sums, 0, (size_t)m * RT_PROBE_SUMS * 8, stream));
+        }
+        if (enqueue_trace(D, ds, &q, q.sample_count, m, S.positions, S.records, stream, slot, first) != 0) return -1;
+        return (coeffs || sums) ? enqueue_project(m, q.sample_count, S.records, S.sums, stream) : 0;
+      };
+      // the scene is checked behind the first launch (edited since the copy: uploaded, traced again); later ones use that copy
+      if (first) d = scene_checked(D, scene, stream, nullptr, trace_slice);
+      if (!d || (!first && trace_slice(d) != 0)) return -1;
+      first = false;
+      if (samples)      // (m whole probes from sample 0 of the range, or one probe's samples from f: contiguous either way)
+        HIP_TRY(hipMemcpy(samples + (size_t)b * (size_t)count + f, S.records, (size_t)m * (size_t)q.sample_count * sizeof(RT_Probe_Sample),
+                          hipMemcpyDeviceToHost));
+    }
+    if (coeffs) {
+      if (enqueue_resolve(m, params->samples, S.sums, S.coeffs, stream) != 0) return -1;
+      HIP_TRY(hipMemcpy(coeffs + (size_t)b * RT_PROBE_SUMS, S.coeffs, (size_t)m * RT_PROBE_SUMS * 4, hipMemcpyDeviceToHost));
+    }
+    if (sums) HIP_TRY(hipMemcpy(sums + (size_t)b * RT_PROBE_SUMS, S.sums, (size_t)m * RT_PROBE_SUMS * 8, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int rt_get_probe_counters(RT_Counters *out) {
+  if (!out) return rt_fail("rt_get_probe_counters: NULL");
+  memset(out, 0, sizeof *out);
+  Device *Dp = g_probe_dev.load();
+  if (!Dp) return 0;                                           // no probe call yet: zeros
+  Device &D = *Dp;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (D.probes.last < 0 || !D.probes.slots) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long c[8];
+  HIP_TRY(hipMemcpy(c, D.probes.slots + (size_t)D.probes.last * RT_PROBE_SLOT_BYTES, sizeof c, hipMemcpyDeviceToHost));
+  out->paths = c[RT_CNT_PATHS];
+  out->rays = c[RT_CNT_RAYS];
+  out->node_visits = c[RT_CNT_NODES];
+  out->leaf_visits = c[RT_CNT_LEAVES];
+  out->shades = c[RT_CNT_SHADES];
+  out->backgrounds = c[RT_CNT_BG];
+  out->textured = c[RT_CNT_TEXTURED];
   return 0;
 }

@@ -158,6 +158,23 @@ RT_FEATURE_CHANNELS = 10          # coverage, albedo rgb, normal xyz, position x
 RT_MOTION_CHANNELS = 3            # THE MOTION xyz, a buffer of its own (rt_render_features_motion)
 
 
+class RT_Probe_Params(C.Structure):  # rt_hip.h: light probes -- samples per probe, the sample range of a call, the path's constants
+    _fields_ = [("samples", C.c_int32), ("sample_first", C.c_int32), ("sample_count", C.c_int32), ("max_bounces", C.c_int32),
+                ("seed", C.c_uint32), ("probe_first", C.c_uint32)]
+
+
+class RT_Probe_Sample(C.Structure):  # rt_hip.h: one traced sample of a probe
+    _fields_ = [("radiance", f32 * 3), ("t", f32), ("direction", f32 * 3), ("pad", C.c_uint32)]
+
+
+PROBE_SAMPLE_DTYPE = np.dtype([("radiance", "<f4", (3,)), ("t", "<f4"), ("direction", "<f4", (3,)), ("pad", "<u4")])
+assert C.sizeof(RT_Probe_Params) == 24
+assert PROBE_SAMPLE_DTYPE.itemsize == C.sizeof(RT_Probe_Sample) == 32
+RT_PROBE_COEFFS = 9               # real spherical harmonics of bands 0-2
+RT_PROBE_MAX_PATHS = 1 << 30
+RT_PROBE_SLICE = 1 << 21
+
+
 class RT_Guided_Params(C.Structure):  # rt_hip.h: the guided denoiser's parameters
     _fields_ = [("iterations", C.c_int32), ("sigma_color", f32), ("sigma_normal", f32), ("sigma_position", f32),
                 ("demodulate", C.c_int32)]
@@ -246,6 +263,7 @@ EXPORTED_SYMBOLS = [
     "rt_query_closest", "rt_query_occluded", "rt_scene_hits", "rt_scene_closest", "rt_scene_occluded", "rt_get_query_counters",
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
     "rt_render_accumulate_features_motion", "rt_resolve_motion", "rt_render_features_motion",
+    "rt_probe_trace", "rt_probe_project", "rt_probe_resolve", "rt_scene_probes", "rt_get_probe_counters",
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
     "rt_history_destroy", "rt_history_set_motion", "rt_render_temporal",

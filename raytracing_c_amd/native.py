@@ -145,6 +145,12 @@ def _declare(d):
         d.rt_render_accumulate_features.argtypes = [vp, P(abi.RT_Render_Params), vp, vp]
         d.rt_resolve_features.argtypes = [P(abi.RT_Render_Params), vp, vp, vp, vp, vp, vp]
         d.rt_render_features.argtypes = [P(abi.Scene), C.c_int32, C.c_int32, abi.isize, abi.isize, P(abi.RT_Features), vp]
+    if hasattr(d, "rt_scene_probes"):                      # (absent from older builds loaded as A/B partners)
+        d.rt_probe_trace.argtypes = [vp, P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp]
+        d.rt_probe_project.argtypes = [P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp]
+        d.rt_probe_resolve.argtypes = [P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp]
+        d.rt_scene_probes.argtypes = [P(abi.Scene), P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp, vp]
+        d.rt_get_probe_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_guided_denoise"):
         d.rt_guided_work_bytes.argtypes = [C.c_int32, C.c_int32]
         d.rt_guided_work_bytes.restype = C.c_int64
