@@ -456,6 +456,96 @@ extern int rt_scene_probes(Scene const *scene, RT_Probe_Params const *params, i6
  * and rt_get_query_counters() are not affected. */
 extern int rt_get_probe_counters(RT_Counters *out);
 
+/* ---- HDR lightmaps --------------------------------------------------------------------- */
+
+/* The light arriving at the texels of a UV layout: the static-lighting product of this library, beside the probes that light
+ * everything not baked.  lightmap_bake() (rt_raytracer.h) stays the reference's entry point -- one u8 image, 8 bounces, no sRGB;
+ * this is the baker a user runs: a float image, sums that can be filled progressively, device pointers, seam padding.
+ *
+ * THE TEXEL LIST of a map of width x height.  Texel (x, y) is owned by the LAST triangle slot i whose UV triangle accepts the
+ * integer point (x, y): raytracer.c:733-747, p_k = uv_k * (width, height), the weights w0, w1 and w2 = 1 - w0 - w1 in the
+ * reference's association, accepted when all three are >= -EPSILON; texels outside the image are skipped.  The list holds the owned
+ * texels in row-major order of x + y * width.  Entry j, 32 bytes, written with two 16-byte stores: */
+typedef struct { f32 origin[3]; u32 texel; /* x + y * width */ f32 normal[3]; i32 triangle; /* the owning slot */ } RT_Lightmap_Texel;
+/*     normal   = n_a * w0 + n_b * w1 + n_c * w2               NOT normalised, as in the reference
+ *     position = v0 * w0 + v1 * w1 + v2 * w2                  over the ORIGINAL vertices triangles.x/y/z[k][i]
+ *     origin   = position + normal * EPSILON
+ * -- plain f32 * and +, left to right, every operation rounded on its own (every unit is built with -ffp-contract=off).
+ *
+ * THE PATH of list entry j (texel index p = texel_j) and sample s of `samples`:
+ *     state = rt_path_seed(seed, p, (u32)s);  tries = 0
+ *     loop:  d = rt_rand_unit_vec3(&state);  c = dot(d, normal);  tries++      accept when c > 0.0f, give up when tries == 64
+ *     accepted:  L = cast_ray(Ray{origin, d}, max_bounces, &state)            raytracer.c:505-558, the stream going on where the
+ *                sums[j][ch] += rt_accum_quantize(L[ch] * c)                   direction left it; ch = 0..2, u64, 32.32, order-free,
+ *                                                                              NaN and negatives count as 0
+ *     given up (a zero or NaN normal): nothing is cast, nothing is added; the path still counts as a path
+ *     max_bounces == 0: nothing is cast, L = 0, nothing to add
+ *
+ * THE RESOLVE.  image f32[height][width][4]: an owned texel gets {rt_accum_resolve(sum_ch, samples) * scale ..., 1.0f} -- the mean
+ * over ALL `samples`, rounded once, then one f32 multiply; a texel nobody owns gets {0, 0, 0, 0}.  scale = 1.0f gives the number the
+ * reference computes before its u8 store, 6.2831855f the irradiance; the baker does not choose.
+ *
+ * THE DILATION is seam padding, so that a bilinear fetch at a chart's edge reads light and not black: `passes` passes (0-254) over
+ * the resolved image, ping-pong.  In pass k = 1..passes every texel whose .w == 0 in the pass's INPUT visits its eight neighbours,
+ * dy = -1, 0, 1 and inside that dx = -1, 0, 1, skipping the centre and neighbours off the image; n = the number of neighbours with
+ * .w > 0; n == 0 copies the texel; otherwise each colour channel is (((a + b) + c) ...) / (float)n -- f32 adds in visiting order from
+ * the first usable neighbour's value, one IEEE division -- and .w = (float)(1 + k).  Texels with .w > 0 are copied.  A consumer reads
+ * .w == 1 as measured and .w > 1 as filled in pass .w - 1.
+ *
+ * Kernels of their own (csrc/rt_lightmap.hip): an owner pass, a row count, a row scan and an ordered row write for the list;
+ * rt_lightmap_kernel, persistent, a sibling of the probe kernel, lanes refilled from ONE sample-major list of paths, three 64-bit
+ * atomic adds per path that ends; a resolve; a dilation pass over 32 x 8 tiles staged in LDS.  Frames, queries, probes, lightmap_bake
+ * and their counters are not affected. */
+#define RT_LIGHTMAP_MAX_TEXELS ((i64)1 << 28)
+#define RT_LIGHTMAP_MAX_PATHS  ((i64)1 << 30)
+#define RT_LIGHTMAP_MAX_PASSES 254
+typedef struct {
+  i32 width, height;           /* the map                                                                                      */
+  i32 samples;                 /* samples per texel: what the image is the mean over                                            */
+  i32 sample_first;            /* a trace call runs samples [sample_first, sample_first + sample_count) of its texels ...      */
+  i32 sample_count;            /* ... 0 = all of them                                                                          */
+  i32 max_bounces;
+  u32 seed;
+  f32 scale;                   /* the resolve's factor                                                                         */
+} RT_Lightmap_Params;          /* 32 bytes */
+
+/* Device level: every pointer is a DEVICE pointer owned by the caller, on the device the scene was uploaded to (resolve and dilate:
+ * the primary device); the calls only enqueue work on `stream` (NULL = default stream); nothing synchronises.
+ *   d_vertices : f32[slots][9], per slot x0 x1 x2 y0 y1 y2 z0 z1 z2 of the original vertices (triangles.x/y/z[k][i])
+ *   d_owner    : i32[width x height + height] scratch: the owners (-1 = none), then the rows' list offsets
+ *   d_texels   : RT_Lightmap_Texel[width x height] (room for every texel; the list fills the front), 16-byte aligned
+ *   d_count    : i64, the list's length n -- what a caller reads back before it sizes the sums and picks texel ranges
+ *   d_sums     : u64[n][3], indexed by LIST entry, zero before the first range; rt_lightmap_trace ADDS (atomics), so a buffer is
+ *                filled progressively by sample ranges and by texel ranges [texel_first, texel_first + texel_count)
+ *   d_image    : f32[height][width][4], 16-byte aligned;  d_work: rt_lightmap_work_bytes() bytes, 16-byte aligned, not d_image
+ * Refused before a device is touched, each with a text of its own in rt_last_error(): a NULL argument; width or height <= 0;
+ * width x height > 2^28; samples <= 0; a sample range outside [0, samples]; max_bounces < 0; a texel range that is empty, negative
+ * or ends beyond width x height (the list cannot be longer; its true length is the caller's to respect); texel_count x sample_count
+ * > 2^30 (the kernel holds path indices in 32-bit integers); n_texels outside [0, width x height]; passes outside [0, 254]; a
+ * misaligned pointer.  A refused call leaves its outputs untouched.  0 on success, -1 + rt_last_error(). */
+extern int rt_lightmap_texels(RT_Device_Scene *dscene, void const *d_vertices, i32 width, i32 height, void *d_owner, void *d_texels,
+                              void *d_count, void *stream);
+extern int rt_lightmap_trace(RT_Device_Scene *dscene, RT_Lightmap_Params const *params, void const *d_texels, i64 texel_first,
+                             i64 texel_count, void *d_sums, void *stream);
+extern int rt_lightmap_resolve(RT_Lightmap_Params const *params, i64 n_texels, void const *d_texels, void const *d_sums, void *d_image,
+                               void *stream);
+extern i64 rt_lightmap_work_bytes(i32 width, i32 height);      /* -1 + rt_last_error() for a size the calls refuse */
+extern int rt_lightmap_dilate(i32 width, i32 height, i32 passes, void *d_image, void *d_work, void *stream);
+
+/* Host level: list, trace, resolve and dilation from a host Scene to host memory, on the cached device copy of `scene` with
+ * rt_render_frame()'s scene check and device lock, on the NULL stream, on the PRIMARY device only.  image f32[height][width][4]
+ * (required); sums u64[n][3] (the sums of THIS call's sample range, from zero), texels RT_Lightmap_Texel[n] and *n_texels are
+ * optional -- a caller who wants sums or texels passes room for width x height entries.  The list is traced in launches of at most
+ * 2^21 paths (RT_LIGHTMAP_SLICE): sample ranges of the whole list, or texel ranges of one sample where the list is longer than a
+ * slice.  The same refusals (texels x sample_count is not bounded here). */
+#define RT_LIGHTMAP_SLICE ((i64)1 << 21)
+extern int rt_scene_lightmap(Scene const *scene, RT_Lightmap_Params const *params, i32 dilate_passes, f32 *image, u64 *sums,
+                             RT_Lightmap_Texel *texels, i64 *n_texels);
+
+/* Counters of the last lightmap trace of this process (device or host level; a host call's launches summed), as
+ * rt_get_probe_counters().  Synchronises.  The other counters are not affected. */
+extern int rt_get_lightmap_counters(RT_Counters *out);
+
 /* ---- guided denoiser ------------------------------------------------------------------ */
 
 /* An edge-stopping a-trous filter (Dammertz et al. 2010) of the linear frame, steered by the feature buffers above: what turns the

@@ -13,6 +13,8 @@ from .query import closest_hits, occluded, closest_hits_device, occluded_device,
 from .features import render_features   # noqa: F401
 from .probes import (bake_probes, bake_probes_device, probe_grid, sh9_basis, sh9_radiance, sh9_irradiance, probe_visibility,   # noqa: F401
                      get_probe_counters)
+from .lightmap import (bake_lightmap, bake_lightmap_device, lightmap_texels, dilate_lightmap, lightmap_vertices,   # noqa: F401
+                       get_lightmap_counters)
 from .guided import guided_denoise, render_denoised   # noqa: F401
 from .temporal import temporal_accumulate, render_temporal, History   # noqa: F401
 from .variance import temporal_accumulate_moments, guided_denoise_variance, render_svgf   # noqa: F401

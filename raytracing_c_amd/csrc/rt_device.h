@@ -217,6 +217,24 @@ typedef struct {
 #define RT_PROBE_RECORD_F4 2   /* float4 per RT_Probe_Sample */
 #define RT_PROBE_SUMS      27  /* u64 per probe: 9 coefficients x rgb, k-major */
 
+/* HDR lightmaps (rt_lightmap_kernel, rt_lightmap.hip; include/rt_hip.h rt_lightmap_trace): what one launch reads and adds to
+ * besides the scene fields of RT_KParams (max_bounces and seed among them).  The work list is SAMPLE-MAJOR: path idx in
+ * [0, n_paths) is sample sample_first + idx / m of list entry texel_first + idx % m, so that neighbouring lanes hold
+ * neighbouring texels of one sample index. */
+typedef struct {
+  const float *texels;         /* RT_Lightmap_Texel[]: origin, texel index, normal, triangle -- two float4 per entry      */
+  unsigned long long *sums;    /* u64[entries][3], 32.32 -- added to with atomics                                         */
+  uint32_t    *head;           /* paths handed out so far (zero at launch)                                                */
+  unsigned long long *counters;/* RT_Counters layout (RT_CNT_PATHS .. RT_CNT_TEXTURED) -- added to                        */
+  int32_t      n_paths;        /* m * sample_count, at most 2^30                                                          */
+  int32_t      m, texel_first; /* the list range of this launch                                                           */
+  int32_t      sample_first;
+  int32_t      grab;           /* paths a wave takes per atomic on `head`                                                 */
+  int32_t      exit_lanes;     /* finished lanes that end a traversal call while paths are left to hand out               */
+} RT_LParams;
+#define RT_LIGHTMAP_TEXEL_F4 2 /* float4 per RT_Lightmap_Texel */
+#define RT_LIGHTMAP_TRIES   64 /* directions tried per sample before the path is given up (raytracer.c:768-772)           */
+
 /* Temporal accumulation (rt_temporal_kernel, rt_temporal.hip; include/rt_hip.h rt_temporal_accumulate): a camera as proj() of the
  * contract reads it, and what the host computes once per launch. */
 typedef struct {

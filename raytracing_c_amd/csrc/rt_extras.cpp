@@ -50,6 +50,318 @@ extern "C" void lightmap_bake(Image const *lightmap, Scene const *scene, isize s
   lightmap_bake_locked(D, lightmap, scene, samples);
 }
 
+// ==== HDR lightmaps (include/rt_hip.h, "HDR lightmaps") ========================================================================
+// The baker a user runs: the texel list of a UV layout, path-traced 32.32 sums per list entry that can be filled by sample and texel
+// ranges, a float image and seam padding -- on the device level (device pointers, launches on the caller's stream) and on the host
+// level (the cached device copy of a Scene through scene_checked, slices of RT_LIGHTMAP_SLICE paths).  The work is the kernels of
+// rt_lightmap.hip; nothing here rasterises, traces or filters on the CPU.  lightmap_bake above stays the reference's entry point.
+
+static_assert(sizeof(RT_Lightmap_Texel) == 32 && sizeof(RT_Lightmap_Texel) == RT_LIGHTMAP_TEXEL_F4 * 16, "RT_Lightmap_Texel is two 16-byte stores");
+static_assert(sizeof(RT_Lightmap_Params) == 32, "RT_Lightmap_Params");
+static_assert(RT_CNT_TEXTURED < 8, "the lightmap counters fit the slot's eight words");
+
+static std::atomic<Device *> g_lightmap_dev{nullptr};   // the device of the most recent lightmap trace (rt_get_lightmap_counters)
+
+static int check_lightmap_size(const char *who, i32 width, i32 height) {
+  if (width <= 0 || height <= 0) return rt_fail("%s: width and height must be positive (got %d x %d)", who, width, height);
+  if ((i64)width * height > RT_LIGHTMAP_MAX_TEXELS) return rt_fail("%s: the map is too large (%d x %d > 2^28 texels)", who, width, height);
+  return 0;
+}
+
+// What can be checked without the device.  *count = the sample range's length (0 = all resolved).
+static int check_lightmap_params(const char *who, RT_Lightmap_Params const *p, i32 *count) {
+  if (!p) return rt_fail("%s: lightmap params are NULL", who);
+  if (check_lightmap_size(who, p->width, p->height) != 0) return -1;
+  if (p->samples <= 0) return rt_fail("%s: samples must be positive (got %d)", who, p->samples);
+  if (p->sample_first < 0 || p->sample_count < 0 || (i64)p->sample_first + p->sample_count > p->samples)
+    return rt_fail("%s: sample range [%d, +%d) outside [0, %d]", who, p->sample_first, p->sample_count, p->samples);
+  if (p->max_bounces < 0) return rt_fail("%s: max_bounces must be >= 0 (got %d)", who, p->max_bounces);
+  *count = p->sample_count ? p->sample_count : p->samples - p->sample_first;
+  return 0;
+}
+
+static int check_lightmap_passes(const char *who, i32 passes) {
+  if (passes < 0 || passes > RT_LIGHTMAP_MAX_PASSES) return rt_fail("%s: passes must be within [0, 254] (got %d)", who, passes);
+  return 0;
+}
+
+void release_lightmap_state(Device &D) {
+  D.lightmap = LightmapState();
+  Device *self = &D;
+  g_lightmap_dev.compare_exchange_strong(self, nullptr);
+}
+
+// The ring slot of a new lightmap call: the query ring's next slot (its event orders the reuse) and this ring's words of it.
+static int acquire_lightmap_slot(Device &D, int *slot) {
+  if (ensure_query_state(D) != 0) return -1;
+  HIP_TRY(D.lightmap.slots.grow(RT_QUERY_SLOTS * RT_PROBE_SLOT_BYTES));
+  if (acquire_slot(D, slot, false) != 0) return -1;
+  D.lightmap.last = *slot;
+  g_lightmap_dev.store(&D);
+  return 0;
+}
+
+// Enqueues the four kernels of the texel list on `stream`.  D.mutex held, D's GPU current, every pointer on D.
+static int enqueue_lightmap_texels(RT_Device_Scene *d, const float *verts, i32 width, i32 height, int *owner, float *texels,
+                                   long long *count, hipStream_t stream) {
+  const size_t pixels = (size_t)width * (size_t)height;
+  HIP_TRY(hipMemsetAsync(owner, 0xFF, pixels * sizeof(int), stream));                      // owner = -1
+  int rc = rt_launch_lightmap_texels(d->tris, verts, d->n_triangles, width, height, owner, owner + pixels, texels, count, stream);
+  if (rc != 0) return rt_fail("lightmap texel kernels launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// Enqueues one launch of the lightmap kernel on `stream`: list entries [j0, j0 + m) x samples [s0, s0 + c).  `fresh`: the slot's
+// counters start at zero (the first launch of a call); its work counter always does.  D.mutex held, D's GPU current.
+static int enqueue_lightmap_trace(Device &D, RT_Device_Scene *d, RT_Lightmap_Params const *q, i32 s0, i32 c, const float *texels, i64 j0,
+                                  i64 m, unsigned long long *sums, hipStream_t stream, int slot, bool fresh) {
+  uint8_t *sl = D.lightmap.slots + (size_t)slot * RT_PROBE_SLOT_BYTES;
+  if (fresh) HIP_TRY(hipMemsetAsync(sl, 0, RT_PROBE_SLOT_BYTES, stream));
+  else HIP_TRY(hipMemsetAsync(sl + 64, 0, 4, stream));
+  RT_KParams K;
+  scene_only_kparams(&K, d);
+  K.max_bounces = q->max_bounces;
+  K.seed = q->seed;
+  RT_LParams R;
+  memset(&R, 0, sizeof R);
+  R.texels = texels;
+  R.sums = sums;
+  R.counters = (unsigned long long *)sl;
+  R.head = (uint32_t *)(sl + 64);
+  const int64_t n_paths = m * (int64_t)c;
+  R.n_paths = (int32_t)n_paths;
+  R.m = (int32_t)m;
+  R.texel_first = (int32_t)j0;
+  R.sample_first = s0;
+
+  // launch geometry: the probe kernel's (rt_query.cpp) -- one workgroup of 16 waves per CU, the tree fills the LDS beside the waves'
+  // perm stacks and the kernel's static sRGB scale table
+  const int wg_waves = 16, wg_lanes = wg_waves * 64;
+  const LdsSplit S = lds_split(d, K.depth, wg_waves, 0, 1, true);
+  K.n_lds_nodes = S.n_lds_nodes;
+  int64_t blocks = (n_paths + wg_lanes - 1) / wg_lanes;
+  if (blocks > D.num_cus) blocks = D.num_cus;
+  if (blocks < 1) blocks = 1;
+  // paths per grab: an eighth of a wave's mean share, in whole wave-fulls, within [64, 512] (why: rt_query_kernel)
+  const int64_t grab = n_paths / (blocks * wg_waves * 8) / 64 * 64;
+  R.grab = grab < 64 ? 64 : (grab > 512 ? 512 : (int)grab);
+  R.exit_lanes = knob_int("RT_LIGHTMAP_EXIT", 48);                // (the probe kernel's: the S block behind it is the same)
+  if (R.exit_lanes < 1 || R.exit_lanes > 64) R.exit_lanes = 48;
+  int rc = rt_launch_lightmap_trace(&K, &R, (int)blocks, S.smem, stream);
+  if (rc != 0) return rt_fail("lightmap kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  HIP_TRY(hipEventRecord(D.query.done[slot], stream));
+  return 0;
+}
+
+static int enqueue_lightmap_resolve(RT_Lightmap_Params const *p, i64 n, const void *texels, const void *sums, void *image, hipStream_t stream) {
+  const size_t pixels = (size_t)p->width * (size_t)p->height;
+  HIP_TRY(hipMemsetAsync(image, 0, pixels * 16, stream));                                  // a texel nobody owns: {0, 0, 0, 0}
+  if (n == 0) return 0;
+  int rc = rt_launch_lightmap_resolve((long long)n, (long long)pixels, p->samples, p->scale, (const float *)texels,
+                                      (const unsigned long long *)sums, (float *)image, stream);
+  if (rc != 0) return rt_fail("lightmap resolve kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// `passes` launches, ping-pong between image and work; an odd number ends with one copy back into image
+static int enqueue_lightmap_dilate(i32 width, i32 height, i32 passes, void *image, void *work, hipStream_t stream) {
+  float *src = (float *)image, *dst = (float *)work;
+  for (i32 k = 1; k <= passes; k++) {
+    int rc = rt_launch_lightmap_dilate(width, height, k, src, dst, stream);
+    if (rc != 0) return rt_fail("lightmap dilation kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    std::swap(src, dst);
+  }
+  if (src != (float *)image) HIP_TRY(hipMemcpyAsync(image, src, (size_t)width * (size_t)height * 16, hipMemcpyDeviceToDevice, stream));
+  return 0;
+}
+
+// ---- device level -------------------------------------------------------------------------------------------------------------
+extern "C" int rt_lightmap_texels(RT_Device_Scene *dscene, void const *d_vertices, i32 width, i32 height, void *d_owner, void *d_texels,
+                                  void *d_count, void *stream) {
+  const char *who = "rt_lightmap_texels";
+  // (everything that can be checked without the device is checked before it is touched)
+  if (!dscene) return rt_fail("%s: device scene is NULL", who);
+  if (check_lightmap_size(who, width, height) != 0) return -1;
+  if (!d_vertices) return rt_fail("%s: d_vertices is NULL", who);
+  if (!d_owner) return rt_fail("%s: d_owner is NULL", who);
+  if (!d_texels) return rt_fail("%s: d_texels is NULL", who);
+  if (!d_count) return rt_fail("%s: d_count is NULL", who);
+  if ((uintptr_t)d_texels & 15) return rt_fail("%s: d_texels is not 16-byte aligned", who);
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  return enqueue_lightmap_texels(dscene, (const float *)d_vertices, width, height, (int *)d_owner, (float *)d_texels, (long long *)d_count,
+                                 (hipStream_t)stream);
+}
+
+extern "C" int rt_lightmap_trace(RT_Device_Scene *dscene, RT_Lightmap_Params const *params, void const *d_texels, i64 texel_first,
+                                 i64 texel_count, void *d_sums, void *stream) {
+  const char *who = "rt_lightmap_trace";
+  if (!dscene) return rt_fail("%s: device scene is NULL", who);
+  i32 count = 0;
+  if (check_lightmap_params(who, params, &count) != 0) return -1;
+  if (!d_texels) return rt_fail("%s: d_texels is NULL", who);
+  if (!d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if ((uintptr_t)d_texels & 15) return rt_fail("%s: d_texels is not 16-byte aligned", who);
+  if (texel_first < 0 || texel_count <= 0 || texel_first + texel_count > (i64)params->width * params->height)
+    return rt_fail("%s: texel range [%lld, +%lld) outside the list (at most %d x %d entries)", who, (long long)texel_first,
+                   (long long)texel_count, params->width, params->height);
+  if (texel_count * (i64)count > RT_LIGHTMAP_MAX_PATHS)
+    return rt_fail("%s: too many paths (%lld texels x %d samples > 2^30 per call)", who, (long long)texel_count, count);
+  if (count == 0) return 0;                                     // (an empty range at the end of the samples: nothing to trace)
+  Device &D = *dscene->dev;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  int slot = 0;
+  if (acquire_lightmap_slot(D, &slot) != 0) return -1;
+  return enqueue_lightmap_trace(D, dscene, params, params->sample_first, count, (const float *)d_texels, texel_first, texel_count,
+                                (unsigned long long *)d_sums, (hipStream_t)stream, slot, true);
+}
+
+extern "C" int rt_lightmap_resolve(RT_Lightmap_Params const *params, i64 n_texels, void const *d_texels, void const *d_sums, void *d_image,
+                                   void *stream) {
+  const char *who = "rt_lightmap_resolve";
+  i32 count = 0;
+  if (check_lightmap_params(who, params, &count) != 0) return -1;
+  if (n_texels < 0 || n_texels > (i64)params->width * params->height)
+    return rt_fail("%s: n_texels %lld outside [0, %d x %d]", who, (long long)n_texels, params->width, params->height);
+  if (!d_image) return rt_fail("%s: d_image is NULL", who);
+  if (n_texels > 0 && !d_texels) return rt_fail("%s: d_texels is NULL", who);
+  if (n_texels > 0 && !d_sums) return rt_fail("%s: d_sums is NULL", who);
+  if (((uintptr_t)d_texels | (uintptr_t)d_image) & 15) return rt_fail("%s: d_texels or d_image is not 16-byte aligned", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_lightmap_resolve(params, n_texels, d_texels, d_sums, d_image, (hipStream_t)stream);
+}
+
+extern "C" i64 rt_lightmap_work_bytes(i32 width, i32 height) {
+  if (check_lightmap_size("rt_lightmap_work_bytes", width, height) != 0) return -1;
+  return (i64)width * height * 16;
+}
+
+extern "C" int rt_lightmap_dilate(i32 width, i32 height, i32 passes, void *d_image, void *d_work, void *stream) {
+  const char *who = "rt_lightmap_dilate";
+  if (check_lightmap_size(who, width, height) != 0 || check_lightmap_passes(who, passes) != 0) return -1;
+  if (!d_image) return rt_fail("%s: d_image is NULL", who);
+  if (!d_work) return rt_fail("%s: d_work is NULL", who);
+  if (d_image == d_work) return rt_fail("%s: d_image and d_work must differ", who);
+  if (((uintptr_t)d_image | (uintptr_t)d_work) & 15) return rt_fail("%s: d_image or d_work is not 16-byte aligned", who);
+  Device &D = dev0();
+  {
+    std::lock_guard<std::mutex> lock(D.mutex);
+    if (ensure_device(D) != 0) return -1;
+  }
+  return enqueue_lightmap_dilate(width, height, passes, d_image, d_work, (hipStream_t)stream);
+}
+
+// ---- host level ---------------------------------------------------------------------------------------------------------------
+// The list goes through the device in launches of at most RT_LIGHTMAP_SLICE paths: sample ranges of the whole list, or -- where one
+// sample of the list exceeds a slice -- texel ranges of one sample.  Launch k of a call, from the list's length n:
+static void lightmap_slice(i64 n, i32 count, i64 k, i64 *j0, i64 *m, i32 *s, i32 *c) {
+  if (n <= RT_LIGHTMAP_SLICE) {
+    const i64 per = RT_LIGHTMAP_SLICE / n;
+    *j0 = 0, *m = n, *s = (i32)(k * per), *c = (i32)(count - *s < per ? count - *s : per);
+  } else {
+    const i64 parts = (n + RT_LIGHTMAP_SLICE - 1) / RT_LIGHTMAP_SLICE;
+    *j0 = (k % parts) * RT_LIGHTMAP_SLICE, *m = n - *j0 < RT_LIGHTMAP_SLICE ? n - *j0 : RT_LIGHTMAP_SLICE, *s = (i32)(k / parts), *c = 1;
+  }
+}
+static i64 lightmap_slices(i64 n, i32 count) {
+  if (n <= 0 || count <= 0) return 0;
+  if (n <= RT_LIGHTMAP_SLICE) { const i64 per = RT_LIGHTMAP_SLICE / n; return (count + per - 1) / per; }
+  return (i64)count * ((n + RT_LIGHTMAP_SLICE - 1) / RT_LIGHTMAP_SLICE);
+}
+
+extern "C" int rt_scene_lightmap(Scene const *scene, RT_Lightmap_Params const *params, i32 dilate_passes, f32 *image, u64 *sums,
+                                 RT_Lightmap_Texel *texels, i64 *n_texels) {
+  const char *who = "rt_scene_lightmap";
+  if (!scene) return rt_fail("%s: scene is NULL", who);
+  i32 count = 0;
+  if (check_lightmap_params(who, params, &count) != 0 || check_lightmap_passes(who, dilate_passes) != 0) return -1;
+  if (!image) return rt_fail("%s: image is NULL", who);
+
+  Device &D = dev0();                                            // (the primary device only, whatever rt_device_count() says)
+  std::lock_guard<std::mutex> lock(D.mutex);
+  if (ensure_device(D) != 0) return -1;
+  LightmapState &S = D.lightmap;
+  const i32 width = params->width, height = params->height;
+  const size_t pixels = (size_t)width * (size_t)height;
+  HIP_TRY(S.owner.grow(pixels + (size_t)height));
+  HIP_TRY(S.texels.grow(pixels * 8));
+  HIP_TRY(S.count.grow(1));
+  HIP_TRY(S.image.grow(pixels * 4));
+  if (dilate_passes > 0) HIP_TRY(S.work.grow(pixels * 4));
+  int slot = 0;
+  if (acquire_lightmap_slot(D, &slot) != 0) return -1;
+  hipStream_t stream = nullptr;
+  long long n = 0;
+  auto trace_slice = [&](RT_Device_Scene *ds, i64 k) -> int {
+    i64 j0, m;
+    i32 s, c;
+    lightmap_slice(n, count, k, &j0, &m, &s, &c);
+    return enqueue_lightmap_trace(D, ds, params, params->sample_first + s, c, S.texels, j0, m, S.sums, stream, slot, k == 0);
+  };
+  // the first launch's enqueue: the vertices as lightmap_bake uploads them, the list, its length, sums from zero -- so that a scene
+  // check that traces again starts from zero, on the list of the scene as it is
+  auto first_slice = [&](RT_Device_Scene *ds) -> int {
+    const Triangles &T = scene->triangles;
+    std::vector<float> verts((size_t)T.len * 9);
+    for (int i = 0; i < T.len; i++)
+      for (int v = 0; v < 3; v++) {
+        verts[(size_t)i * 9 + 0 + v] = T.x[v][i];
+        verts[(size_t)i * 9 + 3 + v] = T.y[v][i];
+        verts[(size_t)i * 9 + 6 + v] = T.z[v][i];
+      }
+    if (ds->n_triangles != (int)T.len) return rt_fail("%s: the device copy has another shape", who);
+    HIP_TRY(S.verts.grow(verts.size()));
+    HIP_TRY(hipMemcpy(S.verts, verts.data(), verts.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (enqueue_lightmap_texels(ds, S.verts, width, height, S.owner, S.texels, S.count, stream) != 0) return -1;
+    HIP_TRY(hipMemcpy(&n, S.count, sizeof n, hipMemcpyDeviceToHost));
+    HIP_TRY(S.sums.grow((size_t)(n > 0 ? n : 1) * 3));
+    HIP_TRY(hipMemsetAsync(S.slots + (size_t)slot * RT_PROBE_SLOT_BYTES, 0, RT_PROBE_SLOT_BYTES, stream));      // (a call without a launch counts nothing)
+    HIP_TRY(hipMemsetAsync(S.sums, 0, (size_t)(n > 0 ? n : 1) * 24, stream));
+    return lightmap_slices(n, count) > 0 ? trace_slice(ds, 0) : 0;
+  };
+  RT_Device_Scene *d = scene_checked(D, scene, stream, nullptr, first_slice);
+  if (!d) return -1;
+  for (i64 k = 1, kn = lightmap_slices(n, count); k < kn; k++)
+    if (trace_slice(d, k) != 0) return -1;
+  if (enqueue_lightmap_resolve(params, n, S.texels, S.sums, S.image, stream) != 0) return -1;
+  if (enqueue_lightmap_dilate(width, height, dilate_passes, S.image, S.work, stream) != 0) return -1;
+  HIP_TRY(hipMemcpy(image, S.image, pixels * 16, hipMemcpyDeviceToHost));
+  if (sums && n > 0) HIP_TRY(hipMemcpy(sums, S.sums, (size_t)n * 24, hipMemcpyDeviceToHost));
+  if (texels && n > 0) HIP_TRY(hipMemcpy(texels, S.texels, (size_t)n * sizeof(RT_Lightmap_Texel), hipMemcpyDeviceToHost));
+  if (n_texels) *n_texels = n;
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int rt_get_lightmap_counters(RT_Counters *out) {
+  if (!out) return rt_fail("rt_get_lightmap_counters: NULL");
+  memset(out, 0, sizeof *out);
+  Device *Dp = g_lightmap_dev.load();
+  if (!Dp) return 0;                                           // no lightmap trace yet: zeros
+  Device &D = *Dp;
+  std::lock_guard<std::mutex> lock(D.mutex);
+  DeviceGuard guard(D);
+  if (D.lightmap.last < 0 || !D.lightmap.slots) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long c[8];
+  HIP_TRY(hipMemcpy(c, D.lightmap.slots + (size_t)D.lightmap.last * RT_PROBE_SLOT_BYTES, sizeof c, hipMemcpyDeviceToHost));
+  out->paths = c[RT_CNT_PATHS];
+  out->rays = c[RT_CNT_RAYS];
+  out->node_visits = c[RT_CNT_NODES];
+  out->leaf_visits = c[RT_CNT_LEAVES];
+  out->shades = c[RT_CNT_SHADES];
+  out->backgrounds = c[RT_CNT_BG];
+  out->textured = c[RT_CNT_TEXTURED];
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------
 // scene_init on the GPU (csrc/rt_build.hip): same Scene, byte for byte, as scene_init()
 

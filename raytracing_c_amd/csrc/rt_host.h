@@ -11,7 +11,8 @@
 //                     adaptive sampling: the merge and the per-chunk resolve on the device level, the frame whose chunks double their
 //                     samples until their error settles (rt_render_adaptive)
 //   rt_multi.cpp      a frame spread over N devices, with one persistent host thread per device slot
-//   rt_extras.cpp     lightmap bake, GPU BVH build and refit, the u8 denoiser
+//   rt_extras.cpp     lightmap bake, HDR lightmaps (texel list, trace, resolve, dilation: device level and host level), GPU BVH build and
+//                     refit, the u8 denoiser
 //   rt_post.cpp       what runs on a frame and its feature planes: guided denoiser (the a-trous filter), temporal accumulation (the
 //                     reprojected history) and the moments, variance and variance-guided filter on top of them, each on the device level, on the host level and behind a frame (one pipeline);
 //                     a stage reads one RT_Frame (rt_device.h) and is launched in one place, which chooses its plain or variance / moments kernel;
@@ -90,6 +91,13 @@ int rt_launch_motion_resolve(int n_pixels, int samples, const unsigned long long
 int rt_launch_probes(const RT_KParams *P, const RT_PParams *R, int n_blocks, int smem_bytes, hipStream_t stream);
 int rt_launch_probe_project(int n_probes, int sample_count, const float *records, unsigned long long *sums, hipStream_t stream);
 int rt_launch_probe_resolve(long long n_coeffs, int samples, const unsigned long long *sums, float *coeffs, hipStream_t stream);
+// ... in rt_lightmap.hip
+int rt_launch_lightmap_texels(const float *tris, const float *verts, int n_tris, int lw, int lh, int *owner, int *rows, float *texels,
+                              long long *count, hipStream_t stream);
+int rt_launch_lightmap_trace(const RT_KParams *P, const RT_LParams *R, int n_blocks, int smem_bytes, hipStream_t stream);
+int rt_launch_lightmap_resolve(long long n, long long n_pixels, int samples, float scale, const float *texels,
+                               const unsigned long long *sums, float *image, hipStream_t stream);
+int rt_launch_lightmap_dilate(int width, int height, int pass, const float *src, float *dst, hipStream_t stream);
 // ... in rt_refit.hip
 int rt_launch_refit(int len, int depth, int n_internal, const void *d_src, const int *d_source_of_slot, float *d_block, float *d_nodes,
                     float *d_leaves, float *d_tris, unsigned char *d_populated, unsigned int *d_max_edge_bits, hipStream_t stream);
@@ -303,6 +311,21 @@ struct ProbeState {
   DevMem<float>              coeffs;          // [probes of a slice][27]
 };
 
+// HDR lightmaps (rt_extras.cpp).  Like ProbeState: a ring of 128-byte slots of its own for what a lightmap launch writes besides
+// its sums, indexed like the query ring and taken with it, so that rt_get_lightmap_counters() shares no word with the queries' or
+// the probes' counters.  The other buffers serve the host-level call; they are kept between calls and given back with the device
+// slot (release_staging).
+struct LightmapState {
+  DevMem<uint8_t>            slots;           // [RT_QUERY_SLOTS][128]: counters u64[8] at +0 (RT_CNT_PATHS .. RT_CNT_TEXTURED), work counter u32 at +64
+  int                        last = -1;       // slot of the most recent lightmap trace (rt_get_lightmap_counters)
+  DevMem<float>              verts;           // [slots][9] original vertices
+  DevMem<int>                owner;           // [width x height + height]: owners, then the rows' list offsets
+  DevMem<float>              texels;          // [width x height][8]
+  DevMem<long long>          count;           // the list's length
+  DevMem<unsigned long long> sums;            // [list entries][3]
+  DevMem<float>              image, work;     // [height][width][4] each
+};
+
 // The four planes of such a buffer, to write (the resolve) ...
 static inline RT_Features split_feature_planes(float *planes, size_t pixels) {
   return {planes, planes + pixels, planes + pixels * 4, planes + pixels * 7};
@@ -410,6 +433,7 @@ struct Device {
   QueryState query;
   FeatureState features;
   ProbeState probes;
+  LightmapState lightmap;
   GuidedState guided;
   RefitState refit;
   TemporalState temporal;
@@ -656,6 +680,9 @@ int  enqueue_feature_pass(Device &D, RT_Device_Scene *d, Camera const *cam, RT_R
 
 // rt_query.cpp, light probes
 void release_probe_state(Device &D);                                                // release_staging()'s part here
+
+// rt_extras.cpp, HDR lightmaps
+void release_lightmap_state(Device &D);                                             // release_staging()'s part here
 
 // rt_post.cpp
 void release_temporal_state(Device &D);                                             // release_staging()'s part here

@@ -653,19 +653,8 @@ __global__ void rt_untile_kernel(int width, int height, int chunks_x, int n_chun
 // (the reference's sequential loop overwrites in triangle order); pass 2 bakes each owned texel:
 // `samples` cosine-weighted paths of 8 bounces from the interpolated surface point.
 
-// barycentric weights of texel (x, y) for the UV triangle (p0, p1, p2), raytracer.c:733-747
-__device__ __forceinline__ bool lightmap_weights(float p0x, float p0y, float p1x, float p1y, float p2x, float p2y,
-                                                 int x, int y, float &w0, float &w1, float &w2) {
-  float denom = (p1y - p2y) * (p0x - p2x) + (p2x - p1x) * (p0y - p2y);
-  float px = (float)x, py = (float)y;
-  w0 = ((p1y - p2y) * (px - p2x) + (p2x - p1x) * (py - p2y)) / denom;
-  w1 = ((p2y - p0y) * (px - p2x) + (p0x - p2x) * (py - p2y)) / denom;
-  w2 = 1.0f - w0 - w1;
-  return w0 >= -RT_EPS && w1 >= -RT_EPS && w2 >= -RT_EPS;
-}
-
-__device__ __forceinline__ float min3f(float a, float b, float c) { float m = b < c ? b : c; return a < m ? a : m; }
-__device__ __forceinline__ float max3f(float a, float b, float c) { float m = b > c ? b : c; return a > m ? a : m; }
+// (the acceptance test, raytracer.c:733-747, and min3f / max3f: one text, shared with rt_lightmap.hip)
+#include "rt_lightmap_weights.hip.h"
 
 __global__ void rt_lightmap_owner_kernel(RT_KParams P, int n_tris, int lw, int lh, int *owner) {
   int i = blockIdx.x;

@@ -81,6 +81,7 @@ void release_staging(Device &D) {
   release_query_state(D);                       // (also forgets that D was the last device to answer a query)
   D.features = FeatureState();
   release_probe_state(D);                       // (also forgets that D was the last device to trace probes)
+  release_lightmap_state(D);                    // (likewise for lightmaps)
   D.guided = GuidedState();
   D.refit = RefitState();
   D.upsample = UpsampleState();

@@ -175,6 +175,24 @@ RT_PROBE_MAX_PATHS = 1 << 30
 RT_PROBE_SLICE = 1 << 21
 
 
+class RT_Lightmap_Params(C.Structure):  # rt_hip.h: HDR lightmaps -- the map, samples per texel, the sample range of a call, the path's constants
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
+                ("sample_count", C.c_int32), ("max_bounces", C.c_int32), ("seed", C.c_uint32), ("scale", f32)]
+
+
+class RT_Lightmap_Texel(C.Structure):  # rt_hip.h: one entry of a map's texel list
+    _fields_ = [("origin", f32 * 3), ("texel", C.c_uint32), ("normal", f32 * 3), ("triangle", C.c_int32)]
+
+
+LIGHTMAP_TEXEL_DTYPE = np.dtype([("origin", "<f4", (3,)), ("texel", "<u4"), ("normal", "<f4", (3,)), ("triangle", "<i4")])
+assert C.sizeof(RT_Lightmap_Params) == 32
+assert LIGHTMAP_TEXEL_DTYPE.itemsize == C.sizeof(RT_Lightmap_Texel) == 32
+RT_LIGHTMAP_MAX_TEXELS = 1 << 28
+RT_LIGHTMAP_MAX_PATHS = 1 << 30
+RT_LIGHTMAP_MAX_PASSES = 254
+RT_LIGHTMAP_SLICE = 1 << 21
+
+
 class RT_Guided_Params(C.Structure):  # rt_hip.h: the guided denoiser's parameters
     _fields_ = [("iterations", C.c_int32), ("sigma_color", f32), ("sigma_normal", f32), ("sigma_position", f32),
                 ("demodulate", C.c_int32)]
@@ -264,6 +282,8 @@ EXPORTED_SYMBOLS = [
     "rt_render_accumulate_features", "rt_resolve_features", "rt_render_features",
     "rt_render_accumulate_features_motion", "rt_resolve_motion", "rt_render_features_motion",
     "rt_probe_trace", "rt_probe_project", "rt_probe_resolve", "rt_scene_probes", "rt_get_probe_counters",
+    "rt_lightmap_texels", "rt_lightmap_trace", "rt_lightmap_resolve", "rt_lightmap_work_bytes", "rt_lightmap_dilate",
+    "rt_scene_lightmap", "rt_get_lightmap_counters",
     "rt_guided_work_bytes", "rt_guided_denoise", "rt_guided_denoise_host", "rt_render_denoised",
     "rt_temporal_history_bytes", "rt_temporal_accumulate", "rt_temporal_accumulate_host", "rt_history_create", "rt_history_reset",
     "rt_history_destroy", "rt_history_set_motion", "rt_render_temporal",

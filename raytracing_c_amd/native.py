@@ -151,6 +151,15 @@ def _declare(d):
         d.rt_probe_resolve.argtypes = [P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp]
         d.rt_scene_probes.argtypes = [P(abi.Scene), P(abi.RT_Probe_Params), C.c_int64, vp, vp, vp, vp]
         d.rt_get_probe_counters.argtypes = [P(abi.RT_Counters)]
+    if hasattr(d, "rt_scene_lightmap"):
+        d.rt_lightmap_texels.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        d.rt_lightmap_trace.argtypes = [vp, P(abi.RT_Lightmap_Params), vp, C.c_int64, C.c_int64, vp, vp]
+        d.rt_lightmap_resolve.argtypes = [P(abi.RT_Lightmap_Params), C.c_int64, vp, vp, vp, vp]
+        d.rt_lightmap_work_bytes.argtypes = [C.c_int32, C.c_int32]
+        d.rt_lightmap_work_bytes.restype = C.c_int64
+        d.rt_lightmap_dilate.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+        d.rt_scene_lightmap.argtypes = [P(abi.Scene), P(abi.RT_Lightmap_Params), C.c_int32, vp, vp, vp, P(C.c_int64)]
+        d.rt_get_lightmap_counters.argtypes = [P(abi.RT_Counters)]
     if hasattr(d, "rt_guided_denoise"):
         d.rt_guided_work_bytes.argtypes = [C.c_int32, C.c_int32]
         d.rt_guided_work_bytes.restype = C.c_int64
