@@ -123,7 +123,9 @@ typedef struct {
   int32_t rank, world, n_local_chunks;
   int32_t shared_taps;         /* host only, no kernel reads it: 1 = launch the path-kernel instance that computes one set of bilinear
                                 * taps per hit -- every material's textures agree in width, height and stride (rt_residency.cpp) */
-  int32_t unused_pad[2];       /* no kernel reads these (work items of retired kernels): they keep the offsets below; zero */
+  int32_t grab_batch;          /* grab_max (below) of the tiles that take the path kernel's batch loop: units per atomic while such a
+                                * tile has plenty left (1 .. 16).  In a slot no kernel read: every other field keeps its offset */
+  int32_t unused_pad;          /* no kernel reads this (a work item of retired kernels): it keeps the offsets below; zero */
   int32_t sched_thresh;        /* lanes waiting for shade / environment / regeneration that trigger that block */
   int32_t n_lds_nodes;         /* BVH nodes [0, n) are also in the workgroup's LDS   */
   /* outputs */

@@ -30,7 +30,7 @@
 //
 //  * A wave OWNS an 8x8-pixel tile (taken from the head counter, expensive tiles first) and pulls UNITS of it --
 //    2 neighbouring pixels x 2^chunk_shift samples (128 paths at 64 samples, pixel-major, so the 64 lanes
-//    sit on one or two pixels: coherent nodes, leaves and texels), one or two per atomic -- from the tile's own counter
+//    sit on one or two pixels: coherent nodes, leaves and texels), one or two per atomic, up to eight in the batch loop -- from the tile's own counter
 //    `tile_next[tile]` until the tile is exhausted.  Lanes whose path ended are refilled across unit boundaries, so
 //    there is no drain at the end of a unit (40 us to 0.4 ms each, measured on the kernel generation that had one); the wave
 //    drains once per TILE.
@@ -203,7 +203,8 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
       typename CamSrc<VIEWS>::type S;
       if constexpr (VIEWS) S = vrec; else S = A;
       const int width = A->width, height = A->height, sample_first = A->sample_first, sample_end = A->sample_end;
-      const uint32_t n_sb = (uint32_t)A->n_sample_blocks, gmax = (uint32_t)A->grab_max;
+      const uint32_t n_sb = (uint32_t)A->n_sample_blocks, gmax = (uint32_t)A->grab_batch;      // (units per atomic: a batch tile's own)
+      if (queue_open) U.grab = gmax;      // (the host has put the tile's size through the taper: the owner's first grab obeys it too)
       PrimaryParams PP;
       primary_params(PP, S, A);
       BgImageParamsLds BP;                // (the environment from its float image: background_lookup_image, rt_dev.hip.h)
@@ -267,7 +268,11 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void rt_path_kernel
           ray_setup<SHORT_DIV>(rs[q], o, dirs[q]);
           slow = slow || (valid[q] && !rs[q].fast);
         }
-        if (__ballot(slow) != 0ull) break;          // the general loop redoes this batch, and the rest of the tile
+        // The general loop redoes this batch, and the rest of the tile.  U.grab stays what this loop left: the general loop's FIRST
+        // grab on the tile may take up to grab_batch units, every later one obeys grab_max (grab_units' taper).  Correct either way
+        // -- u_end is clamped, the tile closed once -- and only frames that hand every tile over see it; clamping U.grab here costs
+        // the VIEWS instances a spilled SGPR (profiles/r17_batch_lanes.md).
+        if (__ballot(slow) != 0ull) break;
         uint32_t nv = 0;
         // (leafless tiles; every lane runs every test -- nothing to save under a lane mask, and no mask to keep in scalar registers;
         //  a sky tile pays one readlane and a branch per batch)

@@ -308,6 +308,19 @@ int render_accumulate_locked(Device &D, RT_Device_Scene *d, Camera const *cam, R
     int v = knob_int("RT_GRAB", 0);
     if (v == 1 || v == 2 || v == 4) K.grab_max = v;
   }
+  // ... of the tiles that take the batch loop (sky, leafless and triangle-less tiles): they hold no bounce chains, so what a wave
+  // still holds at the end of the launch is batches of 64 paths; the taper towards the tile's end is the same.  Every grab is a
+  // returning atomic the wave waits for, once per two batches at 1.  Measured, one process, arms interleaved, 1 / 2 / 4 / 8 / 16:
+  // config #3 25.80 / 25.66 / 25.58 / 25.58 / 25.62 ms, tower 23.42 / 23.03 / 22.85 / 22.81 / 22.85 (profiles/r17_batch_lanes.md).
+  K.grab_batch = 8;
+  {
+    int v = knob_int("RT_GRAB_BATCH", 0);
+    if (v >= 1 && v <= 16) K.grab_batch = v;
+  }
+  // The owner's FIRST grab is grab_batch as it stands, so the taper is applied to the whole tile here: a tile of fewer than
+  // 8 * grab_batch units -- the 32 units of a 16-spp frame -- never reaches grab_batch under the kernel's rule (it grabs 2 while 8
+  // units are left, then 1), and with the constant set to that value its first grab follows the rule as well.  Same grabs otherwise.
+  if (K.n_chunks_tile < 8 * K.grab_batch) K.grab_batch = (K.n_chunks_tile >= 8 && K.grab_batch >= 2) ? 2 : 1;
   K.pyr_nodes = knob_int("RT_PYRAMID", 1) ? K.n_lds_nodes : 0;
   // Leaf blocks with the short reciprocal (rcp_exact, rt_dev.hip.h): equal to the IEEE division while every triangle
   // determinant |e1 . (d x e2)| <= 6 D E^2 stays below 2^102.  E = largest edge component of the scene; D = largest

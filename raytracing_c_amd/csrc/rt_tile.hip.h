@@ -252,7 +252,8 @@ __device__ __forceinline__ int leafless_walk(float4 *smem, const float4 *lds_nod
 // ---- units ----
 // The tile hands out UNITS (2 pixels x one block of samples = 128 paths at 64 samples, lanes on one or two pixels).  A wave
 // grabs `grab` consecutive units per atomic, `grab_max` while the tile has plenty left, fewer towards its end: what a wave still
-// holds when the launch runs dry is its tail.  All wave-uniform.
+// holds when the launch runs dry is its tail.  (The path kernel's batch loop grabs by the same rule with `grab_batch` for
+// `grab_max`: its tiles hold no bounce chains.)  All wave-uniform.
 struct TileUnits {
   uint32_t u_cur, u_end, grab;       // the grabbed units [u_cur, u_end) (u_cur: the current one), units to ask for next
   int  c_next, c_end;                // the current unit: its paths [c_next, c_end) are not handed out yet
